@@ -9,6 +9,7 @@ sparsity pattern (DOLFIN builds it inside the first assemble) are set-up, timed 
 reported separately as `symbolic_ms`.
 
   python bench.py                       # N=1: BASELINE.json configs[1], 1 M DOF unit cube
+  python bench.py --dump-outputs DIR    # + what the last timed step computed, DIR/<name>.npy (dump_outputs): two builds compared
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W      # one rank per GPU (RCCL); the driver's launcher
   python -m fenicssolver_amd.launch --nproc N bench.py --gpus N      # the package's own launcher, same environment
@@ -60,8 +61,10 @@ VARIANTS = ("single_reduction", "pipelined", "single_reduction+p2p")
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --workload th: 10 time steps)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     # (--cells under torch.distributed.run: its own parser claims every abbreviation of --nnodes / --nproc-per-node)
     ap.add_argument("--n", "--cells", dest="n", type=int, default=99, help="cells per axis of the (per-GPU) cube")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
@@ -83,7 +86,12 @@ def parse():
     ap.add_argument("--no-hbm-case", action="store_true", help="skip the extra 10 M-DOF roofline measurement")
     ap.add_argument("--no-cache-free-case", action="store_true",
                     help="skip the 86 M-DOF cube (n = 440) behind the 10 M-DOF roofline measurement: the same kernels where the 256 MiB Infinity Cache cannot help")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps is None:
+        a.steps = 10 if a.workload == "th" else 20
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 class Problem:
@@ -289,6 +297,37 @@ def p2_global_dofs(n):
     return (n + 1) ** 3 + 3 * n * (n + 1) ** 2 + 3 * n * n * (n + 1) + n ** 3      # vertices + axis, face-diagonal and body-diagonal edges
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy per array (float64; float32 stays
+    float32), so that two builds can be compared output for output.  The files of all ranks stay within DUMP_BYTES: an array of
+    more entries than its share is written as a fixed, seeded sample of its rows, their numbers beside it in <name>_rows.npy.
+    Several ranks: every rank writes its own part, <name>_rank<r>.npy."""
+    os.makedirs(directory, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    cap = (DUMP_BYTES - 4096) // (16 * len(arrays) * world)      # entries an array: values + row numbers, 8 B each
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        v = v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+        if v.size > cap:
+            row = v.size // len(v)
+            rows = np.sort(np.random.default_rng(0).choice(len(v), cap // row, replace=False))
+            v = v[rows]
+            np.save(os.path.join(directory, "%s_rows%s.npy" % (name, sfx)), rows.astype(np.float64))
+        np.save(os.path.join(directory, name + sfx + ".npy"), np.ascontiguousarray(v))
+
+
+def step_outputs(prob):
+    """What a caller of the step receives: the solution x and the right-hand side after the Dirichlet elimination, owned rows.
+    A file-order P1 mesh (ShuffledProblem) reports them in the structured cube's numbering, as the parity check does."""
+    x, b = prob.x.get()[:prob.n_owned], prob.b.get()[:prob.n_owned]
+    if hasattr(prob, "to_structured"):
+        x, b = prob.to_structured(x), prob.to_structured(b)
+    return {"x": x, "b": b}
+
+
 def timed_steps(prob, rtol, steps, barrier, reduce=True):
     barrier()
     t0 = time.perf_counter()
@@ -446,9 +485,9 @@ def strong_leg(n, axis, rank, world, rtol, barrier, steps=3):
     return res
 
 
-def p2_leg(n, axis, rank, world, rtol, barrier, steps=2, warmup=1, recurrence="auto", mesh="structured"):
+def p2_leg(n, axis, rank, world, rtol, barrier, steps=2, warmup=1, recurrence="auto", mesh="structured", dump=None):
     """BASELINE configs[3]: P2 heat conduction, unit cube n (107 -> 9 938 375 DOF), z-slabs over the ranks.
-    mesh = shuffled / renumbered (one GPU): the same cube in FILE order (P2FileOrderProblem)."""
+    mesh = shuffled / renumbered (one GPU): the same cube in FILE order (P2FileOrderProblem).  dump: --dump-outputs DIR."""
     zplanes = partition.slab_ranges(n + 1, world)[rank]
     t0 = time.perf_counter()
     if mesh != "structured":
@@ -461,6 +500,8 @@ def p2_leg(n, axis, rank, world, rtol, barrier, steps=2, warmup=1, recurrence="a
     name, trial = choose_recurrence(prob, rtol, world, recurrence, barrier)
     elapsed, asm_ms, st, name = timed_steps_with_fallback(prob, rtol, steps, barrier, name, trial, world, warmup)
     ms = elapsed * 1e3 / steps
+    if dump:
+        dump_outputs(dump, step_outputs(prob), rank, world)
     err = float(np.abs(prob.x.get()[:prob.n_owned] - prob.exact_owned).max())
     err = parallel.max_over_ranks(err)
     n_dof = p2_global_dofs(n)
@@ -479,9 +520,10 @@ def p2_leg(n, axis, rank, world, rtol, barrier, steps=2, warmup=1, recurrence="a
             "update": update_rates(st, prob.n_owned), "iteration": iteration_rates(st, k, prob.n_owned)}
 
 
-def th_leg(n, n_steps, rank, world):
+def th_leg(n, n_steps, rank, world, dump=None):
     """BASELINE configs[4]: lid-driven cavity, Taylor-Hood P2/P1 on the unit cube n (43 -> 1 975 509 velocity + 85 184 pressure
-    dofs), nu = 0.01, rho = 1, dt = 0.01, backward Euler, Newton per step - through the solver class, as a user runs it."""
+    dofs), nu = 0.01, rho = 1, dt = 0.01, backward Euler, Newton per step - through the solver class, as a user runs it.
+    dump: --dump-outputs DIR (the fields after the last time step)."""
     import copy
     import logging
     from collections import OrderedDict
@@ -510,6 +552,9 @@ def th_leg(n, n_steps, rank, world):
     w = solver.solve()
     parallel.barrier()
     t2 = parallel.max_over_ranks(time.perf_counter() - t1)
+    if dump:
+        W4 = w.vector().array().reshape(-1, 4)
+        dump_outputs(dump, {"velocity": W4[:, :3], "pressure": W4[:mesh.num_vertices(), 3]}, rank, world)
     # the dominant kernel of the configuration - the 4 x 4-block product of the FGMRES iterations, k_sell_spmv4_ksplit - timed on the
     # Jacobian of the last Newton step (fs_spmv_benchmark: HIP events around back-to-back launches on the library's stream), against
     # the bytes its storage form has to move: the LIVE value planes (a pressure column / row exists for vertex nodes only: 16 values
@@ -763,7 +808,8 @@ def main():
     if a.workload == "p2":      # BASELINE configs[3] as the timed leg: the fixed 9.94 M-DOF problem over the ranks (strong)
         n = a.n if a.n != 99 else 107
         axis = a.bc_axis if a.bc_axis is not None else 2
-        r = p2_leg(n, axis, rank, world, a.rtol, barrier, steps=a.steps, warmup=a.warmup, recurrence=a.recurrence, mesh=a.mesh)
+        r = p2_leg(n, axis, rank, world, a.rtol, barrier, steps=a.steps, warmup=a.warmup, recurrence=a.recurrence, mesh=a.mesh,
+                   dump=a.dump_outputs)
         if rank == 0:
             out = dict(base, value=r["dof_per_s"], steps=a.steps, warmup=a.warmup, ms_per_step=r["ms_per_step"], scaling="strong",
                        config={"workload": r["workload"], "n_dof": r["n_dof"], "n_cells": 6 * n ** 3, "parallelism": par,
@@ -786,7 +832,7 @@ def main():
         return
     if a.workload == "th":      # BASELINE configs[4] as the timed leg (a "step" = one backward-Euler time step with its Newton solves)
         n = a.n if a.n != 99 else 43
-        r = th_leg(n, a.steps if a.steps != 20 else 10, rank, world)
+        r = th_leg(n, a.steps, rank, world, dump=a.dump_outputs)
         if rank == 0:
             out = dict(base, metric="DOF/s (Taylor-Hood Navier-Stokes time steps, assemble + Newton/FGMRES solve)", value=r["dof_per_s"],
                        steps=r["time_steps"], warmup=0, ms_per_step=round(r["solve_s"] * 1e3 / max(r["time_steps"], 1), 3), scaling="strong",
@@ -844,6 +890,8 @@ def main():
         first_step_ms, warmup_left = (time.perf_counter() - t0) * 1e3, a.warmup - 1
     elapsed, asm_ms_step, stats, recurrence = timed_steps_with_fallback(prob, a.rtol, a.steps, barrier, recurrence, trial, world, warmup_left)
     ms_per_step = elapsed * 1e3 / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, step_outputs(prob), rank, world)
 
     out = None
     if rank == 0:

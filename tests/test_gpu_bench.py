@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -71,3 +72,39 @@ def test_side_workloads_print_a_line(gpu, args, expect):
     assert "roofline" in d and d["n_gpus"] == 1
     if "--workload" in args:       # the CG2 legs carry their own check: the linear profile is in the space
         assert d["parity"]["max_abs_error_vs_exact_profile"] <= 1e-4
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat(gpu, tmp_path):
+    """--dump-outputs: the solution and right-hand side of the last timed step, float64, the same from run to run; --steps is the
+    number of timed steps the line reports and prices."""
+    args = ("--cells", "23", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-hbm-case")
+    d = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["b.npy", "x.npy"]
+    x = np.load(tmp_path / "a" / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (24 ** 3,)
+    # the linear profile between the Dirichlet faces z = 0 (350) and z = 1 (300) is in the P1 space; vertices x-fastest
+    z = (np.arange(24 ** 3) // 24 ** 2) / 23.0
+    assert np.abs(x - (350.0 - 50.0 * z)).max() <= 1e-4
+    for name in ("x", "b"):
+        va, vb = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert np.all(np.isfinite(va)) and np.abs(va).max() > 0
+        assert np.abs(va - vb).max() <= 1e-9 * np.abs(va).max(), name
+
+
+@pytest.mark.parametrize("args,names", [
+    (("--workload", "p2", "--cells", "11", "--mesh", "shuffled", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"), ["b.npy", "x.npy"]),
+    (("--workload", "th", "--cells", "6", "--steps", "2"), ["pressure.npy", "velocity.npy"]),
+])
+def test_side_workloads_dump_their_outputs(gpu, tmp_path, args, names):
+    d = _bench(*args, "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == names
+    for name in names:
+        v = np.load(tmp_path / name)
+        assert v.dtype == np.float64 and v.size > 0 and np.all(np.isfinite(v))
+    if "p2" in args:       # the P2 solution is the linear profile, as the line's own parity check says
+        assert d["parity"]["max_abs_error_vs_exact_profile"] <= 1e-4
+    else:                  # the lid's nodes carry its speed, 1
+        assert 0.99 <= np.abs(np.load(tmp_path / "velocity.npy")).max() <= 1.5
