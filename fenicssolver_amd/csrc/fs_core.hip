@@ -118,10 +118,8 @@ void fs_pool_trim(size_t keep_bytes) {
     }
 }
 
-void* fs_pool_alloc(size_t bytes) {
+static void* pool_take(size_t bytes) {
     block_pool& P = pool();
-    if (bytes == 0) return nullptr;
-    bytes = (bytes + 255) & ~(size_t)255;       // (kernels that read whole 16-byte groups - k_box_spmv's loaders - may touch the bytes behind an odd count)
     std::lock_guard<std::recursive_mutex> lock(P.mu);
     // the smallest idle block that holds the request and wastes at most a quarter of itself (small blocks: half)
     auto it = P.idle.lower_bound(bytes);
@@ -146,6 +144,28 @@ void* fs_pool_alloc(size_t bytes) {
     }
     P.size_of[p] = bytes;
     P.live += bytes;
+    return p;
+}
+
+void* fs_pool_alloc(size_t bytes) {
+    if (bytes == 0) return nullptr;
+    // (kernels that read whole 16-byte groups - the loaders of k_box_spmv, k_lat_march, k_box_cg_iter - may touch the bytes behind an odd count)
+    void* p = pool_take((bytes + 255) & ~(size_t)255);
+    if (!p) return nullptr;
+    // INVARIANT: the last 16 bytes of every request and the rest of its last 16-byte group are zero from the hand-out on.  The
+    // marching-window loaders copy x in pairs of doubles clamped to the last pair that starts inside the vector: for an odd n that
+    // pair is (x[n - 1], x[n]), and x[n] meets zero coefficients - fma(0, NaN, acc) is NaN, so x[n] must be finite.  It lies behind
+    // the request of an n-entry vector and inside it for the n + 2 entries of the Krylov workspaces (kernels write entries [0, n) of
+    // those; only the lattice_check probe fills all n + 2, with finite values).  A re-used block otherwise keeps whatever its last
+    // owner left there (tests/test_gpu_tails.py).  At most 24 bytes, on the stream every user of the block is ordered on (fs_common.h).
+    const size_t lo = bytes < 16 ? 0 : bytes - 16, hi = (bytes + 15) & ~(size_t)15;
+    const hipError_t e = hipMemsetAsync(static_cast<char*>(p) + lo, 0, hi - lo, fs_rt().stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        fs_pool_free(p);
+        fs_set_error("clearing the tail of a %zu-byte block failed: %s", bytes, hipGetErrorString(e));
+        return nullptr;
+    }
     return p;
 }
 
