@@ -16,6 +16,11 @@ Jacobi-CG (the aggregation hierarchy is built on P1 node patterns).  ``von_Mises
 assembled and solved on the device (fs_assemble_von_mises + P1 mass matrix + CG).  Elastodynamics
 (``solving_dynamics = True``, :216-220) subtracts rho * acceleration with the reference's own finite-difference
 acceleration (SolverBase.py:477-482, including its division by 1/dt).
+
+Material: ``elastic_modulus``, ``poisson_ratio``, ``thermal_expansion_coefficient`` and ``density`` may vary from cell to
+cell (the reference multiplies in whatever ``material[...]`` holds, :62-85): a per-region dict
+{'name': {'subdomain_id': i, 'value': v}}, a degree-0 Expression (at the cell mid-points) or, on CG1 spaces, a scalar
+Function / Expression (the mean of its vertex values).  Numbers and scalar Constants keep the homogeneous path.
 """
 from __future__ import annotations
 
@@ -23,9 +28,9 @@ import numbers
 
 import numpy as np
 
-from .fem import Measure, Constant, Expression, Function, DirichletBC, nodal_values, is_constant_value
+from .fem import Measure, Constant, Expression, UserExpression, Function, DirichletBC, nodal_values, is_constant_value
 from .SolverBase import SolverBase, SolverError
-from . import forms
+from . import case, forms
 
 
 class LinearElasticitySolver(SolverBase):
@@ -36,13 +41,64 @@ class LinearElasticitySolver(SolverBase):
         self.solving_dynamics = False
         self.reference_load_sign = True
 
+    def material_field(self, name):
+        """material[name] as a number (homogeneous: a number or a scalar Constant) or an array with one value per cell of
+        self.mesh: a per-region dict, a degree-0 Expression (cell mid-points), on CG1 spaces a scalar Function or Expression
+        (the mean of its vertex values - what the P1 operator integrates exactly for a linear E)."""
+        v = self.material[name]
+        if isinstance(v, numbers.Number):
+            return v
+        if isinstance(v, Constant) and v.value_size() == 1:
+            return float(v)
+        if isinstance(v, forms.VolumeCoefficient) and v.kind in ('const', 'cell'):
+            return float(v.value) if v.kind == 'const' else np.asarray(v.value, dtype=np.float64)
+        if isinstance(v, dict):
+            return case.cellwise_from_regions(v, self.subdomains)
+        if isinstance(v, (Expression, UserExpression)) and v.value_size() == 1:
+            if v.degree == 0:
+                co = self.mesh.coordinates()
+                return np.asarray(v.eval_points(co[self.mesh.cells().astype(np.int64)].mean(axis=1)), dtype=np.float64)
+            self._require_cg1(name, 'an Expression of degree %d' % v.degree)
+            from .fem import FunctionSpace
+            return nodal_values(v, FunctionSpace(self.mesh, 'P', 1))[self.mesh.cells().astype(np.int64)].mean(axis=1)
+        if isinstance(v, Function) and v.function_space()._ncomp == 1:
+            self._require_cg1(name, 'a Function')
+            return np.asarray(v.vertex_values(), dtype=np.float64)[self.mesh.cells().astype(np.int64)].mean(axis=1)
+        raise SolverError("material '{}': a number, a scalar Constant, a per-region dict, a scalar Expression or (CG1) a scalar "
+                          "Function is expected, got {}".format(name, type(v).__name__))
+
+    def _require_cg1(self, name, what):
+        if self.function_space.degree() != 1:
+            raise SolverError("material '{}': {} is a nodal field; on a CG{} displacement space the material must be piecewise "
+                              "constant (a number, a per-region dict or a degree-0 Expression)".format(
+                                  name, what, self.function_space.degree()))
+
+    def _bad_cell(self, name, ok):
+        """SolverError naming the region (per-region input) or the first cell where ``ok`` fails."""
+        bad = int(np.argmin(ok))
+        v = self.material[name]
+        if isinstance(v, dict) and getattr(self, 'subdomains', None) is not None:
+            sid = self.subdomains.array()[bad]
+            region = next((k for k, it in v.items() if it['subdomain_id'] == sid), sid)
+            return SolverError("material '{}' of region '{}' is out of range".format(name, region))
+        return SolverError("material '{}' is out of range in cell {}".format(name, bad))
+
     def lame_parameters(self):
-        elasticity = self.material['elastic_modulus']
-        nu = self.material['poisson_ratio']
-        if not (isinstance(elasticity, numbers.Number) and isinstance(nu, numbers.Number)):
-            raise SolverError('elastic_modulus and poisson_ratio must be numbers (homogeneous material)')
-        mu = elasticity / (2.0 * (1.0 + nu))
-        lmbda = elasticity * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+        """(mu, lambda): numbers for a homogeneous material, arrays [n_cells] when E or nu vary from cell to cell."""
+        elasticity = self.material_field('elastic_modulus')
+        nu = self.material_field('poisson_ratio')
+        if np.ndim(elasticity) == 0 and np.ndim(nu) == 0:
+            mu = elasticity / (2.0 * (1.0 + nu))
+            lmbda = elasticity * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+            return mu, lmbda
+        nc = self.mesh.num_cells()
+        E = np.broadcast_to(np.asarray(elasticity, dtype=np.float64), (nc,))
+        nu = np.broadcast_to(np.asarray(nu, dtype=np.float64), (nc,))
+        for name, ok in (('elastic_modulus', E > 0.0), ('poisson_ratio', (nu > -1.0) & (nu < 0.5))):
+            if not ok.all():
+                raise self._bad_cell(name, ok)
+        mu = E / (2.0 * (1.0 + nu))
+        lmbda = E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
         return mu, lmbda
 
     def _cell_gradients(self, u):
@@ -79,6 +135,8 @@ class LinearElasticitySolver(SolverBase):
         G = self._cell_gradients(u)
         eps = 0.5 * (G + np.transpose(G, (0, 2, 1)))
         tr = np.trace(G, axis1=1, axis2=2)
+        if np.ndim(mu) > 0:                 # per-cell material
+            mu, lmbda = np.asarray(mu)[:, None, None], np.asarray(lmbda)[:, None, None]
         return 2.0 * mu * eps + lmbda * tr[:, None, None] * np.eye(G.shape[1])[None]
 
     def von_Mises(self, u):
@@ -96,6 +154,9 @@ class LinearElasticitySolver(SolverBase):
             uh = loc.nodes(uh)                       # host field -> this rank's owned + ghost entries in device order
         ud = backend.DeviceVector(dV.n_local, uh)
         b = backend.DeviceVector(dP.n_owned)
+        if np.ndim(mu) > 0:                          # per-cell material: (mu, lambda) pairs in device cell order
+            pairs = np.stack([mu, lmbda], axis=1)
+            mu, lmbda = ('cell', pairs if loc is None else loc.cells(pairs)), None
         backend.assemble_von_mises(dV, ud, mu, lmbda, dP, b)
         M = backend.DeviceMatrix(dP)
         M.assemble(mass=1.0)
@@ -117,16 +178,21 @@ class LinearElasticitySolver(SolverBase):
         return f
 
     def thermal_stress_coefficient(self):
-        elasticity = self.material['elastic_modulus']
-        nu = self.material['poisson_ratio']
-        tec = self.material['thermal_expansion_coefficient']
+        """E alpha / (1 - 2 nu): a number, or an array [n_cells] for a material that varies from cell to cell."""
+        elasticity = self.material_field('elastic_modulus')
+        nu = self.material_field('poisson_ratio')
+        tec = self.material_field('thermal_expansion_coefficient')
         return elasticity / (1.0 - 2.0 * nu) * tec
 
     def thermal_stress(self, T):
         """The isotropic thermal stress  E/(1-2nu) * alpha * (T - T_ref)  (the multiplier of Identity(dim),
-        LinearElasticitySolver.py:78-85) for a number, an array of nodal temperatures or a Function."""
+        LinearElasticitySolver.py:78-85) for a number, an array of nodal temperatures or a Function.  A per-cell material
+        gives one value per cell, a nodal temperature entering by its mean at the cell's vertices."""
         vals = T.vector()._values() if isinstance(T, Function) else np.asarray(T, dtype=np.float64)
-        return self.thermal_stress_coefficient() * (vals - float(self.reference_values['temperature']))
+        coef = self.thermal_stress_coefficient()
+        if np.ndim(coef) > 0 and np.ndim(vals) > 0:
+            vals = vals[:self.mesh.num_vertices()][self.mesh.cells().astype(np.int64)].mean(axis=1)
+        return coef * (vals - float(self.reference_values['temperature']))
 
     def strain_energy(self, u):
         raise SolverError("strain_energy: the reference's expression (LinearElasticitySolver.py:87-93) uses an undefined "
@@ -319,7 +385,8 @@ class LinearElasticitySolver(SolverBase):
         F = forms.ElasticityForm(self.function_space)
         if self.transient_settings['transient'] and self.solving_dynamics and time_iter_ >= 1:
             # F -= density * inner(accel, v) * dx (:216-220) with the explicit acceleration of SolverBase.get_acceleration
-            F.inertia = (float(self.material['density']), self.get_acceleration(time_iter_))
+            rho = self.material_field('density')
+            F.inertia = (float(rho) if np.ndim(rho) == 0 else ('cell', rho), self.get_acceleration(time_iter_))
         F.mu, F.lmbda = self.lame_parameters()
         F.load_sign = -1.0 if self.reference_load_sign else 1.0
 

@@ -690,7 +690,10 @@ class SolverBase():
                 B.spmv(tp, tmp)
                 b.axpy(1.0, tmp)
         elif isinstance(F, forms.ElasticityForm):
-            A.assemble(lame=(F.mu, F.lmbda))
+            lame = F.lame_spec()
+            if F.cellwise() and loc is not None:
+                lame = ('cell', loc.cells(lame[1]))     # per-cell (mu, lambda): this rank's cells, in device cell order
+            A.assemble(lame=lame)
             sgn = F.load_sign
             if F.body_force is not None:
                 backend.assemble_vector(V, b, vector_value=[sgn * x for x in F.body_force])
@@ -718,7 +721,12 @@ class SolverBase():
                     backend.assemble_facet_vector(V, b, tri, sgn * np.asarray(g, float))
             if F.thermal is not None:
                 coef, T, T_ref = F.thermal
-                if np.ndim(T) == 0:
+                if np.ndim(coef) > 0:
+                    # per-cell E alpha / (1 - 2 nu): a per-cell coefficient, a nodal temperature by its mean at the cell's vertices
+                    dT = float(T) - T_ref if np.ndim(T) == 0 else \
+                        np.asarray(T, dtype=np.float64)[self.mesh.cells().astype(np.int64)].mean(axis=1) - T_ref
+                    backend.assemble_vector(V, b, div_coef=L_(('cell', np.asarray(coef, dtype=np.float64) * dT)), add=True)
+                elif np.ndim(T) == 0:
                     backend.assemble_vector(V, b, div_coef=coef * (float(T) - T_ref), add=True)
                 else:
                     Tn = np.asarray(T)               # P1 temperature: its vertex values
@@ -1204,6 +1212,10 @@ class SolverBase():
         from . import backend, parallel
         W = F.space.root() if hasattr(F.space, 'root') else F.space
         mesh, loc, nc = W.mesh(), W.localizer(), W._ncomp
+        if F.cellwise() and getattr(mesh, '_slab', None) is not None:
+            raise SolverError("solve_amg: a per-cell material on BoxMesh(distributed=True) under several ranks needs the global "
+                              "cell array, which no rank holds - use the replicated BoxMesh (distributed=False), or "
+                              "solver_parameters {'preconditioner': 'jacobi'}")
         cache = mesh.__dict__.setdefault('_undecomposed_device', {})
         if 'mesh' not in cache:
             if getattr(mesh, '_slab', None) is not None:          # distributed box: the device generates the whole box
@@ -1218,7 +1230,7 @@ class SolverBase():
             cache[skey] = backend.DeviceSpace(cache['mesh'], nc, W.degree(), coupled_pairs=None if per is None else W._periodic_couplings())
         Vg = cache[skey]
         Ag = backend.DeviceMatrix(Vg)
-        Ag.assemble(lame=(F.mu, F.lmbda))
+        Ag.assemble(lame=F.lame_spec())         # (the host mesh's global cells, which is the order this device mesh holds them in)
         if per is not None:
             Ag.tie_nodes(None, per[0], per[1])
         dofs, vals = self._bc_arrays(bcs)
@@ -1240,6 +1252,10 @@ class SolverBase():
         if not isinstance(F, forms.ElasticityForm):
             return None
         dofs = np.concatenate([np.asarray(bc.dofs, dtype=np.int64) for bc in bcs]) if bcs else np.zeros(0, dtype=np.int64)
+        if F.cellwise():        # per-cell material: a digest of the (mu, lambda) pairs
+            pairs = np.ascontiguousarray(F.lame_spec()[1])
+            return ('elasticity', F.space.root().serial(), 'cell', pairs.shape[0], zlib.crc32(pairs.tobytes()), len(dofs),
+                    zlib.crc32(np.ascontiguousarray(dofs).tobytes()))
         return ('elasticity', F.space.root().serial(), float(F.mu), float(F.lmbda), len(dofs), zlib.crc32(np.ascontiguousarray(dofs).tobytes()))
 
     def build_nullspace(self, V, x=None):

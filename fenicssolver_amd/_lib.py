@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libfsamd.so")
 FS_OK = 0
 FS_ERR_COMM, FS_ERR_NUMERIC, FS_ERR_P2P_TIMEOUT = -5, -6, -7      # include/fenicssolver_amd.h
 FS_COEF_NONE, FS_COEF_CONST, FS_COEF_CELL, FS_COEF_TENSOR, FS_COEF_NODAL, FS_COEF_CELL_ROW, FS_COEF_CELL_TENSOR, FS_COEF_CELL_QP = 0, 1, 2, 3, 4, 5, 6, 7
+FS_COEF_CELL_LAME = 8
 FS_KSP_CG = 0
 FS_KSP_BICGSTAB = 1
 FS_PC_NONE, FS_PC_JACOBI = 0, 1
@@ -41,7 +42,7 @@ class fs_coef(C.Structure):
 
 class fs_bilinear_form(C.Structure):
     _fields_ = [("stiffness", fs_coef), ("mass", fs_coef), ("lame_mu", C.c_double), ("lame_lambda", C.c_double),
-                ("advection", fs_coef), ("advection_scale", C.c_double), ("supg_pe", C.c_double)]
+                ("advection", fs_coef), ("advection_scale", C.c_double), ("supg_pe", C.c_double), ("lame", fs_coef)]
 
 
 class fs_linear_form(C.Structure):
@@ -159,6 +160,7 @@ SIGNATURES = {
     "fs_comm_get_unique_id": (C.c_int, [C.c_char_p]),
     "fs_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_char_p]),
     "fs_assemble_von_mises": (C.c_int, [_H, _H, C.c_double, C.c_double, _H, _H]),
+    "fs_assemble_von_mises_cells": (C.c_int, [_H, _H, c_f64p, _H, _H]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),
     "fs_comm_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

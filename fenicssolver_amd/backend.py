@@ -332,8 +332,27 @@ def _bilinear_form(keep, stiffness=None, mass=None, lame=None, advection=None, a
         f.advection_scale = float(advection_scale)
         f.supg_pe = float(supg_pe)
     if lame is not None:
-        f.lame_mu, f.lame_lambda = float(lame[0]), float(lame[1])
+        if _is_cell_lame(lame):
+            f.lame.mode = L.FS_COEF_CELL_LAME              # ('cell', [n_cells, 2]): one (mu, lambda) pair per cell
+            f.lame.data = L.p_f64(_lame_cells(lame, keep))
+        else:
+            f.lame_mu, f.lame_lambda = float(lame[0]), float(lame[1])
     return f
+
+
+def _is_cell_lame(lame):
+    return isinstance(lame, tuple) and len(lame) == 2 and isinstance(lame[0], str)
+
+
+def _lame_cells(lame, keep, n_cells=None):
+    kind, arr = lame
+    if kind != "cell":
+        raise BackendError("Lame parameters: (mu, lambda) numbers or ('cell', array[n_cells, 2]), got kind %r" % (kind,))
+    a = np.ascontiguousarray(arr, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 2 or (n_cells is not None and a.shape[0] != n_cells):
+        raise BackendError("per-cell Lame parameters must be an array [%s, 2], got shape %s" % (n_cells, a.shape))
+    keep.append(a)
+    return a
 
 
 def apply_operator(space, x, y, stiffness=None, mass=None, advection=None, advection_scale=1.0, supg_pe=0.0, reps=0):
@@ -360,6 +379,8 @@ class DeviceMatrix(_Handle):
         """advection: constant velocity (3 numbers) or per-cell array [n_cells,3]; supg_pe > 0: SUPG test function
         q + tau (v . grad q) on the advection and mass terms."""
         keep = []
+        if _is_cell_lame(lame):
+            lame = ("cell", _lame_cells(lame, keep, self.space.mesh.info()[1]))
         f = _bilinear_form(keep, stiffness, mass, lame, advection, advection_scale, supg_pe)
         L.check(L.load().fs_assemble_matrix(self.h, C.byref(f), 1 if add else 0), "fs_assemble_matrix")
 
@@ -497,8 +518,13 @@ def _same_device_mesh(field_space, p1_space, what):
 
 
 def assemble_von_mises(disp_space, u, mu, lmbda, p1_space, b):
-    """b_a = int sqrt(3/2 s:s) phi_a dx, s the deviator of sigma(u), on the scalar CG1 space of the same mesh."""
+    """b_a = int sqrt(3/2 s:s) phi_a dx, s the deviator of sigma(u), on the scalar CG1 space of the same mesh.
+    Per-cell material: mu = ('cell', array[n_cells, 2]) of (mu, lambda) pairs in device cell order, lmbda = None."""
     _same_device_mesh(disp_space, p1_space, "assemble_von_mises")
+    if _is_cell_lame(mu):
+        a = _lame_cells(mu, [], disp_space.mesh.info()[1])
+        L.check(L.load().fs_assemble_von_mises_cells(disp_space.h, u.h, L.p_f64(a), p1_space.h, b.h), "fs_assemble_von_mises_cells")
+        return
     L.check(L.load().fs_assemble_von_mises(disp_space.h, u.h, float(mu), float(lmbda), p1_space.h, b.h), "fs_assemble_von_mises")
 
 

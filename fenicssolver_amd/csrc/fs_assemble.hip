@@ -1072,12 +1072,15 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_elasticity(const int32
 // nodes (inverse slot table, ascending cell order: bit-reproducible), recomputing the four barycentric gradients of
 // each cell - 60 flops against an 8-byte atomic per value.  configs[2] (9.86 M tets, 25 M blocks): 38.8 ms with
 // 1.4 G device-scope fp64 atomics.
-template <bool ADD>
+// CELL: per-cell material (FS_COEF_CELL_LAME) - one (mu, lambda) pair of 16 bytes per source cell, loaded with the cell record;
+// the arithmetic is the constant variant's, so an array that holds the constants gives the same bits.
+template <bool ADD, bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_elasticity_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
                                                                             const int32_t* __restrict__ src,
                                                                             const int32_t* __restrict__ cells,
-                                                                            const double* __restrict__ xyz4, double mu, double lambda,
-                                                                            coef_dev mc, int64_t plane, double* __restrict__ val, const box_snap bx) {
+                                                                            const double* __restrict__ xyz4, double mu0, double lambda0,
+                                                                            coef_dev mc, int64_t plane, double* __restrict__ val, const box_snap bx,
+                                                                            const double2* __restrict__ lame_cell) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; e < n_entries; e += stride) {
@@ -1088,10 +1091,14 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_elasticity_gather(int6
         for (int32_t q0 = ptr[e]; q0 < q1; q0 += PF) {
           int32_t sc[PF];
           int4 vc[PF];
+          double2 lc[PF];
 #pragma unroll
           for (int u = 0; u < PF; ++u) sc[u] = q0 + u < q1 ? src[q0 + u] : -1;
 #pragma unroll
-          for (int u = 0; u < PF; ++u) vc[u] = sc[u] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[u] >> 4] : make_int4(0, 0, 0, 0);
+          for (int u = 0; u < PF; ++u) {
+            vc[u] = sc[u] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[u] >> 4] : make_int4(0, 0, 0, 0);
+            if (CELL) lc[u] = sc[u] >= 0 ? lame_cell[sc[u] >> 4] : make_double2(0.0, 0.0);
+          }
 #pragma unroll
           for (int u = 0; u < PF; ++u) {
             if (q0 + u >= q1) break;
@@ -1099,6 +1106,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_elasticity_gather(int6
             const int64_t c = sidx >> 4;
             const int a = (sidx >> 2) & 3, b = sidx & 3;
             const int4 v4 = vc[u];
+            const double mu = CELL ? lc[u].x : mu0, lambda = CELL ? lc[u].y : lambda0;
             const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
             // (box meshes: edge vectors snapped to the grid spacing, as the scalar kernels do - equal stencils become equal block rows
             // bit for bit, which the row-dictionary product of the AMG fine level lives on)
@@ -1157,12 +1165,13 @@ __device__ __forceinline__ void p2_grad_one(const tet_geom& t, int qp, int a, do
         for (int d = 0; d < 3; ++d) ga[d] = li * tet_g(t, j, d) + lj * tet_g(t, i, d);
     }
 }
-template <bool ADD>
+template <bool ADD, bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p2_elasticity_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
                                                                             const int32_t* __restrict__ src,
                                                                             const int32_t* __restrict__ cells,
-                                                                            const double* __restrict__ xyz4, double mu, double lambda,
-                                                                            coef_dev mc, int64_t plane, double* __restrict__ val) {
+                                                                            const double* __restrict__ xyz4, double mu0, double lambda0,
+                                                                            coef_dev mc, int64_t plane, double* __restrict__ val,
+                                                                            const double2* __restrict__ lame_cell) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; e < n_entries; e += stride) {
@@ -1173,6 +1182,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p2_elasticity_gather(int6
             const int64_t c = sidx / 100;
             const int ab = sidx - (int32_t)c * 100, a = ab / 10, b = ab - 10 * a;
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);     // (issued with the cell record)
+            const double mu = ml.x, lambda = ml.y;
             const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
             const tet_geom t = tet_geometry(xyz4, v);
             const double w = t.adet * (1.0 / 24.0);            // volume * quadrature weight 1/4
@@ -1310,12 +1321,13 @@ __device__ __forceinline__ double supg_tau_tri(const double* __restrict__ xyz4, 
 // One thread per stored 2x2 block sums, in ascending order, the (cell, a, b) sources of the inverse slot table
 // (source index = cell*9 + a*3 + b): K_ab[i][j] = A (lambda d_i phi_a d_j phi_b + mu d_j phi_a d_i phi_b + mu delta_ij
 // grad phi_a . grad phi_b) [+ mass (1 + delta_ab) A / 12 delta_ij].
-template <bool ADD>
+template <bool ADD, bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_assemble_tri_elasticity_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
                                                                              const int32_t* __restrict__ src,
                                                                              const int32_t* __restrict__ cells,
-                                                                             const double* __restrict__ xyz4, double mu, double lambda,
-                                                                             coef_dev mc, int64_t plane, double* __restrict__ val) {
+                                                                             const double* __restrict__ xyz4, double mu0, double lambda0,
+                                                                             coef_dev mc, int64_t plane, double* __restrict__ val,
+                                                                             const double2* __restrict__ lame_cell) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; e < n_entries; e += stride) {
@@ -1327,6 +1339,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_tri_elasticity_gather(int
             const int ab = sidx - (int32_t)(c * 9);
             const int a = ab / 3, b = ab - 3 * a;
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+            const double mu = ml.x, lambda = ml.y;
             const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
             const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
             const double gb[2] = {b == 0 ? t.g[0][0] : (b == 1 ? t.g[1][0] : t.g[2][0]), b == 0 ? t.g[0][1] : (b == 1 ? t.g[1][1] : t.g[2][1])};
@@ -1854,12 +1868,13 @@ __device__ __forceinline__ void p2tri_grad_one(const tri_geom& t, int qp, int a,
 }
 // one thread per stored 2x2 block: the (cell, a, b) sources of the inverse slot table (source = cell*36 + a*6 + b), the
 // quadratic integrand by the 3-point edge-midpoint rule (exact)
-template <bool ADD>
+template <bool ADD, bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p2tri_elasticity_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
                                                                                const int32_t* __restrict__ src,
                                                                                const int32_t* __restrict__ cells,
-                                                                               const double* __restrict__ xyz4, double mu, double lambda,
-                                                                               coef_dev mc, int64_t plane, double* __restrict__ val) {
+                                                                               const double* __restrict__ xyz4, double mu0, double lambda0,
+                                                                               coef_dev mc, int64_t plane, double* __restrict__ val,
+                                                                               const double2* __restrict__ lame_cell) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; e < n_entries; e += stride) {
@@ -1870,6 +1885,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p2tri_elasticity_gather(i
             const int64_t c = sidx / 36;
             const int ab = sidx - (int32_t)c * 36, a = ab / 6, b = ab - 6 * a;
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+            const double mu = ml.x, lambda = ml.y;
             const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
             const double w = t.area * (1.0 / 3.0);
 #pragma unroll
@@ -2594,8 +2611,9 @@ static int make_coef(const fs_coef& in, int64_t expect_len, dbuf<double>& store,
     for (int i = 0; i < 9; ++i) out->tensor[i] = in.tensor[i];
     if (in.mode == FS_COEF_CELL_TENSOR) expect_len *= 9;
     if (in.mode == FS_COEF_CELL_QP) expect_len *= 14;
+    if (in.mode == FS_COEF_CELL_LAME) expect_len *= 2;
     if (in.mode == FS_COEF_CELL || in.mode == FS_COEF_NODAL || in.mode == FS_COEF_CELL_ROW || in.mode == FS_COEF_CELL_TENSOR ||
-        in.mode == FS_COEF_CELL_QP) {
+        in.mode == FS_COEF_CELL_QP || in.mode == FS_COEF_CELL_LAME) {
         FS_REQUIRE(in.data, "%s: coefficient data pointer is null", what);
         FS_CHECK(store.alloc(expect_len));
         FS_CHECK(store.upload(in.data, expect_len, fs_rt().stream));
@@ -2695,6 +2713,16 @@ extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, i
     FS_CHECK(make_coef(form->mass, m->nc, mstore, &mc, "fs_assemble_matrix(mass)"));
     FS_REQUIRE(mc.mode == FS_COEF_NONE || mc.mode == FS_COEF_CONST || mc.mode == FS_COEF_CELL,
                "fs_assemble_matrix: mass coefficient must be constant or per cell");
+    // Lame parameters: the two doubles (FS_COEF_NONE) or one (mu, lambda) pair per cell (FS_COEF_CELL_LAME, vector spaces)
+    dbuf<double> lstore;
+    coef_dev lc;
+    FS_REQUIRE(form->lame.mode == FS_COEF_NONE || form->lame.mode == FS_COEF_CELL_LAME,
+               "fs_assemble_matrix: the Lame coefficient is FS_COEF_NONE (lame_mu / lame_lambda) or FS_COEF_CELL_LAME");
+    FS_REQUIRE(form->lame.mode == FS_COEF_NONE || A->bs == 2 || A->bs == 3,
+               "fs_assemble_matrix: per-cell Lame parameters need a 2- or 3-vector space");
+    FS_CHECK(make_coef(form->lame, m->nc, lstore, &lc, "fs_assemble_matrix(lame)"));
+    const bool lame_cells = lc.mode == FS_COEF_CELL_LAME;
+    const double2* lcp = reinterpret_cast<const double2*>(lc.data);
     const int grid = fs_grid_for(m->nc, FS_BLOCK, 8192);
     if (m->tdim == 2 && A->bs == 2) {
         FS_REQUIRE(sp->slots.p, "fs_assemble_matrix: 2-vector space without slot table");
@@ -2702,15 +2730,18 @@ extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, i
                    "fs_assemble_matrix: a 2-vector space takes the Lame parameters (plane-strain elasticity) and a mass coefficient");
         if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
         const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
+#define FS_ELAST_GATHER(K, ADD_, CELL_) hipLaunchKernelGGL((K<ADD_, CELL_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, \
+                                                        m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, lcp)
         if (sp->degree == 2) {
-            if (add)
-                hipLaunchKernelGGL(k_assemble_p2tri_elasticity_gather<true>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
-            else
-                hipLaunchKernelGGL(k_assemble_p2tri_elasticity_gather<false>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
+            if (lame_cells) { if (add) FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, true, true); else FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, false, true); }
+            else if (add) FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, true, false);
+            else FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, false, false);
+        } else if (lame_cells) {
+            if (add) FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, true, true); else FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, false, true);
         } else if (add)
-            hipLaunchKernelGGL(k_assemble_tri_elasticity_gather<true>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
+            FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, true, false);
         else
-            hipLaunchKernelGGL(k_assemble_tri_elasticity_gather<false>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
+            FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, false, false);
     } else if (m->tdim == 2 && sp->degree == 2) {
         FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: CG2 space on triangles without assembly tables");
         dbuf<double> astore4;
@@ -2837,24 +2868,33 @@ extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, i
         FS_REQUIRE(kc.mode != FS_COEF_NODAL && kc.mode != FS_COEF_CELL_TENSOR, "fs_assemble_matrix: nodal / per-cell tensor stiffness coefficients need the row-gather tables");
         hipLaunchKernelGGL(k_assemble_p1_scalar, dim3(grid), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc, kc, mc, A->val.p);
     } else if (getenv("FS_ELASTICITY_ATOMIC") && sp->degree == 1 && A->bs == 3) {
+        FS_REQUIRE(!lame_cells, "fs_assemble_matrix: the atomic elasticity kernel (FS_ELASTICITY_ATOMIC) takes constant Lame parameters only");
         if (!add) FS_CHECK(A->val.zero(s));
         hipLaunchKernelGGL(k_assemble_p1_elasticity, dim3(grid), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
     } else if (A->bs == 3 && sp->degree == 2) {
         if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
         const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-        if (add)
-            hipLaunchKernelGGL(k_assemble_p2_elasticity_gather<true>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
+        if (lame_cells) {
+            if (add) FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, true, true); else FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, false, true);
+        } else if (add)
+            FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, true, false);
         else
-            hipLaunchKernelGGL(k_assemble_p2_elasticity_gather<false>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
+            FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, false, false);
     } else {
         FS_REQUIRE(A->bs == 3 && sp->degree == 1, "fs_assemble_matrix: no operator for block size %d on CG%d nodes (Taylor-Hood systems: fs_assemble_navier_stokes)", A->bs, sp->degree);
         if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
         const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-        if (add)
-            hipLaunchKernelGGL(k_assemble_p1_elasticity_gather<true>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, make_box_snap(m));
+#define FS_P1_ELAST(ADD_, CELL_) hipLaunchKernelGGL((k_assemble_p1_elasticity_gather<ADD_, CELL_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
+                                                    sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, make_box_snap(m), lcp)
+        if (lame_cells) {
+            if (add) FS_P1_ELAST(true, true); else FS_P1_ELAST(false, true);
+        } else if (add)
+            FS_P1_ELAST(true, false);
         else
-            hipLaunchKernelGGL(k_assemble_p1_elasticity_gather<false>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, make_box_snap(m));
+            FS_P1_ELAST(false, false);
+#undef FS_P1_ELAST
     }
+#undef FS_ELAST_GATHER
     FS_KERNEL_CHECK();
     // (no wait here: host arrays were consumed by make_coef's uploads, the coefficient stores go back to the pool in stream order,
     // and whatever the caller enqueues next - the load vector, the Dirichlet rows - is prepared while the assembly runs)
@@ -2932,12 +2972,13 @@ __device__ __forceinline__ double von_mises_of(const double (&G)[3][3], double m
         }
     return sqrt(1.5 * ss);
 }
-template <int DEG>
+// CELL (all four load kernels): per-cell (mu, lambda) pairs, read with the cell record (fs_assemble_von_mises_cells)
+template <int DEG, bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load(int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ inc_slice_ptr,
                                                              const int32_t* __restrict__ inc_cell, const int32_t* __restrict__ cells,
                                                              const double* __restrict__ xyz4, const int32_t* __restrict__ u_dofs,
-                                                             const double* __restrict__ u, double mu, double lambda,
-                                                             double* __restrict__ b) {
+                                                             const double* __restrict__ u, double mu0, double lambda0,
+                                                             double* __restrict__ b, const double2* __restrict__ lame_cell) {
     const int lane = threadIdx.x & 63;
     int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -2951,6 +2992,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load(int64_t n_rows, int
             if (q < 0) continue;
             const int c = q >> 2, a = q & 3;
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+            const double mu = ml.x, lambda = ml.y;
             const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
             const tet_geom t = tet_geometry(xyz4, v);
             const double vol = t.adet * (1.0 / 6.0);
@@ -3003,11 +3046,12 @@ __device__ __forceinline__ double von_mises_2d(const double (&G)[2][2], double m
     return sqrt(1.5 * ((s00 - pm) * (s00 - pm) + (s11 - pm) * (s11 - pm) + 2.0 * s01 * s01));
 }
 // P2 displacement on triangles: grad u is linear, vm is not a polynomial; 3-point edge-midpoint rule against lambda_a
+template <bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load_tri_p2(int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ inc_slice_ptr,
                                                                     const int32_t* __restrict__ inc_cell, const int32_t* __restrict__ cells,
                                                                     const double* __restrict__ xyz4, const int32_t* __restrict__ u_dofs,
-                                                                    const double* __restrict__ u, double mu, double lambda,
-                                                                    double* __restrict__ b) {
+                                                                    const double* __restrict__ u, double mu0, double lambda0,
+                                                                    double* __restrict__ b, const double2* __restrict__ lame_cell) {
     const int lane = threadIdx.x & 63;
     int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -3021,6 +3065,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load_tri_p2(int64_t n_ro
             if (q < 0) continue;
             const int c = q / 3, a = q - 3 * c;
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+            const double mu = ml.x, lambda = ml.y;
             const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
             double un[6][2];
 #pragma unroll
@@ -3047,10 +3093,11 @@ __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load_tri_p2(int64_t n_ro
         if (row < n_rows) b[row] = acc;
     }
 }
+template <bool CELL = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load_tri(int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ inc_slice_ptr,
                                                                  const int32_t* __restrict__ inc_cell, const int32_t* __restrict__ cells,
-                                                                 const double* __restrict__ xyz4, const double* __restrict__ u, double mu,
-                                                                 double lambda, double* __restrict__ b) {
+                                                                 const double* __restrict__ xyz4, const double* __restrict__ u, double mu0,
+                                                                 double lambda0, double* __restrict__ b, const double2* __restrict__ lame_cell) {
     const int lane = threadIdx.x & 63;
     int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -3064,6 +3111,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_von_mises_load_tri(int64_t n_rows,
             if (q < 0) continue;
             const int c = q / 3;
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+            const double mu = ml.x, lambda = ml.y;
             const int32_t v[3] = {v4.x, v4.y, v4.z};
             const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
             double G[2][2] = {{0, 0}, {0, 0}};
@@ -3322,31 +3371,57 @@ extern "C" int fs_assemble_viscous_stress_nn(fs_space_t th_space, fs_vector_t w,
     return FS_OK;
 }
 
-extern "C" int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, double mu, double lambda, fs_space_t p1_space,
-                                     fs_vector_t b) {
-    FS_REQUIRE(disp_space && u && p1_space && b, "fs_assemble_von_mises: null pointer");
-    FS_REQUIRE(disp_space->mesh == p1_space->mesh, "fs_assemble_von_mises: the two spaces live on different meshes");
-    FS_REQUIRE((disp_space->ncomp == 3 && disp_space->mesh->tdim == 3) || (disp_space->ncomp == 2 && disp_space->mesh->tdim == 2),
-               "fs_assemble_von_mises: needs a 3-vector displacement space on tetrahedra or a 2-vector space on triangles");
-    FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1 && p1_space->inc_cell.p, "fs_assemble_von_mises: the target is the scalar CG1 space of the mesh");
-    FS_REQUIRE(u->d.n >= disp_space->n_dofs_local && b->d.n >= p1_space->n_dofs_owned, "fs_assemble_von_mises: vector too short");
+// lame_host == nullptr: the constants (mu, lambda); otherwise [n_cells][2] (mu, lambda) pairs in device cell order
+template <bool CELL>
+static void von_mises_launch(fs_space_t disp_space, fs_vector_t u, double mu, double lambda, const double2* lc, fs_space_t p1_space,
+                             fs_vector_t b) {
     hipStream_t s = fs_rt().stream;
     fs_mesh_s* m = p1_space->mesh;
     const int g = fs_grid_for(p1_space->n_slices * 64, FS_BLOCK, 8192);
     if (m->tdim == 2 && disp_space->degree == 2)
-        hipLaunchKernelGGL(k_von_mises_load_tri_p2, dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
-                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, disp_space->cell_dofs, u->d.p, mu, lambda, b->d.p);
+        hipLaunchKernelGGL(k_von_mises_load_tri_p2<CELL>, dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
+                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, disp_space->cell_dofs, u->d.p, mu, lambda, b->d.p, lc);
     else if (m->tdim == 2)
-        hipLaunchKernelGGL(k_von_mises_load_tri, dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
-                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, b->d.p);
+        hipLaunchKernelGGL(k_von_mises_load_tri<CELL>, dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
+                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, b->d.p, lc);
     else if (disp_space->degree == 1)
-        hipLaunchKernelGGL(k_von_mises_load<1>, dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
-                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, disp_space->cell_dofs, u->d.p, mu, lambda, b->d.p);
+        hipLaunchKernelGGL((k_von_mises_load<1, CELL>), dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
+                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, disp_space->cell_dofs, u->d.p, mu, lambda, b->d.p, lc);
     else
-        hipLaunchKernelGGL(k_von_mises_load<2>, dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
-                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, disp_space->cell_dofs, u->d.p, mu, lambda, b->d.p);
+        hipLaunchKernelGGL((k_von_mises_load<2, CELL>), dim3(g), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p,
+                           p1_space->inc_cell.p, m->cells.p, m->xyz.p, disp_space->cell_dofs, u->d.p, mu, lambda, b->d.p, lc);
+}
+
+static int von_mises_check(fs_space_t disp_space, fs_vector_t u, fs_space_t p1_space, fs_vector_t b, const char* what) {
+    FS_REQUIRE(disp_space && u && p1_space && b, "%s: null pointer", what);
+    FS_REQUIRE(disp_space->mesh == p1_space->mesh, "%s: the two spaces live on different meshes", what);
+    FS_REQUIRE((disp_space->ncomp == 3 && disp_space->mesh->tdim == 3) || (disp_space->ncomp == 2 && disp_space->mesh->tdim == 2),
+               "%s: needs a 3-vector displacement space on tetrahedra or a 2-vector space on triangles", what);
+    FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1 && p1_space->inc_cell.p, "%s: the target is the scalar CG1 space of the mesh", what);
+    FS_REQUIRE(u->d.n >= disp_space->n_dofs_local && b->d.n >= p1_space->n_dofs_owned, "%s: vector too short", what);
+    return FS_OK;
+}
+
+extern "C" int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, double mu, double lambda, fs_space_t p1_space,
+                                     fs_vector_t b) {
+    FS_CHECK(von_mises_check(disp_space, u, p1_space, b, "fs_assemble_von_mises"));
+    von_mises_launch<false>(disp_space, u, mu, lambda, nullptr, p1_space, b);
     FS_KERNEL_CHECK();
-    FS_HIP(hipStreamSynchronize(s));
+    FS_HIP(hipStreamSynchronize(fs_rt().stream));
+    return FS_OK;
+}
+
+extern "C" int fs_assemble_von_mises_cells(fs_space_t disp_space, fs_vector_t u, const double* lame, fs_space_t p1_space,
+                                           fs_vector_t b) {
+    FS_CHECK(von_mises_check(disp_space, u, p1_space, b, "fs_assemble_von_mises_cells"));
+    FS_REQUIRE(lame, "fs_assemble_von_mises_cells: null (mu, lambda) array");
+    const int64_t nc = p1_space->mesh->nc;
+    dbuf<double> lstore;
+    FS_CHECK(lstore.alloc(2 * nc));
+    FS_CHECK(lstore.upload(lame, 2 * nc, fs_rt().stream));
+    von_mises_launch<true>(disp_space, u, 0.0, 0.0, reinterpret_cast<const double2*>(lstore.p), p1_space, b);
+    FS_KERNEL_CHECK();
+    FS_HIP(hipStreamSynchronize(fs_rt().stream));
     return FS_OK;
 }
 

@@ -123,24 +123,43 @@ class ElasticityForm:
 
     def __init__(self, space):
         self.space = space
-        self.mu = None
+        self.mu = None                # numbers (homogeneous) or arrays [n_cells] (per-cell material, host cell order)
         self.lmbda = None
         self.body_force = None        # (fx, fy, fz) or None
         self.body_force_nodal = None  # [n_nodes, dim]: a body force FIELD by its nodal values (consistent-mass load)
         self.tractions = []           # [FacetLoad] with vector g
-        self.thermal = None           # (coefficient E*alpha/(1-2nu), T nodal array or float, T_ref)
+        self.thermal = None           # (coefficient E*alpha/(1-2nu): number or array [n_cells], T nodal array or float, T_ref)
         self.load_sign = -1.0         # reference adds the load terms to F => rhs = -loads (Appendix B-Q3)
-        self.inertia = None           # (density, acceleration dof array): F -= rho a . v dx => rhs += rho M a (:216-220)
+        self.inertia = None           # (density: number or ('cell', array), acceleration dof array): rhs += rho M a (:216-220)
+
+    def cellwise(self):
+        return np.ndim(self.mu) > 0 or np.ndim(self.lmbda) > 0
+
+    def lame_spec(self):
+        """Lame argument of backend.DeviceMatrix.assemble: (mu, lambda), or ('cell', [n_cells, 2]) in host cell order."""
+        if not self.cellwise():
+            return (self.mu, self.lmbda)
+        n = max(np.size(self.mu), np.size(self.lmbda))
+        return ("cell", np.stack([np.broadcast_to(np.asarray(self.mu, dtype=np.float64), (n,)),
+                                  np.broadcast_to(np.asarray(self.lmbda, dtype=np.float64), (n,))], axis=1))
 
     def describe(self):
         return {
-            "type": "elasticity", "mu": self.mu, "lambda": self.lmbda,
+            "type": "elasticity", "mu": _material(self.mu), "lambda": _material(self.lmbda),
             "body_force": None if self.body_force is None else tuple(float(x) for x in self.body_force),
             "tractions": [(t.marker_id, _plain(t.g), t.origin) if isinstance(t, FacetLoad) else ("nodal", len(t.dofs), t.origin)
                           for t in self.tractions],
-            "thermal": None if self.thermal is None else (self.thermal[0], _plain(self.thermal[1]), self.thermal[2]),
+            "thermal": None if self.thermal is None else (_material(self.thermal[0]), _plain(self.thermal[1]), self.thermal[2]),
             "load_sign": self.load_sign,
         }
+
+
+def _material(v):
+    """A material value: the number itself, or a per-cell array by its shape and range."""
+    if np.ndim(v) == 0:
+        return v
+    a = np.asarray(v, dtype=np.float64)
+    return ("cell", a.shape, float(a.min()), float(a.max()))
 
 
 def _plain(v):

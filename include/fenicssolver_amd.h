@@ -233,6 +233,8 @@ int fs_matrix_destroy(fs_matrix_t A);
                            * conductivity that depends on the P2 temperature iterate, evaluated where the integrand is */
 #define FS_COEF_CELL_ROW 5 /* advection velocity only: data[n_cells][d+1][3], V_a = (d+1)/|K| int_K u phi_a dx per cell and test
                             * function - integrates inner(u, grad T) q dx exactly for a finite-element velocity u */
+#define FS_COEF_CELL_LAME 8 /* fs_bilinear_form.lame only: data[n_cells][2], one (mu, lambda) pair per cell in device cell order -
+                             * an isotropic material that varies from cell to cell (per-region E and nu) */
 
 typedef struct fs_coef {
     int mode;             /* FS_COEF_* */
@@ -245,7 +247,11 @@ typedef struct fs_coef {
  * (scalar space: ScalarTransportSolver.py:284-285 and the 1/dt capacity term
  * :292), or for a vector space the isotropic elasticity operator
  * int (2 mu sym grad u + lambda div u I) : grad v dx  (LinearElasticitySolver.py:62-69, 215)
- * plus  mass * u . v. */
+ * plus  mass * u . v.
+ * Lame parameters: with lame.mode == FS_COEF_NONE (what a zero-initialised struct holds) the constants lame_mu / lame_lambda;
+ * with lame.mode == FS_COEF_CELL_LAME, lame.data[n_cells][2] = (mu, lambda) per cell (host, device cell order) and lame_mu /
+ * lame_lambda are ignored.  Per-cell pairs that all hold the constants give the constant operator bit for bit.  The atomic
+ * P1 kernel (FS_ELASTICITY_ATOMIC) refuses per-cell pairs. */
 typedef struct fs_bilinear_form {
     fs_coef stiffness;   /* scalar spaces */
     fs_coef mass;        /* both */
@@ -261,6 +267,7 @@ typedef struct fs_bilinear_form {
      * (set advection_scale = 0 to get the mass part only, e.g. for the old-step operator).  CG1 and CG2 scalar spaces; on CG2 the
      * diffusion term changes too: grad(q + tau v . grad q) = grad q + tau H_q v with the cell-wise constant Hessian of q. */
     double supg_pe;
+    fs_coef lame;        /* vector spaces: FS_COEF_NONE (lame_mu / lame_lambda) or FS_COEF_CELL_LAME; appended last */
 } fs_bilinear_form;
 
 /* Replaces dolfin.assemble(a) / the matrix half of assemble_system: numeric
@@ -291,6 +298,8 @@ int fs_assemble_vector(fs_space_t space, const fs_linear_form* form, fs_vector_t
  * p1_space: scalar CG1 space on the SAME mesh.  The projection itself is fs_assemble_matrix(mass = 1) on p1_space +
  * fs_krylov_solve.  CG1 displacement: exact; CG2: 4-point degree-2 rule. */
 int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, double mu, double lambda, fs_space_t p1_space, fs_vector_t b);
+/* The same with one (mu, lambda) pair per cell: lame[n_cells][2] (host, device cell order). */
+int fs_assemble_von_mises_cells(fs_space_t disp_space, fs_vector_t u, const double* lame, fs_space_t p1_space, fs_vector_t b);
 
 /* Right-hand sides of the L2 projection of the fluid stress  nu (grad u + grad u^T) - p I  onto CG1
  * (CoupledNavierStokesSolver.py:149-155, viscous_stress): b[vertex*9 + 3 i + j] = int sigma_ij phi_vertex dx for a
