@@ -6,10 +6,14 @@ vector_name='displacement', :55-60), sigma(u) = 2 mu sym(grad u) + lambda div(u)
 :122-131), force / pressure / stress (:165-196), body force (:227-228), thermal stress
 (:78-85, 231-238); 3D problems go through solve_amg (CG), as in the reference (:247-253).
 
+Modal analysis (solve_modal / solve_modal_form, :270-312): the lowest modes of K phi = lambda M phi with the consistent mass
+M = int rho phi . psi dx, by LOBPCG on the device (fs_eigen_solve; AMG-preconditioned in 3D, Jacobi in 2D).  The reference's
+stub asks SLEPc for the largest eigenvalue of K alone, a mesh-scale number of no engineering use.
+
 Reference quirk kept by default (Appendix B-Q3): body forces and tractions are ADDED to
 F (:227-228, 242-243), so they act with reversed sign; set
 ``solver.reference_load_sign = False`` for the physical convention.  The thermal term has
-the conventional sign in both.  Modal analysis (:270-312, SLEPc) is out of scope.
+the conventional sign in both.
 
 Vector P2 (the reference's own example, examples/test_linear_elasticity.py:105-106) runs on one GPU; its solve_amg uses
 Jacobi-CG (the aggregation hierarchy is built on P1 node patterns).  ``von_Mises`` is the consistent L2 projection onto P1,
@@ -198,8 +202,79 @@ class LinearElasticitySolver(SolverBase):
         raise SolverError("strain_energy: the reference's expression (LinearElasticitySolver.py:87-93) uses an undefined "
                           "symbol and '^' on UFL objects; nothing to reproduce")
 
+    _MODAL_DEFAULTS = {'number_of_modes': 6, 'tolerance': 1e-8, 'max_iterations': 500, 'shift': 0.0}
+
+    def modal_settings(self):
+        """settings['solver_settings']['modal_settings'] with its defaults, checked (SolverError on a bad value)."""
+        given = self.solver_settings.get('modal_settings') or {}
+        unknown = set(given) - set(self._MODAL_DEFAULTS)
+        if unknown:
+            raise SolverError('modal_settings: unknown key(s) {}'.format(sorted(unknown)))
+        ms = dict(self._MODAL_DEFAULTS, **given)
+        nm = ms['number_of_modes']
+        if isinstance(nm, bool) or not isinstance(nm, numbers.Integral) or not 1 <= nm <= 32:
+            raise SolverError('modal_settings: number_of_modes must be an integer in 1..32, got {!r}'.format(nm))
+        for key, low in (('tolerance', 0.0), ('max_iterations', 0)):
+            if isinstance(ms[key], bool) or not isinstance(ms[key], numbers.Real) or not ms[key] > low:
+                raise SolverError('modal_settings: {} must be positive, got {!r}'.format(key, ms[key]))
+        if isinstance(ms['shift'], bool) or not isinstance(ms['shift'], numbers.Real) or not ms['shift'] >= 0.0:
+            raise SolverError('modal_settings: shift must be a number >= 0, got {!r}'.format(ms['shift']))
+        return {'number_of_modes': int(nm), 'tolerance': float(ms['tolerance']), 'max_iterations': int(ms['max_iterations']),
+                'shift': float(ms['shift'])}
+
     def solve_modal_form(self, F, bcs):
-        raise SolverError("modal analysis (SLEPc eigen-solver, LinearElasticitySolver.py:283-310) is not built")
+        """The lowest natural modes of the form's stiffness and the consistent mass, the displacement BCs' dofs constrained (their
+        prescribed values and every load are ignored).  Sets self.eigenvalues (ascending, rad^2/s^2), self.natural_frequencies (Hz)
+        and self.modes (M-normalised Functions); returns mode 1."""
+        from . import backend, parallel
+        ms = self.modal_settings()
+        if parallel.world()[1] > 1 or F.space.localizer() is not None:
+            raise SolverError('modal analysis runs on one rank')
+        if hasattr(F.space, 'periodic_pairs') and F.space.periodic_pairs() is not None:
+            raise SolverError('modal analysis on a periodic space is not supported')
+        dofs, vals = self._bc_arrays(bcs)
+        constrained = np.unique(dofs)
+        nm, shift = ms['number_of_modes'], ms['shift']
+        n_free = F.space.dim() - constrained.size
+        if nm >= n_free:
+            raise SolverError('modal_settings: {} modes asked of a space with {} free dofs'.format(nm, n_free))
+        if constrained.size == 0 and shift <= 0.0:
+            raise SolverError('modal analysis of a free-free part (no displacement BC) needs modal_settings shift > 0')
+        if np.any(vals != 0.0):
+            self.logger.info('solve_modal: prescribed displacements are ignored, their dofs are held at zero')
+        rho = self.material_field('density')
+        rho_spec = float(rho) if np.ndim(rho) == 0 else ('cell', np.asarray(rho, dtype=np.float64))
+        shifted = None if shift == 0.0 else (shift * rho_spec if np.ndim(rho) == 0 else ('cell', shift * rho_spec[1]))
+        V = F.space.device()
+        K = backend.DeviceMatrix(V)
+        K.assemble(lame=F.lame_spec(), mass=shifted)              # K + shift M: one form
+        M = backend.DeviceMatrix(V)
+        M.assemble(lame=(0.0, 0.0), mass=rho_spec)
+        if constrained.size:
+            K.apply_dirichlet(None, constrained, np.zeros(constrained.size), symmetric=True)
+        amg = None
+        if self.dimension == 3:
+            amg, _ = self._amg_hierarchy(K, None, "rigid_body")
+        try:
+            lam, modes, st = backend.eigen_solve(K, M, nm, amg=amg, constrained=constrained, tol=ms['tolerance'],
+                                                 max_iter=ms['max_iterations'], shift=shift)
+        finally:
+            if amg is not None:
+                amg.close()
+        self.modal_stats = st
+        if st['n_converged'] < nm:
+            raise SolverError('solve_modal: {} of {} modes converged in {} iterations (largest relative residual {:.3e})'.format(
+                st['n_converged'], nm, st['iterations'], st['max_rel_residual']))
+        self.eigenvalues = np.asarray(lam, dtype=np.float64)
+        self.natural_frequencies = np.sqrt(np.maximum(self.eigenvalues, 0.0)) / (2.0 * np.pi)
+        self.modes = []
+        for x in modes:
+            f = Function(self.function_space)
+            f.vector().set_local(x.get()[:V.n_owned])
+            self.modes.append(f)
+        self.logger.info('solve_modal: %d modes in %d iterations, %.1f ms, f = %s Hz', nm, st['iterations'], st['solve_ms'],
+                         np.array2string(self.natural_frequencies, precision=5))
+        return self.modes[0]
 
     def get_flux(self, u, mag_vector):
         return mag_vector
@@ -442,4 +517,8 @@ class LinearElasticitySolver(SolverBase):
         return out
 
     def solve_modal(self):
-        raise SolverError('modal analysis (SLEPc) is out of scope of the GPU back end')
+        """Modal analysis of the case (LinearElasticitySolver.py:270-281): the form of step 0, then solve_modal_form."""
+        self.modal_settings()
+        self.init_solver()
+        F, bcs = self.generate_form(0, None, None, self.w_current, self.w_prev)
+        return self.solve_modal_form(F, bcs)

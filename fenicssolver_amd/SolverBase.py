@@ -403,17 +403,7 @@ class SolverBase():
             # at configs[2] the set-up (0.15 s) costs more than the solve (0.12 s).  The key holds everything the matrix
             # values depend on; the cached hierarchy keeps its own (identical) fine matrix alive.
             key = operator_key
-            cached = getattr(self, '_amg_cache', None)
-            if key is not None and cached is not None and cached[0] == key:
-                hierarchy, reused = cached[1], True
-            else:
-                if cached is not None:
-                    cached[1].close()
-                    self._amg_cache = None
-                hierarchy, reused = backend.AMG(A, nullspace=near_nullspace,
-                                                strength_threshold=float(sp_.get('amg_strength_threshold', 0.0))), False
-                if key is not None:
-                    self._amg_cache = (key, hierarchy)
+            hierarchy, reused = self._amg_hierarchy(A, key, near_nullspace)
             stats = hierarchy.solve(b, x, rtol=rtol, max_iter=min(max_iter, int(sp_.get('maximum_iterations', 500))),
                                     norm=norm)
             stats.update({'amg_' + k: v for k, v in hierarchy.info().items()})
@@ -461,6 +451,22 @@ class SolverBase():
             ncomp = u.function_space()._ncomp
             u.vector().set_local(parallel.gather_owned(x.get()[:V.n_owned], loc.owned_gids(), loc.n_global, ncomp))
         return u
+
+    def _amg_hierarchy(self, A, key, near_nullspace):
+        """(hierarchy, reused): the smoothed-aggregation hierarchy of A, kept while the next caller names the same operator key;
+        a caller with key None owns (and closes) the hierarchy it gets."""
+        from . import backend
+        sp_ = self.solver_settings.get('solver_parameters', {}) or {}
+        cached = getattr(self, '_amg_cache', None)
+        if key is not None and cached is not None and cached[0] == key:
+            return cached[1], True
+        if cached is not None:
+            cached[1].close()
+            self._amg_cache = None
+        hierarchy = backend.AMG(A, nullspace=near_nullspace, strength_threshold=float(sp_.get('amg_strength_threshold', 0.0)))
+        if key is not None:
+            self._amg_cache = (key, hierarchy)
+        return hierarchy, False
 
     def _replicated_amg_solve(self, b, x, V, loc, ncomp, global_operator, key, near_nullspace, rtol, max_iter, norm, theta, A_local=None):
         """solve_amg on several GPUs.  A hierarchy of the rank-local diagonal blocks (additive Schwarz) has no coarse space that

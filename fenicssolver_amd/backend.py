@@ -701,6 +701,43 @@ class AMG(_Handle):
         return {k: getattr(st, k) for k, _ in L.fs_krylov_stats._fields_}
 
 
+def _handles(vectors):
+    arr = (C.c_void_p * len(vectors))()
+    for i, v in enumerate(vectors):
+        arr[i] = v.h.value
+    return arr
+
+
+def spmv_multi(A, X, Y):
+    """Y[j] = A X[j] for every column in one pass over A's values per chunk of columns (vector spaces of 2 or 3 components);
+    each Y[j] equals A.spmv(X[j], Y[j]) bit for bit."""
+    if len(X) != len(Y) or not X:
+        raise ValueError("spmv_multi: X and Y must be non-empty lists of one length")
+    L.check(L.load().fs_spmv_multi(A.h, len(X), _handles(X), _handles(Y)), "fs_spmv_multi")
+
+
+def gram(X, Y):
+    """G[i, j] = X[i] . Y[j] on the device (deterministic)."""
+    G = np.empty((len(X), len(Y)))
+    L.check(L.load().fs_vector_gram(len(X), _handles(X), len(Y), _handles(Y), L.p_f64(G)), "fs_vector_gram")
+    return G
+
+
+def eigen_solve(K, M, n_modes, amg=None, constrained=None, tol=1e-8, max_iter=500, shift=0.0, block=0, seed=2024):
+    """The n_modes smallest eigenpairs of K phi = lambda M phi on the dofs outside `constrained` (LOBPCG on the device, preconditioned
+    by one V-cycle of `amg` per column or by Jacobi).  K holds K + shift M when shift > 0; the eigenvalues returned are lambda.
+    Returns (eigenvalues [n_modes], modes [DeviceVector, M-orthonormal], stats dict)."""
+    o = L.fs_eigen_opts()
+    o.n_modes, o.block, o.tol, o.max_iter, o.shift, o.seed = int(n_modes), int(block), float(tol), int(max_iter), float(shift), int(seed)
+    cons = L.i32(np.zeros(0) if constrained is None else constrained).ravel()
+    modes = [DeviceVector(K.space.n_owned) for _ in range(int(n_modes))]
+    lam = np.empty(int(n_modes))
+    st = L.fs_eigen_stats()
+    L.check(L.load().fs_eigen_solve(K.h, M.h, amg.h if amg is not None else None, cons.size, L.p_i32(cons) if cons.size else None,
+                                    C.byref(o), L.p_f64(lam), _handles(modes), C.byref(st)), "fs_eigen_solve")
+    return lam, modes, {k: getattr(st, k) for k, _ in L.fs_eigen_stats._fields_}
+
+
 def assemble_navier_stokes(J, g, w0, w_prev=None, nu=1.0, rho=1.0, inv_dt=0.0, body_force=(0.0, 0.0, 0.0),
                            convection=True, newton=True, mesh_velocity=(0.0, 0.0, 0.0), g2=None, viscosity_law=None):
     """Linearised Taylor-Hood system at the state w0 (J w_new = g), J on a DeviceSpace(mesh, ncomp=4, degree=2).

@@ -479,6 +479,44 @@ int fs_amg_apply(fs_amg_t amg, fs_vector_t r, fs_vector_t z);
  * uses rtol, atol, max_iter, nonzero_guess and norm_type of the options. */
 int fs_amg_solve(fs_amg_t amg, fs_vector_t b, fs_vector_t x, const fs_krylov_opts* opts, fs_krylov_stats* stats);
 
+/* ---- block eigensolver (SLEPcEigenSolver, LinearElasticitySolver.py:283-310) ---------------------------------------------
+ * Lowest modes of K phi = lambda M phi by LOBPCG; the reference asks SLEPc for its default (largest magnitude, K alone), this one for
+ * the n_modes smallest eigenvalues of the pencil on the free dofs ("differs from the reference").  One rank. */
+
+/* Y[j] = A X[j] for j < m (the MatMult of every column of the eigensolver's block, LinearElasticitySolver.py:283-310) in one pass over
+ * A's values per chunk of columns; block sizes 2 and 3.  Unmasked; each Y[j] equals fs_spmv(A, X[j], Y[j]) bit for bit. */
+int fs_spmv_multi(fs_matrix_t A, int m, const fs_vector_t* X, fs_vector_t* Y);
+
+/* G[i * q + j] = X[i] . Y[j] (the block inner products of SLEPc's BV, behind LinearElasticitySolver.py:283-310); all vectors of
+ * one length.  Deterministic: the same inputs give the same bits. */
+int fs_vector_gram(int p, const fs_vector_t* X, int q, const fs_vector_t* Y, double* G);
+
+typedef struct fs_eigen_opts {
+    int n_modes;         /* wanted eigenpairs, 1 .. 32 (SLEPcEigenSolver.solve(n), LinearElasticitySolver.py:298) */
+    int block;           /* block size m; 0 = min(2 n_modes, n_modes + 8); at most 40 */
+    double tol;          /* stop when every wanted column has ||K x - lambda M x||_2 <= tol lambda_shifted ||M x||_2 */
+    int max_iter;
+    double shift;        /* sigma >= 0: K holds K + sigma M; the eigenvalues returned are lambda - sigma */
+    uint64_t seed;       /* of the pseudo-random start block */
+} fs_eigen_opts;
+
+typedef struct fs_eigen_stats {
+    int iterations;
+    int n_converged;            /* wanted columns that met the test, on products recomputed from X */
+    double max_rel_residual;    /* largest relative residual of the wanted columns */
+    double solve_ms;            /* wall time (host clock, synchronised) */
+    double block_product_ms;    /* HIP events: block products with K and M */
+    double gram_ms;             /* ... Gram matrices (with their download) */
+    double precond_ms;          /* ... V-cycles or Jacobi */
+} fs_eigen_stats;
+
+/* SLEPcEigenSolver(K).solve (LinearElasticitySolver.py:283-310) for the pencil (K, M): K and M on one space, K Dirichlet-eliminated
+ * or not (constrained rows and columns are masked out), precond = an fs_amg_setup hierarchy of K or NULL (Jacobi).  constrained:
+ * the n_constrained dofs every mode is zero at.  eigenvalues[n_modes] ascending; modes[n_modes] (caller's vectors of >= n_dofs_owned
+ * entries) M-orthonormal. */
+int fs_eigen_solve(fs_matrix_t K, fs_matrix_t M, fs_amg_t precond, int64_t n_constrained, const int32_t* constrained,
+                   const fs_eigen_opts* opts, double* eigenvalues, fs_vector_t* modes, fs_eigen_stats* stats);
+
 /* ---- Taylor-Hood Navier-Stokes (CoupledNavierStokesSolver.py:288-381, 215-245, 492-528) -------------
  * Unknowns: one block (u_x, u_y, u_z, p) per CG2 node of fs_space_create(mesh, FS_FAMILY_CG, 2, 4); the
  * pressure is CG1, the pressure slot of an edge node is a dummy unknown with a unit row. */
