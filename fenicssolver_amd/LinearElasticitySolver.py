@@ -282,8 +282,11 @@ class LinearElasticitySolver(SolverBase):
     # ------------------------------------------------------------------ boundary conditions
     def _facet_normals(self, marker_id):
         """Outward unit normals and areas (lengths in 2-D) of the facets carrying marker_id."""
+        return self._normals_of_facets(self.boundary_facets.where(marker_id))
+
+    def _normals_of_facets(self, sel):
+        """(vertex lists, outward unit normals, areas) of the boundary facets mesh.facets()[sel]."""
         mesh = self.mesh
-        sel = self.boundary_facets.where(marker_id)
         tri = mesh.facets()[sel].astype(np.int64)
         co = mesh.coordinates()
         p = co[tri]
@@ -469,19 +472,7 @@ class LinearElasticitySolver(SolverBase):
         F.tractions.extend(integrals_F)
 
         if self.body_source:
-            bs = self.body_source
-            if isinstance(bs, Expression):
-                vals = bs.eval_points(self.mesh.coordinates()[:1])   # constant body force expected
-                allv = bs.eval_points(self.mesh.coordinates())
-                if np.abs(allv - vals).max() > 1e-12 * max(1.0, np.abs(allv).max()):
-                    # a field (e.g. a centrifugal load): its interpolant in the displacement space, integrated with the
-                    # consistent mass matrix - what FFC's quadrature gives for an Expression of the element's degree
-                    F.body_force_nodal = bs.eval_points(self.function_space.node_coordinates())[:, :self.dimension]
-                    F.body_force = None
-                else:
-                    F.body_force = tuple(float(x) for x in vals[0])
-            else:
-                F.body_force = tuple(float(x) for x in self._vector_of(bs, 'body_source'))
+            self._set_body_force(F)
 
         if not hasattr(self, 'temperature_distribution'):
             if 'temperature_distribution' in self.settings and self.settings['temperature_distribution']:
@@ -497,6 +488,22 @@ class LinearElasticitySolver(SolverBase):
                 Tval = float(nod[0]) if np.ptp(nod) == 0.0 else nod
             F.thermal = (self.thermal_stress_coefficient(), Tval, T_ref)
         return F, bcs
+
+    def _set_body_force(self, F):
+        """F.body_force (a constant vector) or F.body_force_nodal (a field) from self.body_source."""
+        bs = self.body_source
+        if isinstance(bs, Expression):
+            vals = bs.eval_points(self.mesh.coordinates()[:1])   # constant body force expected
+            allv = bs.eval_points(self.mesh.coordinates())
+            if np.abs(allv - vals).max() > 1e-12 * max(1.0, np.abs(allv).max()):
+                # a field (e.g. a centrifugal load): its interpolant in the displacement space, integrated with the
+                # consistent mass matrix - what FFC's quadrature gives for an Expression of the element's degree
+                F.body_force_nodal = bs.eval_points(self.function_space.node_coordinates())[:, :self.dimension]
+                F.body_force = None
+            else:
+                F.body_force = tuple(float(x) for x in vals[0])
+        else:
+            F.body_force = tuple(float(x) for x in self._vector_of(bs, 'body_source'))
 
     def solve_form(self, F, u_, bcs):
         if self.dimension == 3:

@@ -784,6 +784,8 @@ class SolverBase():
         from . import backend
         if isinstance(F, forms.NavierStokesForm):
             return self._navier_stokes_newton(F, u_current, Dirichlet_bcs)
+        if isinstance(F, forms.HyperelasticForm):
+            return self._hyperelastic_newton(F, u_current, Dirichlet_bcs)
         if not isinstance(F, forms.ScalarForm):
             raise SolverError('nonlinear solves are built for scalar transport and Navier-Stokes only')
         per = F.space.periodic_pairs()
@@ -892,6 +894,174 @@ class SolverBase():
             T = T + d
             self.newton_iterations = it + 1
         u_current.vector().set_local(T)
+        return u_current
+
+    # ---- hyperelasticity (NonlinearElasticitySolver) ------------------------------------------------
+    def _hyperelastic_external_loads(self, F, V, loc):
+        """f_ext = int B.v dx + the boundary loads (dead loads, physical sign) on the device: assembled once per load step."""
+        from . import backend
+        b = backend.DeviceVector(V.n_owned)
+        b.fill(0.0)
+        if F.body_force is not None:
+            backend.assemble_vector(V, b, vector_value=list(F.body_force))
+        if F.body_force_nodal is not None:
+            Mb = backend.DeviceMatrix(V)
+            Mb.assemble(lame=(0.0, 0.0), mass=1.0)
+            fh = np.ascontiguousarray(F.body_force_nodal, dtype=np.float64).reshape(-1)
+            fh = fh if loc is None else loc.nodes(fh)
+            fd = backend.DeviceVector(V.n_local, np.concatenate([fh, np.zeros(V.n_local - len(fh))]))
+            tmp = backend.DeviceVector(V.n_owned)
+            Mb.spmv(fd, tmp)
+            b.axpy(1.0, tmp)
+        # boundary loads: summed per dof on the host in a fixed order and added once per dof - the facet kernels scatter with atomics,
+        # whose order would make f_ext, and with it every Newton iterate, differ in the last bits from run to run
+        d = self.dimension
+        n_dofs = F.space.dim()
+        co = self.mesh.coordinates()[:, :d]
+        dof_l, val_l = [], []
+        for t in F.tractions:
+            if isinstance(t, forms.NodalLoad):
+                dof_l.append(np.asarray(t.dofs, dtype=np.int64))
+                val_l.append(np.asarray(t.values, dtype=np.float64))
+                continue
+            tri = np.asarray(self._facets_of(t.marker_id), dtype=np.int64)
+            if not len(tri):
+                continue
+            p = co[tri]
+            if tri.shape[1] == 2:                       # boundary edges of a triangle mesh
+                size = np.linalg.norm(p[:, 1] - p[:, 0], axis=1)
+            else:
+                size = 0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
+            g = np.broadcast_to(np.asarray(t.g, dtype=np.float64), (len(tri), d))
+            w = size / tri.shape[1]                     # int lambda_a ds = |facet| / (number of its vertices)
+            dof_l.append((tri[:, :, None] * d + np.arange(d)[None, None, :]).ravel())
+            val_l.append(np.broadcast_to((w[:, None] * g)[:, None, :], (len(tri), tri.shape[1], d)).ravel())
+        if dof_l:
+            total = np.bincount(np.concatenate(dof_l), weights=np.concatenate(val_l), minlength=n_dofs)
+            nd_ = np.nonzero(total)[0]
+            nv_ = total[nd_]
+            if loc is not None:
+                nd_, nv_ = loc.dofs(nd_, nv_)
+            if len(nd_):
+                b.add_entries(nd_, nv_)
+        return b
+
+    def _hyperelastic_newton(self, F, u_current, bcs):
+        """solve(F == 0, u, bcs, J=J) of NonlinearElasticitySolver (:90-98): Newton on r(u) = f_int(u) - f_ext = 0 with DOLFIN's
+        NewtonSolver defaults and stopping test (the norm of r with the Dirichlet rows zeroed, absolute 1e-10 / relative 1e-9,
+        50 iterations, relaxation 1).  The boundary values are imposed on the first iterate; every correction is zero on the
+        Dirichlet dofs.  Tangent, internal force and inverted cells are assembled on the device in one call per iterate
+        (fs_assemble_hyperelastic; the tangent of the converged iterate is the one unused assembly); each linear step is CG + AMG
+        (3-D, rigid-body near-null space, a hierarchy per tangent) or Jacobi-CG (2-D).  A trial iterate with an inverted cell
+        (J <= 0) or a non-finite residual is halved, at most 10 times."""
+        from . import backend, parallel
+        from .fem import Function
+        if parallel.world()[1] > 1:
+            raise SolverError('hyperelastic Newton solves run on one rank')
+        sp = self.solver_settings.get('solver_parameters', {}) or {}
+        newton = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
+        rtol = float(newton.get('relative_tolerance', 1e-9))
+        atol = float(newton.get('absolute_tolerance', 1e-10))
+        max_it = int(newton.get('maximum_iterations', 50))
+        relax = float(newton.get('relaxation_parameter', 1.0))
+        V = F.space.device()
+        loc = F.space.localizer()          # a mesh file uploaded in locality order: host arrays map through it
+
+        def to_dev(xh):
+            xd = xh if loc is None else loc.nodes(xh)
+            return np.concatenate([xd, np.zeros(V.n_local - len(xd))]) if len(xd) < V.n_local else xd
+
+        steps_hint = ('apply the load in steps: transient_settings with boundary values and loads that change from step to step '
+                      '(a per-step sequence or a callable of time - constant values repeat the full load at every step)')
+        gdofs, gvals = self._bc_arrays(bcs)
+        dofs = gdofs if loc is None else loc.dofs(gdofs, gvals)[0]
+        lame = F.lame_spec()
+        if F.cellwise() and loc is not None:
+            lame = ('cell', loc.cells(lame[1]))
+        f_ext = self._hyperelastic_external_loads(F, V, loc)
+        K = backend.DeviceMatrix(V)
+        r = backend.DeviceVector(V.n_owned)
+        ud = backend.DeviceVector(V.n_local)
+
+        def evaluate(xh):
+            """Tangent, internal force minus loads and inverted cells at xh in ONE call (a per-cell material is uploaded once per
+            iterate); (info, ||r|| with the Dirichlet rows zeroed) - None for a state with an inverted cell.  K and r then belong to
+            the last state evaluated: the tangent of a rejected trial is overwritten by the next one."""
+            ud.set(to_dev(xh))
+            info = backend.assemble_hyperelastic(V, ud, lame, K=K, r=r)
+            if info['n_inverted']:
+                return info, None
+            r.axpy(-1.0, f_ext)
+            if dofs.size:
+                backend.set_dirichlet_values(r, dofs, 0.0)
+            rn = float(np.sqrt(r.dot(r)))
+            return info, (rn if np.isfinite(rn) else None)
+
+        x = u_current.vector()._values().copy()
+        if gdofs.size:
+            x[gdofs] = gvals                                # the first iterate carries the boundary values
+        info, rnorm = evaluate(x)
+        if rnorm is None:
+            if info['n_inverted']:
+                raise SolverError('hyperelastic Newton: the initial iterate (previous solution with the boundary values imposed) inverts '
+                                  '{} cell(s), first cell {}: {}'.format(info['n_inverted'], info['first_inverted_cell'], steps_hint))
+            raise SolverError('hyperelastic Newton: the residual of the initial iterate is not finite')
+        r0 = rnorm
+        self.newton_iterations = 0
+        self.newton_history = [rnorm]
+        self.newton_stats = []
+        self.newton_steps = []                              # the step length taken at each iteration (relaxation, halvings)
+        du = Function(self.function_space)
+        for it in range(max_it + 1):
+            if sp.get('monitor_convergence'):
+                self.logger.info("Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = %.3e (tol = %.3e)",
+                                 it, rnorm, atol, rnorm / r0 if r0 > 0 else 0.0, rtol)
+            if rnorm < atol or (r0 > 0 and rnorm / r0 < rtol):
+                break
+            if it == max_it:
+                raise SolverError('Newton solver did not converge in {} iterations (residual {:.3e})'.format(max_it, rnorm))
+            rhs = backend.DeviceVector(V.n_owned)
+            rhs.axpy(-1.0, r)
+            if dofs.size:
+                K.apply_dirichlet(rhs, dofs, 0.0, symmetric=True)     # the correction is zero on the Dirichlet boundary
+            try:
+                if self.dimension == 3:
+                    self._device_solve(K, rhs, du, 'hyperelastic Newton step', amg=True, near_nullspace="rigid_body", operator_key=None)
+                else:
+                    self._device_solve(K, rhs, du, 'hyperelastic Newton step')
+            except (SolverError, backend.BackendError) as e:
+                st = self.last_solve_stats or {}
+                if isinstance(e, backend.BackendError) and getattr(e, 'rc', None) == -6 or \
+                        (isinstance(e, SolverError) and st.get('converged', 0) < 0):      # FS_ERR_NUMERIC: CG breakdown
+                    raise SolverError('hyperelastic Newton: CG broke down at iteration {} - the tangent is not positive definite there '
+                                      '(a material instability, or a load step too large: {})'.format(it, steps_hint)) from e
+                raise
+            st = self.last_solve_stats
+            self.newton_stats.append({'krylov_iterations': st['iterations'], 'solve_ms': st['solve_ms'],
+                                      'amg_setup_ms': st.get('amg_setup_ms', 0.0)})
+            d = du.vector()._values()
+            if not np.all(np.isfinite(d)):
+                raise SolverError('hyperelastic Newton: the correction of iteration {} is not finite'.format(it))
+            step = relax
+            for cut in range(11):
+                x_try = x + step * d
+                info, rn_try = evaluate(x_try)
+                if rn_try is not None:
+                    break
+                if cut == 10:
+                    what = ('inverts {} cell(s), first cell {}'.format(info['n_inverted'], info['first_inverted_cell'])
+                            if info['n_inverted'] else 'gives a non-finite residual')
+                    raise SolverError('hyperelastic Newton: at iteration {} the step, halved 10 times, still {}: {}'.format(
+                        it, what, steps_hint))
+                step *= 0.5
+            if step != relax:
+                self.logger.info('hyperelastic Newton: step of iteration %d cut to %g (inverted cells at the full step)', it, step)
+            x = x_try
+            rnorm = rn_try
+            self.newton_steps.append(step)
+            self.newton_history.append(rnorm)
+            self.newton_iterations = it + 1
+        u_current.vector().set_local(x)
         return u_current
 
     # ---- Taylor-Hood Navier-Stokes (CoupledNavierStokesSolver) -----------------------------------------

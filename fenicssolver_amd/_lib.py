@@ -19,6 +19,8 @@ FS_OK = 0
 FS_ERR_COMM, FS_ERR_NUMERIC, FS_ERR_P2P_TIMEOUT = -5, -6, -7      # include/fenicssolver_amd.h
 FS_COEF_NONE, FS_COEF_CONST, FS_COEF_CELL, FS_COEF_TENSOR, FS_COEF_NODAL, FS_COEF_CELL_ROW, FS_COEF_CELL_TENSOR, FS_COEF_CELL_QP = 0, 1, 2, 3, 4, 5, 6, 7
 FS_COEF_CELL_LAME = 8
+FS_HYPER_NEO_HOOKEAN = 0
+FS_HYPER_TANGENT, FS_HYPER_FORCE, FS_HYPER_ENERGY = 1, 2, 4
 FS_KSP_CG = 0
 FS_KSP_BICGSTAB = 1
 FS_PC_NONE, FS_PC_JACOBI = 0, 1
@@ -48,6 +50,14 @@ class fs_bilinear_form(C.Structure):
 class fs_linear_form(C.Structure):
     _fields_ = [("source", fs_coef), ("vector_value", C.c_double * 3), ("div_coef", fs_coef), ("supg_velocity", fs_coef),
                 ("supg_pe", C.c_double)]
+
+
+class fs_hyper_form(C.Structure):
+    _fields_ = [("model", C.c_int), ("mu", C.c_double), ("lambda_", C.c_double), ("lame", fs_coef), ("add", C.c_int)]
+
+
+class fs_hyper_info(C.Structure):
+    _fields_ = [("energy", C.c_double), ("n_inverted", C.c_int64), ("first_inverted_cell", C.c_int64)]
 
 
 class fs_krylov_opts(C.Structure):
@@ -174,6 +184,7 @@ SIGNATURES = {
     "fs_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_char_p]),
     "fs_assemble_von_mises": (C.c_int, [_H, _H, C.c_double, C.c_double, _H, _H]),
     "fs_assemble_von_mises_cells": (C.c_int, [_H, _H, c_f64p, _H, _H]),
+    "fs_assemble_hyperelastic": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_hyper_form), C.c_int, C.POINTER(fs_hyper_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),
     "fs_comm_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -528,6 +528,28 @@ def assemble_von_mises(disp_space, u, mu, lmbda, p1_space, b):
     L.check(L.load().fs_assemble_von_mises(disp_space.h, u.h, float(mu), float(lmbda), p1_space.h, b.h), "fs_assemble_von_mises")
 
 
+def assemble_hyperelastic(space, u, lame, K=None, r=None, energy=False, add=False):
+    """Neo-Hookean tangent K, internal force r and energy at the displacement u (DeviceVector of the space's dofs) on a vector CG1
+    space (fs_assemble_hyperelastic).  lame: (mu, lambda) numbers or ('cell', array[n_cells, 2]) in device cell order.  K / r: the
+    DeviceMatrix / DeviceVector to fill (None: not computed).  Returns {'energy', 'n_inverted', 'first_inverted_cell'}; the
+    energy is computed only with energy=True (0.0 otherwise)."""
+    keep = []
+    f = L.fs_hyper_form()
+    f.model = L.FS_HYPER_NEO_HOOKEAN
+    if _is_cell_lame(lame):
+        f.lame.mode = L.FS_COEF_CELL_LAME
+        f.lame.data = L.p_f64(_lame_cells(lame, keep, space.mesh.info()[1]))
+    else:
+        f.mu, f.lambda_ = float(lame[0]), float(lame[1])
+    f.add = 1 if add else 0
+    what = (L.FS_HYPER_TANGENT if K is not None else 0) | (L.FS_HYPER_FORCE if r is not None else 0) | (L.FS_HYPER_ENERGY if energy else 0)
+    info = L.fs_hyper_info()
+    L.check(L.load().fs_assemble_hyperelastic(space.h, K.h if K is not None else None, r.h if r is not None else None, u.h,
+                                              C.byref(f), int(what), C.byref(info)), "fs_assemble_hyperelastic")
+    return {"energy": info.energy if energy else 0.0, "n_inverted": int(info.n_inverted),
+            "first_inverted_cell": int(info.first_inverted_cell)}
+
+
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):
     """b[vertex*9 + 3i + j] = int (nu (grad u + grad u^T) - p I)_ij phi_vertex dx for a Taylor-Hood iterate w.
     viscosity_law = (p_ref, exponent): nu (p / p_ref)^exponent."""

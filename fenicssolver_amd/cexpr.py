@@ -26,6 +26,8 @@ FUNCTIONS = {
     "asin": np.arcsin, "acos": np.arccos, "sinh": np.sinh, "cosh": np.cosh, "tanh": np.tanh,
     "floor": np.floor, "ceil": np.ceil, "fmin": np.minimum, "fmax": np.maximum, "min": np.minimum, "max": np.maximum,
     "erf": np.vectorize(math.erf, otypes=[float]),
+    # dolfin's near(x, x0[, eps]) = |x - x0| < eps (the CompiledSubDomain predicates)
+    "near": lambda a, b, eps=DOLFIN_EPS: (np.abs(a - b) < eps).astype(np.int64),
 }
 CONSTANTS = {"pi": math.pi, "DOLFIN_PI": math.pi, "M_PI": math.pi, "DOLFIN_EPS": DOLFIN_EPS}
 
@@ -161,7 +163,10 @@ def _eval(node, x, names):
     if kind == "name":
         name = node[1]
         if name in names:
-            return float(names[name]), False          # DOLFIN declares every user parameter as a double member
+            v = names[name]
+            if isinstance(v, np.ndarray):             # a per-point value (CompiledSubDomain's on_boundary)
+                return v, False
+            return float(v), False                    # DOLFIN declares every user parameter as a double member
         if name in CONSTANTS:
             return CONSTANTS[name], False
         raise CExprError("unknown name '%s' (parameters: %s)" % (name, ", ".join(sorted(names)) or "none"))
@@ -222,7 +227,8 @@ class CExpr:
         self.src = src
         self.tree = _Parser(src).parse()
 
-    def __call__(self, pts, params=None):
+    def __call__(self, pts, params=None, point_values=None):
+        """point_values: names bound to one value per point (arrays [n])."""
         pts = np.asarray(pts, dtype=np.float64)
         names = {}
         for k, v in (params or {}).items():
@@ -230,5 +236,7 @@ class CExpr:
                 names[k] = v
             elif hasattr(v, "__float__"):
                 names[k] = float(v)
+        for k, v in (point_values or {}).items():
+            names[k] = np.asarray(v, dtype=np.float64)
         v, _ = _eval(self.tree, (pts[:, 0], pts[:, 1], pts[:, 2]), names)
         return np.broadcast_to(np.asarray(v, dtype=np.float64), (pts.shape[0],)).copy()

@@ -9,6 +9,7 @@
 // slot column, hardware fp64 atomics (global_atomic_add_f64) for the scatter.
 #include "fs_common.h"
 #include "fs_kernels.h"
+#include "fs_p1_geometry.h"
 
 __device__ __forceinline__ int fs_find_pos_local(const int32_t* __restrict__ sell_col, int64_t base_lane, int width, int32_t target) {
     for (int k = 0; k < width; ++k)
@@ -16,58 +17,11 @@ __device__ __forceinline__ int fs_find_pos_local(const int32_t* __restrict__ sel
     return -1;
 }
 
-// ---- P1 geometry ---------------------------------------------------------------------------
-struct tet_geom {
-    double g[4][3];  // gradients of the barycentric basis
-    double adet;     // |det J|
-};
-
-// 16 + 8 bytes: the pad of the 32-byte record is not fetched (the gather kernels are bound by the bytes their lanes pull
-// through the per-CU address path, not by HBM)
-__device__ __forceinline__ void load_vertex(const double* __restrict__ xyz4, int32_t v, double (&x)[3]) {
-    const double2 a = reinterpret_cast<const double2*>(xyz4)[2 * (int64_t)v];
-    x[0] = a.x; x[1] = a.y; x[2] = xyz4[4 * (int64_t)v + 2];
-}
-
-__device__ __forceinline__ tet_geom tet_geometry_x(const double (&x0)[3], const double (&x1)[3], const double (&x2)[3],
-                                                   const double (&x3)[3]);
-__device__ __forceinline__ tet_geom tet_geometry(const double* __restrict__ xyz4, const int32_t (&v)[4]) {
-    double x0[3], x1[3], x2[3], x3[3];
-    load_vertex(xyz4, v[0], x0);
-    load_vertex(xyz4, v[1], x1);
-    load_vertex(xyz4, v[2], x2);
-    load_vertex(xyz4, v[3], x3);
-    return tet_geometry_x(x0, x1, x2, x3);
-}
-// snap: grid spacing of a uniform box mesh and its reciprocal (fs_mesh_s::box_h; 0 = general mesh).  An edge-vector component of a
-// box cell is -h, 0 or +h up to the rounding of the two coordinates it is the difference of; h * rint(e / h) removes exactly that
-// noise, so every cell of the same Kuhn type yields the same bits wherever it sits.
-struct box_snap { double h[3], inv[3]; };
-__device__ __forceinline__ tet_geom tet_geometry_e(const double (&e1)[3], const double (&e2)[3], const double (&e3)[3]);
-__device__ __forceinline__ tet_geom tet_geometry_x(const double (&x0)[3], const double (&x1)[3], const double (&x2)[3],
-                                                   const double (&x3)[3]) {
-    const double e1[3] = {x1[0] - x0[0], x1[1] - x0[1], x1[2] - x0[2]};
-    const double e2[3] = {x2[0] - x0[0], x2[1] - x0[1], x2[2] - x0[2]};
-    const double e3[3] = {x3[0] - x0[0], x3[1] - x0[1], x3[2] - x0[2]};
-    return tet_geometry_e(e1, e2, e3);
-}
-__device__ __forceinline__ tet_geom tet_geometry_snapped(const double (&x0)[3], const double (&x1)[3], const double (&x2)[3],
-                                                         const double (&x3)[3], const box_snap& bx) {
-    double e1[3], e2[3], e3[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        e1[d] = bx.h[d] * rint((x1[d] - x0[d]) * bx.inv[d]);
-        e2[d] = bx.h[d] * rint((x2[d] - x0[d]) * bx.inv[d]);
-        e3[d] = bx.h[d] * rint((x3[d] - x0[d]) * bx.inv[d]);
-    }
-    return tet_geometry_e(e1, e2, e3);
-}
-__device__ __forceinline__ tet_geom tet_geometry_box(const double* __restrict__ xyz4, const int32_t (&v)[4], const box_snap& bx);
 static int g_box_snap = -1;          // -1: not set (environment FS_BOX_SNAP, default on)
 void fs_set_box_snap(bool on) { g_box_snap = on; }
 static int g_box_assembly = -1;      // -1: not set (environment FS_BOX_ASSEMBLY, default on): option "box_assembly"
 void fs_set_box_assembly(bool on) { g_box_assembly = on; }
-static box_snap make_box_snap(const fs_mesh_s* m) {
+box_snap make_box_snap(const fs_mesh_s* m) {
     static const bool env_off = getenv("FS_BOX_SNAP") && getenv("FS_BOX_SNAP")[0] == '0';
     const bool off = g_box_snap < 0 ? env_off : g_box_snap == 0;
     box_snap b;
@@ -77,34 +31,6 @@ static box_snap make_box_snap(const fs_mesh_s* m) {
         b.inv[d] = on ? 1.0 / m->box_h[d] : 0.0;
     }
     return b;
-}
-__device__ __forceinline__ tet_geom tet_geometry_e(const double (&e1)[3], const double (&e2)[3], const double (&e3)[3]) {
-    // cofactors: grad lambda_1 = (e2 x e3)/det, grad lambda_2 = (e3 x e1)/det, grad lambda_3 = (e1 x e2)/det
-    const double c1[3] = {e2[1] * e3[2] - e2[2] * e3[1], e2[2] * e3[0] - e2[0] * e3[2], e2[0] * e3[1] - e2[1] * e3[0]};
-    const double c2[3] = {e3[1] * e1[2] - e3[2] * e1[1], e3[2] * e1[0] - e3[0] * e1[2], e3[0] * e1[1] - e3[1] * e1[0]};
-    const double c3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-    const double det = e1[0] * c1[0] + e1[1] * c1[1] + e1[2] * c1[2];
-    const double inv = 1.0 / det;
-    tet_geom t;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        t.g[1][d] = c1[d] * inv;
-        t.g[2][d] = c2[d] * inv;
-        t.g[3][d] = c3[d] * inv;
-        t.g[0][d] = -(t.g[1][d] + t.g[2][d] + t.g[3][d]);
-    }
-    t.adet = fabs(det);
-    return t;
-}
-
-// general mesh: the plain geometry; uniform box (bx.h > 0): edge vectors snapped to the grid spacing
-__device__ __forceinline__ tet_geom tet_geometry_box(const double* __restrict__ xyz4, const int32_t (&v)[4], const box_snap& bx) {
-    double x0[3], x1[3], x2[3], x3[3];
-    load_vertex(xyz4, v[0], x0);
-    load_vertex(xyz4, v[1], x1);
-    load_vertex(xyz4, v[2], x2);
-    load_vertex(xyz4, v[3], x3);
-    return bx.h[0] > 0.0 ? tet_geometry_snapped(x0, x1, x2, x3, bx) : tet_geometry_x(x0, x1, x2, x3);
 }
 
 // SUPG parameter of a cell (ScalarTransportSolver.py:262-266): tau = 0.5 h / (4/(Pe h) + 2 |v|), h = 2 R with R the
@@ -1285,25 +1211,6 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p2_vector_source_gather(i
 
 // ---- 2-D: CG1 on triangles ------------------------------------------------------------------------
 // (the reference's runnable examples are 2-D: examples/test_heat_transfer.py:34, test_electrostatics.py:35)
-struct tri_geom {
-    double g[3][2];   // gradients of the barycentric basis
-    double area;
-};
-__device__ __forceinline__ tri_geom tri_geometry2(const double* __restrict__ xyz4, int32_t a, int32_t b, int32_t c) {
-    const double2 p0 = reinterpret_cast<const double2*>(xyz4)[2 * (int64_t)a];
-    const double2 p1 = reinterpret_cast<const double2*>(xyz4)[2 * (int64_t)b];
-    const double2 p2 = reinterpret_cast<const double2*>(xyz4)[2 * (int64_t)c];
-    const double e1x = p1.x - p0.x, e1y = p1.y - p0.y, e2x = p2.x - p0.x, e2y = p2.y - p0.y;
-    const double det = e1x * e2y - e1y * e2x;
-    const double inv = 1.0 / det;
-    tri_geom t;
-    t.g[1][0] = e2y * inv;  t.g[1][1] = -e2x * inv;
-    t.g[2][0] = -e1y * inv; t.g[2][1] = e1x * inv;
-    t.g[0][0] = -(t.g[1][0] + t.g[2][0]);
-    t.g[0][1] = -(t.g[1][1] + t.g[2][1]);
-    t.area = 0.5 * fabs(det);
-    return t;
-}
 
 // SUPG parameter on a triangle: tau = 0.5 h / (4/(Pe h) + 2 |v|), h = 2 Circumradius = a b c / (2 A)
 __device__ __forceinline__ double supg_tau_tri(const double* __restrict__ xyz4, int32_t v0, int32_t v1, int32_t v2, double area,

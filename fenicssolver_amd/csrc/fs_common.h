@@ -153,6 +153,9 @@ struct fs_mesh_s {
     dbuf<double> box_ref;
     // the same for CG2 (k_assemble_p2_box_gather): [6 types][10 local dofs][11] = (volume, the row's ten quadrature sums of grad phi_a . grad phi_b)
     dbuf<double> box_ref2;
+    // meshes built in locality order (fs_mesh_create_renumbered): cell_order[c] = the caller's number of device cell c; empty:
+    // the device numbers the cells as the caller did
+    std::vector<int32_t> cell_order;
 };
 
 // Peer-to-peer ghost refresh (opt-in, one node): every rank owns a fine-grained receive buffer + arrival flags that its

@@ -1,0 +1,517 @@
+// Compressible neo-Hookean hyperelasticity on vector CG1 spaces (tetrahedra, and triangles in plane strain): the tangent
+// stiffness, the internal force and the stored energy at a displaced state, on the device.
+//
+// Stands in for the two UFL derivatives of FenicsSolver/NonlinearElasticitySolver.py:41-98 that solve(F == 0, u, bcs, J=J)
+// assembles at every Newton iterate:
+//   F = I + grad u,  J = det F,  psi = mu/2 (tr F^T F - 3) - mu ln J + lambda/2 (ln J)^2,
+//   P = d psi / dF = mu (F - F^-T) + lambda ln J F^-T.
+// A P1 displacement has a constant gradient per cell, so every integrand is constant per cell.  With g_a the reference gradients
+// of the barycentric functions, V the cell volume (area) and G_a = F^-T g_a:
+//   internal force   f_a = V P g_a
+//   tangent block    K_ab[i][k] = V (lambda G_a[i] G_b[k] + (mu - lambda ln J) G_a[k] G_b[i] + delta_ik mu g_a . g_b)
+// At u = 0, G = g and ln J = 0 exactly, and the block is the expression of the linear operator (k_assemble_p1_elasticity_gather,
+// k_assemble_tri_elasticity_gather) term for term: the two operators agree bit for bit there.
+//
+// Kernels (no atomics anywhere: two assemblies of one state give the same bits):
+//   k_hyper_tangent_gather / k_hyper_tangent_tri_gather  one thread per STORED block sums its (cell, a, b) sources of the inverse
+//       slot table in ascending order, as the linear gather does, and rebuilds F, F^-1 and ln J of the source cell: 4 vertex
+//       records (24 B) + 4 displacements (24 B) + the 16-B cell record per source, about 400 fp64 flops.
+//   k_hyper_force_gather / k_hyper_force_tri_gather      one thread per owned node over the sources of its diagonal block (the
+//       cells around the node, ascending), P g_a per cell.
+//   k_hyper_cells + k_hyper_cells_finish                 energy V psi per cell and the cells with J <= 0 (or not finite): per-
+//       workgroup partials, then one fixed-order sum.
+#include "fs_common.h"
+#include "fs_kernels.h"
+#include "fs_p1_geometry.h"
+#include <math.h>
+
+#define FS_HYPER_CELL_BLOCKS 1024      // workgroups of the per-cell pass (its partials are summed in this order)
+
+// ---- kinematics ----------------------------------------------------------------------------------------------------------
+// F = I + sum_a u_a g_a^T, its cofactor matrix (F^-T = cof / J) and J
+__device__ __forceinline__ void hyper_kin3(const tet_geom& t, const double (&uv)[4][3], double (&F)[3][3], double (&FiT)[3][3],
+                                           double& J) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            F[i][j] = (i == j ? 1.0 : 0.0) + (((uv[0][i] * t.g[0][j] + uv[1][i] * t.g[1][j]) + uv[2][i] * t.g[2][j]) + uv[3][i] * t.g[3][j]);
+    double c[3][3];
+    c[0][0] = F[1][1] * F[2][2] - F[1][2] * F[2][1];
+    c[0][1] = F[1][2] * F[2][0] - F[1][0] * F[2][2];
+    c[0][2] = F[1][0] * F[2][1] - F[1][1] * F[2][0];
+    c[1][0] = F[0][2] * F[2][1] - F[0][1] * F[2][2];
+    c[1][1] = F[0][0] * F[2][2] - F[0][2] * F[2][0];
+    c[1][2] = F[0][1] * F[2][0] - F[0][0] * F[2][1];
+    c[2][0] = F[0][1] * F[1][2] - F[0][2] * F[1][1];
+    c[2][1] = F[0][2] * F[1][0] - F[0][0] * F[1][2];
+    c[2][2] = F[0][0] * F[1][1] - F[0][1] * F[1][0];
+    J = F[0][0] * c[0][0] + F[0][1] * c[0][1] + F[0][2] * c[0][2];
+    const double inv = 1.0 / J;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) FiT[i][j] = c[i][j] * inv;
+}
+
+__device__ __forceinline__ void hyper_kin2(const tri_geom& t, const double (&uv)[3][2], double (&F)[2][2], double (&FiT)[2][2],
+                                           double& J) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + ((uv[0][i] * t.g[0][j] + uv[1][i] * t.g[1][j]) + uv[2][i] * t.g[2][j]);
+    J = F[0][0] * F[1][1] - F[0][1] * F[1][0];
+    const double inv = 1.0 / J;
+    FiT[0][0] = F[1][1] * inv;  FiT[0][1] = -F[1][0] * inv;
+    FiT[1][0] = -F[0][1] * inv; FiT[1][1] = F[0][0] * inv;
+}
+
+__device__ __forceinline__ void load_disp3(const double* __restrict__ u, const int32_t (&v)[4], double (&uv)[4][3]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) uv[a][k] = u[3 * (int64_t)v[a] + k];
+}
+
+__device__ __forceinline__ void load_disp2(const double* __restrict__ u, int4 v4, double (&uv)[3][2]) {
+    const int32_t v[3] = {v4.x, v4.y, v4.z};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double2 p = reinterpret_cast<const double2*>(u)[v[a]];
+        uv[a][0] = p.x; uv[a][1] = p.y;
+    }
+}
+
+// ---- tangent: tetrahedra -------------------------------------------------------------------------------------------------
+// Same source walk as k_assemble_p1_elasticity_gather (source index = cell * 16 + a * 4 + b, groups of four with their cell
+// records fetched first).  ms0 is the linear kernel's mass term, passed as a run-time 0 so that the diagonal sum below is the
+// same expression (and the same rounding) as there.
+template <bool ADD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
+                                                                   const int32_t* __restrict__ src, const int32_t* __restrict__ cells,
+                                                                   const double* __restrict__ xyz4, const double* __restrict__ u,
+                                                                   double mu0, double lambda0, const double2* __restrict__ lame_cell,
+                                                                   double ms0, int64_t plane, double* __restrict__ val, const box_snap bx) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; e < n_entries; e += stride) {
+        double acc[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        const int32_t q1 = ptr[e + 1];
+        constexpr int PF = 4;
+        for (int32_t q0 = ptr[e]; q0 < q1; q0 += PF) {
+          int32_t sc[PF];
+          int4 vc[PF];
+          double2 lc[PF];
+#pragma unroll
+          for (int w = 0; w < PF; ++w) sc[w] = q0 + w < q1 ? src[q0 + w] : -1;
+#pragma unroll
+          for (int w = 0; w < PF; ++w) {
+            vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[w] >> 4] : make_int4(0, 0, 0, 0);
+            if (CELL) lc[w] = sc[w] >= 0 ? lame_cell[sc[w] >> 4] : make_double2(0.0, 0.0);
+          }
+#pragma unroll
+          for (int w = 0; w < PF; ++w) {
+            if (q0 + w >= q1) break;
+            const int32_t sidx = sc[w];
+            const int a = (sidx >> 2) & 3, b = sidx & 3;
+            const int4 v4 = vc[w];
+            const double mu = CELL ? lc[w].x : mu0, lambda = CELL ? lc[w].y : lambda0;
+            const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+            const tet_geom t = tet_geometry_box(xyz4, v, bx);
+            const double vol = t.adet * (1.0 / 6.0);
+            double uv[4][3], F[3][3], FiT[3][3], J;
+            load_disp3(u, v, uv);
+            hyper_kin3(t, uv, F, FiT, J);
+            const double m2 = mu - lambda * log(J);
+            double ga[3], gb[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
+                gb[k] = b == 0 ? t.g[0][k] : b == 1 ? t.g[1][k] : b == 2 ? t.g[2][k] : t.g[3][k];
+            }
+            double Ga[3], Gb[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                Ga[i] = FiT[i][0] * ga[0] + FiT[i][1] * ga[1] + FiT[i][2] * ga[2];
+                Gb[i] = FiT[i][0] * gb[0] + FiT[i][1] * gb[1] + FiT[i][2] * gb[2];
+            }
+            const double gg = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    double x = vol * (lambda * Ga[i] * Gb[j] + m2 * Ga[j] * Gb[i]);
+                    if (i == j) x += vol * mu * gg + ms0;
+                    acc[i][j] += x;
+                }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int64_t idx = (int64_t)(i * 3 + j) * plane + e;
+                val[idx] = ADD ? val[idx] + acc[i][j] : acc[i][j];
+            }
+    }
+}
+
+// ---- tangent: triangles (plane strain), source index = cell * 9 + a * 3 + b, as k_assemble_tri_elasticity_gather -------------
+template <bool ADD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_tri_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
+                                                                       const int32_t* __restrict__ src, const int32_t* __restrict__ cells,
+                                                                       const double* __restrict__ xyz4, const double* __restrict__ u,
+                                                                       double mu0, double lambda0, const double2* __restrict__ lame_cell,
+                                                                       double ms0, int64_t plane, double* __restrict__ val) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; e < n_entries; e += stride) {
+        double acc[2][2] = {{0, 0}, {0, 0}};
+        const int32_t q1 = ptr[e + 1];
+        for (int32_t q = ptr[e]; q < q1; ++q) {
+            const int32_t sidx = src[q];
+            const int64_t c = sidx / 9;
+            const int ab = sidx - (int32_t)(c * 9);
+            const int a = ab / 3, b = ab - 3 * a;
+            const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+            const double mu = ml.x, lambda = ml.y;
+            const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+            double uv[3][2], F[2][2], FiT[2][2], J;
+            load_disp2(u, v4, uv);
+            hyper_kin2(t, uv, F, FiT, J);
+            const double m2 = mu - lambda * log(J);
+            const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
+            const double gb[2] = {b == 0 ? t.g[0][0] : (b == 1 ? t.g[1][0] : t.g[2][0]), b == 0 ? t.g[0][1] : (b == 1 ? t.g[1][1] : t.g[2][1])};
+            double Ga[2], Gb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                Ga[i] = FiT[i][0] * ga[0] + FiT[i][1] * ga[1];
+                Gb[i] = FiT[i][0] * gb[0] + FiT[i][1] * gb[1];
+            }
+            const double gg = ga[0] * gb[0] + ga[1] * gb[1];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    double x = t.area * (lambda * Ga[i] * Gb[j] + m2 * Ga[j] * Gb[i]);
+                    if (i == j) x += t.area * mu * gg + ms0;
+                    acc[i][j] += x;
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int64_t idx = (int64_t)(i * 2 + j) * plane + e;
+                val[idx] = ADD ? val[idx] + acc[i][j] : acc[i][j];
+            }
+    }
+}
+
+// ---- internal force ------------------------------------------------------------------------------------------------------
+// thread per owned node r: the sources of its diagonal block are (c, a, a) for every cell c holding the node, ascending in c
+__device__ __forceinline__ int64_t hyper_diag_entry(int64_t r, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col) {
+    const int64_t sp0 = slice_ptr[r >> 6];
+    const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
+    const int64_t base = sp0 + (r & 63);
+    for (int k = 0; k < width; ++k)
+        if (sell_col[base + (int64_t)k * FS_SLICE] == (int32_t)r) return base + (int64_t)k * FS_SLICE;
+    return -1;
+}
+
+template <bool ADD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
+                                                                 const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
+                                                                 const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
+                                                                 const double* __restrict__ xyz4, const double* __restrict__ u,
+                                                                 double mu0, double lambda0, const double2* __restrict__ lame_cell,
+                                                                 const box_snap bx, double* __restrict__ f) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; r < n_rows; r += stride) {
+        const int64_t e = hyper_diag_entry(r, slice_ptr, sell_col);
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (e >= 0) {
+            constexpr int PF = 4;
+            const int32_t q1 = gptr[e + 1];
+            for (int32_t q0 = gptr[e]; q0 < q1; q0 += PF) {
+              int32_t sc[PF];
+              int4 vc[PF];
+              double2 lc[PF];
+#pragma unroll
+              for (int w = 0; w < PF; ++w) sc[w] = q0 + w < q1 ? gsrc[q0 + w] : -1;
+#pragma unroll
+              for (int w = 0; w < PF; ++w) {
+                vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[w] >> 4] : make_int4(0, 0, 0, 0);
+                if (CELL) lc[w] = sc[w] >= 0 ? lame_cell[sc[w] >> 4] : make_double2(0.0, 0.0);
+              }
+#pragma unroll
+              for (int w = 0; w < PF; ++w) {
+                if (q0 + w >= q1) break;
+                const int a = (sc[w] >> 2) & 3;
+                const int4 v4 = vc[w];
+                const double mu = CELL ? lc[w].x : mu0, lambda = CELL ? lc[w].y : lambda0;
+                const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+                const tet_geom t = tet_geometry_box(xyz4, v, bx);
+                const double vol = t.adet * (1.0 / 6.0);
+                double uv[4][3], F[3][3], FiT[3][3], J;
+                load_disp3(u, v, uv);
+                hyper_kin3(t, uv, F, FiT, J);
+                const double ll = lambda * log(J);
+                double ga[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) s += (mu * (F[i][j] - FiT[i][j]) + ll * FiT[i][j]) * ga[j];
+                    acc[i] += vol * s;
+                }
+              }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) f[3 * r + i] = ADD ? f[3 * r + i] + acc[i] : acc[i];
+    }
+}
+
+template <bool ADD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_tri_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
+                                                                     const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
+                                                                     const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
+                                                                     const double* __restrict__ xyz4, const double* __restrict__ u,
+                                                                     double mu0, double lambda0, const double2* __restrict__ lame_cell,
+                                                                     double* __restrict__ f) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; r < n_rows; r += stride) {
+        const int64_t e = hyper_diag_entry(r, slice_ptr, sell_col);
+        double acc[2] = {0.0, 0.0};
+        if (e >= 0) {
+            for (int32_t q = gptr[e]; q < gptr[e + 1]; ++q) {
+                const int32_t sidx = gsrc[q];
+                const int64_t c = sidx / 9;
+                const int a = (sidx - (int32_t)(c * 9)) / 3;
+                const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+                const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+                const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+                double uv[3][2], F[2][2], FiT[2][2], J;
+                load_disp2(u, v4, uv);
+                hyper_kin2(t, uv, F, FiT, J);
+                const double ll = ml.y * log(J);
+                const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) s += (ml.x * (F[i][j] - FiT[i][j]) + ll * FiT[i][j]) * ga[j];
+                    acc[i] += t.area * s;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) f[2 * r + i] = ADD ? f[2 * r + i] + acc[i] : acc[i];
+    }
+}
+
+// ---- energy and inverted cells -------------------------------------------------------------------------------------------
+// psi = mu/2 (tr C - 3) - mu ln J + lambda/2 (ln J)^2 with tr C - d = 2 tr H + H : H (H = grad u: no cancellation at small
+// strain); 2-D keeps the reference's "- 3" (Identity(2) with the 3-D constant).  A cell counts as inverted when J <= 0 or J is
+// not finite.  partials[3][FS_HYPER_CELL_BLOCKS]: (energy, count, smallest device cell index) per workgroup.
+template <int TD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hyper_cells(int64_t nc, const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
+                                                          const double* __restrict__ u, double mu0, double lambda0,
+                                                          const double2* __restrict__ lame_cell, const box_snap bx,
+                                                          double* __restrict__ part_e, int64_t* __restrict__ part_n,
+                                                          int64_t* __restrict__ part_first) {
+    double en = 0.0;
+    int64_t n_bad = 0, first = INT64_MAX;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
+        const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+        const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
+        double J, trH = 0.0, HH = 0.0, vol;
+        if (TD == 3) {
+            const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+            const tet_geom t = tet_geometry_box(xyz4, v, bx);
+            vol = t.adet * (1.0 / 6.0);
+            double uv[4][3], F[3][3], FiT[3][3];
+            load_disp3(u, v, uv);
+            hyper_kin3(t, uv, F, FiT, J);
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const double h = F[i][j] - (i == j ? 1.0 : 0.0);
+                    if (i == j) trH += h;
+                    HH += h * h;
+                }
+        } else {
+            const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+            vol = t.area;
+            double uv[3][2], F[2][2], FiT[2][2];
+            load_disp2(u, v4, uv);
+            hyper_kin2(t, uv, F, FiT, J);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const double h = F[i][j] - (i == j ? 1.0 : 0.0);
+                    if (i == j) trH += h;
+                    HH += h * h;
+                }
+        }
+        if (!(J > 0.0) || !isfinite(J)) {
+            ++n_bad;
+            first = c < first ? c : first;
+            continue;
+        }
+        const double lj = log(J);
+        const double ic3 = (2.0 * trH + HH) + (TD == 3 ? 0.0 : -1.0);
+        en += vol * (0.5 * ml.x * ic3 - ml.x * lj + 0.5 * ml.y * lj * lj);
+    }
+    __shared__ double se[FS_BLOCK / 64];
+    __shared__ int64_t sn[FS_BLOCK / 64], sf[FS_BLOCK / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        en += __shfl_down(en, off, 64);
+        n_bad += __shfl_down(n_bad, off, 64);
+        const int64_t o = __shfl_down(first, off, 64);
+        first = o < first ? o : first;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { se[wave] = en; sn[wave] = n_bad; sf[wave] = first; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double te = 0.0;
+        int64_t tn = 0, tf = INT64_MAX;
+        for (int w = 0; w < FS_BLOCK / 64; ++w) {
+            te += se[w];
+            tn += sn[w];
+            tf = sf[w] < tf ? sf[w] : tf;
+        }
+        part_e[blockIdx.x] = te;
+        part_n[blockIdx.x] = tn;
+        part_first[blockIdx.x] = tf;
+    }
+}
+
+__global__ void k_hyper_cells_finish(int nb, const double* __restrict__ part_e, const int64_t* __restrict__ part_n,
+                                     const int64_t* __restrict__ part_first, double* __restrict__ out_e, int64_t* __restrict__ out_n) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double te = 0.0;
+    int64_t tn = 0, tf = INT64_MAX;
+    for (int b = 0; b < nb; ++b) {
+        te += part_e[b];
+        tn += part_n[b];
+        tf = part_first[b] < tf ? part_first[b] : tf;
+    }
+    out_e[0] = te;
+    out_n[0] = tn;
+    out_n[1] = tf;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, const fs_hyper_form* form,
+                                        int what, fs_hyper_info* info) {
+    FS_REQUIRE(space && u && form, "fs_assemble_hyperelastic: null pointer");
+    FS_REQUIRE((what & ~(FS_HYPER_TANGENT | FS_HYPER_FORCE | FS_HYPER_ENERGY)) == 0, "fs_assemble_hyperelastic: unknown bits in what (%d)", what);
+    FS_REQUIRE(form->model == FS_HYPER_NEO_HOOKEAN, "fs_assemble_hyperelastic: unknown energy model %d (FS_HYPER_NEO_HOOKEAN only)", form->model);
+    fs_space_s* sp = space;
+    fs_mesh_s* m = sp->mesh;
+    FS_REQUIRE(sp->degree == 1 && ((m->tdim == 3 && sp->ncomp == 3) || (m->tdim == 2 && sp->ncomp == 2)),
+               "fs_assemble_hyperelastic: vector CG1 spaces on tetrahedra or triangles only (this space: CG%d with %d components on a "
+               "%d-D mesh)", sp->degree, sp->ncomp, m->tdim);
+    FS_REQUIRE(m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local,
+               "fs_assemble_hyperelastic: the space has ghost nodes (several ranks): not supported");
+    FS_REQUIRE(sp->slots.p, "fs_assemble_hyperelastic: vector space without slot table");
+    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "fs_assemble_hyperelastic: displacement vector shorter than the space's dofs");
+    FS_REQUIRE(!(what & FS_HYPER_TANGENT) || (K && K->space == sp), "fs_assemble_hyperelastic: the tangent needs a matrix on this space");
+    FS_REQUIRE(!(what & FS_HYPER_FORCE) || (r && r->d.n >= sp->n_dofs_owned), "fs_assemble_hyperelastic: the internal force needs a vector of "
+               "the space's owned dofs");
+    FS_REQUIRE(!(what & FS_HYPER_ENERGY) || info, "fs_assemble_hyperelastic: the energy needs an info struct");
+    FS_REQUIRE(form->lame.mode == FS_COEF_NONE || form->lame.mode == FS_COEF_CELL_LAME,
+               "fs_assemble_hyperelastic: the Lame coefficient is FS_COEF_NONE (mu / lambda) or FS_COEF_CELL_LAME");
+    FS_REQUIRE(form->lame.mode == FS_COEF_CELL_LAME || (form->mu > 0.0 && form->lambda >= 0.0 && isfinite(form->mu) && isfinite(form->lambda)),
+               "fs_assemble_hyperelastic: mu > 0 and lambda >= 0 are required (mu = %g, lambda = %g)", form->mu, form->lambda);
+    hipStream_t s = fs_rt().stream;
+    dbuf<double> lstore;
+    const bool cellw = form->lame.mode == FS_COEF_CELL_LAME;
+    if (cellw) {
+        FS_REQUIRE(form->lame.data, "fs_assemble_hyperelastic: per-cell Lame data pointer is null");
+        for (int64_t c = 0; c < m->nc; ++c) {
+            const double mc = form->lame.data[2 * c], lc = form->lame.data[2 * c + 1];
+            FS_REQUIRE(mc > 0.0 && lc >= 0.0 && isfinite(mc) && isfinite(lc),
+                       "fs_assemble_hyperelastic: cell %lld (device order) has mu = %g, lambda = %g: mu > 0 and lambda >= 0 are required",
+                       (long long)c, mc, lc);
+        }
+        FS_CHECK(lstore.alloc(2 * m->nc));
+        FS_CHECK(lstore.upload(form->lame.data, 2 * m->nc, s));
+    }
+    const double2* lc = reinterpret_cast<const double2*>(lstore.p);
+    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    const box_snap bx = make_box_snap(m);
+    const double mu = form->mu, lambda = form->lambda, ms0 = 0.0;
+    const bool add = form->add != 0;
+    if (what & FS_HYPER_TANGENT) {
+        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
+#define FS_HT3(A_, C_) hipLaunchKernelGGL((k_hyper_tangent_gather<A_, C_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
+                                          sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p, bx)
+#define FS_HT2(A_, C_) hipLaunchKernelGGL((k_hyper_tangent_tri_gather<A_, C_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
+                                          sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p)
+        if (m->tdim == 3) {
+            if (cellw) { if (add) FS_HT3(true, true); else FS_HT3(false, true); }
+            else if (add) FS_HT3(true, false); else FS_HT3(false, false);
+        } else {
+            if (cellw) { if (add) FS_HT2(true, true); else FS_HT2(false, true); }
+            else if (add) FS_HT2(true, false); else FS_HT2(false, false);
+        }
+#undef FS_HT3
+#undef FS_HT2
+        FS_KERNEL_CHECK();
+    }
+    if (what & FS_HYPER_FORCE) {
+        const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
+#define FS_HF3(A_, C_) hipLaunchKernelGGL((k_hyper_force_gather<A_, C_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
+                                          sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, bx, r->d.p)
+#define FS_HF2(A_, C_) hipLaunchKernelGGL((k_hyper_force_tri_gather<A_, C_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
+                                          sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, r->d.p)
+        if (m->tdim == 3) {
+            if (cellw) { if (add) FS_HF3(true, true); else FS_HF3(false, true); }
+            else if (add) FS_HF3(true, false); else FS_HF3(false, false);
+        } else {
+            if (cellw) { if (add) FS_HF2(true, true); else FS_HF2(false, true); }
+            else if (add) FS_HF2(true, false); else FS_HF2(false, false);
+        }
+#undef FS_HF3
+#undef FS_HF2
+        FS_KERNEL_CHECK();
+    }
+    if (info) {
+        const int nb = FS_HYPER_CELL_BLOCKS;
+        dbuf<double> pe, oe;
+        dbuf<int64_t> pn, pf, on;
+        FS_CHECK(pe.alloc(nb)); FS_CHECK(pn.alloc(nb)); FS_CHECK(pf.alloc(nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
+#define FS_HC(T_, C_) hipLaunchKernelGGL((k_hyper_cells<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu, lambda, \
+                                         lc, bx, pe.p, pn.p, pf.p)
+        if (m->tdim == 3) { if (cellw) FS_HC(3, true); else FS_HC(3, false); }
+        else { if (cellw) FS_HC(2, true); else FS_HC(2, false); }
+#undef FS_HC
+        FS_KERNEL_CHECK();
+        hipLaunchKernelGGL(k_hyper_cells_finish, dim3(1), dim3(64), 0, s, nb, pe.p, pn.p, pf.p, oe.p, on.p);
+        FS_KERNEL_CHECK();
+        double e_host = 0.0;
+        int64_t n_host[2] = {0, 0};
+        FS_CHECK(oe.download(&e_host, 1, s));
+        FS_CHECK(on.download(n_host, 2, s));
+        info->energy = e_host;
+        info->n_inverted = n_host[0];
+        int64_t first = n_host[0] > 0 ? n_host[1] : -1;
+        if (first >= 0 && !m->cell_order.empty()) first = m->cell_order[first];     // the caller's cell number
+        info->first_inverted_cell = first;
+    }
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}

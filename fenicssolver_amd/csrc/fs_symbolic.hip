@@ -1692,6 +1692,7 @@ static int locality_order_impl(int gdim, int64_t nv, const double* xyz, int64_t 
             delete m;
             return FS_ERR_HIP;
         }
+        m->cell_order.assign(cell_order, cell_order + nc);
         *mesh_out = m;
     }
     return FS_OK;

@@ -492,6 +492,47 @@ class AutoSubDomain(SubDomain):
         return self._fn(x) if self._nargs == 1 else self._fn(x, on_boundary)
 
 
+class CompiledSubDomain(SubDomain):
+    """dolfin.CompiledSubDomain(code, **params) (examples/test_nonlinear_elasticity.py): the C++ predicate string of an
+    AutoSubDomain, parsed by cexpr (never eval'ed), with ``on_boundary`` a name and ``near(a, b[, eps])`` a function.  The keyword
+    parameters are the predicate's double members; ``subdomain.name = value`` changes one."""
+
+    def __init__(self, code, **params):
+        from .cexpr import CExpr, CExprError
+        try:
+            self._expr = CExpr(code)
+        except CExprError as e:
+            raise SolverError("CompiledSubDomain('{}'): {}".format(code, e))
+        self.__dict__['_params'] = dict(params)
+        self.code = code
+
+    def __getattr__(self, name):
+        params = self.__dict__.get('_params', {})
+        if name in params:
+            return params[name]
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        if name in self.__dict__.get('_params', {}):
+            self._params[name] = value
+        else:
+            object.__setattr__(self, name, value)
+
+    def _inside_points(self, pts, on_boundary):
+        pts = np.asarray(pts, dtype=np.float64).reshape(len(pts), -1)
+        if pts.shape[1] < 3:
+            pts = np.concatenate([pts, np.zeros((len(pts), 3 - pts.shape[1]))], axis=1)
+        ob = np.broadcast_to(np.asarray(on_boundary, dtype=bool), (pts.shape[0],)).astype(np.float64)
+        from .cexpr import CExprError
+        try:
+            return self._expr(pts, self._params, point_values={'on_boundary': ob}) != 0
+        except CExprError as e:
+            raise SolverError("CompiledSubDomain('{}'): {}".format(self.code, e))
+
+    def inside(self, x, on_boundary):
+        return bool(self._inside_points(np.asarray(x, dtype=np.float64).reshape(1, -1), on_boundary)[0])
+
+
 # --------------------------------------------------------------------------------------------
 # coefficients
 # --------------------------------------------------------------------------------------------

@@ -154,6 +154,32 @@ class ElasticityForm:
         }
 
 
+class HyperelasticForm:
+    """Pi = int psi(F) dx - int B.u dx - loads.u ds, psi the compressible neo-Hookean energy (NonlinearElasticitySolver.py:41-98);
+    the Newton iteration solves dPi/du = 0 (SolverBase._hyperelastic_newton).  The loads are dead loads with their PHYSICAL sign
+    (the reference subtracts them from Pi; no reversed-sign quirk here)."""
+
+    def __init__(self, space):
+        self.space = space
+        self.model = "neo_hookean"
+        self.mu = None                # numbers (homogeneous) or arrays [n_cells] (per-cell material, host cell order)
+        self.lmbda = None
+        self.body_force = None        # (fx, fy[, fz]) or None
+        self.body_force_nodal = None  # [n_nodes, dim]: a body force FIELD by its nodal values (consistent-mass load)
+        self.tractions = []           # [FacetLoad] with vector g, or [NodalLoad] (surface_source, varying pressure)
+
+    cellwise = ElasticityForm.cellwise
+    lame_spec = ElasticityForm.lame_spec
+
+    def describe(self):
+        return {
+            "type": "hyperelasticity", "model": self.model, "mu": _material(self.mu), "lambda": _material(self.lmbda),
+            "body_force": None if self.body_force is None else tuple(float(x) for x in self.body_force),
+            "tractions": [(t.marker_id, _plain(t.g), t.origin) if isinstance(t, FacetLoad) else ("nodal", len(t.dofs), t.origin)
+                          for t in self.tractions],
+        }
+
+
 def _material(v):
     """A material value: the number itself, or a per-cell array by its shape and range."""
     if np.ndim(v) == 0:

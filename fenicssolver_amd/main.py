@@ -29,7 +29,7 @@ def load_settings(case_input):
     raise TypeError('{} is not supported as case input, only path string or dict'.format(type(case_input)))
 
 
-_SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "LinearElasticitySolver")
+_SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "LinearElasticitySolver", "NonlinearElasticitySolver")
 
 
 def main(case_input):
@@ -39,6 +39,8 @@ def main(case_input):
         from .ScalarTransportSolver import ScalarTransportSolver as cls
     elif solver_name == "LinearElasticitySolver":
         from .LinearElasticitySolver import LinearElasticitySolver as cls
+    elif solver_name == "NonlinearElasticitySolver":
+        from .NonlinearElasticitySolver import NonlinearElasticitySolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

@@ -301,6 +301,38 @@ int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, double mu, doubl
 /* The same with one (mu, lambda) pair per cell: lame[n_cells][2] (host, device cell order). */
 int fs_assemble_von_mises_cells(fs_space_t disp_space, fs_vector_t u, const double* lame, fs_space_t p1_space, fs_vector_t b);
 
+/* ---- Hyperelasticity (NonlinearElasticitySolver.py:41-98) -------------------------------------------------------------------
+ * Compressible neo-Hookean energy  psi = mu/2 (tr F^T F - 3) - mu ln J + lambda/2 (ln J)^2,  F = I + grad u,  J = det F
+ * (2-D, plane strain: F is 2 x 2 and the reference's "- 3" is kept).  fs_assemble_hyperelastic evaluates at the displacement u,
+ * on a vector CG1 space over tetrahedra or triangles (one rank):
+ *   FS_HYPER_TANGENT  K = d^2 Pi / du^2, the tangent stiffness (pattern of the space, no Dirichlet rows);
+ *   FS_HYPER_FORCE    r = d Pi / du, the internal force int P : grad v dx (owned dofs);
+ *   FS_HYPER_ENERGY   info->energy = int psi dx.
+ * External loads do not depend on u: they are assembled with fs_assemble_vector / fs_assemble_facet_vector.
+ * u: dof vector (node-interleaved, >= n_dofs_local entries).  K and r are overwritten, or added to with form->add.  Every result is
+ * deterministic (no atomics; the energy is summed in a fixed order).  At u = 0 the tangent equals fs_assemble_matrix of the linear
+ * elasticity operator with the same (mu, lambda) bit for bit.
+ * info (optional unless FS_HYPER_ENERGY): the energy, the number of cells with J <= 0 or J not finite (where the tangent, the force
+ * and the energy are meaningless) and one of them, in the caller's cell numbering (-1: none).  info is filled whatever `what`
+ * holds.  Other spaces, several ranks, mu <= 0 or lambda < 0 (constant or in any cell): FS_ERR_INVALID with a message. */
+#define FS_HYPER_NEO_HOOKEAN 0
+#define FS_HYPER_TANGENT 1
+#define FS_HYPER_FORCE 2
+#define FS_HYPER_ENERGY 4
+typedef struct fs_hyper_form {
+    int model;           /* FS_HYPER_NEO_HOOKEAN */
+    double mu, lambda;   /* Lame parameters when lame.mode == FS_COEF_NONE */
+    fs_coef lame;        /* FS_COEF_NONE or FS_COEF_CELL_LAME: data[n_cells][2] = (mu, lambda), host, device cell order */
+    int add;             /* 0: overwrite K / r; 1: add to them */
+} fs_hyper_form;
+typedef struct fs_hyper_info {
+    double energy;
+    int64_t n_inverted;
+    int64_t first_inverted_cell;
+} fs_hyper_info;
+int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, const fs_hyper_form* form, int what,
+                             fs_hyper_info* info);
+
 /* Right-hand sides of the L2 projection of the fluid stress  nu (grad u + grad u^T) - p I  onto CG1
  * (CoupledNavierStokesSolver.py:149-155, viscous_stress): b[vertex*9 + 3 i + j] = int sigma_ij phi_vertex dx for a
  * Taylor-Hood iterate w (block (u_x,u_y,u_z,p) per CG2 node).  Each of the 9 components is then one CG1 mass-matrix
