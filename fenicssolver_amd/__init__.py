@@ -1,5 +1,5 @@
 """fenicssolver_amd — MI355X-native assemble + Krylov-solve pipeline behind the
-FenicsSolver Python API (SolverBase / ScalarTransportSolver /
+FenicsSolver Python API (SolverBase / ScalarTransportSolver / ScalarTransportDGSolver /
 LinearElasticitySolver / NonlinearElasticitySolver, JSON case settings).
 
 Mirrors FenicsSolver/__init__.py:9-13 of the reference, except that importing

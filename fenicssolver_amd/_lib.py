@@ -23,7 +23,8 @@ FS_HYPER_NEO_HOOKEAN = 0
 FS_HYPER_TANGENT, FS_HYPER_FORCE, FS_HYPER_ENERGY = 1, 2, 4
 FS_KSP_CG = 0
 FS_KSP_BICGSTAB = 1
-FS_PC_NONE, FS_PC_JACOBI = 0, 1
+FS_PC_NONE, FS_PC_JACOBI, FS_PC_BLOCK_JACOBI = 0, 1, 2
+FS_FAMILY_CG, FS_FAMILY_DG = 0, 1
 FS_NORM_UNPRECONDITIONED, FS_NORM_PRECONDITIONED = 0, 1
 FS_UNIQUE_ID_BYTES = 128
 
@@ -58,6 +59,12 @@ class fs_hyper_form(C.Structure):
 
 class fs_hyper_info(C.Structure):
     _fields_ = [("energy", C.c_double), ("n_inverted", C.c_int64), ("first_inverted_cell", C.c_int64)]
+
+
+class fs_dg_form(C.Structure):
+    _fields_ = [("conductivity", C.c_double), ("capacity", C.c_double), ("velocity", C.c_double * 3), ("alpha", C.c_double),
+                ("operator_scale", C.c_double), ("mass_scale", C.c_double), ("n_facets", C.c_int64), ("facet_cell", c_i32p),
+                ("facet_local", c_i32p), ("facet_h", c_f64p), ("facet_g", c_f64p), ("source", c_f64p), ("add", C.c_int)]
 
 
 class fs_krylov_opts(C.Structure):
@@ -184,6 +191,9 @@ SIGNATURES = {
     "fs_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_char_p]),
     "fs_assemble_von_mises": (C.c_int, [_H, _H, C.c_double, C.c_double, _H, _H]),
     "fs_assemble_von_mises_cells": (C.c_int, [_H, _H, c_f64p, _H, _H]),
+    "fs_space_dg_set_plus_key": (C.c_int, [_H, c_i64p]),
+    "fs_assemble_dg_transport": (C.c_int, [_H, _H, C.POINTER(fs_dg_form)]),
+    "fs_assemble_dg_projection": (C.c_int, [_H, _H, _H, _H]),
     "fs_assemble_hyperelastic": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_hyper_form), C.c_int, C.POINTER(fs_hyper_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),

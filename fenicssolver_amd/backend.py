@@ -906,3 +906,89 @@ def last_product_kind():
 
 def set_option(name, value):
     L.check(L.load().fs_set_option(name.encode(), float(value)), "fs_set_option")
+
+
+# ---- DG1 (ScalarTransportDGSolver) -------------------------------------------------------------------------------------------
+class DeviceDGSpace(_Handle):
+    """Discontinuous P1 scalar space on a device mesh: dof (K, a) = (d+1) K + a in device cell order (fs_space_create with
+    FS_FAMILY_DG).  plus_key: one int64 per device cell; on every interior facet the cell with the larger key is '+'."""
+    _destroy = "fs_space_destroy"
+
+    def __init__(self, mesh, plus_key=None):
+        super().__init__()
+        self.mesh = mesh
+        L.check(L.load().fs_space_create(mesh.h, L.FS_FAMILY_DG, 1, 1, C.byref(self.h)), "fs_space_create(DG)")
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(L.load().fs_space_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "fs_space_info")
+        self.n_local, self.n_owned, self.nnz, self.stored_values = a.value, b.value, c.value, d.value
+        self.ncomp = 1
+        if plus_key is not None:
+            self.set_plus_key(plus_key)
+
+    def set_plus_key(self, key):
+        k = L.i64(key).ravel()
+        L.check(L.load().fs_space_dg_set_plus_key(self.h, L.p_i64(k)), "fs_space_dg_set_plus_key")
+
+
+class DeviceDGMatrix(DeviceMatrix):
+    """Cell-block matrix of a DG1 space: (d+2) blocks of (d+1)^2 values per cell (fs_matrix_create on a DG space)."""
+
+    def assemble_transport(self, b=None, conductivity=0.0, capacity=1.0, velocity=(0.0, 0.0, 0.0), alpha=0.0, operator_scale=1.0,
+                           mass_scale=0.0, facet_cell=None, facet_local=None, facet_h=None, facet_g=None, source=None, add=False):
+        """fs_assemble_dg_transport: A (and b) <- operator_scale c a(T, v) + mass_scale M + the listed boundary facets' HTC
+        mass facet_h; b <- int source v dx + int g v ds.  Facets, source: device cell numbering."""
+        f = L.fs_dg_form()
+        f.conductivity, f.capacity, f.alpha = float(conductivity), float(capacity), float(alpha)
+        v = np.zeros(3)
+        v[:len(velocity)] = np.asarray(velocity, dtype=np.float64)
+        f.velocity[:] = list(v)
+        f.operator_scale, f.mass_scale = float(operator_scale), float(mass_scale)
+        keep = []
+        if facet_cell is not None and len(facet_cell):
+            fc, fl = L.i32(facet_cell).ravel(), L.i32(facet_local).ravel()
+            keep += [fc, fl]
+            f.n_facets, f.facet_cell, f.facet_local = fc.size, L.p_i32(fc), L.p_i32(fl)
+            if facet_h is not None:
+                fh = L.f64(np.broadcast_to(facet_h, (fc.size,)))
+                keep.append(fh)
+                f.facet_h = L.p_f64(fh)
+            if facet_g is not None:
+                fg = L.f64(facet_g).reshape(fc.size, -1)
+                keep.append(fg)
+                f.facet_g = L.p_f64(fg)
+        if source is not None:
+            src = L.f64(source)
+            keep.append(src)
+            f.source = L.p_f64(src)
+        f.add = 1 if add else 0
+        L.check(L.load().fs_assemble_dg_transport(self.h, b.h if b is not None else None, C.byref(f)), "fs_assemble_dg_transport")
+
+    def apply_dirichlet(self, b, dofs, vals, symmetric=False):
+        if symmetric:
+            raise BackendError("DG matrices take Dirichlet rows as identity rows (symmetric=False)")
+        DeviceMatrix.apply_dirichlet(self, b, dofs, vals, symmetric=False)
+
+
+def dg_krylov_solve(A, b, x, rtol=1e-12, atol=0.0, max_iter=20000, precond="block_jacobi", batch=0, nonzero_guess=False,
+                    norm="preconditioned"):
+    """BiCGStab on a DG1 cell-block matrix, right-preconditioned by the inverse diagonal blocks ("block_jacobi"), the inverse
+    diagonal ("jacobi") or nothing ("none").  norm: "preconditioned" stops when ||r|| <= rtol ||b|| and ||M^-1 r|| <= rtol ||M^-1 b||
+    both hold, "unpreconditioned" on the first alone (the stats' residuals are in the plain norm); converged = 1 means the TRUE
+    residual met the test.
+    Returns the stats dict of fs_krylov_solve."""
+    o = L.fs_krylov_opts()
+    o.method = L.FS_KSP_BICGSTAB
+    o.precond = {"block_jacobi": L.FS_PC_BLOCK_JACOBI, "jacobi": L.FS_PC_JACOBI, "none": L.FS_PC_NONE, None: L.FS_PC_NONE}[precond]
+    o.rtol, o.atol, o.max_iter, o.batch = float(rtol), float(atol), int(max_iter), int(batch)
+    o.nonzero_guess = 1 if nonzero_guess else 0
+    o.norm_type = {"unpreconditioned": L.FS_NORM_UNPRECONDITIONED, "preconditioned": L.FS_NORM_PRECONDITIONED}[norm]
+    st = L.fs_krylov_stats()
+    rc = L.load().fs_krylov_solve(A.h, b.h, x.h, C.byref(o), C.byref(st))
+    out = {k: getattr(st, k) for k, _ in L.fs_krylov_stats._fields_}
+    L.check(rc, "fs_krylov_solve(DG)")
+    return out
+
+
+def assemble_dg_projection(dg_space, x, cg1_space, b):
+    """b_i = int T_h phi_i dx of the DG1 field x on the CG1 space of the same device mesh (fs_assemble_dg_projection)."""
+    L.check(L.load().fs_assemble_dg_projection(dg_space.h, x.h, cg1_space.h, b.h), "fs_assemble_dg_projection")

@@ -1682,6 +1682,7 @@ static int coarse_inverse(fs_amg_s* M, amg_level* L, hipStream_t s) {
 // ---- C-ABI: setup ---------------------------------------------------------------------------------------
 extern "C" int fs_amg_setup(fs_matrix_t A, int n_nullspace, const double* nullspace, const fs_amg_opts* opts,
                             fs_amg_t* out) {
+    FS_REFUSE_DG(A, "fs_amg_setup");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A && out, "fs_amg_setup: null pointer");
     fs_space_s* sp = A->space;
@@ -1825,6 +1826,7 @@ __global__ void k_sel_gather_dofs(int64_t n_sel, const int32_t* __restrict__ sel
 // the restricted right-hand side summed over the ranks - and applies levels >= 1 as they are: the preconditioner of one GPU,
 // with the fine-level work divided by the number of ranks.  fs_amg_solve then runs CG on the decomposed operator.
 extern "C" int fs_amg_attach_distributed_fine(fs_amg_t M, fs_matrix_t A_local, int64_t n_owned_nodes, const int32_t* owned_global_nodes) {
+    FS_REFUSE_DG(A_local, "fs_amg_attach_distributed_fine");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(M && A_local && owned_global_nodes, "fs_amg_attach_distributed_fine: null pointer");
     FS_REQUIRE(M->lv.size() >= 2, "fs_amg_attach_distributed_fine: the hierarchy has a single level");

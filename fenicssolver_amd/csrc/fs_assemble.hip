@@ -2431,6 +2431,7 @@ __global__ void k_fill_master_of(int64_t n_pairs, const int32_t* __restrict__ sl
 }
 
 extern "C" int fs_matrix_tie_nodes(fs_matrix_t A, fs_vector_t b, int64_t n_pairs, const int32_t* slaves, const int32_t* masters) {
+    FS_REFUSE_DG(A, "fs_matrix_tie_nodes");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A && (n_pairs == 0 || (slaves && masters)), "fs_matrix_tie_nodes: null pointer");
     if (n_pairs == 0) return FS_OK;
@@ -2535,6 +2536,7 @@ static int make_coef(const fs_coef& in, int64_t expect_len, dbuf<double>& store,
 extern "C" int fs_matrix_create(fs_space_t space, fs_matrix_t* out) {
     FS_CHECK(fs_require_init());
     FS_REQUIRE(space && out, "fs_matrix_create: null pointer");
+    if (fs_is_dg(space)) return fs_dg_matrix_create(space, out);
     fs_matrix_s* A = new fs_matrix_s();
     A->space = space;
     A->bs = space->ncomp;
@@ -2551,6 +2553,12 @@ extern "C" int fs_matrix_create(fs_space_t space, fs_matrix_t* out) {
 
 extern "C" int fs_matrix_info(fs_matrix_t A, int64_t* n_rows, int64_t* n_cols, int64_t* nnz) {
     FS_REQUIRE(A, "fs_matrix_info: null matrix");
+    if (fs_is_dg(A->space)) {
+        if (n_rows) *n_rows = A->space->n_dofs_owned;
+        if (n_cols) *n_cols = A->space->n_dofs_local;
+        if (nnz) *nnz = fs_dg_matrix_nnz(A->space);
+        return FS_OK;
+    }
     if (n_rows) *n_rows = A->space->n_dofs_owned;
     if (n_cols) *n_cols = A->space->n_dofs_local;
     if (nnz) *nnz = A->space->nnz_nodes * A->bs * A->bs;
@@ -2565,6 +2573,7 @@ extern "C" int fs_matrix_zero(fs_matrix_t A) {
 }
 
 extern "C" int fs_matrix_axpy(fs_matrix_t Y, double a, fs_matrix_t X) {
+    FS_REFUSE_DG(Y, "fs_matrix_axpy"); FS_REFUSE_DG(X, "fs_matrix_axpy");
     FS_REQUIRE(X && Y && X->space == Y->space, "fs_matrix_axpy: matrices must share a function space");
     hipLaunchKernelGGL(k_mat_axpy, dim3(fs_grid_for(Y->val.n)), dim3(FS_BLOCK), 0, fs_rt().stream, Y->val.p, X->val.p, Y->val.n, a);
     FS_KERNEL_CHECK();
@@ -2573,6 +2582,7 @@ extern "C" int fs_matrix_axpy(fs_matrix_t Y, double a, fs_matrix_t X) {
 }
 
 extern "C" int fs_matrix_copy(fs_matrix_t dst, fs_matrix_t src) {
+    FS_REFUSE_DG(dst, "fs_matrix_copy"); FS_REFUSE_DG(src, "fs_matrix_copy");
     FS_REQUIRE(dst && src && dst->space == src->space && dst->val.n == src->val.n, "fs_matrix_copy: matrices must share a function space");
     FS_HIP(hipMemcpyAsync(dst->val.p, src->val.p, (size_t)src->val.n * sizeof(double), hipMemcpyDeviceToDevice, fs_rt().stream));
     return FS_OK;
@@ -2585,6 +2595,7 @@ extern "C" int fs_matrix_destroy(fs_matrix_t A) {
 
 extern "C" int fs_matrix_get_csr(fs_matrix_t A, int32_t* rowptr, int32_t* colidx, double* vals) {
     FS_REQUIRE(A, "fs_matrix_get_csr: null matrix");
+    if (fs_is_dg(A->space)) return fs_dg_matrix_get_csr(A, rowptr, colidx, vals);
     fs_space_s* sp = A->space;
     hipStream_t s = fs_rt().stream;
     const int bs = A->bs;
@@ -2611,6 +2622,7 @@ extern "C" int fs_matrix_get_csr(fs_matrix_t A, int32_t* rowptr, int32_t* colidx
 }
 
 extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, int add) {
+    FS_REFUSE_DG(A, "fs_assemble_matrix");
     FS_REQUIRE(A && form, "fs_assemble_matrix: null pointer");
     fs_space_s* sp = A->space;
     fs_mesh_s* m = sp->mesh;
@@ -3198,6 +3210,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_viscous_stress_load_tri(int64_t n_
 // coordinates and recomputes 24 cell geometries per row for every product, the assembled form streams 15 doubles per row).
 extern "C" int fs_operator_apply(fs_space_t V, const fs_bilinear_form* form, fs_vector_t x, fs_vector_t y, int reps,
                                  double* ms_per_launch) {
+    FS_REFUSE_DG_SPACE(V, "fs_operator_apply");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(V && form && x && y, "fs_operator_apply: null pointer");
     fs_space_s* sp = V;
@@ -3258,6 +3271,7 @@ extern "C" int fs_assemble_viscous_stress(fs_space_t th_space, fs_vector_t w, do
 }
 extern "C" int fs_assemble_viscous_stress_nn(fs_space_t th_space, fs_vector_t w, double nu, fs_space_t p1_space, fs_vector_t b,
                                              double nn_pref, double nn_exp) {
+    FS_REFUSE_DG_SPACE(th_space, "fs_assemble_viscous_stress"); FS_REFUSE_DG_SPACE(p1_space, "fs_assemble_viscous_stress");
     FS_REQUIRE(th_space && w && p1_space && b && nn_pref >= 0.0, "fs_assemble_viscous_stress: null pointer / negative reference pressure");
     FS_REQUIRE(th_space->mesh == p1_space->mesh, "fs_assemble_viscous_stress: the two spaces live on different meshes");
     FS_REQUIRE(th_space->ncomp == 4 && th_space->degree == 2, "fs_assemble_viscous_stress: needs the Taylor-Hood node-block space");
@@ -3311,6 +3325,7 @@ static int von_mises_check(fs_space_t disp_space, fs_vector_t u, fs_space_t p1_s
 
 extern "C" int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, double mu, double lambda, fs_space_t p1_space,
                                      fs_vector_t b) {
+    FS_REFUSE_DG_SPACE(disp_space, "fs_assemble_von_mises"); FS_REFUSE_DG_SPACE(p1_space, "fs_assemble_von_mises");
     FS_CHECK(von_mises_check(disp_space, u, p1_space, b, "fs_assemble_von_mises"));
     von_mises_launch<false>(disp_space, u, mu, lambda, nullptr, p1_space, b);
     FS_KERNEL_CHECK();
@@ -3320,6 +3335,7 @@ extern "C" int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, doubl
 
 extern "C" int fs_assemble_von_mises_cells(fs_space_t disp_space, fs_vector_t u, const double* lame, fs_space_t p1_space,
                                            fs_vector_t b) {
+    FS_REFUSE_DG_SPACE(disp_space, "fs_assemble_von_mises_cells"); FS_REFUSE_DG_SPACE(p1_space, "fs_assemble_von_mises_cells");
     FS_CHECK(von_mises_check(disp_space, u, p1_space, b, "fs_assemble_von_mises_cells"));
     FS_REQUIRE(lame, "fs_assemble_von_mises_cells: null (mu, lambda) array");
     const int64_t nc = p1_space->mesh->nc;
@@ -3393,6 +3409,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_vector_source_gather(i
 }
 
 extern "C" int fs_assemble_vector(fs_space_t space, const fs_linear_form* form, fs_vector_t b, int add) {
+    FS_REFUSE_DG_SPACE(space, "fs_assemble_vector");
     FS_REQUIRE(space && form && b, "fs_assemble_vector: null pointer");
     FS_REQUIRE(b->d.n >= space->n_dofs_owned, "fs_assemble_vector: vector shorter than the owned dofs");
     fs_mesh_s* m = space->mesh;
@@ -3715,6 +3732,7 @@ __global__ void k_facet_supg_p2tri(int64_t nf, const int32_t* __restrict__ facet
 extern "C" int fs_assemble_facet_supg(fs_space_t space, fs_matrix_t A, fs_vector_t b, int64_t n_facets, const int32_t* facet_cell,
                                       const int32_t* facet_opposite, const double* g, const double* h, const fs_coef* velocity,
                                       double supg_pe) {
+    FS_REFUSE_DG_SPACE(space, "fs_assemble_facet_supg"); FS_REFUSE_DG(A, "fs_assemble_facet_supg");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(space && velocity && supg_pe > 0.0 && n_facets >= 0, "fs_assemble_facet_supg: bad arguments");
     FS_REQUIRE(space->ncomp == 1 && (space->degree == 1 || space->cell_dofs), "fs_assemble_facet_supg: scalar CG1 / CG2 spaces only");
@@ -3761,6 +3779,7 @@ extern "C" int fs_assemble_facet_supg(fs_space_t space, fs_matrix_t A, fs_vector
 
 extern "C" int fs_assemble_facet_vector(fs_space_t space, int64_t n_facets, const int32_t* tri, const double* g,
                                         fs_vector_t b) {
+    FS_REFUSE_DG_SPACE(space, "fs_assemble_facet_vector");
     FS_REQUIRE(space && b && (n_facets == 0 || (tri && g)), "fs_assemble_facet_vector: null pointer");
     if (n_facets == 0) return FS_OK;
     if (space->mesh->tdim == 2) {      // facets are edges: tri holds [n_facets][2] vertex pairs
@@ -3822,6 +3841,7 @@ extern "C" int fs_assemble_facet_vector(fs_space_t space, int64_t n_facets, cons
 }
 
 extern "C" int fs_assemble_facet_matrix(fs_matrix_t A, int64_t n_facets, const int32_t* tri, const double* h) {
+    FS_REFUSE_DG(A, "fs_assemble_facet_matrix");
     FS_REQUIRE(A && (n_facets == 0 || (tri && h)), "fs_assemble_facet_matrix: null pointer");
     if (A->bs != 1) {
         fs_set_error("fs_assemble_facet_matrix: only scalar spaces (Robin/HTC term) are supported");
@@ -3921,6 +3941,7 @@ extern "C" int fs_apply_dirichlet(fs_matrix_t A, fs_vector_t b, int64_t n, const
     FS_REQUIRE(n == 0 || (dofs && vals), "fs_apply_dirichlet: null dof list");
     FS_REQUIRE(n < (int64_t)INT32_MAX, "fs_apply_dirichlet: list too long");
     if (n == 0) return FS_OK;
+    if (A && fs_is_dg(A->space)) return fs_dg_apply_dirichlet(A, b, n, dofs, vals, symmetric);
     hipStream_t s = fs_rt().stream;
     const int64_t n_dofs = A ? A->space->n_dofs_local : b->d.n;
     for (int64_t i = 0; i < n; ++i)
@@ -3972,6 +3993,7 @@ extern "C" int fs_apply_dirichlet(fs_matrix_t A, fs_vector_t b, int64_t n, const
 }
 
 extern "C" int fs_assemble_interior_penalty(fs_matrix_t A, int64_t n_facets, const int32_t* facet_cells, double coefficient) {
+    FS_REFUSE_DG(A, "fs_assemble_interior_penalty");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A && n_facets >= 0 && (n_facets == 0 || facet_cells), "fs_assemble_interior_penalty: bad arguments");
     fs_space_s* sp = A->space;

@@ -518,6 +518,7 @@ int fs_p2p_check(hipStream_t s) {
 static constexpr int P2P_MAX_NB = 16;
 static constexpr int P2P_REC = 4 + 3 * P2P_MAX_NB + 2 * P2P_HANDLE_DOUBLES;
 extern "C" int fs_space_enable_p2p_halo(fs_space_t space, int enable) {
+    FS_REFUSE_DG_SPACE(space, "fs_space_enable_p2p_halo");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(space, "fs_space_enable_p2p_halo: null space");
     static_assert(sizeof(hipIpcMemHandle_t) % sizeof(double) == 0, "handle size");
@@ -798,12 +799,14 @@ static int build_slice_split(fs_space_s* sp) {
 extern "C" int fs_space_set_halo_indexed(fs_space_t space, int n_neighbors, const int32_t* neighbor_ranks,
                                          const int64_t* send_counts, const int32_t* send_idx, const int64_t* recv_counts,
                                          const int32_t* recv_idx) {
+    FS_REFUSE_DG_SPACE(space, "fs_space_set_halo");
     FS_REQUIRE(n_neighbors == 0 || recv_idx, "fs_space_set_halo_indexed: null scatter list");
     return set_halo_impl(space, n_neighbors, neighbor_ranks, send_counts, send_idx, recv_counts, recv_idx);
 }
 
 extern "C" int fs_space_set_halo(fs_space_t space, int n_neighbors, const int32_t* neighbor_ranks,
                                  const int64_t* send_counts, const int32_t* send_idx, const int64_t* recv_counts) {
+    FS_REFUSE_DG_SPACE(space, "fs_space_set_halo");
     return set_halo_impl(space, n_neighbors, neighbor_ranks, send_counts, send_idx, recv_counts, nullptr);
 }
 
@@ -946,6 +949,7 @@ extern "C" int fs_halo_exchange(fs_space_t space, fs_vector_t v) {
 // in the compute stream, and `reps` ghost refreshes of a scratch vector of this space (pack, grouped send / recv on the
 // communication stream, wait), each timed with HIP events on the compute stream.  Collective: every rank calls it.
 extern "C" int fs_comm_benchmark(fs_space_t space, int reps, double* allreduce_ms, double* halo_ms) {
+    FS_REFUSE_DG_SPACE(space, "fs_comm_benchmark");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(reps > 0, "fs_comm_benchmark: reps must be positive");
     if (allreduce_ms) *allreduce_ms = 0.0;

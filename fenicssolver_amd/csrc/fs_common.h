@@ -235,6 +235,14 @@ struct fs_halo_plan {
 struct fs_space_s {
     const uint64_t serial = fs_next_serial();
     fs_mesh_s* mesh = nullptr;
+    int family = FS_FAMILY_CG;
+    // DG1 spaces (fs_dg.hip): neighbour across facet k of cell K at [k * nc + K] (-1: boundary), on the device and on the host;
+    // bit k of dg_plus[K]: K is the '+' side of facet k; vertex -> (cell * 4 + local vertex) incidences, ascending by cell (CSR)
+    dbuf<int32_t> dg_nbr;
+    std::vector<int32_t> dg_nbr_host;
+    dbuf<uint8_t> dg_plus;
+    dbuf<int32_t> dg_vptr, dg_vinc;
+    int64_t dg_interior_sides = 0;
     fs_visc_dev visc;             // Taylor-Hood spaces: the law attached by fs_space_set_viscosity_law (kind 0: the form's own fields)
     int degree = 1;
     int ncomp = 1;
@@ -404,6 +412,30 @@ int fs_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s);
 struct fs_amg_s;
 int fs_amg_apply_dev(fs_amg_s* amg, const double* r, double* z, hipStream_t s);
 int64_t fs_amg_rows(const fs_amg_s* amg);      // scalar rows of the finest level
+
+// fs_dg.hip: DG1 spaces and their cell-block matrices (the generic entry points hand DG handles over to these)
+int fs_dg_space_create(fs_mesh_s* mesh, int degree, int ncomp, fs_space_t* out);
+int fs_dg_matrix_create(fs_space_s* space, fs_matrix_t* out);
+int64_t fs_dg_matrix_nnz(const fs_space_s* sp);
+int fs_dg_matrix_get_csr(fs_matrix_s* A, int32_t* rowptr, int32_t* colidx, double* vals);
+int fs_dg_apply_dirichlet(fs_matrix_s* A, fs_vector_s* b, int64_t n, const int32_t* dofs, const double* vals, int symmetric);
+int fs_dg_spmv(fs_matrix_s* A, fs_vector_s* x, fs_vector_s* y);
+int fs_dg_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s);
+int64_t fs_dg_spmv_bytes(const fs_space_s* sp);
+int fs_dg_krylov_solve(fs_matrix_s* A, fs_vector_s* b, fs_vector_s* x, const fs_krylov_opts* opts, fs_krylov_stats* stats);
+// fs_krylov.hip: what fs_krylov_history / fs_last_product_kind report
+void fs_krylov_set_history(const std::vector<double>& rr);
+void fs_set_last_product_kind(int kind);
+static inline bool fs_is_dg(const fs_space_s* sp) { return sp && sp->family == FS_FAMILY_DG; }
+// entry points that are not built for DG spaces / matrices refuse them with FS_ERR_UNSUPPORTED
+#define FS_REFUSE_DG_SPACE(sp, name)                                                         \
+    do {                                                                                    \
+        if (fs_is_dg(sp)) {                                                                 \
+            fs_set_error("%s: not built for DG spaces", name);                             \
+            return FS_ERR_UNSUPPORTED;                                                      \
+        }                                                                                   \
+    } while (0)
+#define FS_REFUSE_DG(A, name) FS_REFUSE_DG_SPACE((A) ? (A)->space : nullptr, name)
 
 // fs_saddle.hip: the law a Taylor-Hood space carries, else kind 1 from (p_ref, exponent) > 0, else Newtonian
 fs_visc_dev fs_space_viscosity(const fs_space_s* sp, double legacy_pref, double legacy_exp);

@@ -494,6 +494,7 @@ struct triple {
 }  // namespace
 
 extern "C" int fs_spmv_multi(fs_matrix_t A, int m, const fs_vector_t* X, fs_vector_t* Y) {
+    FS_REFUSE_DG(A, "fs_spmv_multi");
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A && X && Y && m >= 1, "fs_spmv_multi: bad arguments");
@@ -536,6 +537,7 @@ extern "C" int fs_vector_gram(int p, const fs_vector_t* X, int q, const fs_vecto
 
 extern "C" int fs_eigen_solve(fs_matrix_t K, fs_matrix_t M, fs_amg_t precond, int64_t n_constrained, const int32_t* constrained,
                               const fs_eigen_opts* opts, double* eigenvalues, fs_vector_t* modes, fs_eigen_stats* stats) {
+    FS_REFUSE_DG(K, "fs_eigen_solve"); FS_REFUSE_DG(M, "fs_eigen_solve");
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     FS_REQUIRE(K && M && opts && eigenvalues && modes && stats, "fs_eigen_solve: null pointer");

@@ -416,6 +416,7 @@ __global__ void k_hyper_cells_finish(int nb, const double* __restrict__ part_e, 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, const fs_hyper_form* form,
                                         int what, fs_hyper_info* info) {
+    FS_REFUSE_DG_SPACE(space, "fs_assemble_hyperelastic"); FS_REFUSE_DG(K, "fs_assemble_hyperelastic");
     FS_REQUIRE(space && u && form, "fs_assemble_hyperelastic: null pointer");
     FS_REQUIRE((what & ~(FS_HYPER_TANGENT | FS_HYPER_FORCE | FS_HYPER_ENERGY)) == 0, "fs_assemble_hyperelastic: unknown bits in what (%d)", what);
     FS_REQUIRE(form->model == FS_HYPER_NEO_HOOKEAN, "fs_assemble_hyperelastic: unknown energy model %d (FS_HYPER_NEO_HOOKEAN only)", form->model);

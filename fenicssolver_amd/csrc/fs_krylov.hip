@@ -1396,6 +1396,7 @@ static int spmv_overlapped(fs_matrix_s* A, double* x, double* y, const double* r
 #include "fs_krylov_block4.inc"      // the product of 4 x 4-block Taylor-Hood operators (k_sell_spmv4_rows, k_sell_spmv4_ksplit)
 
 int fs_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s) {
+    if (fs_is_dg(A->space)) return fs_dg_spmv_dev(A, x, y, s);
     if (A->bs == 4 && !getenv("FS_SPMV4_GENERIC")) {
         fs_space_s* sp = A->space;
         // one slice per workgroup while the grid allows it (dynamic balance)
@@ -1441,6 +1442,7 @@ extern "C" int fs_last_product_kind(void) { return g_last_product_kind; }
 
 extern "C" int fs_spmv(fs_matrix_t A, fs_vector_t x, fs_vector_t y) {
     FS_REQUIRE(A && x && y, "fs_spmv: null pointer");
+    if (fs_is_dg(A->space)) return fs_dg_spmv(A, x, y);
     fs_space_s* sp = A->space;
     FS_REQUIRE(x->d.n >= sp->n_dofs_local, "fs_spmv: x has %lld entries, needs %lld (owned + ghost)", (long long)x->d.n, (long long)sp->n_dofs_local);
     FS_REQUIRE(y->d.n >= sp->n_dofs_owned, "fs_spmv: y too short");
@@ -1457,6 +1459,7 @@ extern "C" int fs_spmv(fs_matrix_t A, fs_vector_t x, fs_vector_t y) {
 // at its end), else the streaming product; *row_classes = number of distinct rows used (0: streaming).  The two products agree bit
 // for bit (same offsets, same order of summation) - this entry point exists so that tests and users can check exactly that.
 extern "C" int fs_spmv_dictionary(fs_matrix_t A, fs_vector_t x, fs_vector_t y, int* row_classes) {
+    FS_REFUSE_DG(A, "fs_spmv_dictionary");
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A && x && y, "fs_spmv_dictionary: null pointer");
@@ -1477,6 +1480,7 @@ extern "C" int fs_spmv_dictionary(fs_matrix_t A, fs_vector_t x, fs_vector_t y, i
 }
 
 extern "C" int fs_spmv_benchmark(fs_matrix_t A, fs_vector_t x, fs_vector_t y, int reps, double* ms_per_launch) {
+    FS_REFUSE_DG(A, "fs_spmv_benchmark");
     FS_REQUIRE(A && x && y && ms_per_launch && reps != 0, "fs_spmv_benchmark: bad arguments");
     // reps < 0: time the CG flavour (SpMV fused with the three dot products, r := y)
     const bool fused = reps < 0;
@@ -1600,6 +1604,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A && b && x && opts, "fs_krylov_solve: null pointer");
+    if (fs_is_dg(A->space)) return fs_dg_krylov_solve(A, b, x, opts, stats);
     if (opts->method != FS_KSP_CG && opts->method != FS_KSP_BICGSTAB) {
         fs_set_error("fs_krylov_solve: unknown Krylov method %d", opts->method);
         return FS_ERR_UNSUPPORTED;
@@ -2445,6 +2450,9 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
     }
     return FS_OK;
 }
+
+void fs_krylov_set_history(const std::vector<double>& rr) { g_ws.last_hist = rr; }
+void fs_set_last_product_kind(int kind) { g_last_product_kind = kind; }
 
 extern "C" int fs_krylov_history(double* out, int capacity, int* count) {
     const int n = (int)g_ws.last_hist.size();

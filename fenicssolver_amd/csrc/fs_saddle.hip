@@ -722,6 +722,7 @@ fs_visc_dev fs_space_viscosity(const fs_space_s* sp, double legacy_pref, double 
 }
 
 extern "C" int fs_space_set_viscosity_law(fs_space_t th_space, const fs_viscosity_law* law) {
+    FS_REFUSE_DG_SPACE(th_space, "fs_space_set_viscosity_law");
     FS_REQUIRE(th_space, "fs_space_set_viscosity_law: null space");
     fs_visc_dev V;
     if (law && law->kind) {
@@ -745,6 +746,7 @@ extern "C" int fs_space_set_viscosity_law(fs_space_t th_space, const fs_viscosit
 
 extern "C" int fs_assemble_navier_stokes(fs_matrix_t J, fs_vector_t g, fs_vector_t w0, fs_vector_t w_prev,
                                          const fs_ns_form* form) {
+    FS_REFUSE_DG(J, "fs_assemble_navier_stokes");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(J && g && form, "fs_assemble_navier_stokes: null pointer");
     fs_space_s* sp = J->space;
@@ -1011,12 +1013,14 @@ extern "C" int fs_assemble_ns_pressure_boundary_nn(fs_matrix_t J, fs_vector_t g,
 extern "C" int fs_assemble_ns_pressure_boundary(fs_matrix_t J, fs_vector_t g, int64_t n_facets, const int32_t* facet_cell,
                                                 const int32_t* facet_opposite, const double* facet_value,
                                                 double kinematic_viscosity) {
+    FS_REFUSE_DG(J, "fs_assemble_ns_pressure_boundary");
     return fs_assemble_ns_pressure_boundary_nn(J, g, n_facets, facet_cell, facet_opposite, facet_value, kinematic_viscosity, nullptr, 0.0, 0.0, 1);
 }
 extern "C" int fs_assemble_ns_pressure_boundary_nn(fs_matrix_t J, fs_vector_t g, int64_t n_facets, const int32_t* facet_cell,
                                                    const int32_t* facet_opposite, const double* facet_value,
                                                    double kinematic_viscosity, fs_vector_t w0, double nn_pref, double nn_exp,
                                                    int values_per_facet) {
+    FS_REFUSE_DG(J, "fs_assemble_ns_pressure_boundary");
     FS_CHECK(fs_require_init());
     FS_REQUIRE(J && J->space && J->space->mesh, "fs_assemble_ns_pressure_boundary: null matrix");
     const int fverts = J->space->mesh->tdim;      // vertices of a boundary facet: 3 (triangle) or 2 (edge of a 2-D mesh)
@@ -1509,6 +1513,7 @@ static int sd_precond(fs_matrix_s* J, fs_matrix_s* Kp, fs_amg_s* Kp_amg, fs_matr
 
 extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, fs_matrix_t Mp, fs_vector_t b, fs_vector_t x,
                                const fs_saddle_opts* o, fs_krylov_stats* stats) {
+    FS_REFUSE_DG(J, "fs_saddle_solve"); FS_REFUSE_DG(Kp, "fs_saddle_solve"); FS_REFUSE_DG(Mp, "fs_saddle_solve");
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     FS_REQUIRE(J && Mp && b && x && o && stats, "fs_saddle_solve: null pointer");

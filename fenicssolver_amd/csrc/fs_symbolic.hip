@@ -1021,6 +1021,10 @@ static int space_create_impl(fs_mesh_t mesh, int family, int degree, int ncomp, 
                              fs_space_t* out) {
     FS_CHECK(fs_require_init());
     FS_REQUIRE(mesh && out, "fs_space_create: null pointer");
+    if (family == FS_FAMILY_DG) {
+        FS_REQUIRE(n_extra == 0, "fs_space_create_coupled: DG spaces carry their facet couplings already");
+        return fs_dg_space_create(mesh, degree, ncomp, out);
+    }
     // ncomp = 4 on CG2 nodes is the Taylor-Hood block layout (u_x, u_y, u_z, p) of fs_assemble_navier_stokes; on triangles the
     // u_z slot is a dummy unknown (unit row) so that the 2-D system runs through the same block-4 operator and solver
     if (family != FS_FAMILY_CG || (degree != 1 && degree != 2) || (ncomp != 1 && ncomp != 3 && ncomp != 4 && ncomp != 2) ||
@@ -1491,6 +1495,14 @@ static int space_create_impl(fs_mesh_t mesh, int family, int degree, int ncomp, 
 extern "C" int fs_space_info(fs_space_t space, int64_t* n_dofs_local, int64_t* n_dofs_owned, int64_t* nnz,
                              int64_t* sell_entries) {
     FS_REQUIRE(space, "fs_space_info: null space");
+    if (fs_is_dg(space)) {
+        const int64_t L = space->mesh->tdim + 1;
+        if (n_dofs_local) *n_dofs_local = space->n_dofs_local;
+        if (n_dofs_owned) *n_dofs_owned = space->n_dofs_owned;
+        if (nnz) *nnz = fs_dg_matrix_nnz(space);
+        if (sell_entries) *sell_entries = (L + 1) * L * L * space->mesh->nc;
+        return FS_OK;
+    }
     if (n_dofs_local) *n_dofs_local = space->n_dofs_local;
     if (n_dofs_owned) *n_dofs_owned = space->n_dofs_owned;
     if (nnz) *nnz = space->nnz_nodes * space->ncomp * space->ncomp;
@@ -1504,6 +1516,7 @@ extern "C" int fs_space_destroy(fs_space_t space) {
 }
 
 extern "C" int fs_space_format_info(fs_space_t space, int64_t* n_slices, int64_t* n_dia_slices, int64_t* spmv_bytes) {
+    FS_REFUSE_DG_SPACE(space, "fs_space_format_info");
     FS_REQUIRE(space, "fs_space_format_info: null space");
     if (n_slices) *n_slices = space->n_slices;
     if (n_dia_slices) *n_dia_slices = space->n_dia_slices;
@@ -1517,6 +1530,7 @@ extern "C" int fs_space_format_info(fs_space_t space, int64_t* n_slices, int64_t
 }
 
 extern "C" int fs_space_get_edges(fs_space_t space, int64_t* n_edges, int32_t* edges) {
+    FS_REFUSE_DG_SPACE(space, "fs_space_get_edges");
     FS_REQUIRE(space, "fs_space_get_edges: null space");
     if (n_edges) *n_edges = space->n_edges;
     if (edges && space->n_edges) FS_CHECK(space->edges.download(edges, 2 * space->n_edges, fs_rt().stream));

@@ -720,7 +720,15 @@ class FunctionSpace:
     2-vector.
     Component i of node n of an ncomp-vector space is dof n*ncomp + i (DOLFIN interleaves the same way).
     Periodic constraints (constrained_domain): P1 and P2, one GPU, slave dofs kept and tied (see periodic_pairs()).
-    Not built: degree > 2."""
+    Not built: degree > 2.
+    FunctionSpace(mesh, "DG" | "Discontinuous Lagrange", 1) returns a DGFunctionSpace (scalar discontinuous P1)."""
+
+    DG_FAMILIES = ("DG", "Discontinuous Lagrange")
+
+    def __new__(cls, mesh=None, family="CG", *args, **kwargs):
+        if cls is FunctionSpace and family in FunctionSpace.DG_FAMILIES:
+            return object.__new__(DGFunctionSpace)
+        return object.__new__(cls)
 
     def __init__(self, mesh, family="CG", degree=1, constrained_domain=None, _ncomp=1, _component=None,
                  _parent=None, _holder=False):
@@ -1246,6 +1254,145 @@ class FunctionSpace:
     def localizer(self):
         """None on one GPU; the global->local mapper of this rank's part otherwise (after device())."""
         return getattr(self.root(), "_localizer", None)
+
+
+class DGFunctionSpace(FunctionSpace):
+    """Discontinuous P1, scalar (FunctionSpace(mesh, "DG", 1), ScalarTransportDGSolver.py:47-57).  Dof (K, a) = (d+1) K + a in the
+    caller's cell numbering and the cell's listed vertex order; node_coordinates() gives the vertex of every dof, so Expressions,
+    interpolate and DirichletBC work as on CG1.  A DirichletBC on it constrains every dof whose vertex lies on a marked facet (the
+    "geometric" rule: cells that touch the boundary only at a vertex or an edge included).
+    The device copy (device()) lives on a device mesh of its own, in locality order for large file meshes, together with the CG1
+    space of the projection; ``dof_to_device`` / ``vertex_order`` translate between the numberings."""
+
+    def __init__(self, mesh, family="DG", degree=1, constrained_domain=None, _ncomp=1, _component=None, _parent=None, _holder=False):
+        if family not in FunctionSpace.DG_FAMILIES:
+            raise SolverError("DGFunctionSpace: family '{}' is not discontinuous Lagrange".format(family))
+        if int(degree) != 1:
+            raise SolverError("fe_degree {} is not built for DG spaces in fenicssolver_amd (DG1 only)".format(degree))
+        if _ncomp != 1:
+            raise SolverError("DG spaces are scalar in fenicssolver_amd")
+        if constrained_domain is not None:
+            raise SolverError("periodic_boundary (constrained_domain) is not built for DG spaces")
+        self._periodic = None
+        self._mesh = mesh
+        self._degree = 1
+        self._ufl_element = _Element("Discontinuous Lagrange", 1, 1)
+        self._ncomp = 1
+        self._component = None
+        self._parent = None
+        self._device = None
+        self._localizer = None
+        FunctionSpace._next_serial += 1
+        self._serial = FunctionSpace._next_serial
+
+    def periodic_pairs(self):
+        return None
+
+    def edge_nodes(self):
+        raise SolverError("DG1 spaces have no edge nodes")
+
+    def cell_nodes(self):
+        """[num_cells, d+1]: the dofs of every cell, (d+1) K + a."""
+        nc, nl = self._mesh.cells().shape
+        return np.arange(nc * nl, dtype=np.int64).reshape(nc, nl)
+
+    def num_nodes(self):
+        return self._mesh.cells().size
+
+    def dim(self):
+        return self.num_nodes()
+
+    def node_coordinates(self):
+        if getattr(self, "_node_co", None) is None:
+            self._node_co = self._mesh.coordinates()[self._mesh.cells().astype(np.int64).ravel()]
+            self._node_co.setflags(write=False)
+        return self._node_co
+
+    def vertex_dofs(self):
+        """Mesh vertex of every dof."""
+        return self._mesh.cells().astype(np.int64).ravel()
+
+    def facet_nodes(self, facet_ids):
+        """Dofs whose vertex lies on one of the given facets, ascending (the geometric rule of a DG DirichletBC)."""
+        verts = np.unique(self._mesh.facets()[facet_ids].astype(np.int64).ravel())
+        on = np.zeros(self._mesh.num_vertices(), dtype=bool)
+        on[verts] = True
+        out = np.nonzero(on[self.vertex_dofs()])[0]
+        out.setflags(write=False)
+        return out
+
+    def facet_node_table(self, facet_vertices):
+        raise SolverError("facet_node_table: not defined for DG spaces")
+
+    def sub(self, i):
+        raise SolverError("sub(): not a vector space")
+
+    def tabulate_dof_coordinates(self):
+        return self.node_coordinates()
+
+    def device(self, facet_coupling=False, renumber=None):
+        """The device side, built once: a record with ``space`` (backend.DeviceDGSpace), ``mesh``, ``cg1`` (the CG1 space of the
+        projection on the same device mesh), ``dof_to_device`` (API dof -> device dof), ``vertex_order`` (device vertex -> API
+        vertex), ``cell_order`` (device cell -> API cell).  File meshes of FunctionSpace.RENUMBER_MIN_VERTICES vertices or more are
+        uploaded in locality order (FS_RENUMBER = 0 / 1 pins the choice, renumber= overrides both).  The '+' side of every interior
+        facet follows the caller's numbering and the cell-region markers given to set_cell_markers()."""
+        if self._device is None:
+            from . import backend
+            mesh = self._mesh
+            co, ce = mesh.coordinates(), mesh.cells()
+            nc, nl = ce.shape
+            if renumber is None:
+                env = os.environ.get("FS_RENUMBER", "")
+                renumber = env == "1" or (env != "0" and getattr(mesh, "_box", None) is None and
+                                          mesh.num_vertices() >= FunctionSpace.RENUMBER_MIN_VERTICES)
+            if renumber:
+                vo, cord = backend.locality_order(co, ce)
+                inv = np.empty_like(vo)
+                inv[vo] = np.arange(len(vo), dtype=vo.dtype)
+                dmesh = backend.DeviceMesh(co[vo], inv[ce[cord].astype(np.int64)])
+            else:
+                vo, cord = np.arange(len(co), dtype=np.int32), np.arange(nc, dtype=np.int32)
+                dmesh = backend.DeviceMesh(co, ce)
+            d2a = (cord.astype(np.int64)[:, None] * nl + np.arange(nl)[None, :]).ravel()
+            a2d = np.empty_like(d2a)
+            a2d[d2a] = np.arange(d2a.size)
+            rec = _DGDevice()
+            rec.mesh, rec.vertex_order, rec.cell_order = dmesh, vo, cord
+            rec.dof_to_device, rec.device_to_dof = a2d, d2a
+            rec.space = backend.DeviceDGSpace(dmesh)
+            rec.cg1 = None
+            self._device = rec
+            self._push_plus_key()
+        return self._device
+
+    def set_cell_markers(self, markers):
+        """Cell-region markers (array or MeshFunction of dimension tdim, caller's numbering): on an interior facet whose two cells
+        carry different markers the cell with the larger marker is '+' (DOLFIN swaps the restriction on the subdomain data of dx)."""
+        arr = None if markers is None else np.asarray(markers.array() if hasattr(markers, "array") else markers, dtype=np.int64)
+        self._cell_markers = arr
+        if self._device is not None:
+            self._push_plus_key()
+
+    def plus_key(self):
+        """One int64 per caller cell: the '+' side of an interior facet is its cell with the larger key (lower cell number, or
+        larger marker where the markers differ)."""
+        nc = self._mesh.num_cells()
+        key = -np.arange(nc, dtype=np.int64)
+        mk = getattr(self, "_cell_markers", None)
+        if mk is not None:
+            key = key + mk.astype(np.int64) * nc
+        return key
+
+    def _push_plus_key(self):
+        rec = self._device
+        rec.space.set_plus_key(self.plus_key()[rec.cell_order.astype(np.int64)])
+
+    def localizer(self):
+        return None
+
+
+class _DGDevice:
+    pass
 
 
 def mesh_dim(space):

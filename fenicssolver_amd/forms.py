@@ -240,3 +240,32 @@ class NavierStokesForm:
                 "g2": None if self.g2 is None else [int(self.g2[0]), float(self.g2[1])],
                 "viscosity_law": None if self.viscosity_law is None else [float(self.viscosity_law[0]), float(self.viscosity_law[1])],
                 "newton": bool(self.newton)}
+
+
+class DGScalarForm:
+    """Upwind SIPG advection-diffusion on a DG1 space (ScalarTransportDGSolver.py:119-147): c a(T, v) - N(T; v) - int f v dx, with
+    constant conductivity (c kappa), capacity c, velocity beta and penalty alpha; transient: the theta = 1/2 scheme
+    c/dt int (T - T_prev) v dx + c (a(T, v) + a(T_prev, v)) / 2 - N(T; v) - int f v dx."""
+
+    def __init__(self, space):
+        self.space = space
+        self.conductivity = None      # c kappa (number)
+        self.capacity = None          # c (number)
+        self.velocity = None          # beta: d numbers
+        self.alpha = None
+        self.transient = False
+        self.dt = None
+        self.T_prev = None            # Function on the DG space
+        self.facet_loads = []         # [FacetLoad]: + int g v ds (g: number or [n_facets, d] vertex values)
+        self.robin = []               # [FacetRobin]: + int h (T - T_a) v ds
+        self.sources = []             # [VolumeCoefficient]: 'const', 'cell' [n_cells] or 'nodal' [n_dofs] (values at every dof)
+
+    def describe(self):
+        return {
+            "type": "dg_transport", "conductivity": self.conductivity, "capacity": self.capacity,
+            "velocity": None if self.velocity is None else tuple(float(x) for x in self.velocity), "alpha": self.alpha,
+            "transient": bool(self.transient), "dt": self.dt,
+            "facet_loads": [(f.marker_id, _plain(f.g), f.origin) for f in self.facet_loads],
+            "robin": [(r.marker_id, float(r.h), _plain(r.ambient)) for r in self.robin],
+            "sources": [s.describe() for s in self.sources],
+        }

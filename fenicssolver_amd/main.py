@@ -29,7 +29,8 @@ def load_settings(case_input):
     raise TypeError('{} is not supported as case input, only path string or dict'.format(type(case_input)))
 
 
-_SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "LinearElasticitySolver", "NonlinearElasticitySolver")
+_SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
+            "NonlinearElasticitySolver")
 
 
 def main(case_input):
@@ -37,6 +38,8 @@ def main(case_input):
     solver_name = settings['solver_name']
     if solver_name == "ScalarTransportSolver":
         from .ScalarTransportSolver import ScalarTransportSolver as cls
+    elif solver_name == "ScalarTransportDGSolver":
+        from .ScalarTransportDGSolver import ScalarTransportDGSolver as cls
     elif solver_name == "LinearElasticitySolver":
         from .LinearElasticitySolver import LinearElasticitySolver as cls
     elif solver_name == "NonlinearElasticitySolver":

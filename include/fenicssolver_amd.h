@@ -147,6 +147,12 @@ int fs_mesh_create_renumbered(int64_t nv, const double* xyz, int64_t nc, const i
  *      the sparsity pattern DOLFIN builds inside the first assemble()) --------- */
 
 #define FS_FAMILY_CG 0
+/* Discontinuous P1 (ScalarTransportDGSolver.py): degree 1, ncomp 1, one rank.  Dof (K, a) = (d+1) K + a in device cell order (a: the
+ * cell's local vertex).  The space holds the cell-facet adjacency (the cell across the facet opposite every local vertex), the '+'
+ * side of every interior facet (fs_space_dg_set_plus_key) and the vertex-to-cell incidences of the projection onto CG1.  Its matrices
+ * are cell blocks (fs_assemble_dg_transport); fs_space_info reports n_dofs_local = n_dofs_owned = (d+1) n_cells and the stored
+ * values as nnz / sell_entries. */
+#define FS_FAMILY_DG 1
 /* degree 1 with ncomp = 1 (scalar) or 3 (vector, node-interleaved dofs as DOLFIN's
  * VectorFunctionSpace lays them out; 2 on triangular meshes: plane-strain elasticity); triangular meshes also carry
  * degree-2 spaces, scalar or 2-vector (3 vertices + 3 edge nodes per cell, UFC edge i opposite vertex i); degree 2 with ncomp = 1 (scalar) or 4 (Taylor-Hood block u_x,u_y,u_z,p):
@@ -163,6 +169,10 @@ int fs_space_create_coupled(fs_mesh_t mesh, int family, int degree, int ncomp, i
                             fs_space_t* out);
 int fs_space_info(fs_space_t space, int64_t* n_dofs_local, int64_t* n_dofs_owned, int64_t* nnz,
                   int64_t* sell_entries);
+/* DG spaces: which cell of an interior facet is its '+' side (DOLFIN's interior-facet assembler, the restriction ('+') of h in
+ * ScalarTransportDGSolver.py): the one with the larger key[cell] (device cell order).  Without a call the key is minus the caller's
+ * cell number (the lower caller number is '+'); a caller with cell-region markers passes marker * n_cells - caller number. */
+int fs_space_dg_set_plus_key(fs_space_t space, const int64_t* key);
 /* A += coefficient * avg(h)^2 jump(grad u, n) jump(grad v, n) dS over the listed interior facets, h = 2 circumradius
  * (the 'IP' stabilisation of ScalarTransportSolver.py:312-315, coefficient = alpha * capacity).  facet_cells
  * [n_facets][2]: the two local cells of every facet.  Scalar CG1 on tetrahedra, space from fs_space_create_coupled. */
@@ -192,7 +202,11 @@ int fs_vector_destroy(fs_vector_t v);
 /* ---- matrices (PETSc AIJ behind dolfin.assemble, SolverBase.py:595, 608-612, 644) */
 
 /* A matrix on the space's sparsity pattern, values zero.  Rows = owned dofs,
- * columns = local (owned + ghost) dofs. */
+ * columns = local (owned + ghost) dofs.  On a DG space: (d+2) blocks of (d+1) x (d+1) values per cell - slot 0 the diagonal block,
+ * slot k+1 the coupling with the cell across facet k - stored with the cell index fastest.  DG matrices are accepted by
+ * fs_matrix_info, fs_matrix_zero, fs_matrix_get_csr (dof order, the zero blocks of boundary facets left out), fs_apply_dirichlet
+ * (symmetric = 0), fs_spmv, fs_krylov_solve (BiCGStab) and fs_assemble_dg_transport; every other entry point returns
+ * FS_ERR_UNSUPPORTED for them. */
 int fs_matrix_create(fs_space_t space, fs_matrix_t* out);
 int fs_matrix_info(fs_matrix_t A, int64_t* n_rows, int64_t* n_cols, int64_t* nnz);
 int fs_matrix_zero(fs_matrix_t A);
@@ -301,6 +315,38 @@ int fs_assemble_von_mises(fs_space_t disp_space, fs_vector_t u, double mu, doubl
 /* The same with one (mu, lambda) pair per cell: lame[n_cells][2] (host, device cell order). */
 int fs_assemble_von_mises_cells(fs_space_t disp_space, fs_vector_t u, const double* lame, fs_space_t p1_space, fs_vector_t b);
 
+/* ---- DG1 advection-diffusion (ScalarTransportDGSolver.py:119-147) -----------------------------------------------------------
+ * On a DG matrix: c a(T, v) with the upwind SIPG form
+ *   a(T, v) = sum_K int_K (kappa grad v . grad T - T beta . grad v) dx
+ *           + sum_F int_F (kappa alpha / h+ [v][T] - kappa {grad v}.n+ [T] - kappa [v] {grad T}.n+ + [v] (b+ T+ - b- T-)) ds
+ *           + sum_boundary int_F v max(beta . n, 0) T ds
+ * (conductivity = c kappa, h = 2 circumradius, n+ out of the '+' cell, b+- = max(+-beta . n+, 0)), times operator_scale, plus
+ * mass_scale int T v dx, plus int h_f T v ds over the listed boundary facets.  b (may be NULL): int source v dx (source: P1 values at
+ * every cell's vertices, [n_cells][d+1], device cell order, NULL = none) + int g v ds over the listed facets (facet_g[n_facets][d+1]:
+ * the load at the cell's local vertices, the entry of the vertex opposite unused; NULL = none).  Facets: facet_cell[i] (device cell),
+ * facet_local[i] (the local vertex opposite), boundary facets only.  One work item per cell writes its own block row: no atomics,
+ * two assemblies give the same bits.  add = 0 overwrites A (and b), 1 adds. */
+typedef struct fs_dg_form {
+    double conductivity;      /* c kappa */
+    double capacity;          /* c (multiplies the upwind terms) */
+    double velocity[3];       /* beta, constant (2-D: the z component is ignored) */
+    double alpha;             /* penalty: 500 in 3-D, 5 in 2-D in the reference */
+    double operator_scale;    /* 1 (steady), 1/2 (theta scheme, new step), -1/2 (theta scheme, the old step's right-hand side) */
+    double mass_scale;        /* c / dt of the transient term, 0 = none */
+    int64_t n_facets;
+    const int32_t* facet_cell;
+    const int32_t* facet_local;
+    const double* facet_h;    /* [n_facets] or NULL */
+    const double* facet_g;    /* [n_facets][d+1] or NULL */
+    const double* source;     /* [n_cells][d+1] or NULL */
+    int add;
+} fs_dg_form;
+int fs_assemble_dg_transport(fs_matrix_t A, fs_vector_t b, const fs_dg_form* form);
+/* Right-hand side of the L2 projection of a DG1 field onto CG1 (ScalarTransportDGSolver.py:194-197): b_i = int T_h phi_i dx, gathered
+ * per vertex over its cells in ascending order (no atomics).  V_cg1: scalar CG1 space on the SAME mesh; b has n_vertices entries.
+ * The projection is then fs_assemble_matrix(mass = 1) on V_cg1 + fs_krylov_solve. */
+int fs_assemble_dg_projection(fs_space_t V_dg, fs_vector_t x, fs_space_t V_cg1, fs_vector_t b);
+
 /* ---- Hyperelasticity (NonlinearElasticitySolver.py:41-98) -------------------------------------------------------------------
  * Compressible neo-Hookean energy  psi = mu/2 (tr F^T F - 3) - mu ln J + lambda/2 (ln J)^2,  F = I + grad u,  J = det F
  * (2-D, plane strain: F is 2 x 2 and the reference's "- 3" is kept).  fs_assemble_hyperelastic evaluates at the displacement u,
@@ -388,6 +434,12 @@ int fs_operator_apply(fs_space_t V, const fs_bilinear_form* form, fs_vector_t x,
 #define FS_KSP_BICGSTAB 1 /* non-symmetric operators (advection); PETSc KSPBCGS, right Jacobi */
 #define FS_PC_NONE 0
 #define FS_PC_JACOBI 1
+#define FS_PC_BLOCK_JACOBI 2 /* DG matrices only: the inverse of every cell's diagonal block, computed on the device at solve start.
+                              * On a DG matrix fs_krylov_solve runs BiCGStab (right-preconditioned) and honours norm_type: with
+                              * FS_NORM_PRECONDITIONED (and a preconditioner) it stops only when ||b - A x||_2 <= max(rtol ||b||_2, atol)
+                              * AND ||M^-1 (b - A x)||_2 <= max(rtol ||M^-1 b||_2, atol) (bnorm / rel_residual / true_rel_residual stay
+                              * in the plain norm); converged = 1 only when the TRUE residual meets the test (the recurrence restarts
+                              * from b - A x while that still lowers it) */
 #define FS_NORM_UNPRECONDITIONED 0 /* ||b - A x||_2 <= rtol ||b||_2 (BASELINE.json's definition) */
 #define FS_NORM_PRECONDITIONED 1   /* ||D^-1 (b - A x)||_2 <= rtol ||D^-1 b||_2: PETSc's KSPCG default, robust when
                                     * constrained (identity) rows and physical rows differ by orders of magnitude */
@@ -438,7 +490,7 @@ typedef struct fs_krylov_stats {
                              * recurrence return on the status word - launches - iterations of them, a few microseconds each */
     int product_kind;       /* kernel family of the solve's products (fs_last_product_kind): 0 streaming, 1 row-dictionary work items
                              * (also inside the one-launch iteration), 2 lattice tiles, 3 marching windows of a P1 box, 4 block rows,
-                             * 5 marching windows of a CG2 box in lattice order */
+                             * 5 marching windows of a CG2 box in lattice order, 6 DG cell blocks (k_dg_spmv) */
 } fs_krylov_stats;
 
 int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, const fs_krylov_opts* opts,
@@ -462,7 +514,7 @@ int fs_spmv_dictionary(fs_matrix_t A, fs_vector_t x, fs_vector_t y, int* row_cla
  * analogue is the -log_view line of MatMult): 0 streaming SELL / DIA kernels, 1 row-dictionary work items (k_dict_spmv), 2 lattice
  * tiles of a CG2 box (k_lattice_spmv), 3 marching windows of a P1 box (k_box_spmv, round 6: options "box_spmv" 1 / 0 and
  * "box_min_rows", default 1 500 000), 4 block-row dictionary (k_dict_spmv3), 5 marching windows of a CG2 box in lattice order
- * (k_lat_march, round 6: option "lattice_march" 1 / 0).  The one-launch iteration k_dict_cg_iter does not count as a product here. */
+ * (k_lat_march, round 6: option "lattice_march" 1 / 0), 6 DG cell blocks (k_dg_spmv).  The one-launch iteration k_dict_cg_iter does not count as a product here. */
 int fs_last_product_kind(void);
 
 /* ---- smoothed-aggregation AMG (PETScPreconditioner("petsc_amg") + set_near_nullspace,
