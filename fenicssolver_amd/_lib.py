@@ -95,7 +95,19 @@ class fs_viscosity_law(C.Structure):
 class fs_saddle_opts(C.Structure):
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_iter", C.c_int), ("restart", C.c_int),
                 ("kinematic_viscosity", C.c_double), ("density", C.c_double), ("inv_dt", C.c_double),
-                ("velocity_sweeps", C.c_int), ("inner_rtol", C.c_double), ("nonzero_guess", C.c_int)]
+                ("velocity_sweeps", C.c_int), ("inner_rtol", C.c_double), ("nonzero_guess", C.c_int),
+                ("block_upper", C.c_int), ("a0", C.c_void_p), ("a0_amg", C.c_void_p), ("a0_rtol", C.c_double),
+                ("schur_scale", C.c_double)]
+
+
+class fs_ld_form(C.Structure):
+    _fields_ = [("dt", C.c_double), ("q", C.c_double), ("mu", C.c_double), ("lambda_", C.c_double), ("body_force", C.c_double * 3),
+                ("dirichlet", C.c_void_p), ("n_facets", C.c_int64), ("facet_cell", C.c_void_p), ("facet_opposite", C.c_void_p),
+                ("facet_g", C.c_void_p)]
+
+
+class fs_ld_info(C.Structure):
+    _fields_ = [("residual_norm", C.c_double), ("n_bad", C.c_int64), ("first_bad_cell", C.c_int64)]
 
 
 class fs_amg_opts(C.Structure):
@@ -195,6 +207,7 @@ SIGNATURES = {
     "fs_assemble_dg_transport": (C.c_int, [_H, _H, C.POINTER(fs_dg_form)]),
     "fs_assemble_dg_projection": (C.c_int, [_H, _H, _H, _H]),
     "fs_assemble_hyperelastic": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_hyper_form), C.c_int, C.POINTER(fs_hyper_info)]),
+    "fs_assemble_large_deformation": (C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),
     "fs_comm_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -834,6 +834,45 @@ def saddle_solve(J, Kp, Mp, b, x, nu, rho=1.0, inv_dt=0.0, rtol=1e-8, atol=0.0, 
     return {k: getattr(st, k) for k, _ in L.fs_krylov_stats._fields_}
 
 
+def assemble_large_deformation(J, rhs, u, w, u0, w0, dt, q, mu, lmbda, dirichlet, body_force=(0.0, 0.0, 0.0), facet_cell=None,
+                               facet_opposite=None, facet_g=None):
+    """Reduced Newton system of one Crank-Nicolson step of large-deformation elasticity (fs_assemble_large_deformation): J and rhs
+    on the CG1 block-4 space, u / u0 vector CG1 dof vectors, w / w0 block vectors (v, p).  dirichlet: uint8 per vertex (bits 0-2
+    displacement, 3-5 velocity, 6 pressure).  Facets (device cells, local opposite vertex, g [nf, 3]) carry follower loads.
+    Returns {'residual_norm', 'n_bad', 'first_bad_cell'}."""
+    f = L.fs_ld_form()
+    f.dt, f.q, f.mu, f.lambda_ = float(dt), float(q), float(mu), float(lmbda)
+    for i, x in enumerate(tuple(body_force)[:3]):
+        f.body_force[i] = float(x)
+    dm = np.ascontiguousarray(dirichlet, dtype=np.uint8)
+    f.dirichlet = dm.ctypes.data
+    keep = [dm]
+    if facet_cell is not None and len(facet_cell):
+        fc, fo = L.i32(facet_cell), L.i32(facet_opposite)
+        g = np.zeros((len(fc), 3))
+        gg = np.asarray(facet_g, dtype=np.float64).reshape(len(fc), -1)
+        g[:, :gg.shape[1]] = gg
+        keep += [fc, fo, g]
+        f.n_facets, f.facet_cell, f.facet_opposite, f.facet_g = len(fc), fc.ctypes.data, fo.ctypes.data, g.ctypes.data
+    info = L.fs_ld_info()
+    L.check(L.load().fs_assemble_large_deformation(J.h, rhs.h, u.h, w.h, u0.h, w0.h, C.byref(f), C.byref(info)),
+            "fs_assemble_large_deformation")
+    del keep
+    return {"residual_norm": info.residual_norm, "n_bad": int(info.n_bad), "first_bad_cell": int(info.first_bad_cell)}
+
+
+def large_deformation_solve(J, Mp, b, x, a0, schur_scale, a0_amg=None, a0_rtol=0.0, rtol=1e-10, atol=0.0, max_iter=0, restart=0):
+    """FGMRES of fs_saddle_solve on the reduced large-deformation operator, right-preconditioned by the block upper triangular
+    [A J_vp; 0 S]^-1: S = schur_scale * Mp, A^-1 one V-cycle of a0_amg or Jacobi-CG on a0 to a0_rtol."""
+    o = L.fs_saddle_opts()
+    o.rtol, o.atol, o.max_iter, o.restart = float(rtol), float(atol), int(max_iter), int(restart)
+    o.block_upper, o.a0, o.a0_rtol, o.schur_scale = 1, a0.h, float(a0_rtol), float(schur_scale)
+    o.a0_amg = a0_amg.h if a0_amg is not None else None
+    st = L.fs_krylov_stats()
+    L.check(L.load().fs_saddle_solve(J.h, None, None, Mp.h, b.h, x.h, C.byref(o), C.byref(st)), "fs_saddle_solve")
+    return {k: getattr(st, k) for k, _ in L.fs_krylov_stats._fields_}
+
+
 def krylov_history():
     n = C.c_int(0)
     L.load().fs_krylov_history(None, 0, C.byref(n))

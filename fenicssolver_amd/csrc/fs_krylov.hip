@@ -1398,6 +1398,7 @@ static int spmv_overlapped(fs_matrix_s* A, double* x, double* y, const double* r
 int fs_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s) {
     if (fs_is_dg(A->space)) return fs_dg_spmv_dev(A, x, y, s);
     if (A->bs == 4 && !getenv("FS_SPMV4_GENERIC")) {
+        g_last_product_kind = 4;      // block rows
         fs_space_s* sp = A->space;
         // one slice per workgroup while the grid allows it (dynamic balance)
         const int grid = (int)std::min<int64_t>(sp->n_slices, 65535);

@@ -1394,6 +1394,9 @@ struct saddle_ws {
     double serial = 0.0;
     dbuf<uint8_t> ident;
     fs_vector_s rp, p1, p2;
+    fs_vector_s ldt, ldz;       // block_upper: the velocity residual / correction on the vector CG1 space of a0
+    dbuf<double> ldy, ldjy;     // block_upper: (0, z_p) and J (0, z_p)
+    int64_t ld_nvec = -1;       // block_upper: n_nodes * tdim the velocity buffers were sized for
     std::vector<dbuf<double>*> V, Z;
     ~saddle_ws() {
         if (h_poll) (void)hipHostFree(h_poll);
@@ -1511,6 +1514,100 @@ static int sd_precond(fs_matrix_s* J, fs_matrix_s* Kp, fs_amg_s* Kp_amg, fs_matr
     return FS_OK;
 }
 
+// ---- block_upper: the large-deformation preconditioner on a CG1 block-4 operator ---------------------------------------------
+// rp[v] = r[4v+3]
+__global__ void k_ld_take_p(int64_t nv, const double* __restrict__ r, double* __restrict__ rp) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += stride) rp[v] = r[4 * v + 3];
+}
+// y = (0, 0, 0, z_p) per vertex: z_p = c p[v], or r_p on identity pressure rows
+__global__ void k_ld_put_p(int64_t nv, double c, const double* __restrict__ p, const double* __restrict__ r, const uint8_t* __restrict__ ident,
+                           double* __restrict__ y) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += stride) {
+        y[4 * v] = 0.0; y[4 * v + 1] = 0.0; y[4 * v + 2] = 0.0; y[4 * v + 3] = ident[v] ? r[4 * v + 3] : c * p[v];
+    }
+}
+// t[v*d + i] = r[4v+i] - jy[4v+i], i < d
+__global__ void k_ld_take_v(int64_t nv, int d, const double* __restrict__ r, const double* __restrict__ jy, double* __restrict__ t) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += stride)
+        for (int i = 0; i < d; ++i) t[v * d + i] = r[4 * v + i] - jy[4 * v + i];
+}
+// z = (zv, [r dummy slot], y_p)
+__global__ void k_ld_put_z(int64_t nv, int d, const double* __restrict__ zv, const double* __restrict__ y, const double* __restrict__ r,
+                           double* __restrict__ z) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += stride) {
+        for (int i = 0; i < d; ++i) z[4 * v + i] = zv[v * d + i];
+        if (d == 2) z[4 * v + 2] = r[4 * v + 2];
+        z[4 * v + 3] = y[4 * v + 3];
+    }
+}
+// pressure rows of the reduced operator that are identity rows: a unit (3,3) diagonal and nothing else in block-row 3
+__global__ void k_ld_ident_p(int64_t nv, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col,
+                             const double* __restrict__ val, int64_t plane, uint8_t* __restrict__ ident) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nv; r += stride) {
+        const int64_t sp0 = slice_ptr[r >> 6];
+        const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
+        const int64_t base = sp0 + (r & 63);
+        bool id = true;
+        for (int k = 0; k < width && id; ++k) {
+            const int64_t e = base + (int64_t)k * FS_SLICE;
+            const int32_t col = sell_col[e];
+            if (col < 0) continue;                       // padding
+            const bool diag = col == (int32_t)r;
+            for (int j = 0; j < 4; ++j)
+                if (val[(12 + j) * plane + e] != ((diag && j == 3) ? 1.0 : 0.0)) id = false;
+        }
+        ident[r] = id ? 1 : 0;
+    }
+}
+
+// z = [A J_vp; 0 S]^-1 r: z_p = S^-1 r_p, then z_v = A^-1 (r_v - J_vp z_p)
+static int sd_precond_ld(fs_matrix_s* J, fs_matrix_s* Mp, const fs_saddle_opts* o, saddle_ws& W, const double* r, double* z, int* inner_its,
+                         hipStream_t s) {
+    fs_space_s* sp = J->space;
+    const int64_t nv = sp->n_nodes_owned;
+    const int d = sp->mesh->tdim;
+    const int gq = fs_grid_for(nv, FS_BLOCK, 2048);
+    hipLaunchKernelGGL(k_ld_take_p, dim3(gq), dim3(FS_BLOCK), 0, s, nv, r, W.rp.d.p);
+    {   // Mp^-1: 5 Chebyshev steps on the Jacobi-scaled P1 mass matrix (spectrum in [1/2, 5/2]), as in sd_precond
+        const double lo = 0.5, up = 2.5, theta = 0.5 * (up + lo), delta = 0.5 * (up - lo), sigma = theta / delta;
+        double rho_c = 1.0 / sigma;
+        hipLaunchKernelGGL(k_sd_cheb<true>, dim3(gq), dim3(FS_BLOCK), 0, s, nv, W.mdinv.p, W.rp.d.p, (const double*)nullptr, W.md.p, W.p2.d.p, 1.0 / theta, 0.0);
+        for (int k = 1; k < 5; ++k) {
+            FS_CHECK(fs_spmv_dev(Mp, W.p2.d.p, W.mt.p, s));
+            const double rho_new = 1.0 / (2.0 * sigma - rho_c);
+            hipLaunchKernelGGL(k_sd_cheb<false>, dim3(gq), dim3(FS_BLOCK), 0, s, nv, W.mdinv.p, W.rp.d.p, W.mt.p, W.md.p, W.p2.d.p, 2.0 * rho_new / delta, rho_new * rho_c);
+            rho_c = rho_new;
+        }
+    }
+    hipLaunchKernelGGL(k_ld_put_p, dim3(gq), dim3(FS_BLOCK), 0, s, nv, 1.0 / o->schur_scale, W.p2.d.p, r, W.ident.p, W.ldy.p);
+    FS_CHECK(fs_spmv_dev(J, W.ldy.p, W.ldjy.p, s));
+    hipLaunchKernelGGL(k_ld_take_v, dim3(gq), dim3(FS_BLOCK), 0, s, nv, d, r, W.ldjy.p, W.ldt.d.p);
+    FS_KERNEL_CHECK();
+    if (o->a0_amg) {
+        FS_CHECK(fs_amg_apply_dev(o->a0_amg, W.ldt.d.p, W.ldz.d.p, s));
+    } else {
+        fs_krylov_opts ko;
+        memset(&ko, 0, sizeof(ko));
+        ko.method = FS_KSP_CG;
+        ko.precond = FS_PC_JACOBI;
+        ko.rtol = o->a0_rtol > 0.0 ? o->a0_rtol : 1e-2;
+        ko.max_iter = 500;
+        ko.norm_type = FS_NORM_UNPRECONDITIONED;
+        fs_krylov_stats ks;
+        const int rc = fs_krylov_solve(o->a0, &W.ldt, &W.ldz, &ko, &ks);
+        if (rc != FS_OK && rc != FS_ERR_NUMERIC) return rc;
+        *inner_its += ks.iterations;
+    }
+    hipLaunchKernelGGL(k_ld_put_z, dim3(gq), dim3(FS_BLOCK), 0, s, nv, d, W.ldz.d.p, W.ldy.p, r, z);
+    FS_KERNEL_CHECK();
+    return FS_OK;
+}
+
 extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, fs_matrix_t Mp, fs_vector_t b, fs_vector_t x,
                                const fs_saddle_opts* o, fs_krylov_stats* stats) {
     FS_REFUSE_DG(J, "fs_saddle_solve"); FS_REFUSE_DG(Kp, "fs_saddle_solve"); FS_REFUSE_DG(Mp, "fs_saddle_solve");
@@ -1518,7 +1615,17 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
     FS_CHECK(fs_require_init());
     FS_REQUIRE(J && Mp && b && x && o && stats, "fs_saddle_solve: null pointer");
     fs_space_s* sp = J->space;
-    FS_REQUIRE(J->bs == 4 && sp->degree == 2, "fs_saddle_solve: the operator must be a Taylor-Hood block matrix");
+    const bool ld = o->block_upper != 0;
+    if (ld) {
+        FS_REQUIRE(J->bs == 4 && sp->degree == 1 && fs_rt().n_ranks == 1 && sp->n_nodes_owned == sp->n_nodes_local,
+                   "fs_saddle_solve: block_upper needs the CG1 block-4 operator of fs_assemble_large_deformation on one rank");
+        FS_REQUIRE(o->a0 && o->a0->space->mesh == sp->mesh && o->a0->space->ncomp == sp->mesh->tdim &&
+                   o->a0->space->degree == 1, "fs_saddle_solve: block_upper needs a0 on the vector CG1 space of the same mesh");
+        FS_REQUIRE(o->schur_scale > 0.0 && isfinite(o->schur_scale), "fs_saddle_solve: block_upper needs schur_scale > 0");
+        FS_REQUIRE(!o->a0_amg || fs_amg_rows(o->a0_amg) == o->a0->space->n_dofs_owned, "fs_saddle_solve: a0_amg is not a hierarchy of a0");
+    } else {
+        FS_REQUIRE(J->bs == 4 && sp->degree == 2, "fs_saddle_solve: the operator must be a Taylor-Hood block matrix");
+    }
     const bool multi = fs_rt().n_ranks > 1;
     const int64_t n = sp->n_dofs_owned, nl = sp->n_dofs_local, nv = sp->mesh->n_owned;
     FS_REQUIRE(Mp->bs == 1 && Mp->space->n_dofs_owned == nv && (!Kp || (Kp->bs == 1 && Kp->space->n_dofs_owned == nv)),
@@ -1538,9 +1645,14 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
     static int64_t g_ws_n = -1;
     static int g_ws_m = -1;
     const int dot_blocks = 512;
-    static int64_t g_ws_nl = -1;
-    if (g_ws && (g_ws_n != n || g_ws_m != m || g_ws_nl != nl)) { delete g_ws; g_ws = nullptr; }
+    static int64_t g_ws_nl = -1, g_ws_nv = -1, g_ws_npl = -1;
+    // every buffer below is sized by these: the operator's rows, the restart length, the local dofs, the owned vertices (pressure
+    // buffers) and the pressure space's local dofs
+    const int64_t npl = Mp->space->n_dofs_local;
+    if (g_ws && (g_ws_n != n || g_ws_m != m || g_ws_nl != nl || g_ws_nv != nv || g_ws_npl != npl)) { delete g_ws; g_ws = nullptr; }
     g_ws_nl = nl;
+    g_ws_nv = nv;
+    g_ws_npl = npl;
     const bool fresh = g_ws == nullptr;
     if (fresh) { g_ws = new saddle_ws(); g_ws_n = n; g_ws_m = m; }
     saddle_ws& W = *g_ws;
@@ -1595,12 +1707,25 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
         const int rc_ws = build_ws();
         if (rc_ws != FS_OK) { delete g_ws; g_ws = nullptr; return rc_ws; }
     }
+    if (ld && (W.ldy.n != n || W.ld_nvec != sp->n_nodes_owned * sp->mesh->tdim)) {
+        const int64_t nvec = sp->n_nodes_owned * sp->mesh->tdim;
+        W.ld_nvec = -1;
+        FS_CHECK(W.ldy.alloc(n));
+        FS_CHECK(W.ldjy.alloc(n));
+        FS_CHECK(W.ldt.d.alloc(nvec));
+        FS_CHECK(W.ldz.d.alloc(nvec));
+        FS_CHECK(W.ldz.d.zero(s));
+        W.ld_nvec = nvec;
+    }
     {
         fs_space_s* q = Mp->space;
         hipLaunchKernelGGL(k_sd_scalar_dinv, dim3(fs_grid_for(nv)), dim3(FS_BLOCK), 0, s, nv, q->slice_ptr.p, q->sell_col.p, Mp->val.p, W.mdinv.p);
     }
     hipLaunchKernelGGL(k_sd_diag, dim3(fs_grid_for(sp->n_nodes_owned)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, J->val.p, sp->sell_entries, W.dinv.p);
-    hipLaunchKernelGGL(k_sd_ident_p, dim3(fs_grid_for(nv)), dim3(FS_BLOCK), 0, s, nv, sp->slice_ptr.p, sp->sell_col.p, J->val.p, sp->sell_entries, W.ident.p);
+    if (ld)
+        hipLaunchKernelGGL(k_ld_ident_p, dim3(fs_grid_for(nv)), dim3(FS_BLOCK), 0, s, nv, sp->slice_ptr.p, sp->sell_col.p, J->val.p, sp->sell_entries, W.ident.p);
+    else
+        hipLaunchKernelGGL(k_sd_ident_p, dim3(fs_grid_for(nv)), dim3(FS_BLOCK), 0, s, nv, sp->slice_ptr.p, sp->sell_col.p, J->val.p, sp->sell_entries, W.ident.p);
     FS_KERNEL_CHECK();
 
     const int g = fs_grid_for(n, FS_BLOCK, 4096);
@@ -1627,7 +1752,7 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
     stats->bnorm = sqrt(bb);
     if (!o->nonzero_guess) FS_HIP(hipMemsetAsync(x->d.p, 0, (size_t)sp->n_dofs_local * sizeof(double), s));
     const double thr = std::max(o->rtol * stats->bnorm, o->atol);
-    int it = 0, conv = 0, inner = 0;
+    int it = 0, conv = 0, inner = 0, j_product_kind = 0;
     double res = 0.0;
     double* const dH = W.hs.p;
     double* const dcs = dH + (size_t)(m + 1) * m;
@@ -1641,7 +1766,7 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
     // 0.35 ms - the enqueue costs the host only 0.1 ms, it is not launch-bound - so direct launches stay the default.
     hipGraph_t pgraph = nullptr;
     hipGraphExec_t pexec = nullptr;
-    bool use_graph = getenv("FS_SADDLE_GRAPH") != nullptr && (!transient_kp || Kp_amg != nullptr) && !multi;
+    bool use_graph = getenv("FS_SADDLE_GRAPH") != nullptr && (!transient_kp || Kp_amg != nullptr) && !multi && !ld;
     if (use_graph) {
         FS_HIP(hipStreamSynchronize(s));
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
@@ -1659,7 +1784,7 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
             (void)hipGetLastError();
         }
     }
-    if (g_sd_timing) {      // back-to-back cost of the preconditioner, graph replay vs direct launches
+    if (g_sd_timing && !ld) {      // back-to-back cost of the preconditioner, graph replay vs direct launches
         int dummy = 0;
         (void)hipStreamSynchronize(s);
         auto t0g = std::chrono::steady_clock::now();
@@ -1744,6 +1869,8 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
                 FS_HIP(hipMemcpyAsync(W.gin.p, W.V[k]->p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
                 FS_HIP(hipGraphLaunch(pexec, s));
                 FS_HIP(hipMemcpyAsync(W.Z[k]->p, W.gout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            } else if (ld) {
+                FS_CHECK(sd_precond_ld(J, Mp, o, W, W.V[k]->p, W.Z[k]->p, &inner, s));
             } else {
                 FS_CHECK(sd_precond(J, Kp, Kp_amg, Mp, o, W, W.V[k]->p, W.Z[k]->p, &inner, s));
             }
@@ -1751,6 +1878,7 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
             if (dbg) { tB = std::chrono::steady_clock::now(); (void)hipStreamSynchronize(s); }
             auto tC = std::chrono::steady_clock::now();
             FS_CHECK(fs_spmv_dev(J, W.Z[k]->p, W.w.p, s));
+            j_product_kind = fs_last_product_kind();
             if (dbg) (void)hipStreamSynchronize(s);
             auto tD = std::chrono::steady_clock::now();
             // classical Gram-Schmidt with one fused multi-dot launch per pass; the last pointer of the list is w itself,
@@ -1810,6 +1938,7 @@ extern "C" int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, f
     stats->converged = conv;
     if (fs_p2p_reduce_enabled()) FS_CHECK(fs_p2p_check(s));      // a peer-to-peer wait timed out: the numbers below mean nothing
     stats->row_classes = 0;
+    if (ld) stats->product_kind = j_product_kind;      // the kernel family of the operator products J z
     stats->rel_residual = stats->bnorm > 0.0 ? res / stats->bnorm : 0.0;
     stats->true_rel_residual = stats->rel_residual;
     stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -331,12 +331,13 @@ class UnitCubeMesh(BoxMesh):
 
 class RectangleMesh(Mesh):
     """dolfin.RectangleMesh(Point, Point, nx, ny[, diagonal]): vertices x-fastest; per square (iy outer, ix inner) the
-    two triangles (v0, v1, v3), (v0, v2, v3) of the default "right" diagonal (examples/test_heat_transfer.py:34 uses
+    two triangles (v0, v1, v3), (v0, v2, v3) of the default "right" diagonal, or the four triangles around a centre vertex of
+    "crossed" (examples/test_heat_transfer.py:34 uses
     UnitSquareMesh(40, 40))."""
 
     def __init__(self, p0, p1, nx, ny, diagonal="right"):
-        if diagonal != "right":
-            raise SolverError("RectangleMesh: only the default 'right' diagonal is built")
+        if diagonal not in ("right", "crossed"):
+            raise SolverError("RectangleMesh: the 'right' and 'crossed' diagonals are built")
         a = (p0.array() if isinstance(p0, Point) else np.asarray(p0, dtype=np.float64))[:2]
         b = (p1.array() if isinstance(p1, Point) else np.asarray(p1, dtype=np.float64))[:2]
         nx, ny = int(nx), int(ny)
@@ -347,6 +348,17 @@ class RectangleMesh(Mesh):
         v0 = (iy * (nx + 1) + ix).ravel().astype(np.int64)
         v1, v2 = v0 + 1, v0 + (nx + 1)
         v3 = v2 + 1
+        if diagonal == "crossed":
+            # DOLFIN's numbering: the grid vertices as above, then one centre vertex per square in square order; four triangles
+            # per square, each with the centre as its last vertex (examples/test_large_deformation.py:48)
+            cx = a[0] + ((ix.ravel() + 0.5) * (b[0] - a[0])) / float(nx)
+            cy = a[1] + ((iy.ravel() + 0.5) * (b[1] - a[1])) / float(ny)
+            coords = np.concatenate([coords, np.stack([cx, cy], axis=1)])
+            c = (nx + 1) * (ny + 1) + np.arange(nx * ny, dtype=np.int64)
+            cells = np.stack([np.stack([v0, v1, c], axis=1), np.stack([v0, v2, c], axis=1), np.stack([v1, v3, c], axis=1),
+                              np.stack([v2, v3, c], axis=1)], axis=1).reshape(-1, 3)
+            Mesh.__init__(self, coords=coords, cells=cells)
+            return
         cells = np.stack([np.stack([v0, v1, v3], axis=1), np.stack([v0, v2, v3], axis=1)], axis=1).reshape(-1, 3)
         Mesh.__init__(self, coords=coords, cells=cells)
 

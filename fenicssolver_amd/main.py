@@ -30,7 +30,7 @@ def load_settings(case_input):
 
 
 _SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
-            "NonlinearElasticitySolver")
+            "NonlinearElasticitySolver", "LargeDeformationSolver")
 
 
 def main(case_input):
@@ -44,6 +44,8 @@ def main(case_input):
         from .LinearElasticitySolver import LinearElasticitySolver as cls
     elif solver_name == "NonlinearElasticitySolver":
         from .NonlinearElasticitySolver import NonlinearElasticitySolver as cls
+    elif solver_name == "LargeDeformationSolver":
+        from .LargeDeformationSolver import LargeDeformationSolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

@@ -120,3 +120,50 @@ def split(w):
     if T is not None:
         return u, p, T
     return u, p
+
+
+class LargeDeformationSpace(FunctionSpace):
+    """MixedElement([V, V, Q]) on CG1 of LargeDeformationSolver (LargeDeformationSolver.py:47-56): displacement u, velocity v and
+    pressure p.  Host layout: one block (u, v, p) of 2d + 1 values per vertex.  The device works on a vector CG1 displacement and
+    the (v_x, v_y, v_z, p) block of fs_assemble_large_deformation (triangles: (v_x, v_y, -, p))."""
+
+    def __init__(self, mesh):
+        d = mesh.geometry().dim()
+        if d not in (2, 3):
+            raise SolverError("the large-deformation space is built for triangular and tetrahedral meshes")
+        FunctionSpace.__init__(self, mesh, "CG", 1, _ncomp=2 * d + 1, _holder=True)
+        self._gdim = d
+        self._ufl_element = _Element("Mixed(P1^d x P1^d x P1)", 1, 2 * d + 1)
+
+    def displacement_space(self):
+        if getattr(self, "_u", None) is None:
+            self._u = FunctionSpace(self._mesh, "CG", 1, _ncomp=self._gdim)
+        return self._u
+
+    def pressure_space(self):
+        if getattr(self, "_q", None) is None:
+            self._q = FunctionSpace(self._mesh, "CG", 1)
+        return self._q
+
+    def num_sub_spaces(self):
+        return 3
+
+    def blocks(self, w):
+        """(u [nv, d], v [nv, d], p [nv]) views of a Function (or a dof array) of this space."""
+        a = (w.vector()._values() if isinstance(w, Function) else np.asarray(w)).reshape(-1, 2 * self._gdim + 1)
+        d = self._gdim
+        return a[:, :d], a[:, d:2 * d], a[:, 2 * d]
+
+
+def split_large_deformation(w):
+    """(u, v, p) copies of a Function of LargeDeformationSpace (dolfin: w.split(deepcopy=True))."""
+    W = w.function_space()
+    if not isinstance(W, LargeDeformationSpace):
+        raise SolverError("split_large_deformation(): not a (u, v, p) function")
+    u, v, p = W.blocks(w)
+    out = []
+    for arr, V in ((u, W.displacement_space()), (v, W.displacement_space()), (p, W.pressure_space())):
+        f = Function(V)
+        f.vector().set_local(np.ascontiguousarray(arr).reshape(-1))
+        out.append(f)
+    return tuple(out)

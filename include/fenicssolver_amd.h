@@ -155,7 +155,7 @@ int fs_mesh_create_renumbered(int64_t nv, const double* xyz, int64_t nc, const i
 #define FS_FAMILY_DG 1
 /* degree 1 with ncomp = 1 (scalar) or 3 (vector, node-interleaved dofs as DOLFIN's
  * VectorFunctionSpace lays them out; 2 on triangular meshes: plane-strain elasticity); triangular meshes also carry
- * degree-2 spaces, scalar or 2-vector (3 vertices + 3 edge nodes per cell, UFC edge i opposite vertex i); degree 2 with ncomp = 1 (scalar) or 4 (Taylor-Hood block u_x,u_y,u_z,p):
+ * degree-2 spaces, scalar or 2-vector (3 vertices + 3 edge nodes per cell, UFC edge i opposite vertex i); degree 2 with ncomp = 1 (scalar) or 4 (Taylor-Hood block u_x,u_y,u_z,p); degree 1 with ncomp = 4 (the (v_x,v_y,v_z,p) block of fs_assemble_large_deformation, one per vertex):
  * nodes = the vertices, then one node per edge, edges numbered lexicographically by their ascending vertex
  * pair - grouped by index difference first on structured meshes.  With ghost vertices
  * (n_owned < nv) the nodes are [owned vertices | owned edges | ghost vertices | ghost edges]; an edge belongs to
@@ -379,6 +379,36 @@ typedef struct fs_hyper_info {
 int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, const fs_hyper_form* form, int what,
                              fs_hyper_info* info);
 
+/* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
+ * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
+ * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
+ * (1-q) v0 where the displacement is free (0 where it is Dirichlet), so the Newton system is assembled for (dv, dp) only:
+ *   Jr = [J_vv + dt q J_vu, J_vp; dt q J_pu, J_pp] on the CG1 block-4 space (block (v_x, v_y, v_z, p) per vertex; triangles:
+ *        (v_x, v_y, -, p), the third slot an identity row), the J_xu columns of Dirichlet displacement components dropped;
+ *   rhs = [-R_v + dt J_vu r_u; -R_p + dt J_pu r_u] (block layout), zero on Dirichlet v / p rows, which become identity rows.
+ * u, u0: vector CG1 dof vectors (d per vertex); w, w0: block vectors (v, p) of the iterate and of the previous step.
+ * dirichlet[n_vertices] (host): bits 0-2 displacement components, 3-5 velocity components, 6 pressure.
+ * Facets: device cell and the cell's local vertex opposite the facet, g[n_facets][3] the load vector on the reference facet (its
+ * integral is added to R_v with the sign as given).  info->residual_norm: ||(R_u, R_v, R_p)||_2 with the Dirichlet rows left out;
+ * n_bad / first_bad_cell (caller's numbering, -1: none): cells with J == 0 or J not finite.  One rank; no atomics (a repeated call
+ * gives the same bits). */
+typedef struct fs_ld_form {
+    double dt, q, mu, lambda;
+    double body_force[3];       /* constant f of + int f . _v dx (the reference's sign) */
+    const uint8_t* dirichlet;
+    int64_t n_facets;
+    const int32_t* facet_cell;
+    const int32_t* facet_opposite;
+    const double* facet_g;
+} fs_ld_form;
+typedef struct fs_ld_info {
+    double residual_norm;
+    int64_t n_bad;
+    int64_t first_bad_cell;
+} fs_ld_info;
+int fs_assemble_large_deformation(fs_matrix_t Jr, fs_vector_t rhs, fs_vector_t u, fs_vector_t w, fs_vector_t u0, fs_vector_t w0,
+                                  const fs_ld_form* form, fs_ld_info* info);
+
 /* Right-hand sides of the L2 projection of the fluid stress  nu (grad u + grad u^T) - p I  onto CG1
  * (CoupledNavierStokesSolver.py:149-155, viscous_stress): b[vertex*9 + 3 i + j] = int sigma_ij phi_vertex dx for a
  * Taylor-Hood iterate w (block (u_x,u_y,u_z,p) per CG2 node).  Each of the 9 components is then one CG1 mass-matrix
@@ -513,7 +543,7 @@ int fs_spmv_dictionary(fs_matrix_t A, fs_vector_t x, fs_vector_t y, int* row_cla
 /* Which kernel the LAST product launched by this process went through (MatMult, SolverBase.py:663-670; a diagnostic - PETSc's
  * analogue is the -log_view line of MatMult): 0 streaming SELL / DIA kernels, 1 row-dictionary work items (k_dict_spmv), 2 lattice
  * tiles of a CG2 box (k_lattice_spmv), 3 marching windows of a P1 box (k_box_spmv, round 6: options "box_spmv" 1 / 0 and
- * "box_min_rows", default 1 500 000), 4 block-row dictionary (k_dict_spmv3), 5 marching windows of a CG2 box in lattice order
+ * "box_min_rows", default 1 500 000), 4 block rows (k_dict_spmv3; k_sell_spmv4_* on 4 x 4-block operators), 5 marching windows of a CG2 box in lattice order
  * (k_lat_march, round 6: option "lattice_march" 1 / 0), 6 DG cell blocks (k_dg_spmv).  The one-launch iteration k_dict_cg_iter does not count as a product here. */
 int fs_last_product_kind(void);
 
@@ -670,6 +700,16 @@ typedef struct fs_saddle_opts {
     int velocity_sweeps;        /* Jacobi sweeps standing in for A^-1, 0 = 1 */
     double inner_rtol;          /* of the pressure Laplacian / mass CG solves, 0 = 1e-2 */
     int nonzero_guess;
+    /* Appended; zero / NULL keeps the Taylor-Hood preconditioner above.  block_upper = 1: J is the reduced large-deformation
+     * operator of fs_assemble_large_deformation (CG1 block-4 space) and the preconditioner is the right, block upper triangular
+     * [A J_vp; 0 S]^-1 with S = schur_scale Mp (Mp: CG1 pressure mass matrix, 5 Chebyshev steps) and A^-1 one V-cycle of a0_amg
+     * (3-D) or, without a hierarchy, Jacobi-CG on a0 to a0_rtol (0 = 1e-2).  a0: vector CG1 operator (d components on the same
+     * mesh) standing in for the velocity block.  Kp, Kp_amg and the Taylor-Hood fields are not used then. */
+    int block_upper;
+    fs_matrix_t a0;
+    fs_amg_t a0_amg;
+    double a0_rtol;
+    double schur_scale;
 } fs_saddle_opts;
 
 /* Restarted FGMRES on the coupled system (the reference lets PETSc LU do this, SolverBase.py:615-626),
