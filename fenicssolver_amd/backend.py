@@ -943,6 +943,12 @@ def last_product_kind():
     return int(L.load().fs_last_product_kind())
 
 
+def last_iteration_form():
+    """Form of the one-launch CG iteration in the last solve (fs_last_iteration_form), 0 if it did not run: bit 0 = p and x updated every
+    second launch (option "cg_pair"), bit 1 = dot weights from the table by row class."""
+    return int(L.load().fs_last_iteration_form())
+
+
 def set_option(name, value):
     L.check(L.load().fs_set_option(name.encode(), float(value)), "fs_set_option")
 

@@ -45,6 +45,11 @@ struct row_dict {
     dbuf<unsigned long long> keys;
     dbuf<int32_t> slot2cls, nnz;
     dbuf<int> info;
+    // dot weights by class (one-launch CG iteration): slot_d[slot] = dvec of the row that founded the class, dtab[class] the same by
+    // class number; EVERY row's weight is compared with its class's, bit for bit, where the class rows are (k_dict_finish: info[4])
+    dbuf<double> slot_d, dtab;
+    bool dtab_valid = false;                // the kept tables come with a dtab
+    bool dtab_ok = false;                   // ... and every row of THIS call's weight vector equals its class's entry
     int ncls = 0, S = 0, C = 0, bs = 1;     // classes, doubles per class row, most classes of any item, block size of the matrix
     const double* built_for = nullptr;      // the value array the classes describe (nullptr: plain form in use)
     uint64_t space_serial = 0;              // ... of this space
@@ -106,6 +111,9 @@ static int g_cg_sub = 16, g_cg_ahead = 6, g_cg_mirror = 1;      // (tools/probes
 static int g_cg_fuse_sums = 1;
 static int g_cg_graph = -1;      // -1: automatic (graphs, unless a profiler's tool library is in the process)
 static int g_update_blocks = 1024;  // (round 3, with the 16 us row-dictionary product at 1 M rows: 256 / 512 / 768 / 1024 / 2048 workgroups: 10.59 / 10.42 / 10.20 / 10.12 / 11.22 ms per step; 10 M rows: flat)
+static int g_cg_pair = getenv("FS_CG_PAIR") ? (atoi(getenv("FS_CG_PAIR")) != 0) : 1;      // option "cg_pair": the one-launch iteration updates p and x every second launch (k_dict_cg_iter, MODE); 0: in every launch
+static int g_cg_poison_p = 0;            // option "cg_poison_p" (tests): the next CG solve finds NaN in its search-direction workspace
+static int g_last_iteration_form = 0;    // fs_last_iteration_form()
 static int g_cg_fused = -1;      // one launch per CG iteration on row-dictionary operators: -1 automatic, 0 never, 1 wherever it applies
 static int g_row_dictionary = 1; // row-dictionary product where the operator allows it (0: always the streaming kernels)
 // the marching-window product of P1 box operators (fs_box.h): option "box_spmv" (0: k_dict_spmv everywhere), from "box_min_rows" rows on
@@ -139,6 +147,10 @@ extern "C" int fs_set_option(const char* name, double value) {
         g_cg_graph = value < 0.0 ? -1 : (value != 0.0);
     } else if (!strcmp(name, "cg_fused")) {
         g_cg_fused = value < 0.0 ? -1 : (value != 0.0);
+    } else if (!strcmp(name, "cg_pair")) {
+        g_cg_pair = value != 0.0;
+    } else if (!strcmp(name, "cg_poison_p")) {
+        g_cg_poison_p = value != 0.0;
     } else if (!strcmp(name, "update_blocks")) {
         FS_REQUIRE(value >= 1 && value <= 65535, "update_blocks must be in [1,65535]");
         g_update_blocks = (int)value;
@@ -651,9 +663,11 @@ static int dict_structure_build(fs_space_s* sp, hipStream_t s) {
 // the solve goes through the dictionary kernels (launch_spmv: whole-space launches of a space without a halo plan).
 struct box_plan_s;
 static const box_plan_s* box_plan_for(const fs_space_s* sp, int ncls);
-static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, const double* raw, const double* sc, const std::function<void()>& materialize) {
+static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, const double* raw, const double* sc, const std::function<void()>& materialize,
+                           const double* dvec) {
     row_dict& D = g_dict;
     D.built_for = nullptr;
+    D.dtab_ok = false;
     fs_space_s* sp = A->space;
     static const bool off = getenv("FS_SPMV_DICT") && getenv("FS_SPMV_DICT")[0] == '0';
     if (off || !g_row_dictionary || (A->bs != 1 && A->bs != 3) || sp->n_slices == 0 || sp->n_dia_slices != sp->n_slices || D.gave_up_on == A->serial) return FS_OK;
@@ -681,7 +695,9 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
         FS_CHECK(D.keys.alloc(FS_DICT_CAP));
         FS_CHECK(D.slot2cls.alloc(FS_DICT_CAP));
         FS_CHECK(D.nnz.alloc(FS_DICT_MAX));
-        FS_CHECK(D.info.alloc(4));
+        FS_CHECK(D.info.alloc(8));
+        FS_CHECK(D.slot_d.alloc(FS_DICT_CAP));
+        FS_CHECK(D.dtab.alloc(FS_DICT_MAX));
     }
     if (D.slot_vals.n < (int64_t)FS_DICT_CAP * S) { D.tables_space = 0; FS_CHECK(D.slot_vals.alloc((int64_t)FS_DICT_CAP * S)); FS_CHECK(D.values.alloc((int64_t)FS_DICT_MAX * S)); }
     const int4* items = reinterpret_cast<const int4*>(sp->dict_items.p);
@@ -703,23 +719,26 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
         if (A->bs == 1 && sp->dict_runs == 8 && sp->dict_run_len == 3) (void)box_plan_for(sp, ncls);     // (the launch plan of k_box_spmv: made here, outside any capture)
     };
     static const bool no_reuse = getenv("FS_DICT_REUSE") && getenv("FS_DICT_REUSE")[0] == '0';
-    if (!no_reuse && D.tables_space == sp->serial && D.tables_bs == A->bs && D.tables_S == S && D.tables_ncls > 0) {
+    // (a weight vector to check and kept tables without weights: described from scratch, which makes them)
+    if (!no_reuse && D.tables_space == sp->serial && D.tables_bs == A->bs && D.tables_S == S && D.tables_ncls > 0 && (!dvec || D.dtab_valid)) {
         if (D.reuse_skip > 0) --D.reuse_skip;
         else {
             FS_CHECK(D.info.zero(s));
             hipLaunchKernelGGL(k_dict_finish, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_dict_items, items, plans, sp->slice_ptr.p, sp->dia_ptr.p, sp->dia_off.p,
                                raw ? raw : val, nq, sp->sell_entries, S, sp->dict_run_len, D.slot2cls.p, D.values.p, D.nnz.p, D.cls_slot.p, D.cls.p, D.info.p,
-                               raw ? sc : nullptr, sp->dict_runs);
+                               raw ? sc : nullptr, sp->dict_runs, dvec, D.dtab.p);
             FS_KERNEL_CHECK();
-            int h[4] = {0, 0, 0, 0};
-            FS_CHECK(D.info.download(h, 4, s));
-            const bool same = usable(h, D.tables_ncls);
+            int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            FS_CHECK(D.info.download(h, 8, s));
+            // (rows as before but other weights - the operator times a constant: from scratch as well, the weights come with the classes)
+            const bool same = usable(h, D.tables_ncls) && h[4] == 0;
             if (getenv("FS_KRYLOV_DEBUG"))
                 fprintf(stderr, "[fs_krylov] row dictionary: the %d classes of the last call against the %lld rows of this one: %d mismatches -> %s\n",
                         D.tables_ncls, (long long)sp->n_nodes_owned, h[2], same ? "kept" : "built again");
             if (same) {
                 adopt(h, D.tables_ncls);
                 D.kept = true;
+                D.dtab_ok = dvec != nullptr;
                 D.reuse_backoff = 0;
                 ++D.n_reused;
                 return FS_OK;
@@ -736,13 +755,15 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
     FS_CHECK(D.info.zero(s));
     FS_HIP(hipMemsetAsync(D.slot_vals.p, 0, (size_t)FS_DICT_CAP * S * sizeof(double), s));
     hipLaunchKernelGGL(k_dict_insert, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_dict_items, items, plans, sp->slice_ptr.p, sp->dia_ptr.p, sp->dia_off.p,
-                       val, nq, sp->sell_entries, S, sp->dict_run_len, D.keys.p, D.keys.p, D.slot_vals.p, D.cls_slot.p, D.info.p, sp->dict_runs);
-    hipLaunchKernelGGL(k_dict_compact, dim3(1), dim3(1024), 0, s, D.keys.p, D.slot_vals.p, S, D.slot2cls.p, D.values.p, D.nnz.p);
+                       val, nq, sp->sell_entries, S, sp->dict_run_len, D.keys.p, D.keys.p, D.slot_vals.p, D.cls_slot.p, D.info.p, sp->dict_runs, dvec, D.slot_d.p);
+    hipLaunchKernelGGL(k_dict_compact, dim3(1), dim3(1024), 0, s, D.keys.p, D.slot_vals.p, S, D.slot2cls.p, D.values.p, D.nnz.p, dvec ? D.slot_d.p : nullptr, D.dtab.p);
     hipLaunchKernelGGL(k_dict_finish, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_dict_items, items, plans, sp->slice_ptr.p, sp->dia_ptr.p, sp->dia_off.p,
-                       val, nq, sp->sell_entries, S, sp->dict_run_len, D.slot2cls.p, D.values.p, D.nnz.p, D.cls_slot.p, D.cls.p, D.info.p, nullptr, sp->dict_runs);
+                       val, nq, sp->sell_entries, S, sp->dict_run_len, D.slot2cls.p, D.values.p, D.nnz.p, D.cls_slot.p, D.cls.p, D.info.p, nullptr, sp->dict_runs,
+                       dvec, D.dtab.p);
     FS_KERNEL_CHECK();
-    int h[4] = {0, 0, 0, 0};
-    FS_CHECK(D.info.download(h, 4, s));
+    D.dtab_valid = false;
+    int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FS_CHECK(D.info.download(h, 8, s));
     lap("classes found + verified");
     const bool ok = usable(h, h[0]);
     if (getenv("FS_KRYLOV_DEBUG"))
@@ -759,6 +780,9 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
     D.tables_bs = A->bs;
     D.tables_S = S;
     D.tables_ncls = h[0];
+    // (rows of one class with different weights - classes are keyed on the SCALED rows, the weights are 1 / a_ii of the unscaled matrix:
+    // the iteration kernel keeps its weight stream for this operator)
+    D.dtab_valid = D.dtab_ok = dvec != nullptr && h[4] == 0;
     ++D.n_built;
     return FS_OK;
 }
@@ -1063,12 +1087,12 @@ static int lat_prepare(fs_matrix_s* A, const double* val, hipStream_t s) {
 }
 
 static int dict_build(fs_matrix_s* A, const double* val, hipStream_t s, const double* raw = nullptr, const double* sc = nullptr,
-                      const std::function<void()>& scale_copy = nullptr) {
+                      const std::function<void()>& scale_copy = nullptr, const double* dvec = nullptr) {
     bool copied = raw == nullptr;
     const auto materialize = [&]() {
         if (!copied) { scale_copy(); copied = true; }
     };
-    const int rc = dict_build_impl(A, val, s, raw, sc, materialize);
+    const int rc = dict_build_impl(A, val, s, raw, sc, materialize, dvec);
     // every outcome but `the kept table describes this matrix` reads val: the streaming kernels, or a table just built from it
     if (!(g_dict.built_for == val && g_dict.kept)) materialize();
     if (rc == FS_OK && A->space->lat_ny > 0) FS_CHECK(lat_prepare(A, val, s));
@@ -1538,6 +1562,7 @@ struct krylov_ws {
     static const int NSAMPLE = 64;
     hipEvent_t ev[NSAMPLE][4];
     int sample_iter[NSAMPLE];   // iteration (within its pass) a sample was taken at
+    int sample_span[NSAMPLE];   // launches a sample covers (2: a LIGHT and a PAIR launch of the one-launch iteration, their mean is reported)
     bool sample_live[NSAMPLE];  // false: the sampled launches came after convergence (no-ops)
     bool events = false;
     std::vector<double> last_hist;
@@ -1575,7 +1600,7 @@ static int ws_prepare(krylov_ws& ws, int64_t n, int64_t nl, int max_iter) {
         FS_CHECK(ws.partials.alloc(4 * (FS_MAX_PARTIAL_BLOCKS + 8)));
         FS_CHECK(ws.sums.alloc(8));
         FS_CHECK(ws.ctrl.alloc(4));
-        FS_CHECK(ws.scal.alloc(4));
+        FS_CHECK(ws.scal.alloc(8));          // ([4], [5]: beta by iteration parity, k_dict_cg_iter with LIGHT / PAIR launches)
         FS_CHECK(ws.status.alloc(4));
         FS_CHECK(ws.d_err.alloc(1));
         FS_HIP(hipHostMalloc((void**)&ws.h_status, 16 * sizeof(int), hipHostMallocDefault));     // ([12 .. 16): the status word at the end of a pass)
@@ -1772,8 +1797,9 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         aval = ws.aval.p;
         if (bs == 1) {
             // a handful of distinct rows (uniform box, constant coefficient)?
-            if (lazy_copy) FS_CHECK(dict_build(A, aval, s, A->val.p, sc_local, scale_copy1));
-            else FS_CHECK(dict_build(A, aval, s));
+            // (with the dot weights of the solve: a table of them by class for the one-launch iteration)
+            if (lazy_copy) FS_CHECK(dict_build(A, aval, s, A->val.p, sc_local, scale_copy1, ws.dvec.p));
+            else FS_CHECK(dict_build(A, aval, s, nullptr, nullptr, nullptr, ws.dvec.p));
             sgrid = spmv_partials(sp, bs);          // (the row-dictionary product has its own launch geometry)
         }
     }
@@ -1805,6 +1831,9 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         }
         if (!ws.it_ctr.p) FS_CHECK(ws.it_ctr.alloc(2));
     }
+    // k_dict_cg_iter: p and x every second launch (option "cg_pair"), dot weights from the class table where every row agrees with it
+    const bool pair_form = g_cg_pair != 0, dtab_form = pair_form && g_dict.dtab_ok;
+    int iteration_form = 0;
     // A pass = fresh recurrences from the current x.  The single-reduction recurrences drift on
     // ill-conditioned operators (the recurrence residual can reach the threshold while b - A x has not):
     // the true residual is recomputed after every pass and, if it misses the tolerance, the solve
@@ -1826,6 +1855,10 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         // initial state
         FS_CHECK(ws.status.zero(s));
         FS_CHECK(ws.scal.zero(s));
+        if (g_cg_poison_p) {          // (a pass sets p_{-1} = 0 itself: the LIGHT launches never write p, the first PAIR launch reads it)
+            FS_HIP(hipMemsetAsync(ws.p.p, 0xff, (size_t)ws.p.n * sizeof(double), s));
+            g_cg_poison_p = 0;
+        }
         // p, s, z and - from a zero guess - x in one launch
         hipLaunchKernelGGL(k_zero4, dim3(fs_grid_for(std::max<int64_t>(nl / 2, 1), FS_BLOCK, 1024)), dim3(FS_BLOCK), 0, s, ws.p.p, ws.p.n, ws.s.p, ws.s.n,
                            ws.z.p, ws.z.n, x->d.p, use_guess ? (int64_t)0 : x->d.n);
@@ -2028,7 +2061,12 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                 double* const W[2] = {ws.w.p, ws.w2.p};
                 double* const SV[2] = {ws.s.p, ws.s2.p};
                 double* const PT[2] = {ws.partials.p, ws.partials.p + 3 * (int64_t)igrid};
-                const size_t lds = (size_t)g_dict.ncls * g_dict.S * sizeof(double);
+                // (one GPU only: behind the exchange kernel of a decomposed space the LIGHT instantiation compiles to 132 VGPRs, three
+                // waves per SIMD instead of the four the launch needs - that form keeps p and x in every launch)
+                const bool pair = pair_form && !fusedp && !BI, dtab = pair && dtab_form;
+                iteration_form = (pair ? 1 : 0) | (dtab ? 2 : 0);
+                const size_t lds = (size_t)g_dict.ncls * (g_dict.S + (dtab ? 1 : 0)) * sizeof(double);
+                const double* const weights = dtab ? g_dict.dtab.p : ws.dvec.p;
                 fs_p2p_rowsred red2[2] = {};
                 fs_p2p_sendrows snd2[2] = {};
                 if (fusedp)
@@ -2042,7 +2080,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                 auto launch_iter = [&](int par) {
 #define FS_ITER_ARGS dim3(igrid), dim3(FS_BLOCK), lds, s, sp->n_nodes_local, sp->n_dict_items, reinterpret_cast<const int4*>(sp->dict_items.p), \
                      reinterpret_cast<const dict_plan_round*>(sp->dict_plans.p), g_dict.cls.p, g_dict.values.p, g_dict.S, g_dict.ncls, \
-                     Z[par], W[par], SV[par], Z[par ^ 1], W[par ^ 1], SV[par ^ 1], ws.p.p, x->d.p, ws.dvec.p, PT[par], PT[par ^ 1], igrid, \
+                     Z[par], W[par], SV[par], Z[par ^ 1], W[par ^ 1], SV[par ^ 1], ws.p.p, x->d.p, weights, PT[par], PT[par ^ 1], igrid, \
                      ws.ctrl.p, ws.scal.p, ws.status.p, ws.it_ctr.p, par, hist_p, dict_map_xcd(), ws.sums.p, mirror_dev
                     if (BI && !fusedp) {
 #define FS_BOX_ITER_ARGS dim3(igrid), dim3(6 * 64), BI->lds, s, BI->g, g_dict.cls.p, g_dict.values.p, g_dict.ncls, Z[par], W[par], SV[par], Z[par ^ 1], W[par ^ 1], \
@@ -2053,7 +2091,14 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                     } else if (fusedp) {
                         launch_exchange(par);
                         hipLaunchKernelGGL((k_dict_cg_iter<3, true>), FS_ITER_ARGS);
-                    } else hipLaunchKernelGGL((k_dict_cg_iter<3, false>), FS_ITER_ARGS);
+                    } else if (!pair) hipLaunchKernelGGL((k_dict_cg_iter<3, false>), FS_ITER_ARGS);
+                    else if (dtab) {           // (launch parity = iteration parity: it_ctr is zeroed at k = 0)
+                        if (par) hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_PAIR, true>), FS_ITER_ARGS);
+                        else hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_LIGHT, true>), FS_ITER_ARGS);
+                    } else {
+                        if (par) hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_PAIR, false>), FS_ITER_ARGS);
+                        else hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_LIGHT, false>), FS_ITER_ARGS);
+                    }
 #undef FS_ITER_ARGS
                 };
                 if (k == 0) {
@@ -2073,11 +2118,11 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                         launch_spmv<3>(A, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, s, aval, nullptr, 0, 0, 0, 0);
                 }
                 if (graph_sized && graphs_allowed && k >= first_plain && kend - k == bsz && kend <= max_iter && (bsz & 1) == 0 && (k & 1) == 0) {
-                    const void* key[24] = {A, aval, x->d.p, hist_p, ws.z.p, ws.w.p, ws.partials.p, ws.status.p, ws.dvec.p, ws.p.p, ws.s.p,
+                    const void* key[24] = {A, aval, x->d.p, hist_p, ws.z.p, ws.w.p, ws.partials.p, ws.status.p, weights, ws.p.p, ws.s.p,
                                            ws.z2.p, ws.w2.p, ws.s2.p, ws.it_ctr.p, g_dict.cls.p, g_dict.values.p, sp->dict_items.p, sp->dict_plans.p,
                                            ws.ctrl.p, ws.scal.p, snd2[0].own_recv, red2[0].own_buf,
                                            fusedp ? reinterpret_cast<const void*>((uintptr_t)sp->halo.p2p.generation + 1) : nullptr};
-                    const int64_t key_i[8] = {n, ((int64_t)g_dict.ncls * 256 + g_dict.S) * 4 + (fusedp ? 1 : 0) + (mirror_dev ? 2 : 0), bsz + 4096 * (BI ? BI->ahead : 0), igrid,
+                    const int64_t key_i[8] = {n, ((int64_t)g_dict.ncls * 256 + g_dict.S) * 4 + (fusedp ? 1 : 0) + (mirror_dev ? 2 : 0), bsz + 4096 * (BI ? BI->ahead : 0) + 65536 * iteration_form, igrid,
                                               (int64_t)dict_map_xcd() + 16 * (int64_t)p2p_rows_cap,
                                               (int64_t)sp->n_dict_items, (int64_t)A->serial, (int64_t)sp->serial};
                     if (!ws.cgf_graph || memcmp(key, ws.cgf_key, sizeof(key)) || memcmp(key_i, ws.cgf_key_i, sizeof(key_i))) {
@@ -2094,18 +2139,27 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                     FS_HIP(hipGraphLaunch(ws.cgf_graph, s));
                     k = kend;
                 }
+                // (LIGHT / PAIR launches: a sample is a PAIR launch and the LIGHT launch behind it, reported as their mean - avg_launch_ms
+                // stays the mean launch of the solve)
+                bool sample_open = false;
                 for (; k < kend; ++k) {
-                    const bool sample = (k % sample_step == 1 % sample_step) && n_samples < krylov_ws::NSAMPLE;
+                    const bool sample = !sample_open && (k % sample_step == 1 % sample_step) && n_samples < krylov_ws::NSAMPLE;
                     if (sample) {
                         ws.sample_iter[n_samples] = k;
+                        ws.sample_span[n_samples] = 0;
                         FS_HIP(hipEventRecord(ws.ev[n_samples][0], s));
+                        sample_open = true;
                     }
                     launch_iter(k & 1);
-                    if (sample) {
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
-                        ++n_samples;
+                    if (sample_open) {
+                        ++ws.sample_span[n_samples];
+                        if (!pair || ws.sample_span[n_samples] == 2 || k + 1 == kend) {
+                            FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
+                            FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
+                            FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
+                            ++n_samples;
+                            sample_open = false;
+                        }
                     }
                 }
             }
@@ -2173,7 +2227,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
             }
             for (; k < kend; ++k) {
                 const bool sample = (k % sample_step == 1 % sample_step) && n_samples < krylov_ws::NSAMPLE;
-                if (sample) ws.sample_iter[n_samples] = k;
+                if (sample) { ws.sample_iter[n_samples] = k; ws.sample_span[n_samples] = 1; }
                 if (bicg) {
                     const int co = k == max_iter ? 1 : 0;
                     // K1: p, y
@@ -2341,6 +2395,11 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         // pipelined: the reduction enqueued behind the last update still reads the partial sums on the communication stream;
         // nothing of the workspace is touched again before it is through
         if (red_stream) FS_HIP(hipStreamWaitEvent(s, ws.ev_red, 0));
+        // LIGHT / PAIR launches: a pass that stopped in an odd launch owes x one step (the kernel looks at the status word itself)
+        if (iteration_form & 1) {
+            hipLaunchKernelGGL(k_cg_pair_flush, dim3(fs_grid_for(n / 2 + 1, FS_BLOCK, 2048)), dim3(FS_BLOCK), 0, s, n, ws.status.p, ws.scal.p, ws.z.p, ws.p.p, x->d.p);
+            FS_KERNEL_CHECK();
+        }
         // The end of a pass used to be six host synchronisations (stream, status word, sums, control block, the un-scaling of x,
         // the history): 0.68 ms of fixed cost per solve at 1 M rows, a tenth of the whole solve.  Nothing of the true-residual
         // computation depends on what the host learns from the status word, so it is enqueued first and status, sums and control
@@ -2361,7 +2420,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         const int iters = h_status[1];
         total_iters += iters;
         // launches enqueued after the recurrence stopped return on the status word: their samples time no-ops
-        for (int i = first_sample; i < n_samples; ++i) ws.sample_live[i] = ws.sample_iter[i] < iters;
+        for (int i = first_sample; i < n_samples; ++i) ws.sample_live[i] = ws.sample_iter[i] + ws.sample_span[i] - 1 < iters;
         if (ws.h_status[8] != 0) {
             fs_set_error("fs_krylov_solve: %d zero%s diagonal entries (Jacobi preconditioner undefined)", ws.h_status[8], ds ? " or negative" : "");
             return FS_ERR_NUMERIC;
@@ -2429,7 +2488,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
             float a = 0.f, c = 0.f;
             if (hipEventElapsedTime(&a, ws.ev[i][0], ws.ev[i][1]) != hipSuccess) break;
             if (hipEventElapsedTime(&c, ws.ev[i][2], ws.ev[i][3]) != hipSuccess) break;
-            t_spmv += a;
+            t_spmv += a / (float)ws.sample_span[i];
             t_upd += c;
             ++cnt;
         }
@@ -2443,6 +2502,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         stats->classes_kept = g_dict.built_for && g_dict.kept ? 1 : 0;
         stats->launches = n_launches;
         stats->product_kind = fused ? (BI ? 3 : 1) : g_last_product_kind;
+        g_last_iteration_form = (fused || fusedp_used) ? iteration_form : 0;
         if (fused) stats->update_ms = 0.0;       // (spmv_ms is the whole iteration: one launch)
     }
     if (h_status[0] == 2) {
@@ -2452,6 +2512,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
     return FS_OK;
 }
 
+extern "C" int fs_last_iteration_form() { return g_last_iteration_form; }
 void fs_krylov_set_history(const std::vector<double>& rr) { g_ws.last_hist = rr; }
 void fs_set_last_product_kind(int kind) { g_last_product_kind = kind; }
 

@@ -192,7 +192,9 @@ __device__ __forceinline__ unsigned long long dict_mix(unsigned long long h, int
 }
 
 // info[0] = classes found, info[1] = 1: gave up (too many classes), info[2] = rows that differ from their class or do not fit their
-// plan (verification), info[3] = most distinct classes in any item
+// plan (verification), info[3] = most distinct classes in any item, info[4] = rows whose dot weight differs from their class's
+// dvec (may be null; scalar operators): the dot weights of the solve, one per row - the row that founds a class leaves its weight in
+// slot_d, k_dict_compact numbers it into dtab, k_dict_finish compares every row's weight with dtab[class] bit for bit
 // Nearly all rows of such an operator carry the SAME hash, so the table is hit where it hurts: the lanes of a wave are first grouped
 // by hash (a wave of interior rows is one group) and only the group's first lane goes to memory, and it looks at the slot with an
 // ordinary cached load before any atomic (a slot goes from 0 to its final key once: a key seen there is final, a stale 0 merely
@@ -201,7 +203,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_insert(int64_t n_items, const
                                                           const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ dia_ptr,
                                                           const int32_t* __restrict__ dia_off, const double* __restrict__ val, int nq, int64_t plane, int S, int RL,
                                                           unsigned long long* keys, const unsigned long long* keys_cached, double* slot_vals,
-                                                          uint16_t* __restrict__ cls_slot, int* info, int NR = 8) {
+                                                          uint16_t* __restrict__ cls_slot, int* info, int NR = 8,
+                                                          const double* __restrict__ dvec = nullptr, double* __restrict__ slot_d = nullptr) {
     const int lane = threadIdx.x & 63;
     int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -238,6 +241,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_insert(int64_t n_items, const
                                 if (atomicAdd(&info[0], 1) >= FS_DICT_MAX) __hip_atomic_store(&info[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                 double* __restrict__ dst = slot_vals + (int64_t)slot * S;       // (zero-filled by the host before the launch)
                                 (void)dict_walk_row(r, slice_ptr, dia_ptr, dia_off, val, nq, plane, pl, n_runs, RL, [&](int sl2, double v) { if (sl2 < S) dst[sl2] = v; }, nullptr, NR);
+                                if (dvec) slot_d[slot] = dvec[r];
                                 break;
                             }
                         }
@@ -256,7 +260,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_insert(int64_t n_items, const
 
 // number the occupied slots; values[id][S] = the class rows in plan layout, nnz[id] = their nonzero positions
 __global__ void __launch_bounds__(1024) k_dict_compact(const unsigned long long* __restrict__ keys, const double* __restrict__ slot_vals,
-                                                       int S, int32_t* __restrict__ slot2cls, double* __restrict__ values, int32_t* __restrict__ nnz) {
+                                                       int S, int32_t* __restrict__ slot2cls, double* __restrict__ values, int32_t* __restrict__ nnz,
+                                                       const double* __restrict__ slot_d = nullptr, double* __restrict__ dtab = nullptr) {
     constexpr int PER = FS_DICT_CAP / 1024;       // consecutive slots per thread
     __shared__ int cnt[1024];
     const int t = threadIdx.x;
@@ -283,6 +288,7 @@ __global__ void __launch_bounds__(1024) k_dict_compact(const unsigned long long*
                 nz += v != 0.0;
             }
             nnz[id] = nz;
+            if (slot_d) dtab[id] = slot_d[slot];
         }
         id += used;
     }
@@ -294,11 +300,12 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_finish(int64_t n_items, const
                                                           const int32_t* __restrict__ dia_off, const double* __restrict__ val, int nq, int64_t plane, int S, int RL,
                                                           const int32_t* __restrict__ slot2cls, const double* __restrict__ values,
                                                           const int32_t* __restrict__ nnz, const uint16_t* __restrict__ cls_slot,
-                                                          uint16_t* __restrict__ cls, int* info, const double* __restrict__ sc = nullptr, int NR = 8) {
+                                                          uint16_t* __restrict__ cls, int* info, const double* __restrict__ sc = nullptr, int NR = 8,
+                                                          const double* __restrict__ dvec = nullptr, const double* __restrict__ dtab = nullptr) {
     const int lane = threadIdx.x & 63;
     int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    int bad = 0, crowded = 0;       // (crowded: most distinct classes of an item so far)
+    int bad = 0, bad_d = 0, crowded = 0;       // (crowded: most distinct classes of an item so far)
     for (; q < n_items; q += stride) {
         const int4 it = items[q];
         const int32_t first = it.x, nr = it.y & 0xffff;
@@ -313,6 +320,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_finish(int64_t n_items, const
             cls[r] = (uint16_t)(id < 0 ? 0 : id);
             if (id < 0 || id >= FS_DICT_MAX) { ++bad; continue; }
             id2[half] = id;
+            if (dvec) bad_d += __double_as_longlong(dvec[r]) != __double_as_longlong(dtab[id]);
             const double* __restrict__ dv = values + (int64_t)id * S;
             int nz = 0, diff = 0;
             const bool fits = dict_walk_row(r, slice_ptr, dia_ptr, dia_off, val, nq, plane, pl, n_runs, RL, [&](int slot, double v) {
@@ -335,6 +343,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_finish(int64_t n_items, const
         crowded = distinct > crowded ? distinct : crowded;
     }
     if (bad) atomicAdd(&info[2], bad);
+    if (bad_d) atomicAdd(&info[4], bad_d);
     // (a look before the atomic: nearly every wave holds the same maximum, and 8 000 atomics on one address were most of this
     // kernel's time at 1 M rows)
     if (crowded && lane == 0 && crowded > __hip_atomic_load(&info[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&info[3], crowded);

@@ -455,10 +455,28 @@ __device__ long long g_iter_dbg[8 * 4096];
 #else
 #define FS_STAMP(k) do { } while (0)
 #endif
+// -DFS_ITER_ABLATE_PXD (probe builds only, wrong numerics): the kernel without the loads and stores of p, x and the dot weights - what
+// the launch costs without the 40 B per row that do nothing for the recurrence (tools/probes/fused_iter_probe.py with FS_PROBE_LIB;
+// profiles/r07_cg_pair_ablation.txt: 18.8 against 21.7 us per launch at 1 M rows)
 // COMM: a decomposed space - the three sums come reduced over the ranks from `sums` (k_cg_p2p_exchange<true> before this launch put
 // them there, stored the neighbours' w into the ghost rows of w_in and advanced the ghost rows of r_out / s_out); the neighbour
 // columns of an item may then be ghost columns: n_cols counts them.
-template <int RL, bool COMM>
+// MODE: p and x feed nothing but each other, so their two row-local steps need not run in every launch (option "cg_pair"):
+//   FS_ITER_EVERY  p_k = r_k + beta_k p_{k-1}, x_{k+1} = x_k + alpha_k p_k in launch k (90 B per row)
+//   FS_ITER_LIGHT  even launches: p and x are not touched (50 B per row); the step of iteration k stays owed
+//   FS_ITER_PAIR   odd launches: the owed step of iteration k - 1, then the step of iteration k, in one pass over p and x (90 B per
+//                  row).  r_{k-1} is still there: launch k writes r_{k+1} into the buffer that holds it, every lane reads its own rows
+//                  of it before it overwrites them, and nobody else reads that buffer during the launch.  alpha_{k-1} is in scal[2 q + 1],
+//                  beta_{k-1} in scal[4 + q] (q = (k - 1) & 1), left there by the leader lane of launch k - 1: the bits cg_scalars_from
+//                  produced.  The same four fmas on the same operands as two launches of FS_ITER_EVERY: the same bits.
+//   A solve that stops in an odd launch still owes x one step: k_cg_pair_flush, enqueued by the host behind the last launch.
+// Measured at 1 M rows (kernel trace of the step workload, profiles/r07_cg_pair_trace_*.csv): LIGHT 16.6 us, PAIR 20.8 us, the flush 6.5 us
+// once per solve, against 20.2 us per launch of FS_ITER_EVERY; 6.53 -> 6.13 ms per step.  One GPU only: behind the exchange kernel
+// (COMM) the LIGHT instantiation needs 132 VGPRs - three waves per SIMD - and COMM stays on FS_ITER_EVERY.
+// DTAB: `dvec` is the table of dot weights by row class (row_dict::dtab, every row verified against it bit for bit), copied into LDS behind
+// the dictionary, instead of the 8 B per row of the weight vector.
+enum { FS_ITER_EVERY = 0, FS_ITER_LIGHT = 1, FS_ITER_PAIR = 2 };
+template <int RL, bool COMM, int MODE = FS_ITER_EVERY, bool DTAB = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64_t n_items, const int4* __restrict__ items,
                                                            const dict_plan_round* __restrict__ plans, const uint16_t* __restrict__ cls,
                                                            const double* __restrict__ dict, int S, int C,
@@ -484,6 +502,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     const int iter = it_ctr[par];
     const double thresh = ctrl[0], it_max = ctrl[2];
     const double sc_g0 = scal[0], sc_a0 = scal[1], sc_g1 = scal[2], sc_a1 = scal[3];
+    double sc_b0 = 0.0, sc_b1 = 0.0;
+    if (MODE == FS_ITER_PAIR) { sc_b0 = scal[4]; sc_b1 = scal[5]; }
+    double dt0 = 0.0;
+    if (DTAB) dt0 = dvec[(int)threadIdx.x < C ? (int)threadIdx.x : 0];
     double pl[3][4];
     double sum_g = 0.0, sum_d = 0.0, sum_r = 0.0;
     if (COMM) { sum_g = sums[0]; sum_d = sums[1]; sum_r = sums[2]; }
@@ -535,27 +557,44 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
             Sb[j] = *reinterpret_cast<const v2du*>(reinterpret_cast<const char*>(s_in + st) + boff);
         }
     };
-    auto load_own = [&](const item_hdr& H, v2d& pp, v2d& xx, v2d& dd) {
+    // (rp: the own rows of r_{k-1}, PAIR only)
+    auto load_own = [&](const item_hdr& H, v2d& pp, v2d& xx, v2d& dd, v2d& rp) {
         const int32_t r = H.first + 2 * lane;
-        pp = xx = dd = v2d{0.0, 0.0};
+        pp = xx = dd = rp = v2d{0.0, 0.0};
+#ifdef FS_ITER_ABLATE_PXD
+        dd = v2d{1.0, 1.0};
+        return;
+#endif
         if (2 * lane + 1 < H.nr) {
-            pp = *reinterpret_cast<const v2du*>(&pv[r]);
-            xx = *reinterpret_cast<const v2du*>(&xv[r]);
-            dd = *reinterpret_cast<const v2du*>(&dvec[r]);
-        } else if (2 * lane < H.nr) { pp.x = pv[r]; xx.x = xv[r]; dd.x = dvec[r]; }
+            if (MODE != FS_ITER_LIGHT) {
+                pp = *reinterpret_cast<const v2du*>(&pv[r]);
+                xx = *reinterpret_cast<const v2du*>(&xv[r]);
+            }
+            if (MODE == FS_ITER_PAIR) rp = *reinterpret_cast<const v2du*>(&r_out[r]);
+            if (!DTAB) dd = *reinterpret_cast<const v2du*>(&dvec[r]);
+        } else if (2 * lane < H.nr) {
+            if (MODE != FS_ITER_LIGHT) { pp.x = pv[r]; xx.x = xv[r]; }
+            if (MODE == FS_ITER_PAIR) rp.x = r_out[r];
+            if (!DTAB) dd.x = dvec[r];
+        }
     };
     // Nothing the first item LOADS depends on alpha, beta: its first twelve run loads and its row-local operands are asked for
     // before the partial sums are reduced (a wave has about two items at 1 M rows; 35.3 -> 27.4 us per iteration with 1024 workgroups)
     item_hdr H0 = {};
-    v2d PA[4], PW[4], PS[4], Ppp = {0.0, 0.0}, Pxx = {0.0, 0.0}, Pdd = {0.0, 0.0};
+    v2d PA[4], PW[4], PS[4], Ppp = {0.0, 0.0}, Pxx = {0.0, 0.0}, Pdd = {0.0, 0.0}, Prp = {0.0, 0.0};
     const bool have0 = it.cur < it.end && it.cur * 4 + wave < n_items;
     if (have0) {
         H0 = decode(it.cur * 4 + wave);
         if (!H0.edge) load_half(H0, 0, 0, (uint32_t)(H0.first + 2 * lane) * 8u, PA, PW, PS);
-        load_own(H0, Ppp, Pxx, Pdd);
+        load_own(H0, Ppp, Pxx, Pdd, Prp);
     }
     FS_STAMP(2);
     fs_fill_lds(sdict, dict, C * S);             // (visible after the barrier of the sum below)
+    double* const sdtab = sdict + C * S;         // (DTAB: C dot weights behind the C class rows)
+    if (DTAB) {
+        if ((int)threadIdx.x < C) sdtab[threadIdx.x] = dt0;
+        for (int i = (int)threadIdx.x + FS_BLOCK; i < C; i += FS_BLOCK) sdtab[i] = dvec[i];
+    }
     if (st0 != 0) return;
     // the three sums of the previous launch's partials, in the order of wg_sum_partials / fs_block_sum (same bits as the update
     // kernel of the two-launch iteration computes), with ONE barrier: a thread's partials in ascending index, the wave's by the
@@ -600,10 +639,12 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     if (leader) {
         scal[2 * (iter & 1) + 0] = gamma;
         scal[2 * (iter & 1) + 1] = alpha;
+        if (MODE != FS_ITER_EVERY) scal[4 + (iter & 1)] = beta;
         it_ctr[par ^ 1] = iter + 1;
         if (mirror) fs_host_store(mirror + 1, iter + 1);
     }
     const double nalpha = -alpha;
+    const double alpha_prev = ((iter - 1) & 1) ? sc_a1 : sc_a0, beta_prev = ((iter - 1) & 1) ? sc_b1 : sc_b0;      // (PAIR)
     FS_STAMP(4);
     double d_rz = 0.0, d_wz = 0.0, d_rr = 0.0;
     // PRE: this item's first half round and row-local operands were loaded before the prologue
@@ -621,9 +662,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
             if (ok1) c1 = (int)cls[r + 1];
         }
         v2d sn0 = {0.0, 0.0}, ro0 = {0.0, 0.0};
-        v2d pp, xx, dd;
-        if (PRE) { pp = Ppp; xx = Pxx; dd = Pdd; }
-        else load_own(H, pp, xx, dd);
+        v2d pp, xx, dd, rp;
+        if (PRE) { pp = Ppp; xx = Pxx; dd = Pdd; rp = Prp; }
+        else load_own(H, pp, xx, dd, rp);
+        if (DTAB) { dd.x = sdtab[ok0 ? c0 : 0]; dd.y = sdtab[ok1 ? c1 : 0]; }
         const double* __restrict__ v0 = sdict + (ok0 ? c0 * S : 0);
         const double* __restrict__ v1 = sdict + (ok1 ? c1 * S : 0);
         double a0 = 0.0, a1 = 0.0;
@@ -685,19 +727,34 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
             }
         }
         // own rows: p, x, and the new s, r, w
-        v2d pn, xn;
-        pn.x = fma(beta, pp.x, ro0.x); pn.y = fma(beta, pp.y, ro0.y);
-        xn.x = fma(alpha, pn.x, xx.x); xn.y = fma(alpha, pn.y, xx.y);
+        v2d pn = {0.0, 0.0}, xn = {0.0, 0.0};
+        if (MODE == FS_ITER_PAIR) {             // the step launch k - 1 left owed, in its operands
+            pp.x = fma(beta_prev, pp.x, rp.x); pp.y = fma(beta_prev, pp.y, rp.y);
+            xx.x = fma(alpha_prev, pp.x, xx.x); xx.y = fma(alpha_prev, pp.y, xx.y);
+        }
+        if (MODE != FS_ITER_LIGHT) {
+            pn.x = fma(beta, pp.x, ro0.x); pn.y = fma(beta, pp.y, ro0.y);
+            xn.x = fma(alpha, pn.x, xx.x); xn.y = fma(alpha, pn.y, xx.y);
+        }
+        constexpr bool PX =
+#ifdef FS_ITER_ABLATE_PXD
+            false;
+#else
+            MODE != FS_ITER_LIGHT;
+#endif
         if (ok1) {
             v2d out;
             out.x = a0; out.y = a1;
             *reinterpret_cast<v2du*>(&w_out[r]) = out;
             *reinterpret_cast<v2du*>(&r_out[r]) = zi;
             *reinterpret_cast<v2du*>(&s_out[r]) = sn0;
-            *reinterpret_cast<v2du*>(&pv[r]) = pn;
-            *reinterpret_cast<v2du*>(&xv[r]) = xn;
+            if (PX) {
+                *reinterpret_cast<v2du*>(&pv[r]) = pn;
+                *reinterpret_cast<v2du*>(&xv[r]) = xn;
+            }
         } else if (ok0) {
-            w_out[r] = a0; r_out[r] = zi.x; s_out[r] = sn0.x; pv[r] = pn.x; xv[r] = xn.x;
+            w_out[r] = a0; r_out[r] = zi.x; s_out[r] = sn0.x;
+            if (PX) { pv[r] = pn.x; xv[r] = xn.x; }
         }
         if (!ok0) { a0 = 0.0; zi.x = 0.0; }
         if (!ok1) { a1 = 0.0; zi.y = 0.0; }
@@ -726,6 +783,31 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     FS_STAMP(7);
     if (threadIdx.x < 3) part_out[(int64_t)threadIdx.x * npart + blockIdx.x] =
         (lds34[threadIdx.x][0] + lds34[threadIdx.x][1]) + (lds34[threadIdx.x][2] + lds34[threadIdx.x][3]);
+}
+
+// The step a solve of LIGHT / PAIR launches still owes x when the recurrence stops in an odd launch k (convergence, iteration limit,
+// breakdown: status[1] = k): x_k = x_{k-1} + alpha_{k-1} (r_{k-1} + beta_{k-1} p_{k-2}), the two fmas launch k - 1 would have applied.
+// Not done inside the stopping launch: a workgroup that starts late there sees the status word already set and returns.  k - 1 is even:
+// r_{k-1} is in the parity-0 buffer, alpha_{k-1} in scal[1], beta_{k-1} in scal[4].  Decides for itself from the status word (no host
+// round trip); p is not written: nothing reads it after the solve.
+__global__ void __launch_bounds__(FS_BLOCK) k_cg_pair_flush(int64_t n, const int* __restrict__ status, const double* __restrict__ scal,
+                                                            const double* __restrict__ r_prev, const double* __restrict__ p, double* __restrict__ x) {
+    const int st0 = status[0], it = status[1];
+    const double alpha = scal[1], beta = scal[4];
+    if (st0 == 0 || !(it & 1)) return;
+    const int64_t n2 = n >> 1;
+    const double2* __restrict__ r2 = reinterpret_cast<const double2*>(r_prev);
+    const double2* __restrict__ p2 = reinterpret_cast<const double2*>(p);
+    double2* __restrict__ x2 = reinterpret_cast<double2*>(x);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+        const double2 rr = r2[i], pp = p2[i];
+        double2 xx = x2[i];
+        xx.x = fma(alpha, fma(beta, pp.x, rr.x), xx.x);
+        xx.y = fma(alpha, fma(beta, pp.y, rr.y), xx.y);
+        x2[i] = xx;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = fma(alpha, fma(beta, p[n - 1], r_prev[n - 1]), x[n - 1]);
 }
 
 // The same update on the rows [0, a) and [b, n) only - the rows a slab sends to its neighbours - so that the halo

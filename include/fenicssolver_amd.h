@@ -89,7 +89,9 @@ const char* fs_version(void);
  * "cg_fuse_sums" (0/1: sum the dot partials inside the update kernel on one GPU),
  * "update_blocks" (grid of the fused vector-update kernel), "cg_graph" (-1 / 0 / 1: CG batches as hipGraphs by size /
  * never / always), "cg_fused" (-1 / 0 / 1: ONE launch per CG iteration on row-dictionary operators - up to 3 M rows /
- * never / wherever it applies; fs_krylov_stats.fused_iteration), "row_dictionary" (0 / 1: allow the row-dictionary form of the product, fs_krylov_stats.row_classes),
+ * never / wherever it applies; fs_krylov_stats.fused_iteration), "cg_pair" (1 / 0, default 1; FS_CG_PAIR in the environment: that launch
+ * updates p and x every second iteration, two steps in one pass, instead of in every launch - the same bits; fs_last_iteration_form), "cg_poison_p" (tests: 1 = the next CG solve
+ * finds NaN in its search-direction workspace before it sets its initial state), "row_dictionary" (0 / 1: allow the row-dictionary form of the product, fs_krylov_stats.row_classes),
  * "box_snap" (0 / 1: box meshes snap their edge vectors to the grid spacing so that equal stencils are equal bit for bit),
  * "box_assembly" (1 / 0: scalar CG1 operators on fs_mesh_create_box meshes are assembled from the reference rows of the six cell types instead of
  * per-incidence geometry - the same bits), "box_spmv" (1 / 0) and "box_min_rows" (default 1 500 000): the marching-window product k_box_spmv,
@@ -546,6 +548,10 @@ int fs_spmv_dictionary(fs_matrix_t A, fs_vector_t x, fs_vector_t y, int* row_cla
  * "box_min_rows", default 1 500 000), 4 block rows (k_dict_spmv3; k_sell_spmv4_* on 4 x 4-block operators), 5 marching windows of a CG2 box in lattice order
  * (k_lat_march, round 6: option "lattice_march" 1 / 0), 6 DG cell blocks (k_dg_spmv).  The one-launch iteration k_dict_cg_iter does not count as a product here. */
 int fs_last_product_kind(void);
+/* Form of the one-launch CG iteration (k_dict_cg_iter) in the LAST solve of this process, 0 if it did not run: bit 0 = p and x updated every
+ * second launch (option "cg_pair"), bit 1 = the dot weights came from the table by row class (every row of the solve's weight vector
+ * equalled its class's entry bit for bit) and not from the weight vector. */
+int fs_last_iteration_form(void);
 
 /* ---- smoothed-aggregation AMG (PETScPreconditioner("petsc_amg") + set_near_nullspace,
  *      SolverBase.py:643-672; Chebyshev/Jacobi level smoother as the PETScOptions there ask) ---- */
