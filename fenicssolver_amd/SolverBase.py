@@ -786,6 +786,8 @@ class SolverBase():
             return self._navier_stokes_newton(F, u_current, Dirichlet_bcs)
         if isinstance(F, forms.HyperelasticForm):
             return self._hyperelastic_newton(F, u_current, Dirichlet_bcs)
+        if isinstance(F, forms.PlasticForm):
+            return self._plastic_newton(F, u_current, Dirichlet_bcs)
         if not isinstance(F, forms.ScalarForm):
             raise SolverError('nonlinear solves are built for scalar transport and Navier-Stokes only')
         per = F.space.periodic_pairs()
@@ -1061,6 +1063,121 @@ class SolverBase():
             self.newton_steps.append(step)
             self.newton_history.append(rnorm)
             self.newton_iterations = it + 1
+        u_current.vector().set_local(x)
+        return u_current
+
+    # ---- J2 plasticity (PlasticitySolver) -----------------------------------------------------------------
+    def _plastic_newton(self, F, u_current, bcs):
+        """One load step of PlasticitySolver: Newton on r(u) = f_int(u; committed history) - f_ext = 0 with the stopping test, the
+        defaults and the linear solvers of _hyperelastic_newton (DOLFIN's NewtonSolver; CG + AMG with the rigid-body near-null space
+        and a hierarchy per tangent in 3-D, Jacobi-CG in 2-D).  Return mapping, consistent tangent and internal force are evaluated
+        on the device in one call per iterate (fs_assemble_plasticity) from the history committed by the previous step; this loop only
+        decides about convergence.  A trial iterate with a non-finite residual is halved, at most 10 times.  The history is committed
+        when the step has converged and not otherwise: an error leaves the committed state as it was."""
+        from . import backend, parallel
+        from .fem import Function
+        if parallel.world()[1] > 1:
+            raise SolverError('plastic Newton solves run on one rank')
+        sp = self.solver_settings.get('solver_parameters', {}) or {}
+        newton = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
+        rtol = float(newton.get('relative_tolerance', 1e-9))
+        atol = float(newton.get('absolute_tolerance', 1e-10))
+        max_it = int(newton.get('maximum_iterations', 50))
+        relax = float(newton.get('relaxation_parameter', 1.0))
+        V = F.space.device()
+        loc = F.space.localizer()
+
+        def to_dev(xh):
+            xd = xh if loc is None else loc.nodes(xh)
+            return np.concatenate([xd, np.zeros(V.n_local - len(xd))]) if len(xd) < V.n_local else xd
+
+        steps_hint = ('apply the load in smaller steps (transient_settings with boundary values and loads that change from step to '
+                      'step), or give the material a hardening_modulus > 0')
+        gdofs, gvals = self._bc_arrays(bcs)
+        dofs = gdofs if loc is None else loc.dofs(gdofs, gvals)[0]
+        material = F.material_spec()
+        if F.cellwise() and loc is not None:
+            material = ('cell', loc.cells(material[1]))
+        history = F.history
+        f_ext = self._hyperelastic_external_loads(F, V, loc)
+        K = backend.DeviceMatrix(V)
+        r = backend.DeviceVector(V.n_owned)
+        ud = backend.DeviceVector(V.n_local)
+
+        def evaluate(xh):
+            """Trial history, tangent and internal force minus loads at xh in ONE call; (info, ||r|| with the Dirichlet rows zeroed) -
+            None for a non-finite state.  K, r and the trial history then belong to the last state evaluated."""
+            ud.set(to_dev(xh))
+            info = backend.assemble_plasticity(V, ud, history, material, K=K, r=r)
+            if info['n_nonfinite']:
+                return info, None
+            r.axpy(-1.0, f_ext)
+            if dofs.size:
+                backend.set_dirichlet_values(r, dofs, 0.0)
+            rn = float(np.sqrt(r.dot(r)))
+            return info, (rn if np.isfinite(rn) else None)
+
+        x = u_current.vector()._values().copy()
+        if gdofs.size:
+            x[gdofs] = gvals                                # the first iterate carries the boundary values
+        info, rnorm = evaluate(x)
+        if rnorm is None:
+            raise SolverError('plastic Newton: the residual of the initial iterate is not finite')
+        r0 = rnorm
+        self.newton_iterations = 0
+        self.newton_history = [rnorm]
+        self.newton_stats = []
+        self.newton_steps = []
+        du = Function(self.function_space)
+        for it in range(max_it + 1):
+            if sp.get('monitor_convergence'):
+                self.logger.info("Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = %.3e (tol = %.3e), %d cells yielding",
+                                 it, rnorm, atol, rnorm / r0 if r0 > 0 else 0.0, rtol, info['n_yielded'])
+            if rnorm < atol or (r0 > 0 and rnorm / r0 < rtol):
+                break
+            if it == max_it:
+                raise SolverError('Newton solver did not converge in {} iterations (residual {:.3e}): {}'.format(max_it, rnorm, steps_hint))
+            rhs = backend.DeviceVector(V.n_owned)
+            rhs.axpy(-1.0, r)
+            if dofs.size:
+                K.apply_dirichlet(rhs, dofs, 0.0, symmetric=True)     # the correction is zero on the Dirichlet boundary
+            try:
+                if self.dimension == 3:
+                    self._device_solve(K, rhs, du, 'plastic Newton step', amg=True, near_nullspace="rigid_body", operator_key=None)
+                else:
+                    self._device_solve(K, rhs, du, 'plastic Newton step')
+            except (SolverError, backend.BackendError) as e:
+                st = self.last_solve_stats or {}
+                if isinstance(e, backend.BackendError) and getattr(e, 'rc', None) == -6 or \
+                        (isinstance(e, SolverError) and st.get('converged', 0) < 0):      # FS_ERR_NUMERIC: CG breakdown
+                    raise SolverError('plastic Newton: CG broke down at iteration {} - the consistent tangent is singular there (a limit '
+                                      'load with hardening_modulus = 0): {}'.format(it, steps_hint)) from e
+                raise
+            st = self.last_solve_stats
+            self.newton_stats.append({'krylov_iterations': st['iterations'], 'solve_ms': st['solve_ms'],
+                                      'amg_setup_ms': st.get('amg_setup_ms', 0.0)})
+            d = du.vector()._values()
+            if not np.all(np.isfinite(d)):
+                raise SolverError('plastic Newton: the correction of iteration {} is not finite: {}'.format(it, steps_hint))
+            step = relax
+            for cut in range(11):
+                x_try = x + step * d
+                info, rn_try = evaluate(x_try)
+                if rn_try is not None:
+                    break
+                if cut == 10:
+                    raise SolverError('plastic Newton: at iteration {} the step, halved 10 times, still gives a non-finite residual: {}'.format(
+                        it, steps_hint))
+                step *= 0.5
+            if step != relax:
+                self.logger.info('plastic Newton: step of iteration %d cut to %g (non-finite residual at the full step)', it, step)
+            x = x_try
+            rnorm = rn_try
+            self.newton_steps.append(step)
+            self.newton_history.append(rnorm)
+            self.newton_iterations = it + 1
+        history.commit()                                    # the last evaluation was at the converged iterate
+        self.yielded_last_step = info['n_yielded']
         u_current.vector().set_local(x)
         return u_current
 

@@ -21,6 +21,9 @@ FS_COEF_NONE, FS_COEF_CONST, FS_COEF_CELL, FS_COEF_TENSOR, FS_COEF_NODAL, FS_COE
 FS_COEF_CELL_LAME = 8
 FS_HYPER_NEO_HOOKEAN = 0
 FS_HYPER_TANGENT, FS_HYPER_FORCE, FS_HYPER_ENERGY = 1, 2, 4
+FS_COEF_CELL_PLASTIC = 9
+FS_PLASTIC_TANGENT, FS_PLASTIC_FORCE = 1, 2
+FS_PLASTIC_COMMITTED, FS_PLASTIC_TRIAL = 0, 1
 FS_KSP_CG = 0
 FS_KSP_BICGSTAB = 1
 FS_PC_NONE, FS_PC_JACOBI, FS_PC_BLOCK_JACOBI = 0, 1, 2
@@ -59,6 +62,15 @@ class fs_hyper_form(C.Structure):
 
 class fs_hyper_info(C.Structure):
     _fields_ = [("energy", C.c_double), ("n_inverted", C.c_int64), ("first_inverted_cell", C.c_int64)]
+
+
+class fs_plastic_form(C.Structure):
+    _fields_ = [("mu", C.c_double), ("lambda_", C.c_double), ("yield_stress", C.c_double), ("hardening", C.c_double),
+                ("material", fs_coef), ("add", C.c_int)]
+
+
+class fs_plastic_info(C.Structure):
+    _fields_ = [("n_yielded", C.c_int64), ("n_nonfinite", C.c_int64), ("first_nonfinite_cell", C.c_int64)]
 
 
 class fs_dg_form(C.Structure):
@@ -208,7 +220,14 @@ SIGNATURES = {
     "fs_assemble_dg_transport": (C.c_int, [_H, _H, C.POINTER(fs_dg_form)]),
     "fs_assemble_dg_projection": (C.c_int, [_H, _H, _H, _H]),
     "fs_assemble_hyperelastic": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_hyper_form), C.c_int, C.POINTER(fs_hyper_info)]),
-    "fs_assemble_large_deformation": (C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
+    "fs_plastic_state_create": (C.c_int, [_H, C.POINTER(_H)]),
+    "fs_plastic_state_destroy": (C.c_int, [_H]),
+    "fs_plastic_state_reset": (C.c_int, [_H]),
+    "fs_plastic_state_commit": (C.c_int, [_H]),
+    "fs_plastic_state_get": (C.c_int, [_H, C.c_int, c_f64p, c_f64p, c_f64p]),
+    "fs_plastic_state_set": (C.c_int, [_H, c_f64p, c_f64p]),
+    "fs_assemble_plasticity": (C.c_int, [_H, _H, _H, _H, _H, C.POINTER(fs_plastic_form), C.c_int, C.POINTER(fs_plastic_info)]),
+    "fs_assemble_large_deformation":(C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),
     "fs_comm_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -550,6 +550,77 @@ def assemble_hyperelastic(space, u, lame, K=None, r=None, energy=False, add=Fals
             "first_inverted_cell": int(info.first_inverted_cell)}
 
 
+class PlasticHistory(_Handle):
+    """Per-cell history of the J2 return mapping on a vector CG1 space (fs_plastic_state_*): the committed state (plastic strain,
+    cumulative plastic strain, returned stress) and the trial state of the last assemble_plasticity.  The device keeps the cells in
+    its own order; ``cell_order`` (device cell -> caller's cell, None: the same order) maps every array that crosses this class, so
+    callers see their own cell numbering.  Tensors: (xx, yy, zz, xy, xz, yz) in 3-D, (xx, yy, zz, xy) in plane strain."""
+    _destroy = "fs_plastic_state_destroy"
+
+    def __init__(self, space, cell_order=None):
+        super().__init__()
+        self.space = space
+        self.n_cells = int(space.mesh.info()[1])
+        self.n_comp = 6 if space.ncomp == 3 else 4
+        self.cell_order = None if cell_order is None else np.asarray(cell_order, dtype=np.int64)
+        L.check(L.load().fs_plastic_state_create(space.h, C.byref(self.h)), "fs_plastic_state_create")
+
+    def reset(self):
+        L.check(L.load().fs_plastic_state_reset(self.h), "fs_plastic_state_reset")
+
+    def commit(self):
+        """trial -> committed: the load step has converged"""
+        L.check(L.load().fs_plastic_state_commit(self.h), "fs_plastic_state_commit")
+
+    def _to_host(self, a):
+        if self.cell_order is None:
+            return a
+        out = np.empty_like(a)
+        out[self.cell_order] = a
+        return out
+
+    def get(self, trial=False):
+        """(eps_p [n_cells, n_comp], p [n_cells], stress [n_cells, n_comp]) of the committed (or the trial) state"""
+        ep, p, sg = np.empty((self.n_cells, self.n_comp)), np.empty(self.n_cells), np.empty((self.n_cells, self.n_comp))
+        L.check(L.load().fs_plastic_state_get(self.h, L.FS_PLASTIC_TRIAL if trial else L.FS_PLASTIC_COMMITTED, L.p_f64(ep), L.p_f64(p),
+                                              L.p_f64(sg)), "fs_plastic_state_get")
+        return self._to_host(ep), self._to_host(p), self._to_host(sg)
+
+    def set(self, eps_p, p):
+        """the committed plastic strain and cumulative plastic strain from host arrays in the caller's cell numbering"""
+        ep = np.asarray(eps_p, dtype=np.float64).reshape(self.n_cells, self.n_comp)
+        p = np.asarray(p, dtype=np.float64).reshape(self.n_cells)
+        if self.cell_order is not None:
+            ep, p = ep[self.cell_order], p[self.cell_order]
+        ep, p = L.f64(ep), L.f64(p)
+        L.check(L.load().fs_plastic_state_set(self.h, L.p_f64(ep), L.p_f64(p)), "fs_plastic_state_set")
+
+
+def assemble_plasticity(space, u, history, material, K=None, r=None, add=False):
+    """Consistent tangent K and internal force r of J2 plasticity at the displacement u (DeviceVector of the space's dofs), from the
+    committed state of ``history`` (fs_assemble_plasticity); the trial state is left in ``history``.  material: (mu, lambda,
+    yield_stress, hardening) numbers or ('cell', array[n_cells, 4]) in DEVICE cell order.  K / r: the DeviceMatrix / DeviceVector to
+    fill (None: not computed).  Returns {'n_yielded', 'n_nonfinite', 'first_nonfinite_cell'}."""
+    f = L.fs_plastic_form()
+    keep = None
+    if isinstance(material, tuple) and len(material) == 2 and isinstance(material[0], str):
+        if material[0] != "cell":
+            raise BackendError("plastic material: four numbers or ('cell', array[n_cells, 4]), got kind %r" % (material[0],))
+        keep = np.ascontiguousarray(material[1], dtype=np.float64)
+        if keep.shape != (history.n_cells, 4):
+            raise BackendError("per-cell plastic material must be an array [%d, 4], got shape %s" % (history.n_cells, keep.shape))
+        f.material.mode = L.FS_COEF_CELL_PLASTIC
+        f.material.data = L.p_f64(keep)
+    else:
+        f.mu, f.lambda_, f.yield_stress, f.hardening = (float(x) for x in material)
+    f.add = 1 if add else 0
+    what = (L.FS_PLASTIC_TANGENT if K is not None else 0) | (L.FS_PLASTIC_FORCE if r is not None else 0)
+    info = L.fs_plastic_info()
+    L.check(L.load().fs_assemble_plasticity(space.h, K.h if K is not None else None, r.h if r is not None else None, u.h, history.h,
+                                            C.byref(f), int(what), C.byref(info)), "fs_assemble_plasticity")
+    return {"n_yielded": int(info.n_yielded), "n_nonfinite": int(info.n_nonfinite), "first_nonfinite_cell": int(info.first_nonfinite_cell)}
+
+
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):
     """b[vertex*9 + 3i + j] = int (nu (grad u + grad u^T) - p I)_ij phi_vertex dx for a Taylor-Hood iterate w.
     viscosity_law = (p_ref, exponent): nu (p / p_ref)^exponent."""

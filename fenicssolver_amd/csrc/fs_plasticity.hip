@@ -1,0 +1,583 @@
+// Small-strain von Mises (J2) plasticity with linear isotropic hardening on vector CG1 spaces (tetrahedra, and triangles in plane
+// strain): the return mapping with its per-cell history, the consistent tangent and the internal force, on the device.
+//
+// The reference names a PlasticitySolver (Readme.md, the docstring of LinearElasticitySolver.py) and never delivers one; the model
+// is the textbook radial return.  A P1 displacement has a constant strain per cell, so the cell is the integration point:
+//   eps = sym grad u,  e = eps - eps_p,  sigma_tr = K tr(e) I + 2 G dev(e),  s = dev sigma_tr,  q = sqrt(3/2) |s|,
+//   f = q - (sigma_y + H p);   f <= 0: elastic;   f > 0: dp = f / (3 G + H), N = s / |s|, beta = 3 G dp / q,
+//   sigma = sigma_tr - 2 G dp sqrt(3/2) N,  eps_p += sqrt(3/2) dp N,  p += dp,
+//   D = C - 2 G beta I_dev - 2 G (3G/(3G+H) - beta) N (x) N
+//     = lambda' I (x) I + 2 mu' I_sym - c N (x) N   with  mu' = G (1 - beta),  lambda' = lambda + 2/3 G beta.
+// D has the shape of the elastic operator with (mu', lambda') plus one rank-one term, so the tangent block of the linear kernel
+// carries over:  K_ab[i][k] = V (lambda' g_a[i] g_b[k] + mu' g_a[k] g_b[i] + delta_ik mu' g_a . g_b) - V c (N g_a)[i] (N g_b)[k].
+//
+// Kernels (no atomics anywhere: two assemblies of one state give the same bits):
+//   k_plastic_cells                       one thread per cell, ONCE per evaluation: strain, trial state, return mapping.  Writes the
+//       trial history (eps_p, p), the returned stress and the tangent record (mu', lambda', c, N); counts the yielded and the
+//       non-finite cells per workgroup (k_plastic_cells_finish sums the partials in a fixed order).
+//   k_plastic_tangent_gather / _tri_gather  one thread per STORED block sums its (cell, a, b) sources of the inverse slot table in
+//       ascending order - the walk of k_assemble_p1_elasticity_gather - and reads the cell's record instead of a material pair.  The
+//       elastic-shaped part is accumulated by the linear kernel's expression, the rank-one part in an accumulator of its own that
+//       stays +0 while no source cell has yielded: the tangent then equals fs_assemble_matrix of the linear operator bit for bit.
+//   k_plastic_force_gather / _tri_gather  one thread per owned node over the cells around it (the sources of its diagonal block,
+//       ascending): V sigma g_a from the stored stress.
+//
+// Tensor storage: 3-D (xx, yy, zz, xy, xz, yz), plane strain (xx, yy, zz, xy) - tensor components, not engineering shears.
+#include "fs_common.h"
+#include "fs_kernels.h"
+#include "fs_p1_geometry.h"
+#include <math.h>
+
+#define FS_PLASTIC_CELL_BLOCKS 1024      // workgroups of the per-cell pass (its partials are summed in this order)
+#define FS_PLASTIC_REC3 10               // doubles per cell of the 3-D tangent record: mu', lambda', c, 0, N[6]
+#define FS_PLASTIC_REC2 6                // plane strain: mu', lambda', c, Nxx, Nyy, Nxy
+
+struct fs_plastic_state_s {
+    fs_space_s* space = nullptr;
+    int tdim = 3;
+    int ne = 6;                          // stored components of eps_p and sigma (4 in plane strain)
+    int64_t nc = 0;
+    dbuf<double> ep, p;                  // committed history [nc][ne], [nc]
+    dbuf<double> ep_trial, p_trial;      // history of the last evaluation
+    dbuf<double> sig, sig_trial;         // returned stress of the committed state / of the last evaluation [nc][ne]
+    dbuf<double> rec;                    // tangent record of the last evaluation
+};
+
+// ---- per-cell return mapping ---------------------------------------------------------------------------------------------
+// mat[nc][4] = (mu, lambda, sigma_y, H) with CELL, else the four constants
+template <int TD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_plastic_cells(int64_t nc, const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
+                                                            const double* __restrict__ u, double mu0, double lambda0, double sy0, double h0,
+                                                            const double* __restrict__ mat, const box_snap bx,
+                                                            const double* __restrict__ ep0, const double* __restrict__ p0,
+                                                            double* __restrict__ ep1, double* __restrict__ p1, double* __restrict__ sig,
+                                                            double* __restrict__ rec, int64_t* __restrict__ part_y,
+                                                            int64_t* __restrict__ part_n, int64_t* __restrict__ part_first) {
+    constexpr int NE = TD == 3 ? 6 : 4;
+    int64_t n_y = 0, n_bad = 0, first = INT64_MAX;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
+        const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+        double mu = mu0, lambda = lambda0, sy = sy0, hm = h0;
+        if (CELL) {
+            const double2 m0 = reinterpret_cast<const double2*>(mat)[2 * c], m1 = reinterpret_cast<const double2*>(mat)[2 * c + 1];
+            mu = m0.x; lambda = m0.y; sy = m1.x; hm = m1.y;
+        }
+        // elastic strain e = sym grad u - eps_p, in the storage order of the file header
+        double e[NE];
+        if (TD == 3) {
+            const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+            const tet_geom t = tet_geometry_box(xyz4, v, bx);
+            double H[3][3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double ua = u[3 * (int64_t)v[a] + i];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) H[i][j] += ua * t.g[a][j];
+                }
+            e[0] = H[0][0]; e[1] = H[1][1]; e[2] = H[2][2];
+            e[3] = 0.5 * (H[0][1] + H[1][0]); e[4] = 0.5 * (H[0][2] + H[2][0]); e[5] = 0.5 * (H[1][2] + H[2][1]);
+        } else {
+            const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+            const int32_t v[3] = {v4.x, v4.y, v4.z};
+            double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double2 ua = reinterpret_cast<const double2*>(u)[v[a]];
+                H[0][0] += ua.x * t.g[a][0]; H[0][1] += ua.x * t.g[a][1];
+                H[1][0] += ua.y * t.g[a][0]; H[1][1] += ua.y * t.g[a][1];
+            }
+            e[0] = H[0][0]; e[1] = H[1][1]; e[2] = 0.0; e[3] = 0.5 * (H[0][1] + H[1][0]);
+        }
+        double epc[NE];
+#pragma unroll
+        for (int k = 0; k < NE; ++k) { epc[k] = ep0[NE * c + k]; e[k] -= epc[k]; }
+        const double pc = p0[c];
+        const double tr = e[0] + e[1] + e[2];
+        const double bulk = lambda + (2.0 / 3.0) * mu;
+        double s[NE];
+#pragma unroll
+        for (int k = 0; k < NE; ++k) s[k] = 2.0 * mu * (k < 3 ? e[k] - tr * (1.0 / 3.0) : e[k]);
+        double ss = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
+#pragma unroll
+        for (int k = 3; k < NE; ++k) ss += 2.0 * s[k] * s[k];
+        const double sn = sqrt(ss);
+        const double r32 = 1.224744871391589049;          // sqrt(3/2)
+        const double q = r32 * sn;
+        const double f = q - (sy + hm * pc);
+        double sg[NE];
+#pragma unroll
+        for (int k = 0; k < NE; ++k) sg[k] = s[k] + (k < 3 ? bulk * tr : 0.0);
+        double mu_t = mu, lambda_t = lambda, cn = 0.0, pn = pc;
+        double N[NE];
+#pragma unroll
+        for (int k = 0; k < NE; ++k) N[k] = 0.0;
+        if (!isfinite(f)) {
+            ++n_bad;
+            first = c < first ? c : first;
+        } else if (f > 0.0) {
+            ++n_y;
+            const double dp = f / (3.0 * mu + hm);
+            const double beta = 3.0 * mu * dp / q;
+            const double inv = 1.0 / sn;
+#pragma unroll
+            for (int k = 0; k < NE; ++k) {
+                N[k] = s[k] * inv;
+                sg[k] -= 2.0 * mu * dp * r32 * N[k];
+                epc[k] += r32 * dp * N[k];
+            }
+            pn = pc + dp;
+            mu_t = mu * (1.0 - beta);
+            lambda_t = lambda + (2.0 / 3.0) * mu * beta;
+            cn = 2.0 * mu * (3.0 * mu / (3.0 * mu + hm) - beta);
+        }
+#pragma unroll
+        for (int k = 0; k < NE; ++k) { ep1[NE * c + k] = epc[k]; sig[NE * c + k] = sg[k]; }
+        p1[c] = pn;
+        if (TD == 3) {
+            double2* rc = reinterpret_cast<double2*>(rec + FS_PLASTIC_REC3 * c);
+            rc[0] = make_double2(mu_t, lambda_t);
+            rc[1] = make_double2(cn, 0.0);
+            rc[2] = make_double2(N[0], N[1]);
+            rc[3] = make_double2(N[2], N[3]);
+            rc[4] = make_double2(N[NE - 2], N[NE - 1]);
+        } else {
+            double2* rc = reinterpret_cast<double2*>(rec + FS_PLASTIC_REC2 * c);
+            rc[0] = make_double2(mu_t, lambda_t);
+            rc[1] = make_double2(cn, N[0]);
+            rc[2] = make_double2(N[1], N[3]);
+        }
+    }
+    __shared__ int64_t sy_[FS_BLOCK / 64], sn_[FS_BLOCK / 64], sf_[FS_BLOCK / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        n_y += __shfl_down(n_y, off, 64);
+        n_bad += __shfl_down(n_bad, off, 64);
+        const int64_t o = __shfl_down(first, off, 64);
+        first = o < first ? o : first;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sy_[wave] = n_y; sn_[wave] = n_bad; sf_[wave] = first; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t ty = 0, tn = 0, tf = INT64_MAX;
+        for (int w = 0; w < FS_BLOCK / 64; ++w) {
+            ty += sy_[w];
+            tn += sn_[w];
+            tf = sf_[w] < tf ? sf_[w] : tf;
+        }
+        part_y[blockIdx.x] = ty;
+        part_n[blockIdx.x] = tn;
+        part_first[blockIdx.x] = tf;
+    }
+}
+
+__global__ void k_plastic_cells_finish(int nb, const int64_t* __restrict__ part_y, const int64_t* __restrict__ part_n,
+                                       const int64_t* __restrict__ part_first, int64_t* __restrict__ out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t ty = 0, tn = 0, tf = INT64_MAX;
+    for (int b = 0; b < nb; ++b) {
+        ty += part_y[b];
+        tn += part_n[b];
+        tf = part_first[b] < tf ? part_first[b] : tf;
+    }
+    out[0] = ty;
+    out[1] = tn;
+    out[2] = tf;
+}
+
+// ---- tangent: tetrahedra -------------------------------------------------------------------------------------------------
+// Same source walk as k_assemble_p1_elasticity_gather (source index = cell * 16 + a * 4 + b, groups of four with their cell
+// records fetched first).  ms0 is the linear kernel's mass term, passed as a run-time 0 so that the diagonal sum below is the
+// same expression (and the same rounding) as there.  N is fetched for yielded cells only (c != 0).
+template <bool ADD>
+__global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
+                                                                     const int32_t* __restrict__ src, const int32_t* __restrict__ cells,
+                                                                     const double* __restrict__ xyz4, const double* __restrict__ rec,
+                                                                     double ms0, int64_t plane, double* __restrict__ val, const box_snap bx) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; e < n_entries; e += stride) {
+        double acc[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        double accn[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        const int32_t q1 = ptr[e + 1];
+        constexpr int PF = 4;
+        for (int32_t q0 = ptr[e]; q0 < q1; q0 += PF) {
+          int32_t sc[PF];
+          int4 vc[PF];
+          double2 lc[PF], cc[PF];
+#pragma unroll
+          for (int w = 0; w < PF; ++w) sc[w] = q0 + w < q1 ? src[q0 + w] : -1;
+#pragma unroll
+          for (int w = 0; w < PF; ++w) {
+            vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[w] >> 4] : make_int4(0, 0, 0, 0);
+            const double2* rc = reinterpret_cast<const double2*>(rec + (int64_t)FS_PLASTIC_REC3 * (sc[w] >= 0 ? sc[w] >> 4 : 0));
+            lc[w] = sc[w] >= 0 ? rc[0] : make_double2(0.0, 0.0);
+            cc[w] = sc[w] >= 0 ? rc[1] : make_double2(0.0, 0.0);
+          }
+#pragma unroll
+          for (int w = 0; w < PF; ++w) {
+            if (q0 + w >= q1) break;
+            const int32_t sidx = sc[w];
+            const int a = (sidx >> 2) & 3, b = sidx & 3;
+            const int4 v4 = vc[w];
+            const double mu = lc[w].x, lambda = lc[w].y;
+            const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+            const tet_geom t = tet_geometry_box(xyz4, v, bx);
+            const double vol = t.adet * (1.0 / 6.0);
+            double ga[3], gb[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
+                gb[k] = b == 0 ? t.g[0][k] : b == 1 ? t.g[1][k] : b == 2 ? t.g[2][k] : t.g[3][k];
+            }
+            const double gg = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    double x = vol * (lambda * ga[i] * gb[j] + mu * ga[j] * gb[i]);
+                    if (i == j) x += vol * mu * gg + ms0;
+                    acc[i][j] += x;
+                }
+            if (cc[w].x != 0.0) {
+                const double2* rc = reinterpret_cast<const double2*>(rec + (int64_t)FS_PLASTIC_REC3 * (sidx >> 4));
+                const double2 n01 = rc[2], n23 = rc[3], n45 = rc[4];
+                // N = [[n0, n3, n4], [n3, n1, n5], [n4, n5, n2]]
+                const double na[3] = {n01.x * ga[0] + n23.y * ga[1] + n45.x * ga[2], n23.y * ga[0] + n01.y * ga[1] + n45.y * ga[2],
+                                      n45.x * ga[0] + n45.y * ga[1] + n23.x * ga[2]};
+                const double nb[3] = {n01.x * gb[0] + n23.y * gb[1] + n45.x * gb[2], n23.y * gb[0] + n01.y * gb[1] + n45.y * gb[2],
+                                      n45.x * gb[0] + n45.y * gb[1] + n23.x * gb[2]};
+                const double vc_ = vol * cc[w].x;
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) accn[i][j] += vc_ * na[i] * nb[j];
+            }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int64_t idx = (int64_t)(i * 3 + j) * plane + e;
+                const double x = acc[i][j] - accn[i][j];
+                val[idx] = ADD ? val[idx] + x : x;
+            }
+    }
+}
+
+// ---- tangent: triangles (plane strain), source index = cell * 9 + a * 3 + b, as k_assemble_tri_elasticity_gather -------------
+template <bool ADD>
+__global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_tri_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
+                                                                         const int32_t* __restrict__ src, const int32_t* __restrict__ cells,
+                                                                         const double* __restrict__ xyz4, const double* __restrict__ rec,
+                                                                         double ms0, int64_t plane, double* __restrict__ val) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; e < n_entries; e += stride) {
+        double acc[2][2] = {{0, 0}, {0, 0}};
+        double accn[2][2] = {{0, 0}, {0, 0}};
+        const int32_t q1 = ptr[e + 1];
+        for (int32_t q = ptr[e]; q < q1; ++q) {
+            const int32_t sidx = src[q];
+            const int64_t c = sidx / 9;
+            const int ab = sidx - (int32_t)(c * 9);
+            const int a = ab / 3, b = ab - 3 * a;
+            const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const double2* rc = reinterpret_cast<const double2*>(rec + FS_PLASTIC_REC2 * c);
+            const double2 ml = rc[0], cn = rc[1], n13 = rc[2];
+            const double mu = ml.x, lambda = ml.y;
+            const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+            const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
+            const double gb[2] = {b == 0 ? t.g[0][0] : (b == 1 ? t.g[1][0] : t.g[2][0]), b == 0 ? t.g[0][1] : (b == 1 ? t.g[1][1] : t.g[2][1])};
+            const double gg = ga[0] * gb[0] + ga[1] * gb[1];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    double x = t.area * (lambda * ga[i] * gb[j] + mu * ga[j] * gb[i]);
+                    if (i == j) x += t.area * mu * gg + ms0;
+                    acc[i][j] += x;
+                }
+            // in-plane part of N: [[Nxx, Nxy], [Nxy, Nyy]]
+            const double na[2] = {cn.y * ga[0] + n13.y * ga[1], n13.y * ga[0] + n13.x * ga[1]};
+            const double nb[2] = {cn.y * gb[0] + n13.y * gb[1], n13.y * gb[0] + n13.x * gb[1]};
+            const double vc_ = t.area * cn.x;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) accn[i][j] += vc_ * na[i] * nb[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int64_t idx = (int64_t)(i * 2 + j) * plane + e;
+                const double x = acc[i][j] - accn[i][j];
+                val[idx] = ADD ? val[idx] + x : x;
+            }
+    }
+}
+
+// ---- internal force ------------------------------------------------------------------------------------------------------
+// thread per owned node r: the sources of its diagonal block are (c, a, a) for every cell c holding the node, ascending in c
+__device__ __forceinline__ int64_t plastic_diag_entry(int64_t r, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col) {
+    const int64_t sp0 = slice_ptr[r >> 6];
+    const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
+    const int64_t base = sp0 + (r & 63);
+    for (int k = 0; k < width; ++k)
+        if (sell_col[base + (int64_t)k * FS_SLICE] == (int32_t)r) return base + (int64_t)k * FS_SLICE;
+    return -1;
+}
+
+template <bool ADD>
+__global__ void __launch_bounds__(FS_BLOCK) k_plastic_force_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
+                                                                   const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
+                                                                   const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
+                                                                   const double* __restrict__ xyz4, const double* __restrict__ sig,
+                                                                   const box_snap bx, double* __restrict__ f) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; r < n_rows; r += stride) {
+        const int64_t e = plastic_diag_entry(r, slice_ptr, sell_col);
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (e >= 0) {
+            const int32_t q1 = gptr[e + 1];
+            for (int32_t q = gptr[e]; q < q1; ++q) {
+                const int32_t sidx = gsrc[q];
+                const int64_t c = sidx >> 4;
+                const int a = (sidx >> 2) & 3;
+                const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+                const double2* sc = reinterpret_cast<const double2*>(sig + 6 * c);
+                const double2 s01 = sc[0], s23 = sc[1], s45 = sc[2];
+                const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+                const tet_geom t = tet_geometry_box(xyz4, v, bx);
+                const double vol = t.adet * (1.0 / 6.0);
+                double ga[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
+                // sigma = [[s0, s3, s4], [s3, s1, s5], [s4, s5, s2]]
+                acc[0] += vol * (s01.x * ga[0] + s23.y * ga[1] + s45.x * ga[2]);
+                acc[1] += vol * (s23.y * ga[0] + s01.y * ga[1] + s45.y * ga[2]);
+                acc[2] += vol * (s45.x * ga[0] + s45.y * ga[1] + s23.x * ga[2]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) f[3 * r + i] = ADD ? f[3 * r + i] + acc[i] : acc[i];
+    }
+}
+
+template <bool ADD>
+__global__ void __launch_bounds__(FS_BLOCK) k_plastic_force_tri_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
+                                                                       const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
+                                                                       const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
+                                                                       const double* __restrict__ xyz4, const double* __restrict__ sig,
+                                                                       double* __restrict__ f) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; r < n_rows; r += stride) {
+        const int64_t e = plastic_diag_entry(r, slice_ptr, sell_col);
+        double acc[2] = {0.0, 0.0};
+        if (e >= 0) {
+            for (int32_t q = gptr[e]; q < gptr[e + 1]; ++q) {
+                const int32_t sidx = gsrc[q];
+                const int64_t c = sidx / 9;
+                const int a = (sidx - (int32_t)(c * 9)) / 3;
+                const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+                const double2* sc = reinterpret_cast<const double2*>(sig + 4 * c);
+                const double2 s01 = sc[0], s23 = sc[1];          // (xx, yy), (zz, xy)
+                const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+                const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
+                acc[0] += t.area * (s01.x * ga[0] + s23.y * ga[1]);
+                acc[1] += t.area * (s23.y * ga[0] + s01.y * ga[1]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) f[2 * r + i] = ADD ? f[2 * r + i] + acc[i] : acc[i];
+    }
+}
+
+// ---- host side: the history object ---------------------------------------------------------------------------------------
+static int plastic_space_ok(const fs_space_s* sp, const char* who) {
+    FS_REFUSE_DG_SPACE(sp, who);
+    FS_REQUIRE(sp, "%s: null space", who);
+    const fs_mesh_s* m = sp->mesh;
+    FS_REQUIRE(sp->degree == 1 && ((m->tdim == 3 && sp->ncomp == 3) || (m->tdim == 2 && sp->ncomp == 2)),
+               "%s: vector CG1 spaces on tetrahedra or triangles only (this space: CG%d with %d components on a %d-D mesh)", who, sp->degree,
+               sp->ncomp, m->tdim);
+    FS_REQUIRE(m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local, "%s: the space has ghost nodes (several ranks): not supported", who);
+    return FS_OK;
+}
+
+extern "C" int fs_plastic_state_create(fs_space_t space, fs_plastic_state_t* out) {
+    FS_CHECK(fs_require_init());
+    FS_REQUIRE(out, "fs_plastic_state_create: null pointer");
+    FS_CHECK(plastic_space_ok(space, "fs_plastic_state_create"));
+    fs_plastic_state_s* st = new fs_plastic_state_s();
+    st->space = space;
+    st->tdim = space->mesh->tdim;
+    st->ne = st->tdim == 3 ? 6 : 4;
+    st->nc = space->mesh->nc;
+    const int64_t ne = st->nc * st->ne;
+    int rc = FS_OK;
+    if ((rc = st->ep.alloc(ne)) || (rc = st->ep_trial.alloc(ne)) || (rc = st->sig.alloc(ne)) || (rc = st->sig_trial.alloc(ne)) ||
+        (rc = st->p.alloc(st->nc)) || (rc = st->p_trial.alloc(st->nc)) ||
+        (rc = st->rec.alloc(st->nc * (st->tdim == 3 ? FS_PLASTIC_REC3 : FS_PLASTIC_REC2)))) {
+        delete st;
+        return rc;
+    }
+    *out = st;
+    rc = fs_plastic_state_reset(st);
+    if (rc != FS_OK) { delete st; *out = nullptr; }
+    return rc;
+}
+
+extern "C" int fs_plastic_state_destroy(fs_plastic_state_t st) {
+    delete st;
+    return FS_OK;
+}
+
+extern "C" int fs_plastic_state_reset(fs_plastic_state_t st) {
+    FS_REQUIRE(st, "fs_plastic_state_reset: null pointer");
+    hipStream_t s = fs_rt().stream;
+    FS_CHECK(st->ep.zero(s)); FS_CHECK(st->ep_trial.zero(s)); FS_CHECK(st->p.zero(s)); FS_CHECK(st->p_trial.zero(s));
+    FS_CHECK(st->sig.zero(s)); FS_CHECK(st->sig_trial.zero(s)); FS_CHECK(st->rec.zero(s));
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}
+
+extern "C" int fs_plastic_state_commit(fs_plastic_state_t st) {
+    FS_REQUIRE(st, "fs_plastic_state_commit: null pointer");
+    hipStream_t s = fs_rt().stream;
+    const size_t be = (size_t)st->nc * st->ne * sizeof(double);
+    if (st->nc) {
+        FS_HIP(hipMemcpyAsync(st->ep.p, st->ep_trial.p, be, hipMemcpyDeviceToDevice, s));
+        FS_HIP(hipMemcpyAsync(st->sig.p, st->sig_trial.p, be, hipMemcpyDeviceToDevice, s));
+        FS_HIP(hipMemcpyAsync(st->p.p, st->p_trial.p, (size_t)st->nc * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}
+
+extern "C" int fs_plastic_state_get(fs_plastic_state_t st, int which, double* eps_p, double* p, double* stress) {
+    FS_REQUIRE(st, "fs_plastic_state_get: null pointer");
+    FS_REQUIRE(which == FS_PLASTIC_COMMITTED || which == FS_PLASTIC_TRIAL, "fs_plastic_state_get: which is FS_PLASTIC_COMMITTED or FS_PLASTIC_TRIAL");
+    hipStream_t s = fs_rt().stream;
+    const bool tr = which == FS_PLASTIC_TRIAL;
+    if (eps_p) FS_CHECK((tr ? st->ep_trial : st->ep).download(eps_p, st->nc * st->ne, s));
+    if (p) FS_CHECK((tr ? st->p_trial : st->p).download(p, st->nc, s));
+    if (stress) FS_CHECK((tr ? st->sig_trial : st->sig).download(stress, st->nc * st->ne, s));
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}
+
+extern "C" int fs_plastic_state_set(fs_plastic_state_t st, const double* eps_p, const double* p) {
+    FS_REQUIRE(st && eps_p && p, "fs_plastic_state_set: null pointer");
+    for (int64_t c = 0; c < st->nc; ++c)
+        FS_REQUIRE(p[c] >= 0.0 && isfinite(p[c]), "fs_plastic_state_set: cell %lld (device order) has cumulative plastic strain %g: p >= 0 is "
+                   "required", (long long)c, p[c]);
+    hipStream_t s = fs_rt().stream;
+    FS_CHECK(st->ep.upload(eps_p, st->nc * st->ne, s));
+    FS_CHECK(st->p.upload(p, st->nc, s));
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}
+
+// ---- host side: the assembly ---------------------------------------------------------------------------------------------
+extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, fs_plastic_state_t state,
+                                      const fs_plastic_form* form, int what, fs_plastic_info* info) {
+    FS_REFUSE_DG_SPACE(space, "fs_assemble_plasticity"); FS_REFUSE_DG(K, "fs_assemble_plasticity");
+    FS_REQUIRE(space && u && form && state, "fs_assemble_plasticity: null pointer");
+    FS_REQUIRE((what & ~(FS_PLASTIC_TANGENT | FS_PLASTIC_FORCE)) == 0, "fs_assemble_plasticity: unknown bits in what (%d)", what);
+    FS_CHECK(plastic_space_ok(space, "fs_assemble_plasticity"));
+    fs_space_s* sp = space;
+    fs_mesh_s* m = sp->mesh;
+    FS_REQUIRE(state->space == sp && state->nc == m->nc, "fs_assemble_plasticity: the history belongs to another space");
+    FS_REQUIRE(sp->slots.p, "fs_assemble_plasticity: vector space without slot table");
+    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "fs_assemble_plasticity: displacement vector shorter than the space's dofs");
+    FS_REQUIRE(!(what & FS_PLASTIC_TANGENT) || (K && K->space == sp), "fs_assemble_plasticity: the tangent needs a matrix on this space");
+    FS_REQUIRE(!(what & FS_PLASTIC_FORCE) || (r && r->d.n >= sp->n_dofs_owned), "fs_assemble_plasticity: the internal force needs a vector of "
+               "the space's owned dofs");
+    FS_REQUIRE(form->material.mode == FS_COEF_NONE || form->material.mode == FS_COEF_CELL_PLASTIC,
+               "fs_assemble_plasticity: the material is FS_COEF_NONE (mu, lambda, yield_stress, hardening) or FS_COEF_CELL_PLASTIC");
+    const bool cellw = form->material.mode == FS_COEF_CELL_PLASTIC;
+    hipStream_t s = fs_rt().stream;
+    dbuf<double> mstore;
+    if (cellw) {
+        FS_REQUIRE(form->material.data, "fs_assemble_plasticity: per-cell material data pointer is null");
+        for (int64_t c = 0; c < m->nc; ++c) {
+            const double* mc = form->material.data + 4 * c;
+            FS_REQUIRE(mc[0] > 0.0 && mc[1] >= 0.0 && mc[2] > 0.0 && mc[3] >= 0.0 && isfinite(mc[0]) && isfinite(mc[1]) && isfinite(mc[2]) &&
+                       isfinite(mc[3]), "fs_assemble_plasticity: cell %lld (device order) has mu = %g, lambda = %g, yield stress = %g, hardening "
+                       "= %g: mu > 0, lambda >= 0, yield stress > 0 and hardening >= 0 are required", (long long)c, mc[0], mc[1], mc[2], mc[3]);
+        }
+        FS_CHECK(mstore.alloc(4 * m->nc));
+        FS_CHECK(mstore.upload(form->material.data, 4 * m->nc, s));
+    } else {
+        FS_REQUIRE(form->mu > 0.0 && form->lambda >= 0.0 && form->yield_stress > 0.0 && form->hardening >= 0.0 && isfinite(form->mu) &&
+                   isfinite(form->lambda) && isfinite(form->yield_stress) && isfinite(form->hardening),
+                   "fs_assemble_plasticity: mu > 0, lambda >= 0, yield stress > 0 and hardening >= 0 are required (mu = %g, lambda = %g, yield "
+                   "stress = %g, hardening = %g)", form->mu, form->lambda, form->yield_stress, form->hardening);
+    }
+    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    const box_snap bx = make_box_snap(m);
+    const bool add = form->add != 0;
+    const double ms0 = 0.0;
+    // 1. the return mapping, once per cell
+    const int nb = FS_PLASTIC_CELL_BLOCKS;
+    dbuf<int64_t> py, pn, pf, on;
+    FS_CHECK(py.alloc(nb)); FS_CHECK(pn.alloc(nb)); FS_CHECK(pf.alloc(nb)); FS_CHECK(on.alloc(3));
+#define FS_PC(T_, C_) hipLaunchKernelGGL((k_plastic_cells<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, form->mu, \
+                                         form->lambda, form->yield_stress, form->hardening, mstore.p, bx, state->ep.p, state->p.p,                \
+                                         state->ep_trial.p, state->p_trial.p, state->sig_trial.p, state->rec.p, py.p, pn.p, pf.p)
+    if (m->tdim == 3) { if (cellw) FS_PC(3, true); else FS_PC(3, false); }
+    else { if (cellw) FS_PC(2, true); else FS_PC(2, false); }
+#undef FS_PC
+    FS_KERNEL_CHECK();
+    hipLaunchKernelGGL(k_plastic_cells_finish, dim3(1), dim3(64), 0, s, nb, py.p, pn.p, pf.p, on.p);
+    FS_KERNEL_CHECK();
+    // 2. the tangent, per stored block
+    if (what & FS_PLASTIC_TANGENT) {
+        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
+#define FS_PT3(A_) hipLaunchKernelGGL((k_plastic_tangent_gather<A_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
+                                      sp->gmap_src.p, m->cells.p, m->xyz.p, state->rec.p, ms0, sp->sell_entries, K->val.p, bx)
+#define FS_PT2(A_) hipLaunchKernelGGL((k_plastic_tangent_tri_gather<A_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
+                                      sp->gmap_src.p, m->cells.p, m->xyz.p, state->rec.p, ms0, sp->sell_entries, K->val.p)
+        if (m->tdim == 3) { if (add) FS_PT3(true); else FS_PT3(false); }
+        else { if (add) FS_PT2(true); else FS_PT2(false); }
+#undef FS_PT3
+#undef FS_PT2
+        FS_KERNEL_CHECK();
+    }
+    // 3. the internal force, per owned node
+    if (what & FS_PLASTIC_FORCE) {
+        const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
+#define FS_PF3(A_) hipLaunchKernelGGL((k_plastic_force_gather<A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
+                                      sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig_trial.p, bx, r->d.p)
+#define FS_PF2(A_) hipLaunchKernelGGL((k_plastic_force_tri_gather<A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
+                                      sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig_trial.p, r->d.p)
+        if (m->tdim == 3) { if (add) FS_PF3(true); else FS_PF3(false); }
+        else { if (add) FS_PF2(true); else FS_PF2(false); }
+#undef FS_PF3
+#undef FS_PF2
+        FS_KERNEL_CHECK();
+    }
+    if (info) {
+        int64_t n_host[3] = {0, 0, 0};
+        FS_CHECK(on.download(n_host, 3, s));
+        info->n_yielded = n_host[0];
+        info->n_nonfinite = n_host[1];
+        int64_t first = n_host[1] > 0 ? n_host[2] : -1;
+        if (first >= 0 && !m->cell_order.empty()) first = m->cell_order[first];     // the caller's cell number
+        info->first_nonfinite_cell = first;
+    }
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}

@@ -180,6 +180,43 @@ class HyperelasticForm:
         }
 
 
+class PlasticForm:
+    """r(u) = int sigma(eps(u); history) : grad v dx - int B.v dx - loads.v ds with sigma the radial return of small-strain J2
+    plasticity with linear isotropic hardening (PlasticitySolver); SolverBase._plastic_newton solves r = 0 per load step.  Dead
+    loads with their physical sign, as in HyperelasticForm.  ``history``: the backend.PlasticHistory the solver keeps across steps."""
+
+    def __init__(self, space):
+        self.space = space
+        self.mu = None                # numbers (homogeneous) or arrays [n_cells] (per-cell material, host cell order)
+        self.lmbda = None
+        self.yield_stress = None
+        self.hardening = 0.0
+        self.body_force = None
+        self.body_force_nodal = None
+        self.tractions = []
+        self.history = None
+
+    def cellwise(self):
+        return any(np.ndim(v) > 0 for v in (self.mu, self.lmbda, self.yield_stress, self.hardening))
+
+    def material_spec(self):
+        """Material argument of backend.assemble_plasticity: four numbers, or ('cell', [n_cells, 4]) in host cell order."""
+        vals = (self.mu, self.lmbda, self.yield_stress, self.hardening)
+        if not self.cellwise():
+            return tuple(float(v) for v in vals)
+        n = max(np.size(v) for v in vals)
+        return ("cell", np.stack([np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)) for v in vals], axis=1))
+
+    def describe(self):
+        return {
+            "type": "plasticity", "mu": _material(self.mu), "lambda": _material(self.lmbda),
+            "yield_stress": _material(self.yield_stress), "hardening": _material(self.hardening),
+            "body_force": None if self.body_force is None else tuple(float(x) for x in self.body_force),
+            "tractions": [(t.marker_id, _plain(t.g), t.origin) if isinstance(t, FacetLoad) else ("nodal", len(t.dofs), t.origin)
+                          for t in self.tractions],
+        }
+
+
 def _material(v):
     """A material value: the number itself, or a per-cell array by its shape and range."""
     if np.ndim(v) == 0:

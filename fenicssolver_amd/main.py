@@ -30,7 +30,7 @@ def load_settings(case_input):
 
 
 _SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
-            "NonlinearElasticitySolver", "LargeDeformationSolver")
+            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver")
 
 
 def main(case_input):
@@ -46,6 +46,8 @@ def main(case_input):
         from .NonlinearElasticitySolver import NonlinearElasticitySolver as cls
     elif solver_name == "LargeDeformationSolver":
         from .LargeDeformationSolver import LargeDeformationSolver as cls
+    elif solver_name == "PlasticitySolver":
+        from .PlasticitySolver import PlasticitySolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

@@ -381,6 +381,56 @@ typedef struct fs_hyper_info {
 int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, const fs_hyper_form* form, int what,
                              fs_hyper_info* info);
 
+/* ---- Small-strain J2 plasticity (PlasticitySolver; the reference names the class in its Readme and never delivers it) ----------
+ * Rate-independent von Mises plasticity with linear isotropic hardening on a vector CG1 space over tetrahedra or triangles (plane
+ * strain), one rank.  One integration point per cell: eps = sym grad u, e = eps - eps_p,
+ *   sigma_tr = K tr(e) I + 2 G dev(e),  s = dev sigma_tr,  q = sqrt(3/2) |s|,  f = q - (yield_stress + hardening * p);
+ *   f <= 0: sigma = sigma_tr, D = C, history unchanged;
+ *   f >  0: dp = f / (3 G + hardening), N = s / |s|, beta = 3 G dp / q, sigma = sigma_tr - 2 G dp sqrt(3/2) N,
+ *           eps_p += sqrt(3/2) dp N, p += dp, D = C - 2 G beta I_dev - 2 G (3G / (3G + hardening) - beta) N (x) N.
+ * The history object holds, per cell in DEVICE cell order, the committed state (eps_p, p, returned stress) and the trial state of
+ * the last fs_assemble_plasticity.  Tensors are stored as (xx, yy, zz, xy, xz, yz) in 3-D and (xx, yy, zz, xy) in plane strain
+ * (eps_zz = 0, but eps_p,zz and sigma_zz are not): n_comp = 6 or 4 tensor components per cell.
+ *   fs_plastic_state_create   a history on the space, all zero          fs_plastic_state_destroy  frees it
+ *   fs_plastic_state_reset    committed and trial state back to zero    fs_plastic_state_commit   trial -> committed (a converged step)
+ *   fs_plastic_state_get      which = FS_PLASTIC_COMMITTED / FS_PLASTIC_TRIAL: eps_p[n_cells][n_comp], p[n_cells],
+ *                             stress[n_cells][n_comp] to the host (any of the three may be NULL)
+ *   fs_plastic_state_set      the committed eps_p and p from the host (p >= 0 in every cell)
+ * fs_assemble_plasticity evaluates at the displacement u from the COMMITTED history, which it does not change:
+ *   FS_PLASTIC_TANGENT  K = int B^T D B dx, the consistent tangent (pattern of the space, no Dirichlet rows);
+ *   FS_PLASTIC_FORCE    r = int sigma : grad v dx, the internal force of the returned stress (owned dofs).
+ * The return mapping runs once per cell and writes the trial state; tangent and force are gathered from it without atomics, so a
+ * repeated call gives the same bits.  While no cell yields, the tangent equals fs_assemble_matrix of the linear elasticity operator
+ * with the same (mu, lambda) bit for bit.  K and r are overwritten, or added to with form->add.
+ * info (optional): the cells with f > 0 in this evaluation, the cells whose f is not finite (their results are meaningless) and one
+ * of those in the caller's cell numbering (-1: none).  Other spaces, several ranks, a history of another space, mu <= 0, lambda < 0,
+ * yield_stress <= 0 or hardening < 0 (constant or in any cell): FS_ERR_INVALID with a message. */
+#define FS_COEF_CELL_PLASTIC 9 /* fs_plastic_form.material only: data[n_cells][4] = (mu, lambda, yield_stress, hardening) per cell */
+#define FS_PLASTIC_TANGENT 1
+#define FS_PLASTIC_FORCE 2
+#define FS_PLASTIC_COMMITTED 0
+#define FS_PLASTIC_TRIAL 1
+typedef struct fs_plastic_state_s* fs_plastic_state_t;
+typedef struct fs_plastic_form {
+    double mu, lambda;              /* Lame parameters (G = mu) when material.mode == FS_COEF_NONE */
+    double yield_stress, hardening; /* sigma_y > 0 and H = d sigma_y / dp >= 0, likewise */
+    fs_coef material;               /* FS_COEF_NONE or FS_COEF_CELL_PLASTIC (host, device cell order) */
+    int add;                        /* 0: overwrite K / r; 1: add to them */
+} fs_plastic_form;
+typedef struct fs_plastic_info {
+    int64_t n_yielded;
+    int64_t n_nonfinite;
+    int64_t first_nonfinite_cell;
+} fs_plastic_info;
+int fs_plastic_state_create(fs_space_t space, fs_plastic_state_t* out);
+int fs_plastic_state_destroy(fs_plastic_state_t state);
+int fs_plastic_state_reset(fs_plastic_state_t state);
+int fs_plastic_state_commit(fs_plastic_state_t state);
+int fs_plastic_state_get(fs_plastic_state_t state, int which, double* eps_p, double* p, double* stress);
+int fs_plastic_state_set(fs_plastic_state_t state, const double* eps_p, const double* p);
+int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, fs_plastic_state_t state,
+                           const fs_plastic_form* form, int what, fs_plastic_info* info);
+
 /* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
  * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
  * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
