@@ -31,13 +31,14 @@ from __future__ import annotations
 
 import numpy as np
 
-from .fem import Measure, Function
+from .fem import Measure
 from .SolverBase import SolverError
 from .LinearElasticitySolver import LinearElasticitySolver
+from .stored_stress import StoredStressVonMises
 from . import forms
 
 
-class PlasticitySolver(LinearElasticitySolver):
+class PlasticitySolver(StoredStressVonMises, LinearElasticitySolver):
     def __init__(self, case_settings):
         LinearElasticitySolver.__init__(self, case_settings)
         self.reference_load_sign = False          # dead loads with their physical sign, as in NonlinearElasticitySolver
@@ -137,36 +138,3 @@ class PlasticitySolver(LinearElasticitySolver):
     def stress(self):
         """The RETURNED stress per cell after the last converged step (same layout as plastic_strain) - not C : eps(u)."""
         return self._committed()[2]
-
-    def von_Mises_cells(self):
-        """sqrt(3/2) |dev sigma| of the returned stress, per cell"""
-        s = self.stress()
-        m = s[:, :3].mean(axis=1)
-        dev2 = ((s[:, :3] - m[:, None]) ** 2).sum(axis=1) + 2.0 * (s[:, 3:] ** 2).sum(axis=1)
-        return np.sqrt(1.5 * dev2)
-
-    def von_Mises(self, u=None):
-        """The consistent L2 projection onto CG1 of the von Mises value of the RETURNED stress (the inherited method would project
-        the elastic stress of u, which is wrong once a cell has yielded): right-hand side int vm phi_a dx with the per-cell value,
-        P1 mass matrix, Jacobi-CG to 1e-12 on the device.  ``u`` is accepted for the inherited signature and not used."""
-        from .fem import FunctionSpace
-        from . import backend
-        vm = self.von_Mises_cells()
-        P = FunctionSpace(self.mesh, 'P', 1)
-        dP = P.device()
-        ploc = P.localizer()
-        b = backend.DeviceVector(dP.n_owned)
-        backend.assemble_vector(dP, b, source=('cell', vm if ploc is None else ploc.cells(vm)))
-        M = backend.DeviceMatrix(dP)
-        M.assemble(mass=1.0)
-        x = backend.DeviceVector(dP.n_local)
-        st = backend.krylov_solve(M, b, x, rtol=1e-12, max_iter=2000, precond="jacobi", norm="preconditioned")
-        if st['converged'] != 1:
-            raise SolverError('von_Mises: the mass-matrix solve did not converge')
-        f = Function(P)
-        xh = x.get()[:dP.n_owned]
-        if ploc is not None:
-            from . import parallel
-            xh = parallel.gather_owned(xh, ploc.owned_gids(), ploc.n_global, 1)
-        f.vector().set_local(xh)
-        return f

@@ -1181,6 +1181,87 @@ class SolverBase():
         u_current.vector().set_local(x)
         return u_current
 
+    # ---- Prony-series viscoelasticity (ViscoelasticitySolver) ------------------------------------------------
+    def _viscoelastic_step(self, F, u_current, bcs):
+        """One step of ViscoelasticitySolver, a single linear solve: (1) the history load -int B^T s_hist dx from the COMMITTED
+        history (fs_assemble_viscoelastic), (2) K(mu_eff, lambda_eff) u = f_ext + history load with the Dirichlet values imposed -
+        CG + AMG with the rigid-body near-null space in 3-D, Jacobi-CG in 2-D, (3) the per-cell update at u, (4) commit.  A solve that
+        does not converge raises before (3): the committed history stays as it was.  The effective operator depends on the step
+        length and the material only, so it is assembled once and kept while both (and the set of Dirichlet dofs) are unchanged,
+        and with it the AMG hierarchy (the operator key of _device_solve): ``operator_assemblies`` and ``amg_setups`` count the
+        builds.  F.steady: the long-term equilibrium - the same solve with mu = G0 g_inf and no history load."""
+        from . import backend, parallel
+        if parallel.world()[1] > 1:
+            raise SolverError('viscoelastic steps run on one rank')
+        V = F.space.device()
+        loc = F.space.localizer()
+
+        def to_dev(xh):
+            xd = xh if loc is None else loc.nodes(xh)
+            return np.concatenate([xd, np.zeros(V.n_local - len(xd))]) if len(xd) < V.n_local else xd
+
+        def cell_spec(spec):
+            return ('cell', loc.cells(spec[1])) if isinstance(spec[0], str) and loc is not None else spec
+
+        gdofs, gvals = self._bc_arrays(bcs)
+        dofs, vals = (gdofs, gvals) if loc is None else loc.dofs(gdofs, gvals)
+        dt = 1.0 if F.steady else float(F.dt)
+        history = F.history
+        # the effective operator and everything derived from the material: once per (dt, material, Dirichlet set).  Forms of one
+        # solve() carry the material under one token, so a step that changes nothing costs no host work per cell here.
+        dof_bytes = np.asarray(dofs, dtype=np.int64).tobytes()
+        ctx = getattr(self, '_visco_ctx', None)
+        token = getattr(F, 'material_token', None)
+        if ctx is None or token is None or ctx['token'] is not token or ctx['steady'] != bool(F.steady) or ctx['dt'] != dt \
+                or ctx['dofs'] != dof_bytes or ctx['space'] is not V:
+            mu_e, lm_e = F.effective_lame(None if F.steady else F.dt)
+            cellwise = np.ndim(mu_e) > 0 or np.ndim(lm_e) > 0
+            lame_host = np.stack(np.broadcast_arrays(np.asarray(mu_e, dtype=np.float64), np.asarray(lm_e, dtype=np.float64)), axis=-1)
+            if F.steady:                                # an elastic material with the long-term moduli, no series
+                material = ('cell', lame_host) if cellwise else (float(mu_e), float(lm_e), [])
+            else:
+                material = F.material_spec()
+            K_raw = backend.DeviceMatrix(V)
+            K_raw.assemble(lame=cell_spec(('cell', lame_host)) if cellwise else (float(mu_e), float(lm_e)))
+            self.operator_assemblies = getattr(self, 'operator_assemblies', 0) + 1
+            self._visco_serial = getattr(self, '_visco_serial', 0) + 1          # never reused: the key of the AMG hierarchy
+            ctx = {'token': token, 'steady': bool(F.steady), 'dt': dt, 'dofs': dof_bytes, 'space': V, 'material': cell_spec(material),
+                   'K_raw': K_raw, 'K': backend.DeviceMatrix(V), 'key': ('viscoelastic', self._visco_serial)}
+            self._visco_ctx = ctx
+        material = ctx['material']
+        # 1. right-hand side: loads plus the history load
+        rhs = self._hyperelastic_external_loads(F, V, loc)
+        times = {'history_load_ms': 0.0}
+        if not F.steady and history.n_terms:
+            info = backend.assemble_viscoelastic(V, history, material, dt, load=rhs, add=True)
+            times['history_load_ms'] = info['load_ms']
+        # 2. the solve; the Dirichlet rows and the lifting of their values go into a copy of the kept operator
+        K = ctx['K']
+        K.copy_from(ctx['K_raw'])
+        if len(dofs):
+            K.apply_dirichlet(rhs, dofs, vals, symmetric=True)
+        if self.dimension == 3:
+            self._device_solve(K, rhs, u_current, 'viscoelastic step', amg=True, near_nullspace="rigid_body", operator_key=ctx['key'])
+        else:
+            self._device_solve(K, rhs, u_current, 'viscoelastic step')
+        st = self.last_solve_stats
+        if 'amg_reused' in st and not st['amg_reused']:
+            self.amg_setups = getattr(self, 'amg_setups', 0) + 1
+        x = u_current.vector()._values()
+        if not np.all(np.isfinite(x)):
+            raise SolverError('viscoelastic step: the displacement is not finite')
+        # 3. the update, 4. commit
+        ud = backend.DeviceVector(V.n_local, to_dev(x))
+        info = backend.assemble_viscoelastic(V, history, material, dt, u=ud)
+        if info['n_nonfinite']:
+            raise SolverError('viscoelastic step: the updated stress is not finite in {} cell(s), first cell {}'.format(
+                info['n_nonfinite'], info['first_nonfinite_cell']))
+        history.commit()
+        times.update({'update_ms': info['update_ms'], 'solve_ms': st['solve_ms'], 'krylov_iterations': st['iterations'],
+                      'amg_setup_ms': st.get('amg_setup_ms', 0.0) if not st.get('amg_reused', True) else 0.0})
+        self.step_stats.append(times)
+        return u_current
+
     # ---- Taylor-Hood Navier-Stokes (CoupledNavierStokesSolver) -----------------------------------------
     def _navier_stokes_context(self, F, bcs):
         """Device objects shared by the steps of one solve: mixed space, pressure operators, BC lists (local

@@ -24,6 +24,10 @@ FS_HYPER_TANGENT, FS_HYPER_FORCE, FS_HYPER_ENERGY = 1, 2, 4
 FS_COEF_CELL_PLASTIC = 9
 FS_PLASTIC_TANGENT, FS_PLASTIC_FORCE = 1, 2
 FS_PLASTIC_COMMITTED, FS_PLASTIC_TRIAL = 0, 1
+FS_VISCO_MAX_TERMS = 8
+FS_COEF_CELL_VISCO = 10
+FS_VISCO_LOAD, FS_VISCO_UPDATE, FS_VISCO_FORCE = 1, 2, 4
+FS_VISCO_COMMITTED, FS_VISCO_TRIAL = 0, 1
 FS_KSP_CG = 0
 FS_KSP_BICGSTAB = 1
 FS_PC_NONE, FS_PC_JACOBI, FS_PC_BLOCK_JACOBI = 0, 1, 2
@@ -71,6 +75,16 @@ class fs_plastic_form(C.Structure):
 
 class fs_plastic_info(C.Structure):
     _fields_ = [("n_yielded", C.c_int64), ("n_nonfinite", C.c_int64), ("first_nonfinite_cell", C.c_int64)]
+
+
+class fs_visco_form(C.Structure):
+    _fields_ = [("mu", C.c_double), ("lambda_", C.c_double), ("n_terms", C.c_int), ("g", C.c_double * FS_VISCO_MAX_TERMS),
+                ("tau", C.c_double * FS_VISCO_MAX_TERMS), ("material", fs_coef), ("dt", C.c_double), ("add", C.c_int)]
+
+
+class fs_visco_info(C.Structure):
+    _fields_ = [("n_nonfinite", C.c_int64), ("first_nonfinite_cell", C.c_int64), ("load_ms", C.c_double), ("update_ms", C.c_double),
+                ("force_ms", C.c_double)]
 
 
 class fs_dg_form(C.Structure):
@@ -227,6 +241,13 @@ SIGNATURES = {
     "fs_plastic_state_get": (C.c_int, [_H, C.c_int, c_f64p, c_f64p, c_f64p]),
     "fs_plastic_state_set": (C.c_int, [_H, c_f64p, c_f64p]),
     "fs_assemble_plasticity": (C.c_int, [_H, _H, _H, _H, _H, C.POINTER(fs_plastic_form), C.c_int, C.POINTER(fs_plastic_info)]),
+    "fs_visco_state_create": (C.c_int, [_H, C.c_int, C.POINTER(_H)]),
+    "fs_visco_state_destroy": (C.c_int, [_H]),
+    "fs_visco_state_reset": (C.c_int, [_H]),
+    "fs_visco_state_commit": (C.c_int, [_H]),
+    "fs_visco_state_get": (C.c_int, [_H, C.c_int, c_f64p, c_f64p, c_f64p]),
+    "fs_visco_state_set": (C.c_int, [_H, c_f64p, c_f64p]),
+    "fs_assemble_viscoelastic": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_visco_form), C.c_int, C.POINTER(fs_visco_info)]),
     "fs_assemble_large_deformation":(C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),

@@ -621,6 +621,97 @@ def assemble_plasticity(space, u, history, material, K=None, r=None, add=False):
     return {"n_yielded": int(info.n_yielded), "n_nonfinite": int(info.n_nonfinite), "first_nonfinite_cell": int(info.first_nonfinite_cell)}
 
 
+class ViscoHistory(_Handle):
+    """Per-cell history of the Prony-series update on a vector CG1 space (fs_visco_state_*): the committed state (deviatoric strain
+    e, viscous strains h_k, stress) and the trial state of the last update.  The device keeps the cells in its own order;
+    ``cell_order`` (device cell -> caller's cell, None: the same order) maps every array that crosses this class, so callers see
+    their own cell numbering.  Tensors: (xx, yy, zz, xy, xz, yz) in 3-D, (xx, yy, zz, xy) in plane strain."""
+    _destroy = "fs_visco_state_destroy"
+
+    def __init__(self, space, n_terms, cell_order=None):
+        super().__init__()
+        self.space = space
+        self.n_cells = int(space.mesh.info()[1])
+        self.n_comp = 6 if space.ncomp == 3 else 4
+        self.n_terms = int(n_terms)
+        self.cell_order = None if cell_order is None else np.asarray(cell_order, dtype=np.int64)
+        L.check(L.load().fs_visco_state_create(space.h, self.n_terms, C.byref(self.h)), "fs_visco_state_create")
+
+    def reset(self):
+        L.check(L.load().fs_visco_state_reset(self.h), "fs_visco_state_reset")
+
+    def commit(self):
+        """trial -> committed: the step has converged"""
+        L.check(L.load().fs_visco_state_commit(self.h), "fs_visco_state_commit")
+
+    def _to_host(self, a):
+        if self.cell_order is None:
+            return a
+        out = np.empty_like(a)
+        out[self.cell_order] = a
+        return out
+
+    def get(self, trial=False):
+        """(e [n_cells, n_comp], h [n_cells, n_terms, n_comp], stress [n_cells, n_comp]) of the committed (or the trial) state"""
+        e, sg = np.empty((self.n_cells, self.n_comp)), np.empty((self.n_cells, self.n_comp))
+        h = np.empty((self.n_cells, self.n_terms, self.n_comp))
+        L.check(L.load().fs_visco_state_get(self.h, L.FS_VISCO_TRIAL if trial else L.FS_VISCO_COMMITTED, L.p_f64(e),
+                                            L.p_f64(h) if self.n_terms else None, L.p_f64(sg)), "fs_visco_state_get")
+        return self._to_host(e), self._to_host(h), self._to_host(sg)
+
+    def set(self, e, h):
+        """the committed deviatoric strain and viscous strains from host arrays in the caller's cell numbering"""
+        e = np.asarray(e, dtype=np.float64).reshape(self.n_cells, self.n_comp)
+        h = np.asarray(h, dtype=np.float64).reshape(self.n_cells, self.n_terms, self.n_comp)
+        if self.cell_order is not None:
+            e, h = e[self.cell_order], h[self.cell_order]
+        e, h = L.f64(e), L.f64(h)
+        L.check(L.load().fs_visco_state_set(self.h, L.p_f64(e), L.p_f64(h) if self.n_terms else None), "fs_visco_state_set")
+
+
+def assemble_viscoelastic(space, history, material, dt, u=None, load=None, force=None, update=None, add=False):
+    """The device passes of one viscoelastic step (fs_assemble_viscoelastic).  material: (mu, lambda, [(g_k, tau_k), ...]) with the
+    INSTANTANEOUS Lame parameters, or ('cell', array[n_cells, 2 + 2 n_terms]) = (mu, lambda, g_1, tau_1, ...) per cell in DEVICE
+    cell order.  load: DeviceVector that receives -int B^T s_hist dx from the committed history; u: displacement (DeviceVector of
+    the space's dofs) at which the trial state is updated (update defaults to ``u is not None``); force: DeviceVector that receives
+    int B^T sigma dx of the trial stress.  Returns {'n_nonfinite', 'first_nonfinite_cell'} and the device milliseconds of the passes
+    that ran ('load_ms', 'update_ms', 'force_ms')."""
+    f = L.fs_visco_form()
+    keep = None
+    nt = history.n_terms
+    if isinstance(material, tuple) and len(material) == 2 and isinstance(material[0], str):
+        if material[0] != "cell":
+            raise BackendError("viscoelastic material: (mu, lambda, terms) or ('cell', array), got kind %r" % (material[0],))
+        keep = np.ascontiguousarray(material[1], dtype=np.float64)
+        if keep.shape != (history.n_cells, 2 + 2 * nt):
+            raise BackendError("per-cell viscoelastic material must be an array [%d, %d], got shape %s" % (
+                history.n_cells, 2 + 2 * nt, keep.shape))
+        f.material.mode = L.FS_COEF_CELL_VISCO
+        f.material.data = L.p_f64(keep)
+        f.n_terms = nt
+    else:
+        mu, lmbda, terms = material
+        terms = [(float(g), float(tau)) for g, tau in terms]
+        if len(terms) > L.FS_VISCO_MAX_TERMS:
+            raise BackendError("viscoelastic material: %d Prony terms, at most %d are supported" % (len(terms), L.FS_VISCO_MAX_TERMS))
+        f.mu, f.lambda_, f.n_terms = float(mu), float(lmbda), len(terms)
+        for k, (g, tau) in enumerate(terms):
+            f.g[k], f.tau[k] = g, tau
+    f.dt = float(dt)
+    f.add = 1 if add else 0
+    if load is not None and force is not None:
+        raise BackendError("assemble_viscoelastic: the history load and the internal force are separate calls")
+    if update is None:
+        update = u is not None
+    what = (L.FS_VISCO_LOAD if load is not None else 0) | (L.FS_VISCO_UPDATE if update else 0) | (L.FS_VISCO_FORCE if force is not None else 0)
+    r = load if load is not None else force
+    info = L.fs_visco_info()
+    L.check(L.load().fs_assemble_viscoelastic(space.h, r.h if r is not None else None, u.h if u is not None else None, history.h,
+                                              C.byref(f), int(what), C.byref(info)), "fs_assemble_viscoelastic")
+    return {"n_nonfinite": int(info.n_nonfinite), "first_nonfinite_cell": int(info.first_nonfinite_cell), "load_ms": info.load_ms,
+            "update_ms": info.update_ms, "force_ms": info.force_ms}
+
+
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):
     """b[vertex*9 + 3i + j] = int (nu (grad u + grad u^T) - p I)_ij phi_vertex dx for a Taylor-Hood iterate w.
     viscosity_law = (p_ref, exponent): nu (p / p_ref)^exponent."""

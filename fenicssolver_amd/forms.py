@@ -217,6 +217,80 @@ class PlasticForm:
         }
 
 
+PRONY_SERIES_X = 1e-5       # below this dt / tau the series of b_k replaces -expm1(-x) / x (fs_viscoelasticity.hip, FS_VISCO_SERIES_X)
+
+
+def prony_step_coefficients(x):
+    """(a, b) of the one-step recursion h^{n+1} = a h^n + b (e^{n+1} - e^n) for x = dt / tau: a = exp(-x), b = -expm1(-x) / x -
+    below PRONY_SERIES_X its series 1 - x/2 + x^2/6 - x^3/24 (dropped term x^4/120 < 1e-22), which covers x -> 0."""
+    x = np.asarray(x, dtype=np.float64)
+    small = x < PRONY_SERIES_X
+    xs = np.where(small, 1.0, x)
+    b = np.where(small, 1.0 - x * (0.5 - x * ((1.0 / 6.0) - x * (1.0 / 24.0))), -np.expm1(-xs) / xs)
+    return np.exp(-x), b
+
+
+class ViscoelasticForm:
+    """One step of small-strain linear viscoelasticity (generalized Maxwell solid, ViscoelasticitySolver):
+    K(mu_eff, lambda_eff) u = int B.v dx + loads.v ds - int B^T s_hist dx, solved by SolverBase._viscoelastic_step.  ``mu``, ``lmbda``:
+    the INSTANTANEOUS Lame parameters, ``terms``: the Prony series [(g_k, tau_k), ...]; each value a number or an array [n_cells]
+    in host cell order.  ``dt``: the step length; ``steady``: the long-term equilibrium (mu = G0 g_inf, no history).  Dead loads with
+    their physical sign, as in PlasticForm.  ``history``: the backend.ViscoHistory the solver keeps across steps."""
+
+    def __init__(self, space):
+        self.space = space
+        self.mu = None
+        self.lmbda = None
+        self.terms = []
+        self.dt = None
+        self.steady = False
+        self.body_force = None
+        self.body_force_nodal = None
+        self.tractions = []
+        self.history = None
+        self.material_token = None     # forms with the same (not None) token carry the same material
+
+    def cellwise(self):
+        return any(np.ndim(v) > 0 for v in [self.mu, self.lmbda] + [x for gt in self.terms for x in gt])
+
+    def material_spec(self):
+        """Material argument of backend.assemble_viscoelastic: (mu, lambda, terms), or ('cell', [n_cells, 2 + 2 n_terms]) in host
+        cell order."""
+        vals = [self.mu, self.lmbda] + [x for gt in self.terms for x in gt]
+        if not self.cellwise():
+            return (float(self.mu), float(self.lmbda), [(float(g), float(tau)) for g, tau in self.terms])
+        n = max(np.size(v) for v in vals)
+        return ("cell", np.stack([np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)) for v in vals], axis=1))
+
+    def long_term_fraction(self):
+        """g_inf = 1 - sum_k g_k (summed in the order of the series)"""
+        gsum = 0.0
+        for g, _ in self.terms:
+            gsum = gsum + np.asarray(g, dtype=np.float64)
+        return 1.0 - gsum
+
+    def effective_lame(self, dt=None):
+        """(mu_eff, lambda_eff) of the step operator: mu_eff = G0 (g_inf + sum_k g_k b_k(dt / tau_k)), lambda_eff = K - 2/3 mu_eff
+        with the bulk modulus K = lambda0 + 2/3 G0.  dt None: the long-term moduli (b_k = 0)."""
+        mu0, lm0 = np.asarray(self.mu, dtype=np.float64), np.asarray(self.lmbda, dtype=np.float64)
+        f = self.long_term_fraction()
+        if dt is not None:
+            for g, tau in self.terms:
+                f = f + np.asarray(g, dtype=np.float64) * prony_step_coefficients(float(dt) / np.asarray(tau, dtype=np.float64))[1]
+        mu = mu0 * f
+        lm = (lm0 + (2.0 / 3.0) * mu0) - (2.0 / 3.0) * mu
+        return (float(mu), float(lm)) if np.ndim(mu) == 0 and np.ndim(lm) == 0 else (mu, lm)
+
+    def describe(self):
+        return {
+            "type": "viscoelasticity", "mu": _material(self.mu), "lambda": _material(self.lmbda),
+            "prony_series": [(_material(g), _material(tau)) for g, tau in self.terms], "dt": self.dt, "steady": self.steady,
+            "body_force": None if self.body_force is None else tuple(float(x) for x in self.body_force),
+            "tractions": [(t.marker_id, _plain(t.g), t.origin) if isinstance(t, FacetLoad) else ("nodal", len(t.dofs), t.origin)
+                          for t in self.tractions],
+        }
+
+
 def _material(v):
     """A material value: the number itself, or a per-cell array by its shape and range."""
     if np.ndim(v) == 0:

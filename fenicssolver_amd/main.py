@@ -30,7 +30,7 @@ def load_settings(case_input):
 
 
 _SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
-            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver")
+            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver")
 
 
 def main(case_input):
@@ -48,6 +48,8 @@ def main(case_input):
         from .LargeDeformationSolver import LargeDeformationSolver as cls
     elif solver_name == "PlasticitySolver":
         from .PlasticitySolver import PlasticitySolver as cls
+    elif solver_name == "ViscoelasticitySolver":
+        from .ViscoelasticitySolver import ViscoelasticitySolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

@@ -431,6 +431,65 @@ int fs_plastic_state_set(fs_plastic_state_t state, const double* eps_p, const do
 int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, fs_plastic_state_t state,
                            const fs_plastic_form* form, int what, fs_plastic_info* info);
 
+/* ---- Small-strain linear viscoelasticity (ViscoelasticitySolver; the reference lists "viscoelastic" in its Readme and has none) ----
+ * Generalized Maxwell solid (Prony series) on a vector CG1 space over tetrahedra or triangles (plane strain), one rank, one
+ * integration point per cell.  Elastic bulk response, relaxing deviatoric response; with e = dev eps:
+ *   sigma(t) = K tr(eps) I + 2 G0 [ g_inf e + sum_k g_k h_k ],  h_k(t) = int_0^t exp(-(t - s) / tau_k) de/ds ds,  g_inf = 1 - sum_k g_k,
+ * G0 = mu and K = lambda + 2/3 mu the INSTANTANEOUS moduli.  One step of length dt (exact for a strain linear within the step), with
+ * x_k = dt / tau_k:  a_k = exp(-x_k),  b_k = -expm1(-x_k) / x_k  (for x_k < 1e-5 the series 1 - x/2 + x^2/6 - x^3/24, which agrees
+ * with the quotient to rounding there and has the limit 1 at x = 0),  h_k^{n+1} = a_k h_k^n + b_k (e^{n+1} - e^n).
+ * A step is one linear solve  K(mu_eff, lambda_eff) u^{n+1} = f_ext - int B^T s_hist dx  with the operator of fs_assemble_matrix and
+ *   mu_eff = G0 (g_inf + sum_k g_k b_k),  lambda_eff = K - 2/3 mu_eff,  s_hist = 2 G0 sum_k g_k (a_k h_k^n - b_k e^n).
+ * The history object holds, per cell in DEVICE cell order, the committed state (e, h_k, stress) and the trial state of the last
+ * update.  Tensors are stored as (xx, yy, zz, xy, xz, yz) in 3-D and (xx, yy, zz, xy) in plane strain (eps_zz = 0, but e_zz, h_k,zz and
+ * sigma_zz are not): n_comp = 6 or 4 tensor components; h is [n_cells][n_terms][n_comp].
+ *   fs_visco_state_create   a history for n_terms Prony terms (0 .. FS_VISCO_MAX_TERMS), all zero     fs_visco_state_destroy  frees it
+ *   fs_visco_state_reset    committed and trial state back to zero    fs_visco_state_commit   trial -> committed (a converged step)
+ *   fs_visco_state_get      which = FS_VISCO_COMMITTED / FS_VISCO_TRIAL: e[n_cells][n_comp], h[n_cells][n_terms][n_comp],
+ *                           stress[n_cells][n_comp] to the host (any of the three may be NULL)
+ *   fs_visco_state_set      the committed e and h from the host (finite values; h may be NULL when n_terms = 0)
+ * fs_assemble_viscoelastic does, in this order, what the bits of `what` ask for; it never changes the committed state:
+ *   FS_VISCO_LOAD    r = -int B^T s_hist dx from the COMMITTED (e, h_k) and this step's (a_k, b_k) (owned dofs; u may be NULL);
+ *   FS_VISCO_UPDATE  the trial state (e, h_k, sigma) at the displacement u from the committed one (r may be NULL);
+ *   FS_VISCO_FORCE   r = int B^T sigma dx of the TRIAL stress (not together with FS_VISCO_LOAD: both write r).
+ * The update runs once per cell; r is gathered per node over the cells around it in ascending order, without atomics: a repeated
+ * call gives the same bits, and a per-cell material that holds one constant gives the bits of that constant.  r is overwritten, or
+ * added to with form->add.  info (optional): the cells whose updated stress is not finite, one of them in the caller's cell
+ * numbering (-1: none), and the device time of each pass.  FS_ERR_INVALID with a message (which names the cell, in device order, for a per-cell material): other spaces,
+ * several ranks, a history of another space or another n_terms, n_terms > FS_VISCO_MAX_TERMS, mu <= 0, lambda + 2/3 mu <= 0,
+ * g_k <= 0, tau_k <= 0, sum g_k >= 1, dt <= 0 or not finite. */
+#define FS_VISCO_MAX_TERMS 8
+#define FS_COEF_CELL_VISCO 10 /* fs_visco_form.material only: data[n_cells][2 + 2 n_terms] = (mu, lambda, g_1, tau_1, g_2, tau_2, ...) per cell */
+#define FS_VISCO_LOAD 1
+#define FS_VISCO_UPDATE 2
+#define FS_VISCO_FORCE 4
+#define FS_VISCO_COMMITTED 0
+#define FS_VISCO_TRIAL 1
+typedef struct fs_visco_state_s* fs_visco_state_t;
+typedef struct fs_visco_form {
+    double mu, lambda;              /* instantaneous Lame parameters (G0 = mu) when material.mode == FS_COEF_NONE */
+    int n_terms;                    /* Prony terms, 0 (elastic) .. FS_VISCO_MAX_TERMS; the history's n_terms */
+    double g[FS_VISCO_MAX_TERMS];   /* relative moduli g_k > 0, sum < 1, when material.mode == FS_COEF_NONE */
+    double tau[FS_VISCO_MAX_TERMS]; /* relaxation times tau_k > 0, likewise */
+    fs_coef material;               /* FS_COEF_NONE or FS_COEF_CELL_VISCO (host, device cell order) */
+    double dt;                      /* the step length, > 0 */
+    int add;                        /* 0: overwrite r; 1: add to it */
+} fs_visco_form;
+typedef struct fs_visco_info {
+    int64_t n_nonfinite;
+    int64_t first_nonfinite_cell;
+    double load_ms, update_ms, force_ms; /* HIP-event time of the passes this call ran (0: not run); load and update include the
+                                            launch that tabulates (a_k, b_k) for a constant material */
+} fs_visco_info;
+int fs_visco_state_create(fs_space_t space, int n_terms, fs_visco_state_t* out);
+int fs_visco_state_destroy(fs_visco_state_t state);
+int fs_visco_state_reset(fs_visco_state_t state);
+int fs_visco_state_commit(fs_visco_state_t state);
+int fs_visco_state_get(fs_visco_state_t state, int which, double* e, double* h, double* stress);
+int fs_visco_state_set(fs_visco_state_t state, const double* e, const double* h);
+int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vector_t u, fs_visco_state_t state, const fs_visco_form* form, int what,
+                             fs_visco_info* info);
+
 /* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
  * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
  * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
