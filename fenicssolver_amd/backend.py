@@ -712,6 +712,75 @@ def assemble_viscoelastic(space, history, material, dt, u=None, load=None, force
             "update_ms": info.update_ms, "force_ms": info.force_ms}
 
 
+class WaveState(_Handle):
+    """Device state of the explicit wave marcher on a scalar CG1 space (fs_wave_state_*): u^{n-1}, u^n and a work field, the lumped
+    mass m, the lumped boundary damping d, the load F, the Dirichlet dofs with their values, and the step counter n.  Arrays are in
+    DEVICE dof order."""
+    _destroy = "fs_wave_state_destroy"
+
+    def __init__(self, space):
+        super().__init__()
+        self.space = space
+        self.n = int(space.n_owned)
+        L.check(L.load().fs_wave_state_create(space.h, C.byref(self.h)), "fs_wave_state_create")
+
+    def configure(self, dt, mass, damping=None, load=None, dirichlet_dofs=None, dirichlet_values=None):
+        m = L.f64(mass).ravel()
+        d = None if damping is None else L.f64(damping).ravel()
+        f = None if load is None else L.f64(load).ravel()
+        for name, a in (("mass", m), ("damping", d), ("load", f)):
+            if a is not None and a.size != self.n:
+                raise BackendError("WaveState.configure: %s has %d entries, the space has %d dofs" % (name, a.size, self.n))
+        dofs = L.i32([] if dirichlet_dofs is None else dirichlet_dofs).ravel()
+        vals = L.f64(np.broadcast_to(0.0 if dirichlet_values is None else dirichlet_values, dofs.shape))
+        L.check(L.load().fs_wave_state_configure(self.h, float(dt), L.p_f64(m), L.p_f64(d), L.p_f64(f), dofs.size, L.p_i32(dofs),
+                                                 L.p_f64(vals)), "fs_wave_state_configure")
+
+    def set(self, u_prev, u, step):
+        a, b = L.f64(u_prev).ravel(), L.f64(u).ravel()
+        if a.size != self.n or b.size != self.n:
+            raise BackendError("WaveState.set: fields of %d and %d entries, the space has %d dofs" % (a.size, b.size, self.n))
+        L.check(L.load().fs_wave_state_set(self.h, L.p_f64(a), L.p_f64(b), int(step)), "fs_wave_state_set")
+
+    def get(self):
+        """(u^{n-1}, u^n, n)"""
+        a, b, k = np.empty(self.n), np.empty(self.n), C.c_int64(0)
+        L.check(L.load().fs_wave_state_get(self.h, L.p_f64(a), L.p_f64(b), C.byref(k)), "fs_wave_state_get")
+        return a, b, k.value
+
+    def start(self, K, u0, v0, load_scale0=1.0, dirichlet_scale1=1.0):
+        """u^1 from (u^0, v^0): the state then holds (u^0, u^1), n = 1"""
+        a, b = L.f64(u0).ravel(), L.f64(v0).ravel()
+        if a.size != self.n or b.size != self.n:
+            raise BackendError("WaveState.start: fields of %d and %d entries, the space has %d dofs" % (a.size, b.size, self.n))
+        L.check(L.load().fs_wave_start(K.h, self.h, L.p_f64(a), L.p_f64(b), float(load_scale0), float(dirichlet_scale1)), "fs_wave_start")
+
+    def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
+        """len(load_scale) steps on the device without a host round trip (fs_wave_advance); step k of the call advances n -> n+1 with
+        load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1].  Returns {'traces': [n_steps, n_receivers] or None, 'energy':
+        [n_steps, 2] = (kinetic, potential) or None, and with info 'device_ms', 'n_nonfinite', 'first_nonfinite_step', 'step'}."""
+        sf, sg = L.f64(load_scale).ravel(), L.f64(dirichlet_scale).ravel()
+        if sf.size != sg.size:
+            raise BackendError("WaveState.advance: %d load factors and %d Dirichlet factors" % (sf.size, sg.size))
+        ns = sf.size
+        rec = L.i32([] if receivers is None else receivers).ravel()
+        tr = np.empty((ns, rec.size)) if (traces and rec.size) else None
+        en = np.empty((ns, 2)) if energy else None
+        inf = L.fs_wave_info() if info else None
+        L.check(L.load().fs_wave_advance(K.h, self.h, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
+                                         L.p_f64(tr), L.p_f64(en), C.byref(inf) if info else None), "fs_wave_advance")
+        out = {"traces": tr, "energy": en}
+        if info:
+            out.update(device_ms=inf.device_ms, n_nonfinite=int(inf.n_nonfinite), first_nonfinite_step=int(inf.first_nonfinite_step),
+                       step=int(inf.step))
+        return out
+
+
+def wave_advance(K, state, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
+    """A batch of explicit wave steps with the stiffness K on a WaveState (fs_wave_advance): see WaveState.advance."""
+    return state.advance(K, load_scale, dirichlet_scale, receivers=receivers, traces=traces, energy=energy, info=info)
+
+
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):
     """b[vertex*9 + 3i + j] = int (nu (grad u + grad u^T) - p I)_ij phi_vertex dx for a Taylor-Hood iterate w.
     viscosity_law = (p_ref, exponent): nu (p / p_ref)^exponent."""

@@ -408,6 +408,8 @@ int fs_dict_classes();
 void fs_amg_set_coarse_fp32(int on);   // fs_amg.hip: hierarchies built from now on keep their coarse / transfer operators in fp32 (1) or fp64 (0)
 // fs_krylov.hip: bare y = A x on the library stream, no halo exchange, no synchronisation.
 int fs_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s);
+// ... and what fs_spmv sets up on a space's first product, for callers that enqueue many fs_spmv_dev products without a wait
+int fs_spmv_prepare(fs_matrix_s* A, hipStream_t s);
 // fs_amg.hip: z = M r (one V-cycle) on device pointers, no synchronisation.
 struct fs_amg_s;
 int fs_amg_apply_dev(fs_amg_s* amg, const double* r, double* z, hipStream_t s);

@@ -1454,6 +1454,14 @@ int fs_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s) {
     return FS_OK;
 }
 
+// What fs_spmv builds on the first product of a space (the pair lists of the two-rows-per-lane kernel), for callers that then
+// enqueue many products through fs_spmv_dev without a synchronisation in between (fs_wave.hip).
+int fs_spmv_prepare(fs_matrix_s* A, hipStream_t s) {
+    fs_space_s* sp = A->space;
+    if (!fs_is_dg(sp) && A->bs == 1 && sp->n_pairs < 0 && spmv_use_pairs(sp, 1)) FS_CHECK(build_pair_lists(sp, s));
+    return FS_OK;
+}
+
 // fs_amg.hip: the products of one fs_amg_solve through the row dictionary where the fine operator's rows repeat (scalar and
 // 3 x 3 block operators of uniform boxes); fs_dict_end drops the table (row_dict_scope by hand: the call sites are in another file)
 int fs_dict_begin(fs_matrix_s* A, hipStream_t s) {

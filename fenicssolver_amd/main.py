@@ -30,7 +30,7 @@ def load_settings(case_input):
 
 
 _SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
-            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver")
+            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver", "WaveSolver")
 
 
 def main(case_input):
@@ -50,6 +50,8 @@ def main(case_input):
         from .PlasticitySolver import PlasticitySolver as cls
     elif solver_name == "ViscoelasticitySolver":
         from .ViscoelasticitySolver import ViscoelasticitySolver as cls
+    elif solver_name == "WaveSolver":
+        from .WaveSolver import WaveSolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

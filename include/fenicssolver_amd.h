@@ -490,6 +490,49 @@ int fs_visco_state_set(fs_visco_state_t state, const double* e, const double* h)
 int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vector_t u, fs_visco_state_t state, const fs_visco_form* form, int what,
                              fs_visco_info* info);
 
+/* ---- Explicit scalar wave propagation (WaveSolver; the reference lists "wave propagation" in its Readme and has none) --------
+ * u_tt = div(c^2 grad u) + f on a scalar CG1 space over tetrahedra or triangles, one rank: central differences with a lumped mass,
+ * so a step is ONE product with the assembled stiffness K (coefficient c^2, fs_assemble_matrix) and one pointwise update - no solve.
+ * Per row i: m_i = int phi_i dx (lumped mass, > 0), d_i >= 0 (lumped first-order absorbing boundary: the sum over the absorbing
+ * facets F around i of c |F| / dim), F_i the load; every load shares one time factor, f^n = s_f[n] F, and Dirichlet rows take
+ * g_i s_g[n].  Step n -> n+1 (n >= 1), with y = K u^n:
+ *   (m/dt^2 + d/(2 dt)) u^{n+1} = s_f[n] F - y + (2 m/dt^2) u^n - (m/dt^2 - d/(2 dt)) u^{n-1},  then u^{n+1}_i = g_i s_g[n+1] on Dirichlet rows.
+ * Start: a^0 = (s_f[0] F - K u^0 - d v^0) / m,  u^1 = u^0 + dt v^0 + dt^2/2 a^0 (Dirichlet rows: g s_g[1]).
+ * Discrete energy of step n -> n+1, its two halves reported separately:
+ *   E_kin = 1/2 sum_i m_i ((u^{n+1} - u^n)_i / dt)^2,   E_pot = 1/2 (u^{n+1})^T y   (constant for d = 0, F = 0 and fixed Dirichlet values).
+ * The state object holds u^{n-1}, u^n and a work field (rotated by pointer), the device copies of m, d, F, the Dirichlet rows and
+ * their values (uploaded once by fs_wave_state_configure; a Dirichlet row keeps g_i in the slot of F_i) and the step counter n.
+ *   fs_wave_state_create     a zero state (n = 0) on a scalar CG1 space             fs_wave_state_destroy   frees it
+ *   fs_wave_state_configure  dt and the arrays mass[n_dofs], damping[n_dofs] (NULL: none), load[n_dofs] (NULL: none), the Dirichlet
+ *                            dofs and values (a dof named twice takes the last value)
+ *   fs_wave_state_set / get  (u^{n-1}, u^n) and the step counter n from / to the host (get: any pointer may be NULL)
+ *   fs_wave_start            forms u^1 from (u^0, v^0) with s_f[0] and s_g[1]: the state then holds (u^0, u^1), n = 1
+ * fs_wave_advance enqueues n_steps steps on the library's stream with no host synchronisation between them: per step the product
+ * of K through the dispatch of fs_spmv, then ONE update kernel over the rows (the formula, the Dirichlet rows, the per-workgroup
+ * partials of both energy halves, the receiver samples).  Step k of the call advances n -> n+1 with load_scale[k] = s_f[n] and
+ * dirichlet_scale[k] = s_g[n+1]; traces[k][r] = u^{n+1}[receiver_dofs[r]] and energy[k] = (E_kin, E_pot) of that step (either may
+ * be NULL).  The partials are summed in a fixed order by a finishing pass (no floating-point atomics): a repeated run gives the
+ * same bits, and so does any split of a march into calls.  A non-finite field value makes the energy of its step non-finite: the
+ * finishing pass counts those steps on the device, read once per call.  The call waits for the device only if it hands data back
+ * (traces, energy or info).  FS_ERR_INVALID with a message: spaces other than scalar CG1, several ranks, a matrix of another space,
+ * dt <= 0 or not finite, m_i <= 0, d_i < 0, a receiver or Dirichlet dof out of range, a state that was not configured / started. */
+typedef struct fs_wave_state_s* fs_wave_state_t;
+typedef struct fs_wave_info {
+    double device_ms;             /* HIP-event time of the whole batch (products, updates, finishing passes) */
+    int64_t n_nonfinite;          /* steps of this call whose energy (hence: field) is not finite */
+    int64_t first_nonfinite_step; /* the first of them, as its index k in this call; -1: none */
+    int64_t step;                 /* the state's step counter n after the call */
+} fs_wave_info;
+int fs_wave_state_create(fs_space_t space, fs_wave_state_t* out);
+int fs_wave_state_destroy(fs_wave_state_t state);
+int fs_wave_state_configure(fs_wave_state_t state, double dt, const double* mass, const double* damping, const double* load,
+                            int64_t n_dirichlet, const int32_t* dirichlet_dofs, const double* dirichlet_values);
+int fs_wave_state_set(fs_wave_state_t state, const double* u_prev, const double* u, int64_t step);
+int fs_wave_state_get(fs_wave_state_t state, double* u_prev, double* u, int64_t* step);
+int fs_wave_start(fs_matrix_t K, fs_wave_state_t state, const double* u0, const double* v0, double load_scale0, double dirichlet_scale1);
+int fs_wave_advance(fs_matrix_t K, fs_wave_state_t state, int64_t n_steps, const double* load_scale, const double* dirichlet_scale,
+                    int64_t n_receivers, const int32_t* receiver_dofs, double* traces, double* energy, fs_wave_info* info);
+
 /* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
  * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
  * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
