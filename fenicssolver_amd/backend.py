@@ -550,12 +550,10 @@ def assemble_hyperelastic(space, u, lame, K=None, r=None, energy=False, add=Fals
             "first_inverted_cell": int(info.first_inverted_cell)}
 
 
-class PlasticHistory(_Handle):
-    """Per-cell history of the J2 return mapping on a vector CG1 space (fs_plastic_state_*): the committed state (plastic strain,
-    cumulative plastic strain, returned stress) and the trial state of the last assemble_plasticity.  The device keeps the cells in
-    its own order; ``cell_order`` (device cell -> caller's cell, None: the same order) maps every array that crosses this class, so
-    callers see their own cell numbering.  Tensors: (xx, yy, zz, xy, xz, yz) in 3-D, (xx, yy, zz, xy) in plane strain."""
-    _destroy = "fs_plastic_state_destroy"
+class _CellHistory(_Handle):
+    """What the per-cell history objects share: the cell and component counts, the map to the caller's cell numbering, and reset /
+    commit through the fs_<_prefix>_state_* calls."""
+    _prefix = None
 
     def __init__(self, space, cell_order=None):
         super().__init__()
@@ -563,14 +561,17 @@ class PlasticHistory(_Handle):
         self.n_cells = int(space.mesh.info()[1])
         self.n_comp = 6 if space.ncomp == 3 else 4
         self.cell_order = None if cell_order is None else np.asarray(cell_order, dtype=np.int64)
-        L.check(L.load().fs_plastic_state_create(space.h, C.byref(self.h)), "fs_plastic_state_create")
+
+    def _call(self, name, *args):
+        name = "fs_%s_state_%s" % (self._prefix, name)
+        L.check(getattr(L.load(), name)(*args), name)
 
     def reset(self):
-        L.check(L.load().fs_plastic_state_reset(self.h), "fs_plastic_state_reset")
+        self._call("reset", self.h)
 
     def commit(self):
-        """trial -> committed: the load step has converged"""
-        L.check(L.load().fs_plastic_state_commit(self.h), "fs_plastic_state_commit")
+        """trial -> committed: the step has converged"""
+        self._call("commit", self.h)
 
     def _to_host(self, a):
         if self.cell_order is None:
@@ -579,11 +580,35 @@ class PlasticHistory(_Handle):
         out[self.cell_order] = a
         return out
 
+
+def _cell_material(material, n_cells, width, kind_error, shape_error):
+    """The array of a ('cell', array[n_cells, width]) material, None for any other material."""
+    if not (isinstance(material, tuple) and len(material) == 2 and isinstance(material[0], str)):
+        return None
+    if material[0] != "cell":
+        raise BackendError(kind_error % (material[0],))
+    a = np.ascontiguousarray(material[1], dtype=np.float64)
+    if a.shape != (n_cells, width):
+        raise BackendError(shape_error % (n_cells, width, a.shape))
+    return a
+
+
+class PlasticHistory(_CellHistory):
+    """Per-cell history of the J2 return mapping on a vector CG1 space (fs_plastic_state_*): the committed state (plastic strain,
+    cumulative plastic strain, returned stress) and the trial state of the last assemble_plasticity.  The device keeps the cells in
+    its own order; ``cell_order`` (device cell -> caller's cell, None: the same order) maps every array that crosses this class, so
+    callers see their own cell numbering.  Tensors: (xx, yy, zz, xy, xz, yz) in 3-D, (xx, yy, zz, xy) in plane strain."""
+    _destroy = "fs_plastic_state_destroy"
+    _prefix = "plastic"
+
+    def __init__(self, space, cell_order=None):
+        super().__init__(space, cell_order)
+        self._call("create", space.h, C.byref(self.h))
+
     def get(self, trial=False):
         """(eps_p [n_cells, n_comp], p [n_cells], stress [n_cells, n_comp]) of the committed (or the trial) state"""
         ep, p, sg = np.empty((self.n_cells, self.n_comp)), np.empty(self.n_cells), np.empty((self.n_cells, self.n_comp))
-        L.check(L.load().fs_plastic_state_get(self.h, L.FS_PLASTIC_TRIAL if trial else L.FS_PLASTIC_COMMITTED, L.p_f64(ep), L.p_f64(p),
-                                              L.p_f64(sg)), "fs_plastic_state_get")
+        self._call("get", self.h, L.FS_PLASTIC_TRIAL if trial else L.FS_PLASTIC_COMMITTED, L.p_f64(ep), L.p_f64(p), L.p_f64(sg))
         return self._to_host(ep), self._to_host(p), self._to_host(sg)
 
     def set(self, eps_p, p):
@@ -593,7 +618,7 @@ class PlasticHistory(_Handle):
         if self.cell_order is not None:
             ep, p = ep[self.cell_order], p[self.cell_order]
         ep, p = L.f64(ep), L.f64(p)
-        L.check(L.load().fs_plastic_state_set(self.h, L.p_f64(ep), L.p_f64(p)), "fs_plastic_state_set")
+        self._call("set", self.h, L.p_f64(ep), L.p_f64(p))
 
 
 def assemble_plasticity(space, u, history, material, K=None, r=None, add=False):
@@ -602,13 +627,9 @@ def assemble_plasticity(space, u, history, material, K=None, r=None, add=False):
     yield_stress, hardening) numbers or ('cell', array[n_cells, 4]) in DEVICE cell order.  K / r: the DeviceMatrix / DeviceVector to
     fill (None: not computed).  Returns {'n_yielded', 'n_nonfinite', 'first_nonfinite_cell'}."""
     f = L.fs_plastic_form()
-    keep = None
-    if isinstance(material, tuple) and len(material) == 2 and isinstance(material[0], str):
-        if material[0] != "cell":
-            raise BackendError("plastic material: four numbers or ('cell', array[n_cells, 4]), got kind %r" % (material[0],))
-        keep = np.ascontiguousarray(material[1], dtype=np.float64)
-        if keep.shape != (history.n_cells, 4):
-            raise BackendError("per-cell plastic material must be an array [%d, 4], got shape %s" % (history.n_cells, keep.shape))
+    keep = _cell_material(material, history.n_cells, 4, "plastic material: four numbers or ('cell', array[n_cells, 4]), got kind %r",
+                          "per-cell plastic material must be an array [%d, %d], got shape %s")
+    if keep is not None:
         f.material.mode = L.FS_COEF_CELL_PLASTIC
         f.material.data = L.p_f64(keep)
     else:
@@ -621,42 +642,25 @@ def assemble_plasticity(space, u, history, material, K=None, r=None, add=False):
     return {"n_yielded": int(info.n_yielded), "n_nonfinite": int(info.n_nonfinite), "first_nonfinite_cell": int(info.first_nonfinite_cell)}
 
 
-class ViscoHistory(_Handle):
+class ViscoHistory(_CellHistory):
     """Per-cell history of the Prony-series update on a vector CG1 space (fs_visco_state_*): the committed state (deviatoric strain
     e, viscous strains h_k, stress) and the trial state of the last update.  The device keeps the cells in its own order;
     ``cell_order`` (device cell -> caller's cell, None: the same order) maps every array that crosses this class, so callers see
     their own cell numbering.  Tensors: (xx, yy, zz, xy, xz, yz) in 3-D, (xx, yy, zz, xy) in plane strain."""
     _destroy = "fs_visco_state_destroy"
+    _prefix = "visco"
 
     def __init__(self, space, n_terms, cell_order=None):
-        super().__init__()
-        self.space = space
-        self.n_cells = int(space.mesh.info()[1])
-        self.n_comp = 6 if space.ncomp == 3 else 4
+        super().__init__(space, cell_order)
         self.n_terms = int(n_terms)
-        self.cell_order = None if cell_order is None else np.asarray(cell_order, dtype=np.int64)
-        L.check(L.load().fs_visco_state_create(space.h, self.n_terms, C.byref(self.h)), "fs_visco_state_create")
-
-    def reset(self):
-        L.check(L.load().fs_visco_state_reset(self.h), "fs_visco_state_reset")
-
-    def commit(self):
-        """trial -> committed: the step has converged"""
-        L.check(L.load().fs_visco_state_commit(self.h), "fs_visco_state_commit")
-
-    def _to_host(self, a):
-        if self.cell_order is None:
-            return a
-        out = np.empty_like(a)
-        out[self.cell_order] = a
-        return out
+        self._call("create", space.h, self.n_terms, C.byref(self.h))
 
     def get(self, trial=False):
         """(e [n_cells, n_comp], h [n_cells, n_terms, n_comp], stress [n_cells, n_comp]) of the committed (or the trial) state"""
         e, sg = np.empty((self.n_cells, self.n_comp)), np.empty((self.n_cells, self.n_comp))
         h = np.empty((self.n_cells, self.n_terms, self.n_comp))
-        L.check(L.load().fs_visco_state_get(self.h, L.FS_VISCO_TRIAL if trial else L.FS_VISCO_COMMITTED, L.p_f64(e),
-                                            L.p_f64(h) if self.n_terms else None, L.p_f64(sg)), "fs_visco_state_get")
+        self._call("get", self.h, L.FS_VISCO_TRIAL if trial else L.FS_VISCO_COMMITTED, L.p_f64(e), L.p_f64(h) if self.n_terms else None,
+                   L.p_f64(sg))
         return self._to_host(e), self._to_host(h), self._to_host(sg)
 
     def set(self, e, h):
@@ -666,7 +670,7 @@ class ViscoHistory(_Handle):
         if self.cell_order is not None:
             e, h = e[self.cell_order], h[self.cell_order]
         e, h = L.f64(e), L.f64(h)
-        L.check(L.load().fs_visco_state_set(self.h, L.p_f64(e), L.p_f64(h) if self.n_terms else None), "fs_visco_state_set")
+        self._call("set", self.h, L.p_f64(e), L.p_f64(h) if self.n_terms else None)
 
 
 def assemble_viscoelastic(space, history, material, dt, u=None, load=None, force=None, update=None, add=False):
@@ -677,15 +681,10 @@ def assemble_viscoelastic(space, history, material, dt, u=None, load=None, force
     int B^T sigma dx of the trial stress.  Returns {'n_nonfinite', 'first_nonfinite_cell'} and the device milliseconds of the passes
     that ran ('load_ms', 'update_ms', 'force_ms')."""
     f = L.fs_visco_form()
-    keep = None
     nt = history.n_terms
-    if isinstance(material, tuple) and len(material) == 2 and isinstance(material[0], str):
-        if material[0] != "cell":
-            raise BackendError("viscoelastic material: (mu, lambda, terms) or ('cell', array), got kind %r" % (material[0],))
-        keep = np.ascontiguousarray(material[1], dtype=np.float64)
-        if keep.shape != (history.n_cells, 2 + 2 * nt):
-            raise BackendError("per-cell viscoelastic material must be an array [%d, %d], got shape %s" % (
-                history.n_cells, 2 + 2 * nt, keep.shape))
+    keep = _cell_material(material, history.n_cells, 2 + 2 * nt, "viscoelastic material: (mu, lambda, terms) or ('cell', array), got kind %r",
+                          "per-cell viscoelastic material must be an array [%d, %d], got shape %s")
+    if keep is not None:
         f.material.mode = L.FS_COEF_CELL_VISCO
         f.material.data = L.p_f64(keep)
         f.n_terms = nt

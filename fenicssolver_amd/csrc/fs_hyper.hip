@@ -18,17 +18,19 @@
 //       records (24 B) + 4 displacements (24 B) + the 16-B cell record per source, about 400 fp64 flops.
 //   k_hyper_force_gather / k_hyper_force_tri_gather      one thread per owned node over the sources of its diagonal block (the
 //       cells around the node, ascending), P g_a per cell.
-//   k_hyper_cells + k_hyper_cells_finish                 energy V psi per cell and the cells with J <= 0 (or not finite): per-
-//       workgroup partials, then one fixed-order sum.
+//   k_hyper_cells + k_cell_tally_finish (fs_p1_cell.h)   energy V psi per cell and the cells with J <= 0 (or not finite): per-
+//       workgroup partials (p1_cell_tally), then one fixed-order sum.
 #include "fs_common.h"
 #include "fs_kernels.h"
-#include "fs_p1_geometry.h"
+#include "fs_p1_cell.h"
 #include <math.h>
 
 #define FS_HYPER_CELL_BLOCKS 1024      // workgroups of the per-cell pass (its partials are summed in this order)
 
 // ---- kinematics ----------------------------------------------------------------------------------------------------------
 // F = I + sum_a u_a g_a^T, its cofactor matrix (F^-T = cof / J) and J
+// (ld_kinematics of fs_large_deformation.hip computes the same F but sums the vertices into an accumulator that starts at 0, where
+// this file groups them ((a0 + a1) + a2) + a3: the two round differently, so each file keeps its own.)
 __device__ __forceinline__ void hyper_kin3(const tet_geom& t, const double (&uv)[4][3], double (&F)[3][3], double (&FiT)[3][3],
                                            double& J) {
 #pragma unroll
@@ -106,14 +108,15 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_gather(int64_t n_ent
           for (int w = 0; w < PF; ++w) sc[w] = q0 + w < q1 ? src[q0 + w] : -1;
 #pragma unroll
           for (int w = 0; w < PF; ++w) {
-            vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[w] >> 4] : make_int4(0, 0, 0, 0);
-            if (CELL) lc[w] = sc[w] >= 0 ? lame_cell[sc[w] >> 4] : make_double2(0.0, 0.0);
+            vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[p1_source_cell<3>(sc[w])] : make_int4(0, 0, 0, 0);
+            if (CELL) lc[w] = sc[w] >= 0 ? lame_cell[p1_source_cell<3>(sc[w])] : make_double2(0.0, 0.0);
           }
 #pragma unroll
           for (int w = 0; w < PF; ++w) {
             if (q0 + w >= q1) break;
-            const int32_t sidx = sc[w];
-            const int a = (sidx >> 2) & 3, b = sidx & 3;
+            int64_t c;
+            int a, b;
+            p1_source<3>(sc[w], c, a, b);
             const int4 v4 = vc[w];
             const double mu = CELL ? lc[w].x : mu0, lambda = CELL ? lc[w].y : lambda0;
             const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
@@ -124,11 +127,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_gather(int64_t n_ent
             hyper_kin3(t, uv, F, FiT, J);
             const double m2 = mu - lambda * log(J);
             double ga[3], gb[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
-                gb[k] = b == 0 ? t.g[0][k] : b == 1 ? t.g[1][k] : b == 2 ? t.g[2][k] : t.g[3][k];
-            }
+            P1_GRAD_TET(t, a, ga);
+            P1_GRAD_TET(t, b, gb);
             double Ga[3], Gb[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -169,10 +169,9 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_tri_gather(int64_t n
         double acc[2][2] = {{0, 0}, {0, 0}};
         const int32_t q1 = ptr[e + 1];
         for (int32_t q = ptr[e]; q < q1; ++q) {
-            const int32_t sidx = src[q];
-            const int64_t c = sidx / 9;
-            const int ab = sidx - (int32_t)(c * 9);
-            const int a = ab / 3, b = ab - 3 * a;
+            int64_t c;
+            int a, b;
+            p1_source<2>(src[q], c, a, b);
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
             const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
             const double mu = ml.x, lambda = ml.y;
@@ -181,8 +180,9 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_tri_gather(int64_t n
             load_disp2(u, v4, uv);
             hyper_kin2(t, uv, F, FiT, J);
             const double m2 = mu - lambda * log(J);
-            const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
-            const double gb[2] = {b == 0 ? t.g[0][0] : (b == 1 ? t.g[1][0] : t.g[2][0]), b == 0 ? t.g[0][1] : (b == 1 ? t.g[1][1] : t.g[2][1])};
+            double ga[2], gb[2];
+            p1_grad(t, a, ga);
+            p1_grad(t, b, gb);
             double Ga[2], Gb[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -211,15 +211,6 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_tangent_tri_gather(int64_t n
 
 // ---- internal force ------------------------------------------------------------------------------------------------------
 // thread per owned node r: the sources of its diagonal block are (c, a, a) for every cell c holding the node, ascending in c
-__device__ __forceinline__ int64_t hyper_diag_entry(int64_t r, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col) {
-    const int64_t sp0 = slice_ptr[r >> 6];
-    const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
-    const int64_t base = sp0 + (r & 63);
-    for (int k = 0; k < width; ++k)
-        if (sell_col[base + (int64_t)k * FS_SLICE] == (int32_t)r) return base + (int64_t)k * FS_SLICE;
-    return -1;
-}
-
 template <bool ADD, bool CELL>
 __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
                                                                  const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
@@ -230,7 +221,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_gather(int64_t n_rows,
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; r < n_rows; r += stride) {
-        const int64_t e = hyper_diag_entry(r, slice_ptr, sell_col);
+        const int64_t e = p1_diag_entry(r, slice_ptr, sell_col);
         double acc[3] = {0.0, 0.0, 0.0};
         if (e >= 0) {
             constexpr int PF = 4;
@@ -243,13 +234,15 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_gather(int64_t n_rows,
               for (int w = 0; w < PF; ++w) sc[w] = q0 + w < q1 ? gsrc[q0 + w] : -1;
 #pragma unroll
               for (int w = 0; w < PF; ++w) {
-                vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[w] >> 4] : make_int4(0, 0, 0, 0);
-                if (CELL) lc[w] = sc[w] >= 0 ? lame_cell[sc[w] >> 4] : make_double2(0.0, 0.0);
+                vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[p1_source_cell<3>(sc[w])] : make_int4(0, 0, 0, 0);
+                if (CELL) lc[w] = sc[w] >= 0 ? lame_cell[p1_source_cell<3>(sc[w])] : make_double2(0.0, 0.0);
               }
 #pragma unroll
               for (int w = 0; w < PF; ++w) {
                 if (q0 + w >= q1) break;
-                const int a = (sc[w] >> 2) & 3;
+                int64_t c;
+                int a, b;
+                p1_source<3>(sc[w], c, a, b);
                 const int4 v4 = vc[w];
                 const double mu = CELL ? lc[w].x : mu0, lambda = CELL ? lc[w].y : lambda0;
                 const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
@@ -260,8 +253,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_gather(int64_t n_rows,
                 hyper_kin3(t, uv, F, FiT, J);
                 const double ll = lambda * log(J);
                 double ga[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
+                P1_GRAD_TET(t, a, ga);
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     double s = 0.0;
@@ -287,13 +279,13 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_tri_gather(int64_t n_r
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; r < n_rows; r += stride) {
-        const int64_t e = hyper_diag_entry(r, slice_ptr, sell_col);
+        const int64_t e = p1_diag_entry(r, slice_ptr, sell_col);
         double acc[2] = {0.0, 0.0};
         if (e >= 0) {
             for (int32_t q = gptr[e]; q < gptr[e + 1]; ++q) {
-                const int32_t sidx = gsrc[q];
-                const int64_t c = sidx / 9;
-                const int a = (sidx - (int32_t)(c * 9)) / 3;
+                int64_t c;
+                int a, b;
+                p1_source<2>(gsrc[q], c, a, b);
                 const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
                 const double2 ml = CELL ? lame_cell[c] : make_double2(mu0, lambda0);
                 const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
@@ -301,7 +293,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_tri_gather(int64_t n_r
                 load_disp2(u, v4, uv);
                 hyper_kin2(t, uv, F, FiT, J);
                 const double ll = ml.y * log(J);
-                const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
+                double ga[2];
+                p1_grad(t, a, ga);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     double s = 0.0;
@@ -319,15 +312,14 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_force_tri_gather(int64_t n_r
 // ---- energy and inverted cells -------------------------------------------------------------------------------------------
 // psi = mu/2 (tr C - 3) - mu ln J + lambda/2 (ln J)^2 with tr C - d = 2 tr H + H : H (H = grad u: no cancellation at small
 // strain); 2-D keeps the reference's "- 3" (Identity(2) with the 3-D constant).  A cell counts as inverted when J <= 0 or J is
-// not finite.  partials[3][FS_HYPER_CELL_BLOCKS]: (energy, count, smallest device cell index) per workgroup.
+// not finite.  Partials per workgroup: the energy in part_e, (count, smallest device cell index) in part (p1_cell_tally).
 template <int TD, bool CELL>
 __global__ void __launch_bounds__(FS_BLOCK) k_hyper_cells(int64_t nc, const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
                                                           const double* __restrict__ u, double mu0, double lambda0,
                                                           const double2* __restrict__ lame_cell, const box_snap bx,
-                                                          double* __restrict__ part_e, int64_t* __restrict__ part_n,
-                                                          int64_t* __restrict__ part_first) {
+                                                          double* __restrict__ part_e, int64_t* __restrict__ part) {
     double en = 0.0;
-    int64_t n_bad = 0, first = INT64_MAX;
+    int64_t n_bad[1] = {0}, first = INT64_MAX;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
         const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
@@ -364,7 +356,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_cells(int64_t nc, const int3
                 }
         }
         if (!(J > 0.0) || !isfinite(J)) {
-            ++n_bad;
+            ++n_bad[0];
             first = c < first ? c : first;
             continue;
         }
@@ -372,45 +364,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hyper_cells(int64_t nc, const int3
         const double ic3 = (2.0 * trH + HH) + (TD == 3 ? 0.0 : -1.0);
         en += vol * (0.5 * ml.x * ic3 - ml.x * lj + 0.5 * ml.y * lj * lj);
     }
-    __shared__ double se[FS_BLOCK / 64];
-    __shared__ int64_t sn[FS_BLOCK / 64], sf[FS_BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        en += __shfl_down(en, off, 64);
-        n_bad += __shfl_down(n_bad, off, 64);
-        const int64_t o = __shfl_down(first, off, 64);
-        first = o < first ? o : first;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { se[wave] = en; sn[wave] = n_bad; sf[wave] = first; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double te = 0.0;
-        int64_t tn = 0, tf = INT64_MAX;
-        for (int w = 0; w < FS_BLOCK / 64; ++w) {
-            te += se[w];
-            tn += sn[w];
-            tf = sf[w] < tf ? sf[w] : tf;
-        }
-        part_e[blockIdx.x] = te;
-        part_n[blockIdx.x] = tn;
-        part_first[blockIdx.x] = tf;
-    }
-}
-
-__global__ void k_hyper_cells_finish(int nb, const double* __restrict__ part_e, const int64_t* __restrict__ part_n,
-                                     const int64_t* __restrict__ part_first, double* __restrict__ out_e, int64_t* __restrict__ out_n) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    double te = 0.0;
-    int64_t tn = 0, tf = INT64_MAX;
-    for (int b = 0; b < nb; ++b) {
-        te += part_e[b];
-        tn += part_n[b];
-        tf = part_first[b] < tf ? part_first[b] : tf;
-    }
-    out_e[0] = te;
-    out_n[0] = tn;
-    out_n[1] = tf;
+    p1_cell_tally<1, true>(n_bad, first, en, part, part_e);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
@@ -422,11 +376,7 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
     FS_REQUIRE(form->model == FS_HYPER_NEO_HOOKEAN, "fs_assemble_hyperelastic: unknown energy model %d (FS_HYPER_NEO_HOOKEAN only)", form->model);
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(sp->degree == 1 && ((m->tdim == 3 && sp->ncomp == 3) || (m->tdim == 2 && sp->ncomp == 2)),
-               "fs_assemble_hyperelastic: vector CG1 spaces on tetrahedra or triangles only (this space: CG%d with %d components on a "
-               "%d-D mesh)", sp->degree, sp->ncomp, m->tdim);
-    FS_REQUIRE(m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local,
-               "fs_assemble_hyperelastic: the space has ghost nodes (several ranks): not supported");
+    FS_CHECK(fs_require_vector_cg1(sp, "fs_assemble_hyperelastic"));
     FS_REQUIRE(sp->slots.p, "fs_assemble_hyperelastic: vector space without slot table");
     FS_REQUIRE(u->d.n >= sp->n_dofs_local, "fs_assemble_hyperelastic: displacement vector shorter than the space's dofs");
     FS_REQUIRE(!(what & FS_HYPER_TANGENT) || (K && K->space == sp), "fs_assemble_hyperelastic: the tangent needs a matrix on this space");
@@ -493,15 +443,15 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
     if (info) {
         const int nb = FS_HYPER_CELL_BLOCKS;
         dbuf<double> pe, oe;
-        dbuf<int64_t> pn, pf, on;
-        FS_CHECK(pe.alloc(nb)); FS_CHECK(pn.alloc(nb)); FS_CHECK(pf.alloc(nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
+        dbuf<int64_t> part, on;
+        FS_CHECK(pe.alloc(nb)); FS_CHECK(part.alloc(2 * nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
 #define FS_HC(T_, C_) hipLaunchKernelGGL((k_hyper_cells<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu, lambda, \
-                                         lc, bx, pe.p, pn.p, pf.p)
+                                         lc, bx, pe.p, part.p)
         if (m->tdim == 3) { if (cellw) FS_HC(3, true); else FS_HC(3, false); }
         else { if (cellw) FS_HC(2, true); else FS_HC(2, false); }
 #undef FS_HC
         FS_KERNEL_CHECK();
-        hipLaunchKernelGGL(k_hyper_cells_finish, dim3(1), dim3(64), 0, s, nb, pe.p, pn.p, pf.p, oe.p, on.p);
+        hipLaunchKernelGGL((k_cell_tally_finish<1, true>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
         FS_KERNEL_CHECK();
         double e_host = 0.0;
         int64_t n_host[2] = {0, 0};
@@ -509,9 +459,7 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
         FS_CHECK(on.download(n_host, 2, s));
         info->energy = e_host;
         info->n_inverted = n_host[0];
-        int64_t first = n_host[0] > 0 ? n_host[1] : -1;
-        if (first >= 0 && !m->cell_order.empty()) first = m->cell_order[first];     // the caller's cell number
-        info->first_inverted_cell = first;
+        info->first_inverted_cell = fs_first_cell(m, n_host[0], n_host[1]);
     }
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;

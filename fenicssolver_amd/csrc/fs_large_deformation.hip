@@ -26,10 +26,12 @@
 //   k_ld_nodes<TD>      one thread per node: R_u, R_v, R_p over the cells around the node (ascending), the J_xu r_u corrections,
 //                       the facet loads of the node, the reduced right-hand side, the squared full residual of the node (Dirichlet
 //                       rows left out) and the identity rows of Dirichlet v / p unknowns.
-//   k_ld_cells<TD> + k_ld_finish   cells with J == 0 or J not finite, and the fixed-order sum of the node residuals.
+//   k_ld_cells<TD> + k_ld_finish   cells with J == 0 or J not finite, and the fixed-order sum of the node residuals.  The workgroup
+//                       part is p1_cell_tally (fs_p1_cell.h); k_ld_finish keeps its own order (a strided sum per thread, then a tree
+//                       in LDS), which the one-thread k_cell_tally_finish would change.
 #include "fs_common.h"
 #include "fs_kernels.h"
-#include "fs_p1_geometry.h"
+#include "fs_p1_cell.h"
 #include <math.h>
 #include <algorithm>
 #include <numeric>
@@ -73,6 +75,8 @@ __device__ __forceinline__ void ld_geometry(const int32_t* __restrict__ cells, c
 }
 
 // F = I + sum_a u_a g_a^T, F^-T = cof / J, J
+// (hyper_kin3 / hyper_kin2 of fs_hyper.hip compute the same F but group the sum over the vertices ((a0 + a1) + a2) + a3, where this
+// one accumulates from 0: the two round differently, so each file keeps its own.)
 template <int TD>
 __device__ __forceinline__ void ld_kinematics(const double* __restrict__ u, ld_cell<TD>& k) {
     double uv[TD + 1][TD];
@@ -174,17 +178,6 @@ __device__ __forceinline__ void ld_tangent(const ld_cell<TD>& k, int a, int b, d
             Kt[i][q] = k.vol * (mJ * (Gb[q] * Fga[i] + (i == q ? gg : 0.0)) - pJ * (Gb[q] * Ga[i] - Gb[i] * Ga[q]));
 }
 
-template <int TD>
-__device__ __forceinline__ void ld_source(int32_t sidx, int64_t& c, int& a, int& b) {
-    if constexpr (TD == 3) {
-        c = sidx >> 4; a = (sidx >> 2) & 3; b = sidx & 3;
-    } else {
-        c = sidx / 9;
-        const int ab = sidx - (int32_t)(c * 9);
-        a = ab / 3; b = ab - 3 * a;
-    }
-}
-
 struct ld_params {
     double dt, q, mu, lambda;
     double body[3];
@@ -209,7 +202,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_ld_jacobian(int64_t n_entries, con
         for (int32_t s = ptr[e]; s < q1; ++s) {
             int64_t c;
             int a, b;
-            ld_source<TD>(src[s], c, a, b);
+            p1_source<TD>(src[s], c, a, b);
             ld_cell<TD> k;
             ld_geometry<TD>(cells, xyz4, c, bx, k);
             ld_kinematics<TD>(u, k);
@@ -347,15 +340,6 @@ __global__ void k_ld_facet_entries(int64_t n_touched, const int32_t* __restrict_
 }
 
 // ---- residuals, right-hand side, Dirichlet rows ----------------------------------------------------------------------------
-__device__ __forceinline__ int64_t ld_diag_entry(int64_t r, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col) {
-    const int64_t sp0 = slice_ptr[r >> 6];
-    const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
-    const int64_t base = sp0 + (r & 63);
-    for (int k = 0; k < width; ++k)
-        if (sell_col[base + (int64_t)k * FS_SLICE] == (int32_t)r) return base + (int64_t)k * FS_SLICE;
-    return -1;
-}
-
 template <int TD>
 __global__ void __launch_bounds__(FS_BLOCK) k_ld_nodes(int64_t n_rows, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col,
                                                        const int32_t* __restrict__ gptr, const int32_t* __restrict__ gsrc,
@@ -371,13 +355,13 @@ __global__ void __launch_bounds__(FS_BLOCK) k_ld_nodes(int64_t n_rows, const int
     const double q = P.q, dt = P.dt, mu = P.mu, il = 1.0 / P.lambda;
     const double mc = 1.0 / ((TD + 1) * (TD + 2)), ic = 1.0 / (TD + 1);
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += stride) {
-        const int64_t e = ld_diag_entry(r, slice_ptr, sell_col);
+        const int64_t e = p1_diag_entry(r, slice_ptr, sell_col);
         double Ru[TD] = {}, Rv[TD] = {}, Rp = 0.0, cv[TD] = {}, cp = 0.0;
         if (e >= 0) {
             for (int32_t s = gptr[e]; s < gptr[e + 1]; ++s) {
                 int64_t c;
                 int a, bb;
-                ld_source<TD>(gsrc[s], c, a, bb);
+                p1_source<TD>(gsrc[s], c, a, bb);
                 ld_cell<TD> k, k0;
                 ld_geometry<TD>(cells, xyz4, c, bx, k);
                 k0 = k;
@@ -475,8 +459,8 @@ template <int TD>
 __global__ void __launch_bounds__(FS_BLOCK) k_ld_cells(int64_t nc, const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
                                                        const double* __restrict__ u, const box_snap bx, int64_t n_rows,
                                                        const double* __restrict__ rn2, double* __restrict__ part_r,
-                                                       int64_t* __restrict__ part_n, int64_t* __restrict__ part_first) {
-    int64_t n_bad = 0, first = INT64_MAX;
+                                                       int64_t* __restrict__ part) {
+    int64_t n_bad[1] = {0}, first = INT64_MAX;
     double rs = 0.0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
@@ -484,35 +468,12 @@ __global__ void __launch_bounds__(FS_BLOCK) k_ld_cells(int64_t nc, const int32_t
         ld_geometry<TD>(cells, xyz4, c, bx, k);
         ld_kinematics<TD>(u, k);
         if (k.J == 0.0 || !isfinite(k.J)) {
-            ++n_bad;
+            ++n_bad[0];
             first = c < first ? c : first;
         }
     }
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += stride) rs += rn2[r];
-    __shared__ double sr[FS_BLOCK / 64];
-    __shared__ int64_t sn[FS_BLOCK / 64], sf[FS_BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        rs += __shfl_down(rs, off, 64);
-        n_bad += __shfl_down(n_bad, off, 64);
-        const int64_t o = __shfl_down(first, off, 64);
-        first = o < first ? o : first;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sr[wave] = rs; sn[wave] = n_bad; sf[wave] = first; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tr = 0.0;
-        int64_t tn = 0, tf = INT64_MAX;
-        for (int w = 0; w < FS_BLOCK / 64; ++w) {
-            tr += sr[w];
-            tn += sn[w];
-            tf = sf[w] < tf ? sf[w] : tf;
-        }
-        part_r[blockIdx.x] = tr;
-        part_n[blockIdx.x] = tn;
-        part_first[blockIdx.x] = tf;
-    }
+    p1_cell_tally<1, true>(n_bad, first, rs, part, part_r);
 }
 
 // one workgroup of FS_BLOCK threads: thread t sums the partials t, t + FS_BLOCK, ... in order, then a tree in LDS - a fixed order
@@ -556,7 +517,7 @@ struct ld_cache {
     dbuf<int32_t> d_fcell, d_fopp, ent, eptr, esrc, nptr, nsrc;
     dbuf<uint8_t> d_mask;
     dbuf<double> fg, fr, fk, rn2, part_r, out_r;
-    dbuf<int64_t> part_n, part_f, out_n;
+    dbuf<int64_t> part, out_n;                  // part: (count, smallest index)[FS_LD_BLOCKS]
     int64_t n_touched = 0;
 };
 
@@ -613,8 +574,7 @@ extern "C" int fs_assemble_large_deformation(fs_matrix_t Jr, fs_vector_t rhs, fs
     if (!same_space) {
         FS_CHECK(C.rn2.alloc(nn));
         FS_CHECK(C.part_r.alloc(FS_LD_BLOCKS));
-        FS_CHECK(C.part_n.alloc(FS_LD_BLOCKS));
-        FS_CHECK(C.part_f.alloc(FS_LD_BLOCKS));
+        FS_CHECK(C.part.alloc(2 * FS_LD_BLOCKS));
         FS_CHECK(C.out_r.alloc(1));
         FS_CHECK(C.out_n.alloc(2));
     }
@@ -704,7 +664,7 @@ extern "C" int fs_assemble_large_deformation(fs_matrix_t Jr, fs_vector_t rhs, fs
                            m->cells.p, m->xyz.p, u->d.p, w->d.p, u0->d.p, w0->d.p, C.d_mask.p, P, bx, C.nptr.p, C.nsrc.p, C.d_fcell.p,
                            C.fr.p, C.fk.p, plane, Jr->val.p, rhs->d.p, C.rn2.p);
         hipLaunchKernelGGL(k_ld_cells<3>, dim3(FS_LD_BLOCKS), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, bx, nn, C.rn2.p,
-                           C.part_r.p, C.part_n.p, C.part_f.p);
+                           C.part_r.p, C.part.p);
     } else {
         hipLaunchKernelGGL(k_ld_jacobian<2>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p,
                            m->xyz.p, u->d.p, w->d.p, C.d_mask.p, P, bx, plane, Jr->val.p);
@@ -718,10 +678,11 @@ extern "C" int fs_assemble_large_deformation(fs_matrix_t Jr, fs_vector_t rhs, fs
                            m->cells.p, m->xyz.p, u->d.p, w->d.p, u0->d.p, w0->d.p, C.d_mask.p, P, bx, C.nptr.p, C.nsrc.p, C.d_fcell.p,
                            C.fr.p, C.fk.p, plane, Jr->val.p, rhs->d.p, C.rn2.p);
         hipLaunchKernelGGL(k_ld_cells<2>, dim3(FS_LD_BLOCKS), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, bx, nn, C.rn2.p,
-                           C.part_r.p, C.part_n.p, C.part_f.p);
+                           C.part_r.p, C.part.p);
     }
     FS_KERNEL_CHECK();
-    hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(FS_BLOCK), 0, s, FS_LD_BLOCKS, C.part_r.p, C.part_n.p, C.part_f.p, C.out_r.p, C.out_n.p);
+    hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(FS_BLOCK), 0, s, FS_LD_BLOCKS, C.part_r.p, C.part.p, C.part.p + FS_LD_BLOCKS, C.out_r.p,
+                       C.out_n.p);
     FS_KERNEL_CHECK();
     double r2 = 0.0;
     int64_t nb[2] = {0, 0};
@@ -730,8 +691,6 @@ extern "C" int fs_assemble_large_deformation(fs_matrix_t Jr, fs_vector_t rhs, fs
     FS_HIP(hipStreamSynchronize(s));
     info->residual_norm = sqrt(r2);
     info->n_bad = nb[0];
-    int64_t first = nb[0] > 0 ? nb[1] : -1;
-    if (first >= 0 && !m->cell_order.empty()) first = m->cell_order[first];     // the caller's cell number
-    info->first_bad_cell = first;
+    info->first_bad_cell = fs_first_cell(m, nb[0], nb[1]);
     return FS_OK;
 }

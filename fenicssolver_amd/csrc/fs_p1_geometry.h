@@ -1,4 +1,4 @@
-// P1 cell geometry shared by the assembly kernels (fs_assemble.hip) and the hyperelastic kernels (fs_hyper.hip).
+// P1 cell geometry shared by the assembly kernels (fs_assemble.hip) and, through fs_p1_cell.h, the solid-mechanics kernel files.
 #pragma once
 #include "fs_common.h"
 

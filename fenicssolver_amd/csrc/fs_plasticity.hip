@@ -14,18 +14,18 @@
 // Kernels (no atomics anywhere: two assemblies of one state give the same bits):
 //   k_plastic_cells                       one thread per cell, ONCE per evaluation: strain, trial state, return mapping.  Writes the
 //       trial history (eps_p, p), the returned stress and the tangent record (mu', lambda', c, N); counts the yielded and the
-//       non-finite cells per workgroup (k_plastic_cells_finish sums the partials in a fixed order).
+//       non-finite cells per workgroup (p1_cell_tally; k_cell_tally_finish sums the partials in a fixed order).
 //   k_plastic_tangent_gather / _tri_gather  one thread per STORED block sums its (cell, a, b) sources of the inverse slot table in
 //       ascending order - the walk of k_assemble_p1_elasticity_gather - and reads the cell's record instead of a material pair.  The
 //       elastic-shaped part is accumulated by the linear kernel's expression, the rank-one part in an accumulator of its own that
 //       stays +0 while no source cell has yielded: the tangent then equals fs_assemble_matrix of the linear operator bit for bit.
-//   k_plastic_force_gather / _tri_gather  one thread per owned node over the cells around it (the sources of its diagonal block,
-//       ascending): V sigma g_a from the stored stress.
+//   k_p1_stress_force_gather (fs_p1_cell.h)  one thread per owned node over the cells around it (the sources of its diagonal
+//       block, ascending): V sigma g_a from the stored stress.
 //
 // Tensor storage: 3-D (xx, yy, zz, xy, xz, yz), plane strain (xx, yy, zz, xy) - tensor components, not engineering shears.
 #include "fs_common.h"
 #include "fs_kernels.h"
-#include "fs_p1_geometry.h"
+#include "fs_p1_cell.h"
 #include <math.h>
 
 #define FS_PLASTIC_CELL_BLOCKS 1024      // workgroups of the per-cell pass (its partials are summed in this order)
@@ -37,9 +37,7 @@ struct fs_plastic_state_s {
     int tdim = 3;
     int ne = 6;                          // stored components of eps_p and sigma (4 in plane strain)
     int64_t nc = 0;
-    dbuf<double> ep, p;                  // committed history [nc][ne], [nc]
-    dbuf<double> ep_trial, p_trial;      // history of the last evaluation
-    dbuf<double> sig, sig_trial;         // returned stress of the committed state / of the last evaluation [nc][ne]
+    fs_history_pair ep, p, sig;          // plastic strain [nc][ne], cumulative plastic strain [nc], returned stress [nc][ne]
     dbuf<double> rec;                    // tangent record of the last evaluation
 };
 
@@ -51,10 +49,9 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_cells(int64_t nc, const in
                                                             const double* __restrict__ mat, const box_snap bx,
                                                             const double* __restrict__ ep0, const double* __restrict__ p0,
                                                             double* __restrict__ ep1, double* __restrict__ p1, double* __restrict__ sig,
-                                                            double* __restrict__ rec, int64_t* __restrict__ part_y,
-                                                            int64_t* __restrict__ part_n, int64_t* __restrict__ part_first) {
+                                                            double* __restrict__ rec, int64_t* __restrict__ part) {
     constexpr int NE = TD == 3 ? 6 : 4;
-    int64_t n_y = 0, n_bad = 0, first = INT64_MAX;
+    int64_t n[2] = {0, 0}, first = INT64_MAX;      // yielded, non-finite
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
         const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
@@ -65,36 +62,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_cells(int64_t nc, const in
         }
         // elastic strain e = sym grad u - eps_p, in the storage order of the file header
         double e[NE];
-        if (TD == 3) {
-            const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
-            const tet_geom t = tet_geometry_box(xyz4, v, bx);
-            double H[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const double ua = u[3 * (int64_t)v[a] + i];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) H[i][j] += ua * t.g[a][j];
-                }
-            e[0] = H[0][0]; e[1] = H[1][1]; e[2] = H[2][2];
-            e[3] = 0.5 * (H[0][1] + H[1][0]); e[4] = 0.5 * (H[0][2] + H[2][0]); e[5] = 0.5 * (H[1][2] + H[2][1]);
-        } else {
-            const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-            const int32_t v[3] = {v4.x, v4.y, v4.z};
-            double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double2 ua = reinterpret_cast<const double2*>(u)[v[a]];
-                H[0][0] += ua.x * t.g[a][0]; H[0][1] += ua.x * t.g[a][1];
-                H[1][0] += ua.y * t.g[a][0]; H[1][1] += ua.y * t.g[a][1];
-            }
-            e[0] = H[0][0]; e[1] = H[1][1]; e[2] = 0.0; e[3] = 0.5 * (H[0][1] + H[1][0]);
-        }
+        p1_strain<TD>(v4, xyz4, u, bx, e);
         double epc[NE];
 #pragma unroll
         for (int k = 0; k < NE; ++k) { epc[k] = ep0[NE * c + k]; e[k] -= epc[k]; }
@@ -119,10 +87,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_cells(int64_t nc, const in
 #pragma unroll
         for (int k = 0; k < NE; ++k) N[k] = 0.0;
         if (!isfinite(f)) {
-            ++n_bad;
+            ++n[1];
             first = c < first ? c : first;
         } else if (f > 0.0) {
-            ++n_y;
+            ++n[0];
             const double dp = f / (3.0 * mu + hm);
             const double beta = 3.0 * mu * dp / q;
             const double inv = 1.0 / sn;
@@ -154,42 +122,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_cells(int64_t nc, const in
             rc[2] = make_double2(N[1], N[3]);
         }
     }
-    __shared__ int64_t sy_[FS_BLOCK / 64], sn_[FS_BLOCK / 64], sf_[FS_BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        n_y += __shfl_down(n_y, off, 64);
-        n_bad += __shfl_down(n_bad, off, 64);
-        const int64_t o = __shfl_down(first, off, 64);
-        first = o < first ? o : first;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sy_[wave] = n_y; sn_[wave] = n_bad; sf_[wave] = first; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t ty = 0, tn = 0, tf = INT64_MAX;
-        for (int w = 0; w < FS_BLOCK / 64; ++w) {
-            ty += sy_[w];
-            tn += sn_[w];
-            tf = sf_[w] < tf ? sf_[w] : tf;
-        }
-        part_y[blockIdx.x] = ty;
-        part_n[blockIdx.x] = tn;
-        part_first[blockIdx.x] = tf;
-    }
-}
-
-__global__ void k_plastic_cells_finish(int nb, const int64_t* __restrict__ part_y, const int64_t* __restrict__ part_n,
-                                       const int64_t* __restrict__ part_first, int64_t* __restrict__ out) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int64_t ty = 0, tn = 0, tf = INT64_MAX;
-    for (int b = 0; b < nb; ++b) {
-        ty += part_y[b];
-        tn += part_n[b];
-        tf = part_first[b] < tf ? part_first[b] : tf;
-    }
-    out[0] = ty;
-    out[1] = tn;
-    out[2] = tf;
+    p1_cell_tally<2, false>(n, first, 0.0, part, nullptr);
 }
 
 // ---- tangent: tetrahedra -------------------------------------------------------------------------------------------------
@@ -216,27 +149,25 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_gather(int64_t n_e
           for (int w = 0; w < PF; ++w) sc[w] = q0 + w < q1 ? src[q0 + w] : -1;
 #pragma unroll
           for (int w = 0; w < PF; ++w) {
-            vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[sc[w] >> 4] : make_int4(0, 0, 0, 0);
-            const double2* rc = reinterpret_cast<const double2*>(rec + (int64_t)FS_PLASTIC_REC3 * (sc[w] >= 0 ? sc[w] >> 4 : 0));
+            vc[w] = sc[w] >= 0 ? reinterpret_cast<const int4*>(cells)[p1_source_cell<3>(sc[w])] : make_int4(0, 0, 0, 0);
+            const double2* rc = reinterpret_cast<const double2*>(rec + (int64_t)FS_PLASTIC_REC3 * (sc[w] >= 0 ? p1_source_cell<3>(sc[w]) : 0));
             lc[w] = sc[w] >= 0 ? rc[0] : make_double2(0.0, 0.0);
             cc[w] = sc[w] >= 0 ? rc[1] : make_double2(0.0, 0.0);
           }
 #pragma unroll
           for (int w = 0; w < PF; ++w) {
             if (q0 + w >= q1) break;
-            const int32_t sidx = sc[w];
-            const int a = (sidx >> 2) & 3, b = sidx & 3;
+            int64_t c;
+            int a, b;
+            p1_source<3>(sc[w], c, a, b);
             const int4 v4 = vc[w];
             const double mu = lc[w].x, lambda = lc[w].y;
             const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
             const tet_geom t = tet_geometry_box(xyz4, v, bx);
             const double vol = t.adet * (1.0 / 6.0);
             double ga[3], gb[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
-                gb[k] = b == 0 ? t.g[0][k] : b == 1 ? t.g[1][k] : b == 2 ? t.g[2][k] : t.g[3][k];
-            }
+            P1_GRAD_TET(t, a, ga);
+            P1_GRAD_TET(t, b, gb);
             const double gg = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
@@ -247,13 +178,12 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_gather(int64_t n_e
                     acc[i][j] += x;
                 }
             if (cc[w].x != 0.0) {
-                const double2* rc = reinterpret_cast<const double2*>(rec + (int64_t)FS_PLASTIC_REC3 * (sidx >> 4));
+                const double2* rc = reinterpret_cast<const double2*>(rec + (int64_t)FS_PLASTIC_REC3 * c);
                 const double2 n01 = rc[2], n23 = rc[3], n45 = rc[4];
-                // N = [[n0, n3, n4], [n3, n1, n5], [n4, n5, n2]]
-                const double na[3] = {n01.x * ga[0] + n23.y * ga[1] + n45.x * ga[2], n23.y * ga[0] + n01.y * ga[1] + n45.y * ga[2],
-                                      n45.x * ga[0] + n45.y * ga[1] + n23.x * ga[2]};
-                const double nb[3] = {n01.x * gb[0] + n23.y * gb[1] + n45.x * gb[2], n23.y * gb[0] + n01.y * gb[1] + n45.y * gb[2],
-                                      n45.x * gb[0] + n45.y * gb[1] + n23.x * gb[2]};
+                const double N[6] = {n01.x, n01.y, n23.x, n23.y, n45.x, n45.y};
+                double na[3], nb[3];
+                p1_sym_mul<3>(N, ga, na);
+                p1_sym_mul<3>(N, gb, nb);
                 const double vc_ = vol * cc[w].x;
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
@@ -286,17 +216,17 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_tri_gather(int64_t
         double accn[2][2] = {{0, 0}, {0, 0}};
         const int32_t q1 = ptr[e + 1];
         for (int32_t q = ptr[e]; q < q1; ++q) {
-            const int32_t sidx = src[q];
-            const int64_t c = sidx / 9;
-            const int ab = sidx - (int32_t)(c * 9);
-            const int a = ab / 3, b = ab - 3 * a;
+            int64_t c;
+            int a, b;
+            p1_source<2>(src[q], c, a, b);
             const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
             const double2* rc = reinterpret_cast<const double2*>(rec + FS_PLASTIC_REC2 * c);
             const double2 ml = rc[0], cn = rc[1], n13 = rc[2];
             const double mu = ml.x, lambda = ml.y;
             const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-            const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
-            const double gb[2] = {b == 0 ? t.g[0][0] : (b == 1 ? t.g[1][0] : t.g[2][0]), b == 0 ? t.g[0][1] : (b == 1 ? t.g[1][1] : t.g[2][1])};
+            double ga[2], gb[2];
+            p1_grad(t, a, ga);
+            p1_grad(t, b, gb);
             const double gg = ga[0] * gb[0] + ga[1] * gb[1];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -306,9 +236,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_tri_gather(int64_t
                     if (i == j) x += t.area * mu * gg + ms0;
                     acc[i][j] += x;
                 }
-            // in-plane part of N: [[Nxx, Nxy], [Nxy, Nyy]]
-            const double na[2] = {cn.y * ga[0] + n13.y * ga[1], n13.y * ga[0] + n13.x * ga[1]};
-            const double nb[2] = {cn.y * gb[0] + n13.y * gb[1], n13.y * gb[0] + n13.x * gb[1]};
+            const double N[4] = {cn.y, n13.x, 0.0, n13.y};      // (Nxx, Nyy, -, Nxy): the in-plane part
+            double na[2], nb[2];
+            p1_sym_mul<2>(N, ga, na);
+            p1_sym_mul<2>(N, gb, nb);
             const double vc_ = t.area * cn.x;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -326,100 +257,11 @@ __global__ void __launch_bounds__(FS_BLOCK) k_plastic_tangent_tri_gather(int64_t
     }
 }
 
-// ---- internal force ------------------------------------------------------------------------------------------------------
-// thread per owned node r: the sources of its diagonal block are (c, a, a) for every cell c holding the node, ascending in c
-__device__ __forceinline__ int64_t plastic_diag_entry(int64_t r, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col) {
-    const int64_t sp0 = slice_ptr[r >> 6];
-    const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
-    const int64_t base = sp0 + (r & 63);
-    for (int k = 0; k < width; ++k)
-        if (sell_col[base + (int64_t)k * FS_SLICE] == (int32_t)r) return base + (int64_t)k * FS_SLICE;
-    return -1;
-}
-
-template <bool ADD>
-__global__ void __launch_bounds__(FS_BLOCK) k_plastic_force_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
-                                                                   const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
-                                                                   const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
-                                                                   const double* __restrict__ xyz4, const double* __restrict__ sig,
-                                                                   const box_snap bx, double* __restrict__ f) {
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; r < n_rows; r += stride) {
-        const int64_t e = plastic_diag_entry(r, slice_ptr, sell_col);
-        double acc[3] = {0.0, 0.0, 0.0};
-        if (e >= 0) {
-            const int32_t q1 = gptr[e + 1];
-            for (int32_t q = gptr[e]; q < q1; ++q) {
-                const int32_t sidx = gsrc[q];
-                const int64_t c = sidx >> 4;
-                const int a = (sidx >> 2) & 3;
-                const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
-                const double2* sc = reinterpret_cast<const double2*>(sig + 6 * c);
-                const double2 s01 = sc[0], s23 = sc[1], s45 = sc[2];
-                const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
-                const tet_geom t = tet_geometry_box(xyz4, v, bx);
-                const double vol = t.adet * (1.0 / 6.0);
-                double ga[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
-                // sigma = [[s0, s3, s4], [s3, s1, s5], [s4, s5, s2]]
-                acc[0] += vol * (s01.x * ga[0] + s23.y * ga[1] + s45.x * ga[2]);
-                acc[1] += vol * (s23.y * ga[0] + s01.y * ga[1] + s45.y * ga[2]);
-                acc[2] += vol * (s45.x * ga[0] + s45.y * ga[1] + s23.x * ga[2]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) f[3 * r + i] = ADD ? f[3 * r + i] + acc[i] : acc[i];
-    }
-}
-
-template <bool ADD>
-__global__ void __launch_bounds__(FS_BLOCK) k_plastic_force_tri_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
-                                                                       const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
-                                                                       const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
-                                                                       const double* __restrict__ xyz4, const double* __restrict__ sig,
-                                                                       double* __restrict__ f) {
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; r < n_rows; r += stride) {
-        const int64_t e = plastic_diag_entry(r, slice_ptr, sell_col);
-        double acc[2] = {0.0, 0.0};
-        if (e >= 0) {
-            for (int32_t q = gptr[e]; q < gptr[e + 1]; ++q) {
-                const int32_t sidx = gsrc[q];
-                const int64_t c = sidx / 9;
-                const int a = (sidx - (int32_t)(c * 9)) / 3;
-                const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
-                const double2* sc = reinterpret_cast<const double2*>(sig + 4 * c);
-                const double2 s01 = sc[0], s23 = sc[1];          // (xx, yy), (zz, xy)
-                const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-                const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
-                acc[0] += t.area * (s01.x * ga[0] + s23.y * ga[1]);
-                acc[1] += t.area * (s23.y * ga[0] + s01.y * ga[1]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) f[2 * r + i] = ADD ? f[2 * r + i] + acc[i] : acc[i];
-    }
-}
-
 // ---- host side: the history object ---------------------------------------------------------------------------------------
-static int plastic_space_ok(const fs_space_s* sp, const char* who) {
-    FS_REFUSE_DG_SPACE(sp, who);
-    FS_REQUIRE(sp, "%s: null space", who);
-    const fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(sp->degree == 1 && ((m->tdim == 3 && sp->ncomp == 3) || (m->tdim == 2 && sp->ncomp == 2)),
-               "%s: vector CG1 spaces on tetrahedra or triangles only (this space: CG%d with %d components on a %d-D mesh)", who, sp->degree,
-               sp->ncomp, m->tdim);
-    FS_REQUIRE(m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local, "%s: the space has ghost nodes (several ranks): not supported", who);
-    return FS_OK;
-}
-
 extern "C" int fs_plastic_state_create(fs_space_t space, fs_plastic_state_t* out) {
     FS_CHECK(fs_require_init());
     FS_REQUIRE(out, "fs_plastic_state_create: null pointer");
-    FS_CHECK(plastic_space_ok(space, "fs_plastic_state_create"));
+    FS_CHECK(fs_require_vector_cg1(space, "fs_plastic_state_create"));
     fs_plastic_state_s* st = new fs_plastic_state_s();
     st->space = space;
     st->tdim = space->mesh->tdim;
@@ -427,8 +269,7 @@ extern "C" int fs_plastic_state_create(fs_space_t space, fs_plastic_state_t* out
     st->nc = space->mesh->nc;
     const int64_t ne = st->nc * st->ne;
     int rc = FS_OK;
-    if ((rc = st->ep.alloc(ne)) || (rc = st->ep_trial.alloc(ne)) || (rc = st->sig.alloc(ne)) || (rc = st->sig_trial.alloc(ne)) ||
-        (rc = st->p.alloc(st->nc)) || (rc = st->p_trial.alloc(st->nc)) ||
+    if ((rc = st->ep.alloc(ne)) || (rc = st->sig.alloc(ne)) || (rc = st->p.alloc(st->nc)) ||
         (rc = st->rec.alloc(st->nc * (st->tdim == 3 ? FS_PLASTIC_REC3 : FS_PLASTIC_REC2)))) {
         delete st;
         return rc;
@@ -447,8 +288,7 @@ extern "C" int fs_plastic_state_destroy(fs_plastic_state_t st) {
 extern "C" int fs_plastic_state_reset(fs_plastic_state_t st) {
     FS_REQUIRE(st, "fs_plastic_state_reset: null pointer");
     hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->ep.zero(s)); FS_CHECK(st->ep_trial.zero(s)); FS_CHECK(st->p.zero(s)); FS_CHECK(st->p_trial.zero(s));
-    FS_CHECK(st->sig.zero(s)); FS_CHECK(st->sig_trial.zero(s)); FS_CHECK(st->rec.zero(s));
+    FS_CHECK(st->ep.zero(s)); FS_CHECK(st->p.zero(s)); FS_CHECK(st->sig.zero(s)); FS_CHECK(st->rec.zero(s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -456,12 +296,7 @@ extern "C" int fs_plastic_state_reset(fs_plastic_state_t st) {
 extern "C" int fs_plastic_state_commit(fs_plastic_state_t st) {
     FS_REQUIRE(st, "fs_plastic_state_commit: null pointer");
     hipStream_t s = fs_rt().stream;
-    const size_t be = (size_t)st->nc * st->ne * sizeof(double);
-    if (st->nc) {
-        FS_HIP(hipMemcpyAsync(st->ep.p, st->ep_trial.p, be, hipMemcpyDeviceToDevice, s));
-        FS_HIP(hipMemcpyAsync(st->sig.p, st->sig_trial.p, be, hipMemcpyDeviceToDevice, s));
-        FS_HIP(hipMemcpyAsync(st->p.p, st->p_trial.p, (size_t)st->nc * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
+    FS_CHECK(st->ep.commit(s)); FS_CHECK(st->sig.commit(s)); FS_CHECK(st->p.commit(s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -471,9 +306,9 @@ extern "C" int fs_plastic_state_get(fs_plastic_state_t st, int which, double* ep
     FS_REQUIRE(which == FS_PLASTIC_COMMITTED || which == FS_PLASTIC_TRIAL, "fs_plastic_state_get: which is FS_PLASTIC_COMMITTED or FS_PLASTIC_TRIAL");
     hipStream_t s = fs_rt().stream;
     const bool tr = which == FS_PLASTIC_TRIAL;
-    if (eps_p) FS_CHECK((tr ? st->ep_trial : st->ep).download(eps_p, st->nc * st->ne, s));
-    if (p) FS_CHECK((tr ? st->p_trial : st->p).download(p, st->nc, s));
-    if (stress) FS_CHECK((tr ? st->sig_trial : st->sig).download(stress, st->nc * st->ne, s));
+    if (eps_p) FS_CHECK(st->ep.pick(tr).download(eps_p, st->nc * st->ne, s));
+    if (p) FS_CHECK(st->p.pick(tr).download(p, st->nc, s));
+    if (stress) FS_CHECK(st->sig.pick(tr).download(stress, st->nc * st->ne, s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -484,8 +319,8 @@ extern "C" int fs_plastic_state_set(fs_plastic_state_t st, const double* eps_p, 
         FS_REQUIRE(p[c] >= 0.0 && isfinite(p[c]), "fs_plastic_state_set: cell %lld (device order) has cumulative plastic strain %g: p >= 0 is "
                    "required", (long long)c, p[c]);
     hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->ep.upload(eps_p, st->nc * st->ne, s));
-    FS_CHECK(st->p.upload(p, st->nc, s));
+    FS_CHECK(st->ep.committed.upload(eps_p, st->nc * st->ne, s));
+    FS_CHECK(st->p.committed.upload(p, st->nc, s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -496,7 +331,7 @@ extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector
     FS_REFUSE_DG_SPACE(space, "fs_assemble_plasticity"); FS_REFUSE_DG(K, "fs_assemble_plasticity");
     FS_REQUIRE(space && u && form && state, "fs_assemble_plasticity: null pointer");
     FS_REQUIRE((what & ~(FS_PLASTIC_TANGENT | FS_PLASTIC_FORCE)) == 0, "fs_assemble_plasticity: unknown bits in what (%d)", what);
-    FS_CHECK(plastic_space_ok(space, "fs_assemble_plasticity"));
+    FS_CHECK(fs_require_vector_cg1(space, "fs_assemble_plasticity"));
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
     FS_REQUIRE(state->space == sp && state->nc == m->nc, "fs_assemble_plasticity: the history belongs to another space");
@@ -532,16 +367,16 @@ extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector
     const double ms0 = 0.0;
     // 1. the return mapping, once per cell
     const int nb = FS_PLASTIC_CELL_BLOCKS;
-    dbuf<int64_t> py, pn, pf, on;
-    FS_CHECK(py.alloc(nb)); FS_CHECK(pn.alloc(nb)); FS_CHECK(pf.alloc(nb)); FS_CHECK(on.alloc(3));
+    dbuf<int64_t> part, on;
+    FS_CHECK(part.alloc(3 * nb)); FS_CHECK(on.alloc(3));
 #define FS_PC(T_, C_) hipLaunchKernelGGL((k_plastic_cells<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, form->mu, \
-                                         form->lambda, form->yield_stress, form->hardening, mstore.p, bx, state->ep.p, state->p.p,                \
-                                         state->ep_trial.p, state->p_trial.p, state->sig_trial.p, state->rec.p, py.p, pn.p, pf.p)
+                                         form->lambda, form->yield_stress, form->hardening, mstore.p, bx, state->ep.committed.p,                 \
+                                         state->p.committed.p, state->ep.trial.p, state->p.trial.p, state->sig.trial.p, state->rec.p, part.p)
     if (m->tdim == 3) { if (cellw) FS_PC(3, true); else FS_PC(3, false); }
     else { if (cellw) FS_PC(2, true); else FS_PC(2, false); }
 #undef FS_PC
     FS_KERNEL_CHECK();
-    hipLaunchKernelGGL(k_plastic_cells_finish, dim3(1), dim3(64), 0, s, nb, py.p, pn.p, pf.p, on.p);
+    hipLaunchKernelGGL((k_cell_tally_finish<2, false>), dim3(1), dim3(64), 0, s, nb, part.p, nullptr, on.p, nullptr);
     FS_KERNEL_CHECK();
     // 2. the tangent, per stored block
     if (what & FS_PLASTIC_TANGENT) {
@@ -559,14 +394,11 @@ extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector
     // 3. the internal force, per owned node
     if (what & FS_PLASTIC_FORCE) {
         const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
-#define FS_PF3(A_) hipLaunchKernelGGL((k_plastic_force_gather<A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
-                                      sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig_trial.p, bx, r->d.p)
-#define FS_PF2(A_) hipLaunchKernelGGL((k_plastic_force_tri_gather<A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
-                                      sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig_trial.p, r->d.p)
-        if (m->tdim == 3) { if (add) FS_PF3(true); else FS_PF3(false); }
-        else { if (add) FS_PF2(true); else FS_PF2(false); }
-#undef FS_PF3
-#undef FS_PF2
+#define FS_PF(T_, A_) hipLaunchKernelGGL((k_p1_stress_force_gather<T_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
+                                         sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig.trial.p, bx, r->d.p)
+        if (m->tdim == 3) { if (add) FS_PF(3, true); else FS_PF(3, false); }
+        else { if (add) FS_PF(2, true); else FS_PF(2, false); }
+#undef FS_PF
         FS_KERNEL_CHECK();
     }
     if (info) {
@@ -574,9 +406,7 @@ extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector
         FS_CHECK(on.download(n_host, 3, s));
         info->n_yielded = n_host[0];
         info->n_nonfinite = n_host[1];
-        int64_t first = n_host[1] > 0 ? n_host[2] : -1;
-        if (first >= 0 && !m->cell_order.empty()) first = m->cell_order[first];     // the caller's cell number
-        info->first_nonfinite_cell = first;
+        info->first_nonfinite_cell = fs_first_cell(m, n_host[1], n_host[2]);
     }
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;

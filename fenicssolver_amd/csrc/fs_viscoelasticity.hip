@@ -18,16 +18,17 @@
 //       uniform loads.  A per-cell material evaluates visco_ab() per cell instead - the same function on the same inputs, so a
 //       per-cell array holding one constant gives the constant's bits.
 //   k_visco_update    one thread per cell: strain from the P1 geometry, trial e, h_k and sigma^{n+1} from the COMMITTED (e, h_k); counts
-//       the non-finite cells per workgroup (k_visco_update_finish sums the partials in a fixed order).
-//   k_visco_gather    one thread per owned node over the cells around it (the sources of its diagonal block, ascending - the walk of
-//       k_plastic_force_gather).  LOAD: -V s_hist g_a with s_hist evaluated in place from the committed state and this step's
-//       (a_k, b_k); FORCE: +V sigma g_a from the trial stress (the equilibrium check int B^T sigma dx).
+//       the non-finite cells per workgroup (p1_cell_tally; k_cell_tally_finish sums the partials in a fixed order).
+//   k_visco_gather    the history load: one thread per owned node over the cells around it (the sources of its diagonal
+//       block, ascending), -V s_hist g_a with s_hist evaluated in place from the committed state and this step's (a_k, b_k).
+//   k_p1_stress_force_gather (fs_p1_cell.h)  the internal force +V sigma g_a from the trial stress (the equilibrium check
+//       int B^T sigma dx), by the same walk.
 //
 // Tensor storage follows fs_plasticity.hip: 3-D (xx, yy, zz, xy, xz, yz), plane strain (xx, yy, zz, xy) - tensor components, not
 // engineering shears; plane strain keeps e_zz = -tr(eps)/3, h_k,zz and sigma_zz.  h is stored [cell][term][component].
 #include "fs_common.h"
 #include "fs_kernels.h"
-#include "fs_p1_geometry.h"
+#include "fs_p1_cell.h"
 #include <math.h>
 
 #define FS_VISCO_CELL_BLOCKS 1024        // workgroups of the per-cell pass (its partials are summed in this order)
@@ -39,8 +40,7 @@ struct fs_visco_state_s {
     int ne = 6;                          // stored tensor components (4 in plane strain)
     int nt = 0;                          // Prony terms
     int64_t nc = 0;
-    dbuf<double> e, h, sig;              // committed: dev eps [nc][ne], h_k [nc][nt][ne], stress [nc][ne]
-    dbuf<double> e_trial, h_trial, sig_trial;      // the last update
+    fs_history_pair e, h, sig;           // dev eps [nc][ne], h_k [nc][nt][ne], stress [nc][ne]
     hipEvent_t ev[8] = {};               // (start, stop) of the table launch and of the three passes: created once, on first use
     ~fs_visco_state_s() {
         for (hipEvent_t e_ : ev)
@@ -82,9 +82,9 @@ __global__ void __launch_bounds__(FS_BLOCK) k_visco_update(int64_t nc, const int
                                                            const double* __restrict__ mat, const box_snap bx,
                                                            const double* __restrict__ e0, const double* __restrict__ h0,
                                                            double* __restrict__ e1, double* __restrict__ h1, double* __restrict__ sig,
-                                                           int64_t* __restrict__ part_n, int64_t* __restrict__ part_first) {
+                                                           int64_t* __restrict__ part) {
     constexpr int NE = TD == 3 ? 6 : 4;
-    int64_t n_bad = 0, first = INT64_MAX;
+    int64_t n_bad[1] = {0}, first = INT64_MAX;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int ms = 2 + 2 * nt;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
@@ -97,36 +97,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_visco_update(int64_t nc, const int
         }
         // strain of the P1 displacement, in the storage order of the file header
         double ed[NE];
-        if (TD == 3) {
-            const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
-            const tet_geom t = tet_geometry_box(xyz4, v, bx);
-            double H[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const double ua = u[3 * (int64_t)v[a] + i];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) H[i][j] += ua * t.g[a][j];
-                }
-            ed[0] = H[0][0]; ed[1] = H[1][1]; ed[2] = H[2][2];
-            ed[3] = 0.5 * (H[0][1] + H[1][0]); ed[4] = 0.5 * (H[0][2] + H[2][0]); ed[5] = 0.5 * (H[1][2] + H[2][1]);
-        } else {
-            const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-            const int32_t v[3] = {v4.x, v4.y, v4.z};
-            double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double2 ua = reinterpret_cast<const double2*>(u)[v[a]];
-                H[0][0] += ua.x * t.g[a][0]; H[0][1] += ua.x * t.g[a][1];
-                H[1][0] += ua.y * t.g[a][0]; H[1][1] += ua.y * t.g[a][1];
-            }
-            ed[0] = H[0][0]; ed[1] = H[1][1]; ed[2] = 0.0; ed[3] = 0.5 * (H[0][1] + H[1][0]);
-        }
+        p1_strain<TD>(v4, xyz4, u, bx, ed);
         double sg[NE];
         {
 #pragma clang fp contract(off)
@@ -172,7 +143,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_visco_update(int64_t nc, const int
                 ok = ok && isfinite(sg[j]);
             }
             if (!ok) {
-                ++n_bad;
+                ++n_bad[0];
                 first = c < first ? c : first;
             }
         }
@@ -184,50 +155,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_visco_update(int64_t nc, const int
             so[j >> 1] = make_double2(sg[j], sg[j + 1]);
         }
     }
-    __shared__ int64_t sn_[FS_BLOCK / 64], sf_[FS_BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        n_bad += __shfl_down(n_bad, off, 64);
-        const int64_t o = __shfl_down(first, off, 64);
-        first = o < first ? o : first;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sn_[wave] = n_bad; sf_[wave] = first; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t tn = 0, tf = INT64_MAX;
-        for (int w = 0; w < FS_BLOCK / 64; ++w) {
-            tn += sn_[w];
-            tf = sf_[w] < tf ? sf_[w] : tf;
-        }
-        part_n[blockIdx.x] = tn;
-        part_first[blockIdx.x] = tf;
-    }
+    p1_cell_tally<1, false>(n_bad, first, 0.0, part, nullptr);
 }
 
-__global__ void k_visco_update_finish(int nb, const int64_t* __restrict__ part_n, const int64_t* __restrict__ part_first,
-                                      int64_t* __restrict__ out) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int64_t tn = 0, tf = INT64_MAX;
-    for (int b = 0; b < nb; ++b) {
-        tn += part_n[b];
-        tf = part_first[b] < tf ? part_first[b] : tf;
-    }
-    out[0] = tn;
-    out[1] = tf;
-}
-
-// ---- node gathers: the history load and the internal force ------------------------------------------------------------------
-// thread per owned node r: the sources of its diagonal block are (c, a, a) for every cell c holding the node, ascending in c
-__device__ __forceinline__ int64_t visco_diag_entry(int64_t r, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col) {
-    const int64_t sp0 = slice_ptr[r >> 6];
-    const int width = (int)((slice_ptr[(r >> 6) + 1] - sp0) >> 6);
-    const int64_t base = sp0 + (r & 63);
-    for (int k = 0; k < width; ++k)
-        if (sell_col[base + (int64_t)k * FS_SLICE] == (int32_t)r) return base + (int64_t)k * FS_SLICE;
-    return -1;
-}
-
+// ---- the history load --------------------------------------------------------------------------------------------------------
 // s_hist = 2 G0 sum_k g_k (a_k h_k - b_k e) of cell c from the committed state
 template <int NE, bool CELL>
 __device__ __forceinline__ void visco_s_hist(int64_t c, double mu0, int nt, const visco_terms& tm, const double* __restrict__ coef, double dt,
@@ -266,66 +197,36 @@ __device__ __forceinline__ void visco_s_hist(int64_t c, double mu0, int nt, cons
     for (int j = 0; j < NE; ++j) s[j] = 2.0 * mu * acc[j];
 }
 
-// LOAD: f = -int B^T s_hist dx (sig unused); else f = +int B^T sigma dx from sig (the material arguments unused)
-template <int TD, bool LOAD, bool CELL, bool ADD>
+// f = -int B^T s_hist dx
+template <int TD, bool CELL, bool ADD>
 __global__ void __launch_bounds__(FS_BLOCK) k_visco_gather(int64_t n_rows, const int64_t* __restrict__ slice_ptr,
                                                            const int32_t* __restrict__ sell_col, const int32_t* __restrict__ gptr,
                                                            const int32_t* __restrict__ gsrc, const int32_t* __restrict__ cells,
                                                            const double* __restrict__ xyz4, const box_snap bx, double mu0, int nt,
                                                            const visco_terms tm, const double* __restrict__ coef, double dt,
                                                            const double* __restrict__ mat, const double* __restrict__ e0,
-                                                           const double* __restrict__ h0, const double* __restrict__ sig,
-                                                           double* __restrict__ f) {
+                                                           const double* __restrict__ h0, double* __restrict__ f) {
     constexpr int NE = TD == 3 ? 6 : 4;
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; r < n_rows; r += stride) {
-        const int64_t e = visco_diag_entry(r, slice_ptr, sell_col);
         double acc[TD];
 #pragma unroll
         for (int i = 0; i < TD; ++i) acc[i] = 0.0;
+        const int64_t e = p1_diag_entry(r, slice_ptr, sell_col);
         if (e >= 0) {
             const int32_t q1 = gptr[e + 1];
             for (int32_t q = gptr[e]; q < q1; ++q) {
-                const int32_t sidx = gsrc[q];
                 int64_t c;
-                int a;
-                if (TD == 3) { c = sidx >> 4; a = (sidx >> 2) & 3; }
-                else { c = sidx / 9; a = (sidx - (int32_t)(c * 9)) / 3; }
+                int a, b;
+                p1_source<TD>(gsrc[q], c, a, b);
                 const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
-                double s[NE];
-                if (LOAD) {
-                    visco_s_hist<NE, CELL>(c, mu0, nt, tm, coef, dt, mat, e0, h0, s);
-                } else {
-                    const double2* sc = reinterpret_cast<const double2*>(sig + NE * c);
+                double s[NE], ga[TD], w[TD], vol;
+                visco_s_hist<NE, CELL>(c, mu0, nt, tm, coef, dt, mat, e0, h0, s);
+                p1_weighted_grad<TD>(v4, xyz4, bx, a, ga, vol);
+                p1_sym_mul<TD>(s, ga, w);
 #pragma unroll
-                    for (int j = 0; j < NE; j += 2) {
-                        const double2 x = sc[j >> 1];
-                        s[j] = x.x; s[j + 1] = x.y;
-                    }
-                }
-                if (TD == 3) {
-                    const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
-                    const tet_geom t = tet_geometry_box(xyz4, v, bx);
-                    const double vol = t.adet * (1.0 / 6.0);
-                    double ga[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) ga[k] = a == 0 ? t.g[0][k] : a == 1 ? t.g[1][k] : a == 2 ? t.g[2][k] : t.g[3][k];
-                    // s = [[s0, s3, s4], [s3, s1, s5], [s4, s5, s2]]
-                    const double w0 = vol * (s[0] * ga[0] + s[3] * ga[1] + s[NE - 2] * ga[2]);
-                    const double w1 = vol * (s[3] * ga[0] + s[1] * ga[1] + s[NE - 1] * ga[2]);
-                    const double w2 = vol * (s[NE - 2] * ga[0] + s[NE - 1] * ga[1] + s[2] * ga[2]);
-                    if (LOAD) { acc[0] -= w0; acc[1] -= w1; acc[TD - 1] -= w2; }
-                    else { acc[0] += w0; acc[1] += w1; acc[TD - 1] += w2; }
-                } else {
-                    const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-                    const double ga[2] = {a == 0 ? t.g[0][0] : (a == 1 ? t.g[1][0] : t.g[2][0]), a == 0 ? t.g[0][1] : (a == 1 ? t.g[1][1] : t.g[2][1])};
-                    // in-plane part of s: [[s0, s3], [s3, s1]]
-                    const double w0 = t.area * (s[0] * ga[0] + s[3] * ga[1]);
-                    const double w1 = t.area * (s[3] * ga[0] + s[1] * ga[1]);
-                    if (LOAD) { acc[0] -= w0; acc[1] -= w1; }
-                    else { acc[0] += w0; acc[1] += w1; }
-                }
+                for (int i = 0; i < TD; ++i) acc[i] -= vol * w[i];
             }
         }
 #pragma unroll
@@ -334,21 +235,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_visco_gather(int64_t n_rows, const
 }
 
 // ---- host side: the history object ---------------------------------------------------------------------------------------
-static int visco_space_ok(const fs_space_s* sp, const char* who) {
-    FS_REFUSE_DG_SPACE(sp, who);
-    FS_REQUIRE(sp, "%s: null space", who);
-    const fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(sp->degree == 1 && ((m->tdim == 3 && sp->ncomp == 3) || (m->tdim == 2 && sp->ncomp == 2)),
-               "%s: vector CG1 spaces on tetrahedra or triangles only (this space: CG%d with %d components on a %d-D mesh)", who, sp->degree,
-               sp->ncomp, m->tdim);
-    FS_REQUIRE(m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local, "%s: the space has ghost nodes (several ranks): not supported", who);
-    return FS_OK;
-}
-
 extern "C" int fs_visco_state_create(fs_space_t space, int n_terms, fs_visco_state_t* out) {
     FS_CHECK(fs_require_init());
     FS_REQUIRE(out, "fs_visco_state_create: null pointer");
-    FS_CHECK(visco_space_ok(space, "fs_visco_state_create"));
+    FS_CHECK(fs_require_vector_cg1(space, "fs_visco_state_create"));
     FS_REQUIRE(n_terms >= 0 && n_terms <= FS_VISCO_MAX_TERMS, "fs_visco_state_create: %d Prony terms: 0 to FS_VISCO_MAX_TERMS = %d are "
                "supported", n_terms, FS_VISCO_MAX_TERMS);
     fs_visco_state_s* st = new fs_visco_state_s();
@@ -360,8 +250,7 @@ extern "C" int fs_visco_state_create(fs_space_t space, int n_terms, fs_visco_sta
     const int64_t ne = st->nc * st->ne;
     const int64_t nh = ne * (n_terms > 0 ? n_terms : 1);          // (never an empty allocation)
     int rc = FS_OK;
-    if ((rc = st->e.alloc(ne)) || (rc = st->e_trial.alloc(ne)) || (rc = st->sig.alloc(ne)) || (rc = st->sig_trial.alloc(ne)) ||
-        (rc = st->h.alloc(nh)) || (rc = st->h_trial.alloc(nh))) {
+    if ((rc = st->e.alloc(ne)) || (rc = st->sig.alloc(ne)) || (rc = st->h.alloc(nh))) {
         delete st;
         return rc;
     }
@@ -379,8 +268,7 @@ extern "C" int fs_visco_state_destroy(fs_visco_state_t st) {
 extern "C" int fs_visco_state_reset(fs_visco_state_t st) {
     FS_REQUIRE(st, "fs_visco_state_reset: null pointer");
     hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->e.zero(s)); FS_CHECK(st->e_trial.zero(s)); FS_CHECK(st->h.zero(s)); FS_CHECK(st->h_trial.zero(s));
-    FS_CHECK(st->sig.zero(s)); FS_CHECK(st->sig_trial.zero(s));
+    FS_CHECK(st->e.zero(s)); FS_CHECK(st->h.zero(s)); FS_CHECK(st->sig.zero(s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -388,12 +276,8 @@ extern "C" int fs_visco_state_reset(fs_visco_state_t st) {
 extern "C" int fs_visco_state_commit(fs_visco_state_t st) {
     FS_REQUIRE(st, "fs_visco_state_commit: null pointer");
     hipStream_t s = fs_rt().stream;
-    const size_t be = (size_t)st->nc * st->ne * sizeof(double);
-    if (st->nc) {
-        FS_HIP(hipMemcpyAsync(st->e.p, st->e_trial.p, be, hipMemcpyDeviceToDevice, s));
-        FS_HIP(hipMemcpyAsync(st->sig.p, st->sig_trial.p, be, hipMemcpyDeviceToDevice, s));
-        if (st->nt) FS_HIP(hipMemcpyAsync(st->h.p, st->h_trial.p, be * st->nt, hipMemcpyDeviceToDevice, s));
-    }
+    FS_CHECK(st->e.commit(s)); FS_CHECK(st->sig.commit(s));
+    if (st->nt) FS_CHECK(st->h.commit(s));               // (without terms h is one unused record per cell)
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -403,9 +287,9 @@ extern "C" int fs_visco_state_get(fs_visco_state_t st, int which, double* e, dou
     FS_REQUIRE(which == FS_VISCO_COMMITTED || which == FS_VISCO_TRIAL, "fs_visco_state_get: which is FS_VISCO_COMMITTED or FS_VISCO_TRIAL");
     hipStream_t s = fs_rt().stream;
     const bool tr = which == FS_VISCO_TRIAL;
-    if (e) FS_CHECK((tr ? st->e_trial : st->e).download(e, st->nc * st->ne, s));
-    if (h && st->nt) FS_CHECK((tr ? st->h_trial : st->h).download(h, st->nc * st->ne * st->nt, s));
-    if (stress) FS_CHECK((tr ? st->sig_trial : st->sig).download(stress, st->nc * st->ne, s));
+    if (e) FS_CHECK(st->e.pick(tr).download(e, st->nc * st->ne, s));
+    if (h && st->nt) FS_CHECK(st->h.pick(tr).download(h, st->nc * st->ne * st->nt, s));
+    if (stress) FS_CHECK(st->sig.pick(tr).download(stress, st->nc * st->ne, s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -419,8 +303,8 @@ extern "C" int fs_visco_state_set(fs_visco_state_t st, const double* e, const do
         FS_REQUIRE(ok, "fs_visco_state_set: cell %lld (device order) has a non-finite strain", (long long)c);
     }
     hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->e.upload(e, st->nc * st->ne, s));
-    if (st->nt) FS_CHECK(st->h.upload(h, st->nc * st->ne * st->nt, s));
+    FS_CHECK(st->e.committed.upload(e, st->nc * st->ne, s));
+    if (st->nt) FS_CHECK(st->h.committed.upload(h, st->nc * st->ne * st->nt, s));
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -451,7 +335,7 @@ extern "C" int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vect
     FS_REQUIRE((what & ~(FS_VISCO_LOAD | FS_VISCO_UPDATE | FS_VISCO_FORCE)) == 0, "fs_assemble_viscoelastic: unknown bits in what (%d)", what);
     FS_REQUIRE(!((what & FS_VISCO_LOAD) && (what & FS_VISCO_FORCE)), "fs_assemble_viscoelastic: FS_VISCO_LOAD and FS_VISCO_FORCE write the "
                "same vector: one of them per call");
-    FS_CHECK(visco_space_ok(space, "fs_assemble_viscoelastic"));
+    FS_CHECK(fs_require_vector_cg1(space, "fs_assemble_viscoelastic"));
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
     FS_REQUIRE(state->space == sp && state->nc == m->nc, "fs_assemble_viscoelastic: the history belongs to another space");
@@ -503,46 +387,49 @@ extern "C" int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vect
     const box_snap bx = make_box_snap(m);
     const bool add = form->add != 0;
     const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
-#define FS_VG(T_, L_, C_, A_, SIG_) hipLaunchKernelGGL((k_visco_gather<T_, L_, C_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned,      \
-                                                       sp->slice_ptr.p, sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, bx, \
-                                                       form->mu, nt, tm, coef.p, form->dt, mstore.p, state->e.p, state->h.p, SIG_, r->d.p)
-#define FS_VG_ADD(T_, L_, C_, SIG_) do { if (add) FS_VG(T_, L_, C_, true, SIG_); else FS_VG(T_, L_, C_, false, SIG_); } while (0)
+#define FS_VG(T_, C_, A_) hipLaunchKernelGGL((k_visco_gather<T_, C_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p,   \
+                                             sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, bx, form->mu, nt, tm, coef.p, \
+                                             form->dt, mstore.p, state->e.committed.p, state->h.committed.p, r->d.p)
+#define FS_VG_ADD(T_, C_) do { if (add) FS_VG(T_, C_, true); else FS_VG(T_, C_, false); } while (0)
+#define FS_VF(T_, A_) hipLaunchKernelGGL((k_p1_stress_force_gather<T_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
+                                         sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig.trial.p, bx, r->d.p)
     // 1. the history load, from the committed state
     if (what & FS_VISCO_LOAD) {
         FS_VT(2);
-        if (m->tdim == 3) { if (cellw) FS_VG_ADD(3, true, true, nullptr); else FS_VG_ADD(3, true, false, nullptr); }
-        else { if (cellw) FS_VG_ADD(2, true, true, nullptr); else FS_VG_ADD(2, true, false, nullptr); }
+        if (m->tdim == 3) { if (cellw) FS_VG_ADD(3, true); else FS_VG_ADD(3, false); }
+        else { if (cellw) FS_VG_ADD(2, true); else FS_VG_ADD(2, false); }
         FS_KERNEL_CHECK();
         FS_VT(3);
     }
     // 2. the update, once per cell
-    dbuf<int64_t> pn, pf, on;
+    dbuf<int64_t> part, on;
     if (what & FS_VISCO_UPDATE) {
         const int nb = FS_VISCO_CELL_BLOCKS;
-        FS_CHECK(pn.alloc(nb)); FS_CHECK(pf.alloc(nb)); FS_CHECK(on.alloc(2));
+        FS_CHECK(part.alloc(2 * nb)); FS_CHECK(on.alloc(2));
         FS_VT(4);
 #define FS_VU(T_, C_) hipLaunchKernelGGL((k_visco_update<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, form->mu, \
-                                         form->lambda, nt, tm, coef.p, form->dt, mstore.p, bx, state->e.p, state->h.p, state->e_trial.p,         \
-                                         state->h_trial.p, state->sig_trial.p, pn.p, pf.p)
+                                         form->lambda, nt, tm, coef.p, form->dt, mstore.p, bx, state->e.committed.p, state->h.committed.p,       \
+                                         state->e.trial.p, state->h.trial.p, state->sig.trial.p, part.p)
         if (m->tdim == 3) { if (cellw) FS_VU(3, true); else FS_VU(3, false); }
         else { if (cellw) FS_VU(2, true); else FS_VU(2, false); }
 #undef FS_VU
         FS_KERNEL_CHECK();
-        hipLaunchKernelGGL(k_visco_update_finish, dim3(1), dim3(64), 0, s, nb, pn.p, pf.p, on.p);
+        hipLaunchKernelGGL((k_cell_tally_finish<1, false>), dim3(1), dim3(64), 0, s, nb, part.p, nullptr, on.p, nullptr);
         FS_KERNEL_CHECK();
         FS_VT(5);
     }
     // 3. the internal force of the trial stress
     if (what & FS_VISCO_FORCE) {
         FS_VT(6);
-        if (m->tdim == 3) FS_VG_ADD(3, false, false, state->sig_trial.p);
-        else FS_VG_ADD(2, false, false, state->sig_trial.p);
+        if (m->tdim == 3) { if (add) FS_VF(3, true); else FS_VF(3, false); }
+        else { if (add) FS_VF(2, true); else FS_VF(2, false); }
         FS_KERNEL_CHECK();
         FS_VT(7);
     }
 #undef FS_VT
 #undef FS_VG_ADD
 #undef FS_VG
+#undef FS_VF
     if (info) {
         info->n_nonfinite = 0;
         info->first_nonfinite_cell = -1;
@@ -550,9 +437,7 @@ extern "C" int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vect
             int64_t n_host[2] = {0, 0};
             FS_CHECK(on.download(n_host, 2, s));
             info->n_nonfinite = n_host[0];
-            int64_t first = n_host[0] > 0 ? n_host[1] : -1;
-            if (first >= 0 && !m->cell_order.empty()) first = m->cell_order[first];     // the caller's cell number
-            info->first_nonfinite_cell = first;
+            info->first_nonfinite_cell = fs_first_cell(m, n_host[0], n_host[1]);
         }
     }
     FS_HIP(hipStreamSynchronize(s));

@@ -100,6 +100,33 @@ def test_per_cell_array_of_one_constant_gives_the_constant_bits(d):
 
 
 @pytest.mark.parametrize("d", [3, 2])
+@pytest.mark.parametrize("cellwise", [False, True])
+def test_add_accumulates_onto_the_target_bit_for_bit(d, cellwise):
+    """Tangent and force with add=True equal y + x bit for bit (one fp64 addition per entry): y the target's content (the linear
+    operator in the matrix, known values in the vector), x the result with add=False.  3 x 3 x 4 box: 216 cells, 80 nodes (a partial
+    second slice); 5 x 4 square: 40 cells, 30 nodes."""
+    from fenicssolver_amd import backend
+    mesh = _box((3, 3, 4)) if d == 3 else _rect((5, 4))
+    V, dV = _device(mesh, d)
+    nc = mesh.num_cells()
+    assert (nc, mesh.num_vertices()) == ((216, 80) if d == 3 else (40, 30))
+    rng = np.random.default_rng(80 + d)
+    lame = ("cell", np.stack([3.1 * (1 + rng.random(nc)), 4.7 * (1 + rng.random(nc))], axis=1)) if cellwise else (3.1, 4.7)
+    u = backend.DeviceVector(dV.n_local, _smooth_u(mesh.coordinates(), d))
+    K, r = backend.DeviceMatrix(dV), backend.DeviceVector(dV.n_owned)
+    info = backend.assemble_hyperelastic(dV, u, lame, K=K, r=r)
+    assert info["n_inverted"] == 0
+    xk, xr = K.to_csr()[2], r.get()
+    y = 0.37 + rng.standard_normal(dV.n_owned)
+    Ka, ra = backend.DeviceMatrix(dV), backend.DeviceVector(dV.n_owned, y)
+    Ka.assemble(lame=(3.1, 4.7))
+    yk = Ka.to_csr()[2]
+    backend.assemble_hyperelastic(dV, u, lame, K=Ka, r=ra, add=True)
+    assert np.array_equal(Ka.to_csr()[2], yk + xk)
+    assert np.array_equal(ra.get(), y + xr)
+
+
+@pytest.mark.parametrize("d", [3, 2])
 def test_kernels_match_the_host_reference_and_are_deterministic(d):
     from fenicssolver_amd import backend
     mesh = _box() if d == 3 else _rect()

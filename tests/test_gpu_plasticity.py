@@ -244,6 +244,36 @@ def test_kernels_match_the_host_reference_and_are_deterministic(d):
     assert np.array_equal(epc, pr.pack(ep, d)) and np.array_equal(pc, p)
 
 
+# ---- 2b. add=True adds to what the target holds ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("d", [3, 2])
+def test_add_accumulates_onto_the_target_bit_for_bit(d):
+    """Tangent and force with add=True equal y + x bit for bit (one fp64 addition per entry): y the target's content (the linear
+    operator in the matrix, known values in the vector), x the result with add=False.  3 x 3 x 4 box: 216 cells, 80 nodes (a partial
+    second slice); 5 x 4 square: 40 cells, 30 nodes."""
+    from fenicssolver_amd import backend
+    mesh = _box((3, 3, 4)) if d == 3 else _rect((5, 4))
+    V, dV = _device(mesh)
+    nc = mesh.num_cells()
+    assert (nc, mesh.num_vertices()) == ((216, 80) if d == 3 else (40, 30))
+    rng = np.random.default_rng(60 + d)
+    uh = _smooth_u(mesh.coordinates(), d, 1.7e-3 if d == 3 else 2.5e-3)
+    mat = np.stack([MU_ * (1 + 0.2 * rng.random(nc)), LM_ * (1 + 0.2 * rng.random(nc)), 0.2 * (1 + 0.2 * rng.random(nc)),
+                    20.0 * rng.random(nc)], axis=1)
+    hist = backend.PlasticHistory(dV)
+    u = backend.DeviceVector(dV.n_local, uh)
+    K, r = backend.DeviceMatrix(dV), backend.DeviceVector(dV.n_owned)
+    info = backend.assemble_plasticity(dV, u, hist, ("cell", mat), K=K, r=r)
+    assert 0 < info["n_yielded"] < nc                      # the rank-one part of the tangent takes part
+    xk, xr = K.to_csr()[2], r.get()
+    y = 0.37 + rng.standard_normal(dV.n_owned)
+    Ka, ra = backend.DeviceMatrix(dV), backend.DeviceVector(dV.n_owned, y)
+    Ka.assemble(lame=(MU_, LM_))
+    yk = Ka.to_csr()[2]
+    backend.assemble_plasticity(dV, u, hist, ("cell", mat), K=Ka, r=ra, add=True)
+    assert np.array_equal(Ka.to_csr()[2], yk + xk)
+    assert np.array_equal(ra.get(), y + xr)
+
+
 # ---- 3. the uniaxial closed form ------------------------------------------------------------------------------------------------
 def _uniaxial_case(d, path, H, n=None, L=1.0):
     from fenicssolver_amd.fem import BoxMesh, RectangleMesh, Point, VectorFunctionSpace, AutoSubDomain, Constant, near

@@ -160,6 +160,39 @@ def test_kernels_match_the_host_reference_and_are_deterministic(d, kind):
             assert np.array_equal(a, b)
 
 
+# ---- 1b. add=True adds to what the target holds ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("d", [3, 2])
+@pytest.mark.parametrize("kind", ["cell3", "const1"])
+def test_add_accumulates_onto_the_target_bit_for_bit(d, kind):
+    """History load and internal force with add=True equal y + x bit for bit (one fp64 addition per entry): y the known content of
+    the vector, x the result with add=False.  3 x 3 x 4 box: 216 cells, 80 nodes (a partial second slice); 5 x 4 square: 40 cells,
+    30 nodes."""
+    from fenicssolver_amd import backend
+    mesh = _box((3, 3, 4)) if d == 3 else _rect((5, 4))
+    V, dV = _device(mesh)
+    nc = mesh.num_cells()
+    assert (nc, mesh.num_vertices()) == ((216, 80) if d == 3 else (40, 30))
+    dev_mat, (mu, lm, g, tau) = _material(kind, nc)
+    nt = g.shape[-1]
+    rng = np.random.default_rng(70 + d)
+    hist = backend.ViscoHistory(dV, nt)
+    hist.set(vr.pack(_random_dev(rng, (nc,), d, 1e-3), d), _pack_h(_random_dev(rng, (nc, nt), d, 1e-3), d))
+    u = backend.DeviceVector(dV.n_local, _smooth_u(mesh.coordinates(), d, 2e-3))
+    dt = 0.4
+    y = 0.37 + rng.standard_normal(dV.n_owned)
+    x = backend.DeviceVector(dV.n_owned)
+    backend.assemble_viscoelastic(dV, hist, dev_mat, dt, load=x, u=u)            # the load, then the trial stress of u
+    ya = backend.DeviceVector(dV.n_owned, y)
+    backend.assemble_viscoelastic(dV, hist, dev_mat, dt, load=ya, add=True)
+    assert np.abs(x.get()).max() > 0.0
+    assert np.array_equal(ya.get(), y + x.get())
+    backend.assemble_viscoelastic(dV, hist, dev_mat, dt, force=x)
+    ya.set(y)
+    backend.assemble_viscoelastic(dV, hist, dev_mat, dt, force=ya, add=True)
+    assert np.abs(x.get()).max() > 0.0
+    assert np.array_equal(ya.get(), y + x.get())
+
+
 def test_a_nonfinite_displacement_is_counted_and_the_c_abi_refuses_bad_input():
     from fenicssolver_amd import backend
     mesh = _box()
