@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfsamd.so")
 
 FS_OK = 0
-FS_ERR_COMM, FS_ERR_NUMERIC, FS_ERR_P2P_TIMEOUT = -5, -6, -7      # include/fenicssolver_amd.h
+FS_ERR_UNSUPPORTED, FS_ERR_COMM, FS_ERR_NUMERIC, FS_ERR_P2P_TIMEOUT = -4, -5, -6, -7      # include/fenicssolver_amd.h
 FS_COEF_NONE, FS_COEF_CONST, FS_COEF_CELL, FS_COEF_TENSOR, FS_COEF_NODAL, FS_COEF_CELL_ROW, FS_COEF_CELL_TENSOR, FS_COEF_CELL_QP = 0, 1, 2, 3, 4, 5, 6, 7
 FS_COEF_CELL_LAME = 8
 FS_HYPER_NEO_HOOKEAN = 0

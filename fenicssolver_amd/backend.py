@@ -936,6 +936,20 @@ class AMG(_Handle):
         L.check(L.load().fs_amg_level_get(self.h, int(level), 2, None, None, L.p_f64(out)), "fs_amg_level_get")
         return out.reshape(-1, nb)
 
+    def coarse_inverse(self):
+        """The dense inverse that the V-cycle applies on the coarsest level ([n, n], row-major), or None where it runs Chebyshev
+        sweeps there instead (a single level, or a coarsest level of more than 2500 rows)."""
+        last = self.info()["levels"] - 1
+        li = self.level_info(last)
+        n = li["n_nodes"] * li["block_size"]
+        rc = L.load().fs_amg_level_get(self.h, last, 3, None, None, None)        # no buffer: only asks whether there is one
+        if rc == L.FS_ERR_UNSUPPORTED:
+            return None
+        L.check(rc, "fs_amg_level_get")
+        out = np.empty(n * n)
+        L.check(L.load().fs_amg_level_get(self.h, last, 3, None, None, L.p_f64(out)), "fs_amg_level_get")
+        return out.reshape(n, n)
+
     def apply(self, r, z):
         L.check(L.load().fs_amg_apply(self.h, r.h, z.h), "fs_amg_apply")
 

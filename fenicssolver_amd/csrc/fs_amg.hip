@@ -1695,6 +1695,11 @@ extern "C" int fs_amg_setup(fs_matrix_t A, int n_nullspace, const double* nullsp
                "fs_amg_setup: rigid-body modes are built for 3-vector CG1 / CG2 spaces on tetrahedra");
     const int nb = nullspace ? n_nullspace : (rigid ? 6 : A->bs);
     FS_REQUIRE(nb == 1 || nb == 3 || nb == 6, "fs_amg_setup: %d near-null-space vectors (1, 3 or 6 are built)", nb);
+    // the transfers of level 0 are blocks of bs x nb: the V-cycle has a restriction for 1 x 1, 3 x 3, 3 x 6 (and 6 x 6 below) only -
+    // any other pair would pass the set-up through the run-time-shaped SpGEMM and fail in the first fs_amg_apply
+    FS_REQUIRE((A->bs == 1 && nb == 1) || (A->bs == 3 && (nb == 3 || nb == 6)),
+               "fs_amg_setup: %d near-null-space vectors for a matrix of %d x %d blocks: no restriction is built for %d x %d transfer blocks "
+               "(1 vector for scalar matrices, 3 or 6 for 3 x 3 blocks)", nb, A->bs, A->bs, A->bs, nb);
     // 0 = default 0.05; negative = keep every coupling above the summation-order noise (1e-8)
     const double theta = (!opts || opts->strength_threshold == 0.0) ? 0.05 : std::max(opts->strength_threshold, 1e-8);
     const int max_levels = opts && opts->max_levels > 0 ? opts->max_levels : 10;
@@ -1919,6 +1924,16 @@ extern "C" int fs_amg_level_get(fs_amg_t M, int level, int which, int32_t* rowpt
     if (which == 2) {
         FS_REQUIRE(val, "fs_amg_level_get: null pointer");
         return L->B.download(val, L->B.n, s);
+    }
+    if (which == 3) {       // the dense inverse the V-cycle applies on the coarsest level (k_dense_apply); val == NULL only asks for it
+        FS_REQUIRE(level == (int)M->lv.size() - 1, "fs_amg_level_get: the dense inverse belongs to the coarsest level %d, not to level %d",
+                   (int)M->lv.size() - 1, level);
+        if (!M->cinv.p) {
+            fs_set_error("fs_amg_level_get: the hierarchy has no dense inverse (%lld rows on its coarsest level %d: Chebyshev sweeps)",
+                         (long long)L->n, level);
+            return FS_ERR_UNSUPPORTED;
+        }
+        return val ? M->cinv.download(val, M->nc * M->nc, s) : FS_OK;
     }
     FS_REQUIRE(X.nnz > 0, "fs_amg_level_get: level %d has no such operator", level);
     if (rowptr) FS_CHECK(X.rowptr.download(rowptr, X.nrows + 1, s));

@@ -743,7 +743,11 @@ int fs_amg_info(fs_amg_t amg, int* n_levels, double* operator_complexity, double
 int fs_amg_level_info(fs_amg_t amg, int level, int64_t* n_nodes, int* block_size, int64_t* nnz_blocks,
                       int64_t* p_nnz_blocks, int* p_block_cols, double* lambda_max);
 /* which: 0 = level operator A (block CSR, blocks row-major), 1 = prolongator to this level from the
- * next, 2 = near-null space [n_dofs][nb] (val only).  Test/inspection hook. */
+ * next, 2 = near-null space [n_dofs][nb] (val only), 3 = the dense inverse of the coarsest operator
+ * that the V-cycle applies there ([n_dofs][n_dofs] row-major, val only, level = the last one;
+ * FS_ERR_UNSUPPORTED when the hierarchy has none: a single level, or more than 2500 rows on the
+ * coarsest, where the cycle runs Chebyshev sweeps instead; val == NULL only asks whether there is
+ * one).  Test/inspection hook. */
 int fs_amg_level_get(fs_amg_t amg, int level, int which, int32_t* rowptr, int32_t* col, double* val);
 /* z = M r: one V-cycle from a zero guess (PCApply). */
 int fs_amg_apply(fs_amg_t amg, fs_vector_t r, fs_vector_t z);

@@ -58,21 +58,28 @@ def _vector_from_cache(gpu, n):
 
 def _host_product(A, x):
     """y = A x from the assembled CSR in float64 with the row sums rounded once (extended precision: 64-bit products and sums, ~2^-60
-    relative to |A| |x| for the row lengths here, then one rounding), and |A| |x|."""
-    rp, ci, va, (nr, _) = A.to_csr()
-    rp = rp.astype(np.int64)
-    y = np.empty(nr)
-    ax = np.empty(nr)
-    if np.finfo(np.longdouble).nmant >= 63:
+    relative to |A| |x| for the row lengths here, then one rounding), and |A| |x|.  A: a device matrix (to_csr(); every row has an
+    entry) or a scipy CSR matrix, whose rows without entries give 0."""
+    if hasattr(A, "to_csr"):
+        rp, ci, va, (nr, _) = A.to_csr()
         assert np.all(np.diff(rp) > 0), "a row without entries"
+    else:
+        rp, ci, va, nr = A.indptr, A.indices, A.data, A.shape[0]
+    rp = rp.astype(np.int64)
+    y = np.zeros(nr)
+    ax = np.zeros(nr)
+    if np.finfo(np.longdouble).nmant >= 63:
         step = 1 << 18
         for r0 in range(0, nr, step):
             r1 = min(nr, r0 + step)
             e0, e1 = rp[r0], rp[r1]
-            off = rp[r0:r1] - e0
+            rows = r0 + np.flatnonzero(rp[r0 + 1:r1 + 1] > rp[r0:r1])      # (reduceat takes the starts of the rows that have entries)
+            if len(rows) == 0:
+                continue
+            off = rp[rows] - e0
             prod = va[e0:e1].astype(np.longdouble) * x[ci[e0:e1]].astype(np.longdouble)
-            y[r0:r1] = np.add.reduceat(prod, off).astype(np.float64)
-            ax[r0:r1] = np.add.reduceat(np.abs(prod), off).astype(np.float64)
+            y[rows] = np.add.reduceat(prod, off).astype(np.float64)
+            ax[rows] = np.add.reduceat(np.abs(prod), off).astype(np.float64)
     else:
         for i in range(nr):
             sl = slice(rp[i], rp[i + 1])

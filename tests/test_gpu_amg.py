@@ -227,6 +227,20 @@ def test_amg_rejects_bad_input(gpu):
         gpu.AMG(A, nullspace=np.ones((1, 3)))
     with pytest.raises(BackendError):
         gpu.AMG(A, nullspace=np.ones((2, V.n_owned)))      # 2 vectors: not 1, 3 or 6
+    # pairs (block size, vectors) whose level-0 transfer blocks have no restriction kernel: refused by the set-up, with a message that
+    # names the pair, instead of by the first apply ("restriction for 3x1 blocks is not built", as the last one was before)
+    co, ce = fo.box_mesh((0, 0, 0), (1, 1, 1), 4, 4, 4)
+    x, y, z = co.T
+    one = np.ones_like(x)
+    V3 = gpu.DeviceSpace(gpu.DeviceMesh(co, ce), ncomp=3)
+    A3 = gpu.DeviceMatrix(V3)
+    A3.assemble(lame=(1.0, 1.5), mass=1.0)
+    for M, ns, pair in ((A, np.stack([one, x, y]), "1 x 3"), (A, np.stack([one, x, y, z, x * y, y * z]), "1 x 6"),
+                        (A3, np.ones((1, V3.n_owned)), "3 x 1")):
+        with pytest.raises(BackendError, match="fs_amg_setup.*%s transfer blocks" % pair):
+            gpu.AMG(M, nullspace=ns)
+    for M, ns in ((A, one[None, :]), (A3, None), (A3, fo.rigid_body_modes(co))):      # (the pairs that are built still are)
+        gpu.AMG(M, nullspace=ns).close()
 
 
 def test_solve_amg_is_the_default_of_the_elasticity_solver(gpu):
