@@ -1730,10 +1730,9 @@ extern "C" int fs_amg_setup(fs_matrix_t A, int n_nullspace, const double* nullsp
         fs_set_error("fs_amg_setup: device copy failed");
         return fail(FS_ERR_HIP);
     }
-    if (A->bs == 1)
-        hipLaunchKernelGGL(k_amg_extract<1>, dim3(fs_grid_for(L0->nn)), dim3(FS_BLOCK), 0, s, L0->nn, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, L0->A.val.p);
-    else
-        hipLaunchKernelGGL(k_amg_extract<3>, dim3(fs_grid_for(L0->nn)), dim3(FS_BLOCK), 0, s, L0->nn, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, L0->A.val.p);
+    fs_dispatch_int<1, 3>(A->bs, [&](auto BS) {
+        hipLaunchKernelGGL(k_amg_extract<decltype(BS)::value>, dim3(fs_grid_for(L0->nn)), dim3(FS_BLOCK), 0, s, L0->nn, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, L0->A.val.p);
+    });
     // near-null space [n][nb] (the caller's layout is [nb][n]: transposed on the device)
     {
         if ((rc = L0->B.alloc(L0->n * nb)) != FS_OK) return fail(rc);

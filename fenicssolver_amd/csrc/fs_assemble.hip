@@ -21,6 +21,10 @@ static int g_box_snap = -1;          // -1: not set (environment FS_BOX_SNAP, de
 void fs_set_box_snap(bool on) { g_box_snap = on; }
 static int g_box_assembly = -1;      // -1: not set (environment FS_BOX_ASSEMBLY, default on): option "box_assembly"
 void fs_set_box_assembly(bool on) { g_box_assembly = on; }
+static bool box_assembly_on() {      // the option if set, else the environment (read once per process); default on
+    static const bool env_off = getenv("FS_BOX_ASSEMBLY") && getenv("FS_BOX_ASSEMBLY")[0] == '0';
+    return g_box_assembly < 0 ? !env_off : g_box_assembly != 0;
+}
 box_snap make_box_snap(const fs_mesh_s* m) {
     static const bool env_off = getenv("FS_BOX_SNAP") && getenv("FS_BOX_SNAP")[0] == '0';
     const bool off = g_box_snap < 0 ? env_off : g_box_snap == 0;
@@ -68,6 +72,51 @@ struct coef_dev {
     double value;
     const double* data;
     double tensor[9];
+};
+
+// ---- host helpers -------------------------------------------------------------------------------------------------
+// Launch shape of the scalar row-gather matrix kernels.  LDS: one accumulator column of max_row doubles per thread; one wave
+// per workgroup for very long rows.  The grid is a multiple of 8: XCD map.
+struct row_gather_shape {
+    int bd;
+    size_t lds;
+    int grid;
+};
+static int make_row_gather_shape(const fs_space_s* sp, row_gather_shape* out) {
+    out->bd = (int64_t)sp->max_row * FS_BLOCK * 8 <= 64 * 1024 ? FS_BLOCK : 64;
+    out->lds = (size_t)sp->max_row * out->bd * sizeof(double);
+    FS_REQUIRE(out->lds <= 64 * 1024, "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator", sp->max_row);
+    const int wpb = out->bd / 64;
+    out->grid = (fs_grid_for((sp->n_slices + wpb - 1) / wpb, 1, 8192) + 7) & ~7;
+    return FS_OK;
+}
+
+// What a facet or constraint entry point sends along with its launch: a list of int32, a list of doubles (both optional) and the
+// one-int counter in which the kernel counts what it could not place.
+struct launch_lists {
+    dbuf<int32_t> idx;
+    dbuf<double> val;
+    dbuf<int> err;
+    int ints(const int32_t* host, int64_t n, hipStream_t s) {
+        FS_CHECK(idx.alloc(n));
+        return idx.upload(host, n, s);
+    }
+    int doubles(const double* host, int64_t n, hipStream_t s) {
+        FS_CHECK(val.alloc(n));
+        return val.upload(host, n, s);
+    }
+    int count_errors(hipStream_t s) {
+        FS_CHECK(err.alloc(1));
+        return err.zero(s);
+    }
+    // after the launch: waits for it and fails with the caller's message (its one %d: the count) unless the counter is still zero
+    int check(hipStream_t s, const char* message) {
+        FS_KERNEL_CHECK();
+        int n_err = 0;
+        FS_CHECK(err.download(&n_err, 1, s));
+        FS_REQUIRE(n_err == 0, message, n_err);
+        return FS_OK;
+    }
 };
 
 // ---- scalar P1:  Ke = k vol grad_a.K.grad_b + m |J|/120 (1+delta_ab) ------------------------
@@ -2446,30 +2495,24 @@ extern "C" int fs_matrix_tie_nodes(fs_matrix_t A, fs_vector_t b, int64_t n_pairs
                    (slaves[i] >= sp->n_nodes_owned || masters[i] < sp->n_nodes_owned),
                    "fs_matrix_tie_nodes: pair %lld (%d -> %d) out of range (a slave this rank owns needs its master on this rank too)", (long long)i, slaves[i], masters[i]);
     hipStream_t s = fs_rt().stream;
-    dbuf<int32_t> d_s, d_m, master_of;
-    dbuf<int> d_err;
-    FS_CHECK(d_s.alloc(n_pairs)); FS_CHECK(d_m.alloc(n_pairs)); FS_CHECK(master_of.alloc(sp->n_nodes_local)); FS_CHECK(d_err.alloc(1));
-    FS_CHECK(d_s.upload(slaves, n_pairs, s)); FS_CHECK(d_m.upload(masters, n_pairs, s));
-    FS_CHECK(d_err.zero(s));
+    launch_lists S, M;      // slaves (with the counter) and masters
+    dbuf<int32_t> master_of;
+    FS_CHECK(S.ints(slaves, n_pairs, s));
+    FS_CHECK(M.ints(masters, n_pairs, s));
+    FS_CHECK(master_of.alloc(sp->n_nodes_local));
+    FS_CHECK(S.count_errors(s));
     FS_HIP(hipMemsetAsync(master_of.p, 0xff, (size_t)sp->n_nodes_local * sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_fill_master_of, dim3(fs_grid_for(n_pairs)), dim3(FS_BLOCK), 0, s, n_pairs, d_s.p, d_m.p, master_of.p);
+    hipLaunchKernelGGL(k_fill_master_of, dim3(fs_grid_for(n_pairs)), dim3(FS_BLOCK), 0, s, n_pairs, S.idx.p, M.idx.p, master_of.p);
     const int grid = fs_grid_for(sp->n_slices * 64, FS_BLOCK, 8192), gp = fs_grid_for(n_pairs);
     double* bp = b ? b->d.p : nullptr;
-#define FS_TIE(BS_)                                                                                                                       \
-    {                                                                                                                                     \
-        hipLaunchKernelGGL(k_tie_columns<BS_>, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p,        \
-                           sp->sell_col.p, A->val.p, sp->sell_entries, master_of.p, d_err.p);                                             \
-        hipLaunchKernelGGL(k_tie_rows<BS_>, dim3(gp), dim3(FS_BLOCK), 0, s, n_pairs, d_s.p, d_m.p, sp->n_nodes_owned, sp->slice_ptr.p,    \
-                           sp->sell_col.p, A->val.p, sp->sell_entries, bp, d_err.p);                                                      \
-    }
-    if (A->bs == 1) FS_TIE(1) else if (A->bs == 2) FS_TIE(2) else if (A->bs == 3) FS_TIE(3) else FS_TIE(4)
-#undef FS_TIE
+    fs_dispatch_int<1, 2, 3, 4>(A->bs, [&](auto BS) {
+        hipLaunchKernelGGL(k_tie_columns<decltype(BS)::value>, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p,
+                           sp->sell_col.p, A->val.p, sp->sell_entries, master_of.p, S.err.p);
+        hipLaunchKernelGGL(k_tie_rows<decltype(BS)::value>, dim3(gp), dim3(FS_BLOCK), 0, s, n_pairs, S.idx.p, M.idx.p, sp->n_nodes_owned, sp->slice_ptr.p,
+                           sp->sell_col.p, A->val.p, sp->sell_entries, bp, S.err.p);
+    });
     if (A->bs == 4 && A->taylor_hood) fs_ns_reset_dummy_rows(A, s);     // the folded dummy diagonals of edge masters: 2 -> 1
-    FS_KERNEL_CHECK();
-    int h_err = 0;
-    FS_CHECK(d_err.download(&h_err, 1, s));
-    FS_REQUIRE(h_err == 0, "fs_matrix_tie_nodes: %d folded entries have no place in the sparsity pattern (create the space with fs_space_create_coupled and the (master, neighbour-of-slave) pairs)", h_err);
-    return FS_OK;
+    return S.check(s, "fs_matrix_tie_nodes: %d folded entries have no place in the sparsity pattern (create the space with fs_space_create_coupled and the (master, neighbour-of-slave) pairs)");
 }
 
 // ---- CSR export ---------------------------------------------------------------------------------------
@@ -2606,14 +2649,10 @@ extern "C" int fs_matrix_get_csr(fs_matrix_t A, int32_t* rowptr, int32_t* colidx
     if (rowptr) FS_CHECK(d_rp.alloc(n_rows * bs + 1));
     if (colidx) FS_CHECK(d_ci.alloc(nnz));
     if (vals) FS_CHECK(d_v.alloc(nnz));
-    if (bs == 1)
-        hipLaunchKernelGGL(k_export_csr<1>, dim3(fs_grid_for(n_rows)), dim3(FS_BLOCK), 0, s, n_rows, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, d_rp.p, d_ci.p, d_v.p);
-    else if (bs == 2)
-        hipLaunchKernelGGL(k_export_csr<2>, dim3(fs_grid_for(n_rows)), dim3(FS_BLOCK), 0, s, n_rows, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, d_rp.p, d_ci.p, d_v.p);
-    else if (bs == 3)
-        hipLaunchKernelGGL(k_export_csr<3>, dim3(fs_grid_for(n_rows)), dim3(FS_BLOCK), 0, s, n_rows, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, d_rp.p, d_ci.p, d_v.p);
-    else
-        hipLaunchKernelGGL(k_export_csr<4>, dim3(fs_grid_for(n_rows)), dim3(FS_BLOCK), 0, s, n_rows, sp->slice_ptr.p, sp->rowptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, d_rp.p, d_ci.p, d_v.p);
+    fs_dispatch_int<1, 2, 3, 4>(bs, [&](auto BS) {
+        hipLaunchKernelGGL(k_export_csr<decltype(BS)::value>, dim3(fs_grid_for(n_rows)), dim3(FS_BLOCK), 0, s, n_rows, sp->slice_ptr.p, sp->rowptr.p,
+                           sp->sell_col.p, A->val.p, sp->sell_entries, d_rp.p, d_ci.p, d_v.p);
+    });
     FS_KERNEL_CHECK();
     if (rowptr) FS_CHECK(d_rp.download(rowptr, n_rows * bs + 1, s));
     if (colidx) FS_CHECK(d_ci.download(colidx, nnz, s));
@@ -2621,14 +2660,197 @@ extern "C" int fs_matrix_get_csr(fs_matrix_t A, int32_t* rowptr, int32_t* colidx
     return FS_OK;
 }
 
-extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, int add) {
-    FS_REFUSE_DG(A, "fs_assemble_matrix");
-    FS_REQUIRE(A && form, "fs_assemble_matrix: null pointer");
+// ---- fs_assemble_matrix: one function per family, selected by (dimension, degree, block size) ---------------------------
+static int assemble_matrix_scalar_tri(fs_matrix_s* A, const fs_bilinear_form* form, const coef_dev& mc, bool add) {
     fs_space_s* sp = A->space;
     fs_mesh_s* m = sp->mesh;
     hipStream_t s = fs_rt().stream;
-    dbuf<double> kstore, mstore;
-    coef_dev kc, mc;
+    dbuf<double> kstore, astore;
+    coef_dev kc, ac;
+    row_gather_shape sh;
+    if (sp->degree == 2) {
+        FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: CG2 space on triangles without assembly tables");
+        FS_CHECK(make_coef(form->advection, 3 * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
+        FS_REQUIRE(ac.mode == FS_COEF_NONE || ac.mode == FS_COEF_CONST || ac.mode == FS_COEF_CELL,
+                   "fs_assemble_matrix: CG2 advection (and its SUPG test function) takes a constant or per-cell velocity");
+        FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
+        FS_REQUIRE(kc.mode == FS_COEF_NONE || kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL || kc.mode == FS_COEF_CELL_QP,
+                   "fs_assemble_matrix: CG2 stiffness coefficient must be constant, per cell or per quadrature point");
+        FS_CHECK(make_row_gather_shape(sp, &sh));
+        fs_dispatch_bool(add, [&](auto ADD) {
+            hipLaunchKernelGGL(k_assemble_p2tri_scalar_gather<decltype(ADD)::value>, dim3(sh.grid), dim3(sh.bd), sh.lds, s, sp->n_nodes_owned, sp->n_slices,
+                               sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p,
+                               ac, form->advection_scale, form->supg_pe);
+        });
+        return FS_OK;
+    }
+    FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: triangular meshes carry scalar CG1 spaces");
+    FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
+    FS_REQUIRE(kc.mode != FS_COEF_NODAL, "fs_assemble_matrix: nodal stiffness coefficient is not supported");
+    FS_CHECK(make_coef(form->advection, (form->advection.mode == FS_COEF_CELL_ROW ? 9 : 3) * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
+    FS_REQUIRE(ac.mode == FS_COEF_NONE || ac.mode == FS_COEF_CONST || ac.mode == FS_COEF_CELL || ac.mode == FS_COEF_CELL_ROW,
+               "fs_assemble_matrix: advection velocity must be constant, per cell or per (cell, test function)");
+    FS_REQUIRE(!(ac.mode == FS_COEF_CELL_ROW && form->supg_pe > 0.0), "fs_assemble_matrix: SUPG takes a constant or per-cell velocity");
+    FS_CHECK(make_row_gather_shape(sp, &sh));
+    fs_dispatch_bool(add, [&](auto ADD) {
+        hipLaunchKernelGGL(k_assemble_tri_scalar_gather<decltype(ADD)::value>, dim3(sh.grid), dim3(sh.bd), sh.lds, s, sp->n_nodes_owned, sp->n_slices,
+                           sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, ac, form->advection_scale,
+                           A->val.p, form->supg_pe);
+    });
+    return FS_OK;
+}
+
+static int assemble_matrix_p2_scalar(fs_matrix_s* A, const fs_bilinear_form* form, const coef_dev& mc, bool add) {
+    fs_space_s* sp = A->space;
+    fs_mesh_s* m = sp->mesh;
+    hipStream_t s = fs_rt().stream;
+    FS_REQUIRE(sp->inc_cell.p, "fs_assemble_matrix: CG2 space has no assembly tables");
+    dbuf<double> kstore, astore;
+    coef_dev kc, ac;
+    FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
+    FS_REQUIRE(kc.mode == FS_COEF_NONE || kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL || kc.mode == FS_COEF_CELL_QP,
+               "fs_assemble_matrix: CG2 stiffness coefficient must be constant, per cell or per quadrature point");
+    FS_CHECK(make_coef(form->advection, 3 * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
+    FS_REQUIRE(ac.mode == FS_COEF_NONE || ac.mode == FS_COEF_CONST || ac.mode == FS_COEF_CELL,
+               "fs_assemble_matrix: CG2 advection (and its SUPG test function) takes a constant or per-cell velocity");
+    row_gather_shape sh;
+    FS_CHECK(make_row_gather_shape(sp, &sh));
+    const box_snap bxs = make_box_snap(m);
+    if (box_assembly_on() && bxs.h[0] > 0.0 && m->nc >= 6 && ac.mode == FS_COEF_NONE &&
+        (kc.mode == FS_COEF_NONE || kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL) &&
+        (mc.mode == FS_COEF_NONE || mc.mode == FS_COEF_CONST || mc.mode == FS_COEF_CELL) && sh.lds + 660 * sizeof(double) <= 64 * 1024) {
+        // a mesh made by fs_mesh_create_box: the geometry-free form (k_assemble_p2_box_gather)
+        if (!m->box_ref2.p) {
+            FS_CHECK(m->box_ref2.alloc(660));
+            hipLaunchKernelGGL(k_box_ref_rows_p2, dim3(1), dim3(64), 0, s, m->cells.p, m->xyz.p, bxs, m->box_ref2.p);
+        }
+        const int accd = sp->max_row * sh.bd;
+        fs_dispatch_bool(add, [&](auto ADD) {
+            hipLaunchKernelGGL(k_assemble_p2_box_gather<decltype(ADD)::value>, dim3(sh.grid), dim3(sh.bd), sh.lds + 660 * sizeof(double), s, sp->n_nodes_owned,
+                               sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->box_ref2.p, kc, mc,
+                               A->val.p, sp->slice_order.p, accd);
+        });
+        return FS_OK;
+    }
+    // the advection instantiation takes the velocity, its scale and the SUPG Peclet number; the symmetric one its defaults
+    auto gather = [&](auto kernel, const coef_dev& vel, double scale, double pe) {
+        hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(sh.bd), sh.lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p,
+                           sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, sp->slice_order.p, bxs, vel, scale, pe,
+                           (const int32_t*)nullptr, (const double*)nullptr);
+    };
+    const bool adv = ac.mode != FS_COEF_NONE || kc.mode == FS_COEF_CELL_QP;
+    fs_dispatch_bool(add, [&](auto ADD) {
+        if (adv) gather(k_assemble_p2_scalar_gather<decltype(ADD)::value, true>, ac, form->advection_scale, form->supg_pe);
+        else gather(k_assemble_p2_scalar_gather<decltype(ADD)::value>, coef_dev(), 0.0, 0.0);
+    });
+    return FS_OK;
+}
+
+// row-gather path: every SELL entry (padding included) is written exactly once, no memset
+static int assemble_matrix_p1_scalar_gather(fs_matrix_s* A, const fs_bilinear_form* form, const coef_dev& mc, bool add) {
+    fs_space_s* sp = A->space;
+    fs_mesh_s* m = sp->mesh;
+    hipStream_t s = fs_rt().stream;
+    dbuf<double> kstore, astore;
+    coef_dev kc, ac;
+    FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
+    FS_REQUIRE(kc.mode != FS_COEF_NODAL, "fs_assemble_matrix: nodal stiffness coefficient is not supported");
+    FS_CHECK(make_coef(form->advection, (form->advection.mode == FS_COEF_CELL_ROW ? 12 : 3) * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
+    FS_REQUIRE(ac.mode == FS_COEF_NONE || ac.mode == FS_COEF_CONST || ac.mode == FS_COEF_CELL || ac.mode == FS_COEF_CELL_ROW,
+               "fs_assemble_matrix: advection velocity must be constant, per cell or per (cell, test function)");
+    FS_REQUIRE(!(ac.mode == FS_COEF_CELL_ROW && form->supg_pe > 0.0), "fs_assemble_matrix: SUPG takes a constant or per-cell velocity");
+    row_gather_shape sh;
+    FS_CHECK(make_row_gather_shape(sp, &sh));
+    // a mesh made by fs_mesh_create_box, snapped geometry, scalar coefficients, no advection: the geometry-free form
+    const box_snap bxs = make_box_snap(m);
+    if (box_assembly_on() && bxs.h[0] > 0.0 && m->nc >= 6 && ac.mode == FS_COEF_NONE && sh.bd == FS_BLOCK &&
+        (kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL) &&
+        (mc.mode == FS_COEF_NONE || mc.mode == FS_COEF_CONST || mc.mode == FS_COEF_CELL) && sh.lds + 120 * sizeof(double) <= 64 * 1024) {
+        if (!m->box_ref.p) {
+            FS_CHECK(m->box_ref.alloc(120));
+            hipLaunchKernelGGL(k_box_ref_rows, dim3(1), dim3(64), 0, s, m->cells.p, m->xyz.p, bxs, m->box_ref.p);
+        }
+        const int accd = sp->max_row * sh.bd;
+        fs_dispatch_bool(add, [&](auto ADD) {
+            hipLaunchKernelGGL(k_assemble_p1_box_gather<decltype(ADD)::value>, dim3(sh.grid), dim3(sh.bd), sh.lds + 120 * sizeof(double), s, sp->n_nodes_owned,
+                               sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->box_ref.p, kc, mc, A->val.p,
+                               sp->slice_order.p, accd);
+        });
+        return FS_OK;
+    }
+    fs_dispatch_bool(add, [&](auto ADD) {      // MODE 1: A +=, MODE 0: A =
+        hipLaunchKernelGGL(k_assemble_p1_scalar_gather<(decltype(ADD)::value ? 1 : 0)>, dim3(sh.grid), dim3(sh.bd), sh.lds, s, sp->n_nodes_owned, sp->n_slices,
+                           sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, ac, form->advection_scale,
+                           form->supg_pe, A->val.p, sp->slice_order.p, bxs);
+    });
+    return FS_OK;
+}
+
+static int assemble_matrix_scalar(fs_matrix_s* A, const fs_bilinear_form* form, const coef_dev& mc, bool add) {
+    fs_space_s* sp = A->space;
+    if (sp->degree == 2) return assemble_matrix_p2_scalar(A, form, mc, add);
+    if (sp->inc_cell.p) return assemble_matrix_p1_scalar_gather(A, form, mc, add);
+    // spaces without row-gather tables: thread per cell, fp64 atomics
+    fs_mesh_s* m = sp->mesh;
+    hipStream_t s = fs_rt().stream;
+    FS_REQUIRE(sp->slots.p, "fs_assemble_matrix: space has no assembly tables");
+    FS_REQUIRE(form->advection.mode == FS_COEF_NONE, "fs_assemble_matrix: advection needs the row-gather tables");
+    if (!add) FS_CHECK(A->val.zero(s));
+    dbuf<double> kstore;
+    coef_dev kc;
+    FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
+    FS_REQUIRE(kc.mode != FS_COEF_NODAL && kc.mode != FS_COEF_CELL_TENSOR, "fs_assemble_matrix: nodal / per-cell tensor stiffness coefficients need the row-gather tables");
+    hipLaunchKernelGGL(k_assemble_p1_scalar, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc, kc, mc, A->val.p);
+    return FS_OK;
+}
+
+// 3-vector CG1 / CG2 on tetrahedra, 2-vector CG1 / CG2 on triangles (plane strain): the Lame parameters and a mass coefficient
+static int assemble_matrix_elasticity(fs_matrix_s* A, const fs_bilinear_form* form, const coef_dev& mc, const coef_dev& lc, bool add) {
+    fs_space_s* sp = A->space;
+    fs_mesh_s* m = sp->mesh;
+    hipStream_t s = fs_rt().stream;
+    const bool lame_cells = lc.mode == FS_COEF_CELL_LAME;
+    const double2* lcp = reinterpret_cast<const double2*>(lc.data);
+    const bool tri = m->tdim == 2;
+    if (tri) {
+        FS_REQUIRE(sp->slots.p, "fs_assemble_matrix: 2-vector space without slot table");
+        FS_REQUIRE(form->stiffness.mode == FS_COEF_NONE && form->advection.mode == FS_COEF_NONE && !(form->supg_pe > 0.0),
+                   "fs_assemble_matrix: a 2-vector space takes the Lame parameters (plane-strain elasticity) and a mass coefficient");
+    } else if (getenv("FS_ELASTICITY_ATOMIC") && sp->degree == 1 && A->bs == 3) {
+        FS_REQUIRE(!lame_cells, "fs_assemble_matrix: the atomic elasticity kernel (FS_ELASTICITY_ATOMIC) takes constant Lame parameters only");
+        if (!add) FS_CHECK(A->val.zero(s));
+        hipLaunchKernelGGL(k_assemble_p1_elasticity, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc,
+                           form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
+        return FS_OK;
+    } else {
+        FS_REQUIRE(A->bs == 3 && (sp->degree == 1 || sp->degree == 2),
+                   "fs_assemble_matrix: no operator for block size %d on CG%d nodes (Taylor-Hood systems: fs_assemble_navier_stokes)", A->bs, sp->degree);
+    }
+    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    // one thread per stored block; the four kernels share their arguments up to the per-cell (mu, lambda) pairs (CG1 on
+    // tetrahedra: the box snap before them)
+    auto gather = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p,
+                           m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, tail...);
+    };
+    fs_dispatch_bool(add, [&](auto ADD) {
+        fs_dispatch_bool(lame_cells, [&](auto CELL) {
+            constexpr bool a = decltype(ADD)::value, c = decltype(CELL)::value;
+            if (tri && sp->degree == 2) gather(k_assemble_p2tri_elasticity_gather<a, c>, lcp);
+            else if (tri) gather(k_assemble_tri_elasticity_gather<a, c>, lcp);
+            else if (sp->degree == 2) gather(k_assemble_p2_elasticity_gather<a, c>, lcp);
+            else gather(k_assemble_p1_elasticity_gather<a, c>, make_box_snap(m), lcp);
+        });
+    });
+    return FS_OK;
+}
+
+extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, int add) {
+    FS_REFUSE_DG(A, "fs_assemble_matrix");
+    FS_REQUIRE(A && form, "fs_assemble_matrix: null pointer");
+    fs_mesh_s* m = A->space->mesh;
+    dbuf<double> mstore;
+    coef_dev mc;
     FS_CHECK(make_coef(form->mass, m->nc, mstore, &mc, "fs_assemble_matrix(mass)"));
     FS_REQUIRE(mc.mode == FS_COEF_NONE || mc.mode == FS_COEF_CONST || mc.mode == FS_COEF_CELL,
                "fs_assemble_matrix: mass coefficient must be constant or per cell");
@@ -2640,180 +2862,12 @@ extern "C" int fs_assemble_matrix(fs_matrix_t A, const fs_bilinear_form* form, i
     FS_REQUIRE(form->lame.mode == FS_COEF_NONE || A->bs == 2 || A->bs == 3,
                "fs_assemble_matrix: per-cell Lame parameters need a 2- or 3-vector space");
     FS_CHECK(make_coef(form->lame, m->nc, lstore, &lc, "fs_assemble_matrix(lame)"));
-    const bool lame_cells = lc.mode == FS_COEF_CELL_LAME;
-    const double2* lcp = reinterpret_cast<const double2*>(lc.data);
-    const int grid = fs_grid_for(m->nc, FS_BLOCK, 8192);
-    if (m->tdim == 2 && A->bs == 2) {
-        FS_REQUIRE(sp->slots.p, "fs_assemble_matrix: 2-vector space without slot table");
-        FS_REQUIRE(form->stiffness.mode == FS_COEF_NONE && form->advection.mode == FS_COEF_NONE && !(form->supg_pe > 0.0),
-                   "fs_assemble_matrix: a 2-vector space takes the Lame parameters (plane-strain elasticity) and a mass coefficient");
-        if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
-        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-#define FS_ELAST_GATHER(K, ADD_, CELL_) hipLaunchKernelGGL((K<ADD_, CELL_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, \
-                                                        m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, lcp)
-        if (sp->degree == 2) {
-            if (lame_cells) { if (add) FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, true, true); else FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, false, true); }
-            else if (add) FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, true, false);
-            else FS_ELAST_GATHER(k_assemble_p2tri_elasticity_gather, false, false);
-        } else if (lame_cells) {
-            if (add) FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, true, true); else FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, false, true);
-        } else if (add)
-            FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, true, false);
-        else
-            FS_ELAST_GATHER(k_assemble_tri_elasticity_gather, false, false);
-    } else if (m->tdim == 2 && sp->degree == 2) {
-        FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: CG2 space on triangles without assembly tables");
-        dbuf<double> astore4;
-        coef_dev ac4;
-        FS_CHECK(make_coef(form->advection, 3 * m->nc, astore4, &ac4, "fs_assemble_matrix(advection)"));
-        FS_REQUIRE(ac4.mode == FS_COEF_NONE || ac4.mode == FS_COEF_CONST || ac4.mode == FS_COEF_CELL,
-                   "fs_assemble_matrix: CG2 advection (and its SUPG test function) takes a constant or per-cell velocity");
-        FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
-        FS_REQUIRE(kc.mode == FS_COEF_NONE || kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL || kc.mode == FS_COEF_CELL_QP,
-                   "fs_assemble_matrix: CG2 stiffness coefficient must be constant, per cell or per quadrature point");
-        const int bd = (int64_t)sp->max_row * FS_BLOCK * 8 <= 64 * 1024 ? FS_BLOCK : 64;
-        const size_t lds = (size_t)sp->max_row * bd * sizeof(double);
-        FS_REQUIRE(lds <= 64 * 1024, "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator", sp->max_row);
-        const int wpb = bd / 64;
-        const int g = (fs_grid_for((sp->n_slices + wpb - 1) / wpb, 1, 8192) + 7) & ~7;
-        if (add)
-            hipLaunchKernelGGL(k_assemble_p2tri_scalar_gather<true>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, ac4, form->advection_scale, form->supg_pe);
-        else
-            hipLaunchKernelGGL(k_assemble_p2tri_scalar_gather<false>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, ac4, form->advection_scale, form->supg_pe);
-    } else if (m->tdim == 2) {
-        FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: triangular meshes carry scalar CG1 spaces");
-        FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
-        FS_REQUIRE(kc.mode != FS_COEF_NODAL, "fs_assemble_matrix: nodal stiffness coefficient is not supported");
-        dbuf<double> astore2;
-        coef_dev ac2;
-        FS_CHECK(make_coef(form->advection, (form->advection.mode == FS_COEF_CELL_ROW ? 9 : 3) * m->nc, astore2, &ac2, "fs_assemble_matrix(advection)"));
-        FS_REQUIRE(ac2.mode == FS_COEF_NONE || ac2.mode == FS_COEF_CONST || ac2.mode == FS_COEF_CELL || ac2.mode == FS_COEF_CELL_ROW,
-                   "fs_assemble_matrix: advection velocity must be constant, per cell or per (cell, test function)");
-        FS_REQUIRE(!(ac2.mode == FS_COEF_CELL_ROW && form->supg_pe > 0.0), "fs_assemble_matrix: SUPG takes a constant or per-cell velocity");
-        const int bd = (int64_t)sp->max_row * FS_BLOCK * 8 <= 64 * 1024 ? FS_BLOCK : 64;
-        const size_t lds = (size_t)sp->max_row * bd * sizeof(double);
-        FS_REQUIRE(lds <= 64 * 1024, "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator", sp->max_row);
-        const int wpb = bd / 64;
-        const int g = (fs_grid_for((sp->n_slices + wpb - 1) / wpb, 1, 8192) + 7) & ~7;
-        if (add)
-            hipLaunchKernelGGL(k_assemble_tri_scalar_gather<true>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, ac2, form->advection_scale, A->val.p, form->supg_pe);
-        else
-            hipLaunchKernelGGL(k_assemble_tri_scalar_gather<false>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, ac2, form->advection_scale, A->val.p, form->supg_pe);
-    } else if (A->bs == 1 && sp->degree == 2) {
-        FS_REQUIRE(sp->inc_cell.p, "fs_assemble_matrix: CG2 space has no assembly tables");
-        FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
-        FS_REQUIRE(kc.mode == FS_COEF_NONE || kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL || kc.mode == FS_COEF_CELL_QP,
-                   "fs_assemble_matrix: CG2 stiffness coefficient must be constant, per cell or per quadrature point");
-        dbuf<double> astore3;
-        coef_dev ac3;
-        FS_CHECK(make_coef(form->advection, 3 * m->nc, astore3, &ac3, "fs_assemble_matrix(advection)"));
-        FS_REQUIRE(ac3.mode == FS_COEF_NONE || ac3.mode == FS_COEF_CONST || ac3.mode == FS_COEF_CELL,
-                   "fs_assemble_matrix: CG2 advection (and its SUPG test function) takes a constant or per-cell velocity");
-        const int bd = (int64_t)sp->max_row * FS_BLOCK * 8 <= 64 * 1024 ? FS_BLOCK : 64;
-        const size_t lds = (size_t)sp->max_row * bd * sizeof(double);
-        FS_REQUIRE(lds <= 64 * 1024, "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator", sp->max_row);
-        const int wpb = bd / 64;
-        const int g = (fs_grid_for((sp->n_slices + wpb - 1) / wpb, 1, 8192) + 7) & ~7;
-        static const bool box_env_off2 = getenv("FS_BOX_ASSEMBLY") && getenv("FS_BOX_ASSEMBLY")[0] == '0';
-        const bool box_fast_off2 = g_box_assembly < 0 ? box_env_off2 : g_box_assembly == 0;
-        const box_snap bxs2 = make_box_snap(m);
-        if (!box_fast_off2 && bxs2.h[0] > 0.0 && m->nc >= 6 && ac3.mode == FS_COEF_NONE &&
-            (kc.mode == FS_COEF_NONE || kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL) &&
-            (mc.mode == FS_COEF_NONE || mc.mode == FS_COEF_CONST || mc.mode == FS_COEF_CELL) && lds + 660 * sizeof(double) <= 64 * 1024) {
-            // a mesh made by fs_mesh_create_box: the geometry-free form (k_assemble_p2_box_gather)
-            if (!m->box_ref2.p) {
-                FS_CHECK(m->box_ref2.alloc(660));
-                hipLaunchKernelGGL(k_box_ref_rows_p2, dim3(1), dim3(64), 0, s, m->cells.p, m->xyz.p, bxs2, m->box_ref2.p);
-            }
-            const int accd = sp->max_row * bd;
-            if (add)
-                hipLaunchKernelGGL(k_assemble_p2_box_gather<true>, dim3(g), dim3(bd), lds + 660 * sizeof(double), s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p,
-                                   sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->box_ref2.p, kc, mc, A->val.p, sp->slice_order.p, accd);
-            else
-                hipLaunchKernelGGL(k_assemble_p2_box_gather<false>, dim3(g), dim3(bd), lds + 660 * sizeof(double), s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p,
-                                   sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->box_ref2.p, kc, mc, A->val.p, sp->slice_order.p, accd);
-        } else if (ac3.mode != FS_COEF_NONE || kc.mode == FS_COEF_CELL_QP) {
-            if (add)
-                hipLaunchKernelGGL((k_assemble_p2_scalar_gather<true, true>), dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, sp->slice_order.p, make_box_snap(m), ac3, form->advection_scale, form->supg_pe);
-            else
-                hipLaunchKernelGGL((k_assemble_p2_scalar_gather<false, true>), dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, sp->slice_order.p, make_box_snap(m), ac3, form->advection_scale, form->supg_pe);
-        } else if (add)
-            hipLaunchKernelGGL(k_assemble_p2_scalar_gather<true>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, sp->slice_order.p, make_box_snap(m));
-        else
-            hipLaunchKernelGGL(k_assemble_p2_scalar_gather<false>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_entries, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, A->val.p, sp->slice_order.p, make_box_snap(m));
-    } else if (A->bs == 1 && sp->inc_cell.p) {
-        // row-gather path: every SELL entry (padding included) is written exactly once, no memset
-        FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
-        FS_REQUIRE(kc.mode != FS_COEF_NODAL, "fs_assemble_matrix: nodal stiffness coefficient is not supported");
-        dbuf<double> astore;
-        coef_dev ac;
-        FS_CHECK(make_coef(form->advection, (form->advection.mode == FS_COEF_CELL_ROW ? 12 : 3) * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
-        FS_REQUIRE(ac.mode == FS_COEF_NONE || ac.mode == FS_COEF_CONST || ac.mode == FS_COEF_CELL || ac.mode == FS_COEF_CELL_ROW,
-                   "fs_assemble_matrix: advection velocity must be constant, per cell or per (cell, test function)");
-        FS_REQUIRE(!(ac.mode == FS_COEF_CELL_ROW && form->supg_pe > 0.0), "fs_assemble_matrix: SUPG takes a constant or per-cell velocity");
-        // LDS: one accumulator column per thread; fall to one wave per workgroup for very long rows
-        const int bd = (int64_t)sp->max_row * FS_BLOCK * 8 <= 64 * 1024 ? FS_BLOCK : 64;
-        const size_t lds = (size_t)sp->max_row * bd * sizeof(double);
-        FS_REQUIRE(lds <= 64 * 1024, "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator", sp->max_row);
-        const int wpb = bd / 64;
-        const int g = (fs_grid_for((sp->n_slices + wpb - 1) / wpb, 1, 8192) + 7) & ~7;  // multiple of 8: XCD map
-        // a mesh made by fs_mesh_create_box, snapped geometry, scalar coefficients, no advection: the geometry-free form
-        static const bool box_env_off = getenv("FS_BOX_ASSEMBLY") && getenv("FS_BOX_ASSEMBLY")[0] == '0';
-        const bool box_fast_off = g_box_assembly < 0 ? box_env_off : g_box_assembly == 0;
-        const box_snap bxs = make_box_snap(m);
-        if (!box_fast_off && bxs.h[0] > 0.0 && m->nc >= 6 && ac.mode == FS_COEF_NONE && bd == FS_BLOCK &&
-            (kc.mode == FS_COEF_CONST || kc.mode == FS_COEF_CELL) &&
-            (mc.mode == FS_COEF_NONE || mc.mode == FS_COEF_CONST || mc.mode == FS_COEF_CELL) && lds + 120 * sizeof(double) <= 64 * 1024) {
-            if (!m->box_ref.p) {
-                FS_CHECK(m->box_ref.alloc(120));
-                hipLaunchKernelGGL(k_box_ref_rows, dim3(1), dim3(64), 0, s, m->cells.p, m->xyz.p, bxs, m->box_ref.p);
-            }
-            const int accd = sp->max_row * bd;
-            if (add)
-                hipLaunchKernelGGL(k_assemble_p1_box_gather<true>, dim3(g), dim3(bd), lds + 120 * sizeof(double), s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p,
-                                   sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->box_ref.p, kc, mc, A->val.p, sp->slice_order.p, accd);
-            else
-                hipLaunchKernelGGL(k_assemble_p1_box_gather<false>, dim3(g), dim3(bd), lds + 120 * sizeof(double), s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p,
-                                   sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->box_ref.p, kc, mc, A->val.p, sp->slice_order.p, accd);
-        } else if (add)
-            hipLaunchKernelGGL(k_assemble_p1_scalar_gather<1>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, ac, form->advection_scale, form->supg_pe, A->val.p, sp->slice_order.p, make_box_snap(m));
-        else
-            hipLaunchKernelGGL(k_assemble_p1_scalar_gather<0>, dim3(g), dim3(bd), lds, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->inc_slice_ptr.p, sp->inc_cell.p, sp->inc_pos.p, m->cells.p, m->xyz.p, kc, mc, ac, form->advection_scale, form->supg_pe, A->val.p, sp->slice_order.p, make_box_snap(m));
-    } else if (A->bs == 1) {
-        FS_REQUIRE(sp->slots.p, "fs_assemble_matrix: space has no assembly tables");
-        FS_REQUIRE(form->advection.mode == FS_COEF_NONE, "fs_assemble_matrix: advection needs the row-gather tables");
-        if (!add) FS_CHECK(A->val.zero(s));
-        FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
-        FS_REQUIRE(kc.mode != FS_COEF_NODAL && kc.mode != FS_COEF_CELL_TENSOR, "fs_assemble_matrix: nodal / per-cell tensor stiffness coefficients need the row-gather tables");
-        hipLaunchKernelGGL(k_assemble_p1_scalar, dim3(grid), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc, kc, mc, A->val.p);
-    } else if (getenv("FS_ELASTICITY_ATOMIC") && sp->degree == 1 && A->bs == 3) {
-        FS_REQUIRE(!lame_cells, "fs_assemble_matrix: the atomic elasticity kernel (FS_ELASTICITY_ATOMIC) takes constant Lame parameters only");
-        if (!add) FS_CHECK(A->val.zero(s));
-        hipLaunchKernelGGL(k_assemble_p1_elasticity, dim3(grid), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p);
-    } else if (A->bs == 3 && sp->degree == 2) {
-        if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
-        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-        if (lame_cells) {
-            if (add) FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, true, true); else FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, false, true);
-        } else if (add)
-            FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, true, false);
-        else
-            FS_ELAST_GATHER(k_assemble_p2_elasticity_gather, false, false);
-    } else {
-        FS_REQUIRE(A->bs == 3 && sp->degree == 1, "fs_assemble_matrix: no operator for block size %d on CG%d nodes (Taylor-Hood systems: fs_assemble_navier_stokes)", A->bs, sp->degree);
-        if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
-        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-#define FS_P1_ELAST(ADD_, CELL_) hipLaunchKernelGGL((k_assemble_p1_elasticity_gather<ADD_, CELL_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
-                                                    sp->gmap_src.p, m->cells.p, m->xyz.p, form->lame_mu, form->lame_lambda, mc, sp->sell_entries, A->val.p, make_box_snap(m), lcp)
-        if (lame_cells) {
-            if (add) FS_P1_ELAST(true, true); else FS_P1_ELAST(false, true);
-        } else if (add)
-            FS_P1_ELAST(true, false);
-        else
-            FS_P1_ELAST(false, false);
-#undef FS_P1_ELAST
-    }
-#undef FS_ELAST_GATHER
+    if (m->tdim == 2 && A->bs != 2)       // (triangles carry scalar and 2-vector spaces: any other block size is refused there)
+        FS_CHECK(assemble_matrix_scalar_tri(A, form, mc, add != 0));
+    else if (m->tdim != 2 && A->bs == 1)
+        FS_CHECK(assemble_matrix_scalar(A, form, mc, add != 0));
+    else
+        FS_CHECK(assemble_matrix_elasticity(A, form, mc, lc, add != 0));
     FS_KERNEL_CHECK();
     // (no wait here: host arrays were consumed by make_coef's uploads, the coefficient stores go back to the pool in stream order,
     // and whatever the caller enqueues next - the load vector, the Dirichlet rows - is prepared while the assembly runs)
@@ -3408,6 +3462,109 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_vector_source_gather(i
     }
 }
 
+// ---- fs_assemble_vector: the branches choose and launch, the caller checks and waits ------------------------------------
+static int assemble_vector_scalar_tri(fs_space_s* space, const fs_linear_form* form, const coef_dev& f, fs_vector_s* b) {
+    fs_mesh_s* m = space->mesh;
+    hipStream_t s = fs_rt().stream;
+    if (space->degree == 2)
+        FS_REQUIRE(f.mode != FS_COEF_TENSOR && space->inc_cell.p, "fs_assemble_vector: unsupported option on a CG2 space on triangles");
+    else
+        FS_REQUIRE(f.mode != FS_COEF_TENSOR, "fs_assemble_vector: unsupported option on a triangular mesh");
+    dbuf<double> sstore;
+    coef_dev sv;
+    FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore, &sv, "fs_assemble_vector(supg_velocity)"));
+    FS_REQUIRE(!(form->supg_pe > 0.0) || sv.mode == FS_COEF_NONE || sv.mode == FS_COEF_CONST || sv.mode == FS_COEF_CELL,
+               "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
+    if (space->degree == 2)
+        hipLaunchKernelGGL(k_assemble_p2tri_source_gather, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                           space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, space->cell_dofs, m->cells.p,
+                           m->xyz.p, f, b->d.p, sv, form->supg_pe);
+    else
+        hipLaunchKernelGGL(k_assemble_tri_source, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, m->nc,
+                           space->n_nodes_owned, f, b->d.p, sv, form->supg_pe);
+    return FS_OK;
+}
+
+static int assemble_vector_p2_scalar(fs_space_s* space, const fs_linear_form* form, const coef_dev& f, fs_vector_s* b) {
+    fs_mesh_s* m = space->mesh;
+    hipStream_t s = fs_rt().stream;
+    FS_REQUIRE(space->ncomp == 1, "fs_assemble_vector: %d-component CG2 node blocks have no load-vector kernel", space->ncomp);
+    FS_REQUIRE(f.mode != FS_COEF_TENSOR, "fs_assemble_vector: tensor coefficient is meaningless here");
+    dbuf<double> sstore;
+    coef_dev sv;
+    FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore, &sv, "fs_assemble_vector(supg_velocity)"));
+    const bool supg = form->supg_pe > 0.0 && sv.mode != FS_COEF_NONE;
+    FS_REQUIRE(!supg || ((sv.mode == FS_COEF_CONST || sv.mode == FS_COEF_CELL) && space->inc_cell.p),
+               "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
+    if (space->ncomp == 1 && space->inc_cell.p && (supg || !getenv("FS_SOURCE_ATOMIC")))
+        hipLaunchKernelGGL(k_assemble_p2_source_gather, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                           space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, space->cell_dofs, m->cells.p,
+                           m->xyz.p, f, b->d.p, sv, form->supg_pe);
+    else
+        hipLaunchKernelGGL(k_assemble_p2_source, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, space->cell_dofs, m->cells.p, m->xyz.p, m->nc,
+                           space->n_nodes_owned, f, b->d.p);
+    return FS_OK;
+}
+
+// CG1, scalar or 3-vector: the two gather kernels, or the atomic one (FS_SOURCE_ATOMIC, SUPG sources, spaces without tables)
+static int assemble_vector_p1(fs_space_s* space, const fs_linear_form* form, const coef_dev& f, const coef_dev& dv, fs_vector_s* b) {
+    fs_mesh_s* m = space->mesh;
+    hipStream_t s = fs_rt().stream;
+    FS_REQUIRE(f.mode != FS_COEF_TENSOR && dv.mode != FS_COEF_TENSOR, "fs_assemble_vector: tensor coefficient is meaningless here");
+    dbuf<double> sstore;
+    coef_dev sv;
+    FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore, &sv, "fs_assemble_vector(supg_velocity)"));
+    FS_REQUIRE(!(form->supg_pe > 0.0) || sv.mode == FS_COEF_NONE || space->ncomp == 1,
+               "fs_assemble_vector: the SUPG source term is built for scalar spaces");
+    if (space->ncomp == 1 && space->inc_cell.p && !(form->supg_pe > 0.0 && sv.mode != FS_COEF_NONE) && !getenv("FS_SOURCE_ATOMIC")) {
+        // b was zeroed by the caller unless add: the gather kernel adds to what is there either way
+        hipLaunchKernelGGL(k_assemble_p1_source_gather<true>, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                           space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, m->cells.p, m->xyz.p, f, b->d.p);
+    } else if (space->ncomp == 3 && space->slots.p && !getenv("FS_SOURCE_ATOMIC")) {
+        if (!space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(space, s));
+        hipLaunchKernelGGL(k_assemble_p1_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                           space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
+                           m->xyz.p, form->vector_value[0], form->vector_value[1], form->vector_value[2], dv, b->d.p);
+    } else {
+        hipLaunchKernelGGL(k_assemble_p1_source, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, m->nc, m->n_owned, f,
+                           space->ncomp, form->vector_value[0], form->vector_value[1], form->vector_value[2], dv, sv, form->supg_pe, b->d.p);
+    }
+    return FS_OK;
+}
+
+// body force (form->vector_value) and div_coef loads of the CG2 3-vector space and of the 2-vector spaces on triangles
+static int assemble_vector_p2_vector(fs_space_s* space, const fs_linear_form* form, const coef_dev& f, const coef_dev& dv, fs_vector_s* b) {
+    fs_mesh_s* m = space->mesh;
+    hipStream_t s = fs_rt().stream;
+    FS_REQUIRE(f.mode == FS_COEF_NONE, "fs_assemble_vector: vector spaces take their body force in vector_value");
+    FS_REQUIRE(dv.mode != FS_COEF_TENSOR, "fs_assemble_vector: tensor coefficient is meaningless here");
+    FS_REQUIRE(space->slots.p, "fs_assemble_vector: vector CG2 space without slot table");
+    if (!space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(space, s));
+    hipLaunchKernelGGL(k_assemble_p2_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                       space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
+                       m->xyz.p, form->vector_value[0], form->vector_value[1], form->vector_value[2], dv, m->n_owned,
+                       space->n_edges_owned, b->d.p);
+    return FS_OK;
+}
+
+static int assemble_vector_tri_vector(fs_space_s* space, const fs_linear_form* form, const coef_dev& f, const coef_dev& dv, fs_vector_s* b) {
+    fs_mesh_s* m = space->mesh;
+    hipStream_t s = fs_rt().stream;
+    FS_REQUIRE(f.mode == FS_COEF_NONE, "fs_assemble_vector: vector spaces take their body force in vector_value");
+    FS_REQUIRE(dv.mode != FS_COEF_TENSOR && !(form->supg_pe > 0.0), "fs_assemble_vector: unsupported option on a 2-vector space");
+    FS_REQUIRE(space->slots.p, "fs_assemble_vector: 2-vector space without slot table");
+    if (!space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(space, s));
+    if (space->degree == 2)
+        hipLaunchKernelGGL(k_assemble_p2tri_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                           space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
+                           m->xyz.p, form->vector_value[0], form->vector_value[1], dv, m->n_owned, space->n_edges_owned, b->d.p);
+    else
+        hipLaunchKernelGGL(k_assemble_tri_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
+                           space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
+                           m->xyz.p, form->vector_value[0], form->vector_value[1], dv, b->d.p);
+    return FS_OK;
+}
+
 extern "C" int fs_assemble_vector(fs_space_t space, const fs_linear_form* form, fs_vector_t b, int add) {
     FS_REFUSE_DG_SPACE(space, "fs_assemble_vector");
     FS_REQUIRE(space && form && b, "fs_assemble_vector: null pointer");
@@ -3424,111 +3581,20 @@ extern "C" int fs_assemble_vector(fs_space_t space, const fs_linear_form* form, 
     const int64_t dlen = form->div_coef.mode == FS_COEF_NODAL ? space->n_nodes_local : m->nc;
     FS_CHECK(make_coef(form->div_coef, dlen, dstore, &dv, "fs_assemble_vector(div_coef)"));
     FS_REQUIRE(dv.mode == FS_COEF_NONE || space->ncomp == 3 || space->ncomp == 2, "fs_assemble_vector: div_coef needs a vector space");
-    if (space->ncomp == 1 && f.mode == FS_COEF_NONE) {
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    if (m->tdim == 2 && space->ncomp == 2) {
-        FS_REQUIRE(f.mode == FS_COEF_NONE, "fs_assemble_vector: vector spaces take their body force in vector_value");
-        FS_REQUIRE(dv.mode != FS_COEF_TENSOR && !(form->supg_pe > 0.0), "fs_assemble_vector: unsupported option on a 2-vector space");
-        FS_REQUIRE(space->slots.p, "fs_assemble_vector: 2-vector space without slot table");
-        if (!space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(space, s));
-        if (space->degree == 2)
-            hipLaunchKernelGGL(k_assemble_p2tri_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                               space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
-                               m->xyz.p, form->vector_value[0], form->vector_value[1], dv, m->n_owned, space->n_edges_owned, b->d.p);
+    if (space->ncomp != 1 || f.mode != FS_COEF_NONE) {      // (a scalar space without a source: nothing to launch)
+        // the branches choose and launch; the scalar ones upload form->supg_velocity, the vector-space ones do not look at it
+        if (m->tdim == 2 && space->ncomp == 2)
+            FS_CHECK(assemble_vector_tri_vector(space, form, f, dv, b));
+        else if (m->tdim == 2)
+            FS_CHECK(assemble_vector_scalar_tri(space, form, f, b));
+        else if (space->degree == 2 && space->ncomp == 3)
+            FS_CHECK(assemble_vector_p2_vector(space, form, f, dv, b));
+        else if (space->degree == 2)
+            FS_CHECK(assemble_vector_p2_scalar(space, form, f, b));
         else
-        hipLaunchKernelGGL(k_assemble_tri_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                           space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
-                           m->xyz.p, form->vector_value[0], form->vector_value[1], dv, b->d.p);
+            FS_CHECK(assemble_vector_p1(space, form, f, dv, b));
         FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
     }
-    if (m->tdim == 2 && space->degree == 2) {
-        FS_REQUIRE(f.mode != FS_COEF_TENSOR && space->inc_cell.p, "fs_assemble_vector: unsupported option on a CG2 space on triangles");
-        dbuf<double> sstore4;
-        coef_dev sv4;
-        FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore4, &sv4, "fs_assemble_vector(supg_velocity)"));
-        FS_REQUIRE(!(form->supg_pe > 0.0) || sv4.mode == FS_COEF_NONE || sv4.mode == FS_COEF_CONST || sv4.mode == FS_COEF_CELL,
-                   "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
-        hipLaunchKernelGGL(k_assemble_p2tri_source_gather, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                           space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, space->cell_dofs, m->cells.p,
-                           m->xyz.p, f, b->d.p, sv4, form->supg_pe);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    if (m->tdim == 2) {
-        FS_REQUIRE(f.mode != FS_COEF_TENSOR, "fs_assemble_vector: unsupported option on a triangular mesh");
-        dbuf<double> sstore2;
-        coef_dev sv2;
-        FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore2, &sv2, "fs_assemble_vector(supg_velocity)"));
-        FS_REQUIRE(!(form->supg_pe > 0.0) || sv2.mode == FS_COEF_NONE || sv2.mode == FS_COEF_CONST || sv2.mode == FS_COEF_CELL,
-                   "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
-        hipLaunchKernelGGL(k_assemble_tri_source, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, m->nc, space->n_nodes_owned, f, b->d.p,
-                           sv2, form->supg_pe);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    if (space->degree == 2 && space->ncomp == 3) {
-        FS_REQUIRE(f.mode == FS_COEF_NONE, "fs_assemble_vector: vector spaces take their body force in vector_value");
-        FS_REQUIRE(dv.mode != FS_COEF_TENSOR, "fs_assemble_vector: tensor coefficient is meaningless here");
-        FS_REQUIRE(space->slots.p, "fs_assemble_vector: vector CG2 space without slot table");
-        if (!space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(space, s));
-        hipLaunchKernelGGL(k_assemble_p2_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                           space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
-                           m->xyz.p, form->vector_value[0], form->vector_value[1], form->vector_value[2], dv, m->n_owned,
-                           space->n_edges_owned, b->d.p);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    if (space->degree == 2) {
-        FS_REQUIRE(space->ncomp == 1, "fs_assemble_vector: %d-component CG2 node blocks have no load-vector kernel", space->ncomp);
-        FS_REQUIRE(f.mode != FS_COEF_TENSOR, "fs_assemble_vector: tensor coefficient is meaningless here");
-        dbuf<double> sstore3;
-        coef_dev sv3;
-        FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore3, &sv3, "fs_assemble_vector(supg_velocity)"));
-        const bool supg3 = form->supg_pe > 0.0 && sv3.mode != FS_COEF_NONE;
-        FS_REQUIRE(!supg3 || ((sv3.mode == FS_COEF_CONST || sv3.mode == FS_COEF_CELL) && space->inc_cell.p),
-                   "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
-        if (space->ncomp == 1 && space->inc_cell.p && (supg3 || !getenv("FS_SOURCE_ATOMIC")))
-            hipLaunchKernelGGL(k_assemble_p2_source_gather, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                               space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, space->cell_dofs, m->cells.p,
-                               m->xyz.p, f, b->d.p, sv3, form->supg_pe);
-        else
-            hipLaunchKernelGGL(k_assemble_p2_source, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, space->cell_dofs, m->cells.p, m->xyz.p, m->nc, space->n_nodes_owned, f, b->d.p);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    FS_REQUIRE(f.mode != FS_COEF_TENSOR && dv.mode != FS_COEF_TENSOR, "fs_assemble_vector: tensor coefficient is meaningless here");
-    dbuf<double> sstore;
-    coef_dev sv;
-    FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore, &sv, "fs_assemble_vector(supg_velocity)"));
-    FS_REQUIRE(!(form->supg_pe > 0.0) || sv.mode == FS_COEF_NONE || space->ncomp == 1,
-               "fs_assemble_vector: the SUPG source term is built for scalar spaces");
-    if (space->ncomp == 1 && space->inc_cell.p && !(form->supg_pe > 0.0 && sv.mode != FS_COEF_NONE) && !getenv("FS_SOURCE_ATOMIC")) {
-        // b was zeroed above unless add: the gather kernel adds to what is there either way
-        hipLaunchKernelGGL(k_assemble_p1_source_gather<true>, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                           space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, m->cells.p, m->xyz.p, f, b->d.p);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    if (space->ncomp == 3 && space->slots.p && !getenv("FS_SOURCE_ATOMIC")) {
-        if (!space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(space, s));
-        hipLaunchKernelGGL(k_assemble_p1_vector_source_gather, dim3(fs_grid_for(space->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
-                           space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, space->gmap_ptr.p, space->gmap_src.p, m->cells.p,
-                           m->xyz.p, form->vector_value[0], form->vector_value[1], form->vector_value[2], dv, b->d.p);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
-    }
-    hipLaunchKernelGGL(k_assemble_p1_source, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, m->nc, m->n_owned, f, space->ncomp, form->vector_value[0], form->vector_value[1], form->vector_value[2], dv, sv, form->supg_pe, b->d.p);
-    FS_KERNEL_CHECK();
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }
@@ -3743,38 +3809,28 @@ extern "C" int fs_assemble_facet_supg(fs_space_t space, fs_matrix_t A, fs_vector
         FS_REQUIRE(facet_cell[i] >= 0 && facet_cell[i] < m->nc && facet_opposite[i] >= 0 && facet_opposite[i] <= m->tdim,
                    "fs_assemble_facet_supg: facet %lld names cell %d / local vertex %d", (long long)i, facet_cell[i], facet_opposite[i]);
     hipStream_t s = fs_rt().stream;
-    dbuf<int32_t> dc, dop;
-    dbuf<double> dg, dh, vstore;
-    dbuf<int> d_err;
+    launch_lists cell_g, opp_h;      // (facet_cell, g) and (facet_opposite, h); the counter is cell_g's
+    dbuf<double> vstore;
     coef_dev vel;
     FS_CHECK(make_coef(*velocity, 3 * m->nc, vstore, &vel, "fs_assemble_facet_supg(velocity)"));
     FS_REQUIRE(vel.mode == FS_COEF_CONST || vel.mode == FS_COEF_CELL, "fs_assemble_facet_supg: velocity must be constant or per cell");
-    FS_CHECK(dc.alloc(n_facets)); FS_CHECK(dop.alloc(n_facets)); FS_CHECK(d_err.alloc(1)); FS_CHECK(d_err.zero(s));
-    FS_CHECK(dc.upload(facet_cell, n_facets, s));
-    FS_CHECK(dop.upload(facet_opposite, n_facets, s));
-    if (g) { FS_CHECK(dg.alloc(n_facets)); FS_CHECK(dg.upload(g, n_facets, s)); }
-    if (h) { FS_CHECK(dh.alloc(n_facets)); FS_CHECK(dh.upload(h, n_facets, s)); }
-    if (space->degree == 2 && m->tdim == 2)
-        hipLaunchKernelGGL(k_facet_supg_p2tri, dim3(fs_grid_for(n_facets * 6)), dim3(FS_BLOCK), 0, s, n_facets, dc.p, dop.p, g ? dg.p : (const double*)nullptr,
-                           h ? dh.p : (const double*)nullptr, vel, supg_pe, m->cells.p, space->cell_dofs, m->xyz.p, space->n_nodes_owned, space->slice_ptr.p,
-                           space->sell_col.p, A ? A->val.p : (double*)nullptr, b ? b->d.p : (double*)nullptr, d_err.p);
-    else if (space->degree == 2)
-        hipLaunchKernelGGL(k_facet_supg_p2, dim3(fs_grid_for(n_facets * 10)), dim3(FS_BLOCK), 0, s, n_facets, dc.p, dop.p, g ? dg.p : (const double*)nullptr,
-                           h ? dh.p : (const double*)nullptr, vel, supg_pe, m->cells.p, space->cell_dofs, m->xyz.p, space->n_nodes_owned, space->slice_ptr.p,
-                           space->sell_col.p, A ? A->val.p : (double*)nullptr, b ? b->d.p : (double*)nullptr, d_err.p);
-    else if (m->tdim == 2)
-        hipLaunchKernelGGL(k_facet_supg_tri, dim3(fs_grid_for(n_facets * 3)), dim3(FS_BLOCK), 0, s, n_facets, dc.p, dop.p, g ? dg.p : (const double*)nullptr,
-                           h ? dh.p : (const double*)nullptr, vel, supg_pe, m->cells.p, m->xyz.p, space->n_nodes_owned, space->slice_ptr.p,
-                           space->sell_col.p, A ? A->val.p : (double*)nullptr, b ? b->d.p : (double*)nullptr, d_err.p);
-    else
-        hipLaunchKernelGGL(k_facet_supg, dim3(fs_grid_for(n_facets * 4)), dim3(FS_BLOCK), 0, s, n_facets, dc.p, dop.p, g ? dg.p : (const double*)nullptr,
-                           h ? dh.p : (const double*)nullptr, vel, supg_pe, m->cells.p, m->xyz.p, space->n_nodes_owned, space->slice_ptr.p,
-                           space->sell_col.p, A ? A->val.p : (double*)nullptr, b ? b->d.p : (double*)nullptr, d_err.p);
-    FS_KERNEL_CHECK();
-    int h_err = 0;
-    FS_CHECK(d_err.download(&h_err, 1, s));
-    FS_REQUIRE(h_err == 0, "fs_assemble_facet_supg: %d facet pairs missing from the sparsity pattern", h_err);
-    return FS_OK;
+    FS_CHECK(cell_g.count_errors(s));
+    FS_CHECK(cell_g.ints(facet_cell, n_facets, s));
+    FS_CHECK(opp_h.ints(facet_opposite, n_facets, s));
+    if (g) FS_CHECK(cell_g.doubles(g, n_facets, s));
+    if (h) FS_CHECK(opp_h.doubles(h, n_facets, s));
+    const double *dg = cell_g.val.p, *dh = opp_h.val.p;      // null without g / h
+    double *Ap = A ? A->val.p : nullptr, *bp = b ? b->d.p : nullptr;
+    // thread per (facet, cell dof); the CG2 kernels take the cell -> dof table after the cells
+    auto supg = [&](auto kernel, int dofs_per_cell, auto... cell_dofs) {
+        hipLaunchKernelGGL(kernel, dim3(fs_grid_for(n_facets * dofs_per_cell)), dim3(FS_BLOCK), 0, s, n_facets, cell_g.idx.p, opp_h.idx.p, dg, dh, vel, supg_pe,
+                           m->cells.p, cell_dofs..., m->xyz.p, space->n_nodes_owned, space->slice_ptr.p, space->sell_col.p, Ap, bp, cell_g.err.p);
+    };
+    if (space->degree == 2 && m->tdim == 2) supg(k_facet_supg_p2tri, 6, space->cell_dofs);
+    else if (space->degree == 2) supg(k_facet_supg_p2, 10, space->cell_dofs);
+    else if (m->tdim == 2) supg(k_facet_supg_tri, 3);
+    else supg(k_facet_supg, 4);
+    return cell_g.check(s, "fs_assemble_facet_supg: %d facet pairs missing from the sparsity pattern");
 }
 
 extern "C" int fs_assemble_facet_vector(fs_space_t space, int64_t n_facets, const int32_t* tri, const double* g,
@@ -3782,59 +3838,34 @@ extern "C" int fs_assemble_facet_vector(fs_space_t space, int64_t n_facets, cons
     FS_REFUSE_DG_SPACE(space, "fs_assemble_facet_vector");
     FS_REQUIRE(space && b && (n_facets == 0 || (tri && g)), "fs_assemble_facet_vector: null pointer");
     if (n_facets == 0) return FS_OK;
-    if (space->mesh->tdim == 2) {      // facets are edges: tri holds [n_facets][2] vertex pairs
-        for (int64_t i = 0; i < 2 * n_facets; ++i)
-            FS_REQUIRE(tri[i] >= 0 && tri[i] < space->n_nodes_local, "fs_assemble_facet_vector: edge vertex %d out of range", tri[i]);
-        hipStream_t s2 = fs_rt().stream;
-        dbuf<int32_t> d_ed;
-        dbuf<double> d_g2;
-        FS_CHECK(d_ed.alloc(2 * n_facets));
-        FS_CHECK(d_g2.alloc(n_facets * space->ncomp));
-        FS_CHECK(d_ed.upload(tri, 2 * n_facets, s2));
-        FS_CHECK(d_g2.upload(g, n_facets * space->ncomp, s2));
-        if (space->degree == 2) {
-            dbuf<int> d_e2;
-            FS_CHECK(d_e2.alloc(1));
-            FS_CHECK(d_e2.zero(s2));
-            if (space->ncomp == 2)
-                hipLaunchKernelGGL(k_edge_vector2_p2, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s2, space->mesh->xyz.p, d_ed.p, n_facets, d_g2.p, space->edge_keys.p, space->n_edges, space->edge_grouped, space->edge_node.p, space->n_nodes_owned, b->d.p, d_e2.p);
-            else
-            hipLaunchKernelGGL(k_edge_vector_p2, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s2, space->mesh->xyz.p, d_ed.p, n_facets, d_g2.p, space->edge_keys.p, space->n_edges, space->edge_grouped, space->edge_node.p, space->n_nodes_owned, b->d.p, d_e2.p);
-            FS_KERNEL_CHECK();
-            int h_e2 = 0;
-            FS_CHECK(d_e2.download(&h_e2, 1, s2));
-            FS_REQUIRE(h_e2 == 0, "fs_assemble_facet_vector: %d boundary edges are not mesh edges", h_e2);
-            return FS_OK;
-        }
-        if (space->ncomp == 2)
-            hipLaunchKernelGGL(k_edge_vector2, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s2, space->mesh->xyz.p, d_ed.p, n_facets, d_g2.p, space->n_nodes_owned, b->d.p);
-        else
-            hipLaunchKernelGGL(k_edge_vector, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s2, space->mesh->xyz.p, d_ed.p, n_facets, d_g2.p, space->n_nodes_owned, b->d.p);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s2));
-        return FS_OK;
-    }
-    for (int64_t i = 0; i < 3 * n_facets; ++i)
-        FS_REQUIRE(tri[i] >= 0 && tri[i] < space->n_nodes_local, "fs_assemble_facet_vector: facet vertex %d out of range", tri[i]);
+    const bool edges = space->mesh->tdim == 2;      // facets are edges: tri holds [n_facets][2] vertex pairs
+    const int nv = edges ? 2 : 3;
+    for (int64_t i = 0; i < nv * n_facets; ++i)
+        FS_REQUIRE(tri[i] >= 0 && tri[i] < space->n_nodes_local,
+                   edges ? "fs_assemble_facet_vector: edge vertex %d out of range" : "fs_assemble_facet_vector: facet vertex %d out of range", tri[i]);
     hipStream_t s = fs_rt().stream;
-    dbuf<int32_t> d_tri;
-    dbuf<double> d_g;
-    FS_CHECK(d_tri.alloc(3 * n_facets));
-    FS_CHECK(d_g.alloc(n_facets * space->ncomp));
-    FS_CHECK(d_tri.upload(tri, 3 * n_facets, s));
-    FS_CHECK(d_g.upload(g, n_facets * space->ncomp, s));
-    if (space->degree == 2) {
-        dbuf<int> d_err;
-        FS_CHECK(d_err.alloc(1));
-        FS_CHECK(d_err.zero(s));
-        hipLaunchKernelGGL(k_facet_vector_p2, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s, space->mesh->xyz.p, d_tri.p, n_facets, d_g.p, space->edge_keys.p, space->n_edges, space->edge_grouped, space->edge_node.p, space->n_nodes_owned, space->ncomp, b->d.p, d_err.p);
-        FS_KERNEL_CHECK();
-        int h_err = 0;
-        FS_CHECK(d_err.download(&h_err, 1, s));
-        FS_REQUIRE(h_err == 0, "fs_assemble_facet_vector: %d facet edges are not mesh edges", h_err);
-        return FS_OK;
+    launch_lists L;
+    FS_CHECK(L.ints(tri, nv * n_facets, s));
+    FS_CHECK(L.doubles(g, n_facets * space->ncomp, s));
+    const double* xyz = space->mesh->xyz.p;
+    const int grid = fs_grid_for(n_facets);
+    if (space->degree == 2) {      // the mid nodes are found through the edge keys: a facet edge that is no mesh edge is counted
+        FS_CHECK(L.count_errors(s));
+        auto load = [&](auto kernel, auto... ncomp) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, space->edge_keys.p, space->n_edges, space->edge_grouped,
+                               space->edge_node.p, space->n_nodes_owned, ncomp..., b->d.p, L.err.p);
+        };
+        if (edges && space->ncomp == 2) load(k_edge_vector2_p2);
+        else if (edges) load(k_edge_vector_p2);
+        else load(k_facet_vector_p2, space->ncomp);
+        return L.check(s, edges ? "fs_assemble_facet_vector: %d boundary edges are not mesh edges" : "fs_assemble_facet_vector: %d facet edges are not mesh edges");
     }
-    hipLaunchKernelGGL(k_facet_vector, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s, space->mesh->xyz.p, d_tri.p, n_facets, d_g.p, space->ncomp, space->n_nodes_owned, b->d.p);
+    if (edges && space->ncomp == 2)
+        hipLaunchKernelGGL(k_edge_vector2, dim3(grid), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, space->n_nodes_owned, b->d.p);
+    else if (edges)
+        hipLaunchKernelGGL(k_edge_vector, dim3(grid), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, space->n_nodes_owned, b->d.p);
+    else
+        hipLaunchKernelGGL(k_facet_vector, dim3(grid), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, space->ncomp, space->n_nodes_owned, b->d.p);
     FS_KERNEL_CHECK();
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
@@ -3849,89 +3880,38 @@ extern "C" int fs_assemble_facet_matrix(fs_matrix_t A, int64_t n_facets, const i
     }
     if (n_facets == 0) return FS_OK;
     fs_space_s* sp = A->space;
-    if (sp->degree == 2 && sp->mesh->tdim == 2) {
-        for (int64_t i = 0; i < 2 * n_facets; ++i)
-            FS_REQUIRE(tri[i] >= 0 && tri[i] < sp->mesh->nv, "fs_assemble_facet_matrix: edge vertex %d out of range", tri[i]);
-        hipStream_t s4 = fs_rt().stream;
-        dbuf<int32_t> d_e;
-        dbuf<double> d_h4;
-        dbuf<int> d_err4;
-        FS_CHECK(d_e.alloc(2 * n_facets));
-        FS_CHECK(d_h4.alloc(n_facets));
-        FS_CHECK(d_err4.alloc(1));
-        FS_CHECK(d_err4.zero(s4));
-        FS_CHECK(d_e.upload(tri, 2 * n_facets, s4));
-        FS_CHECK(d_h4.upload(h, n_facets, s4));
-        hipLaunchKernelGGL(k_edge_matrix_p2, dim3(fs_grid_for(3 * n_facets)), dim3(FS_BLOCK), 0, s4, sp->mesh->xyz.p, d_e.p, n_facets, d_h4.p,
-                           sp->edge_keys.p, sp->n_edges, sp->edge_grouped, sp->edge_node.p, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p,
-                           A->val.p, d_err4.p);
-        FS_KERNEL_CHECK();
-        int h_err4 = 0;
-        FS_CHECK(d_err4.download(&h_err4, 1, s4));
-        FS_REQUIRE(h_err4 == 0, "fs_assemble_facet_matrix: %d boundary edges / entries are not in the space", h_err4);
-        return FS_OK;
-    }
-    if (sp->degree == 2) {
-        FS_REQUIRE(sp->mesh->tdim == 3, "fs_assemble_facet_matrix: CG2 facet matrices are built for tetrahedral meshes");
-        for (int64_t i = 0; i < 3 * n_facets; ++i)
-            FS_REQUIRE(tri[i] >= 0 && tri[i] < sp->mesh->nv, "fs_assemble_facet_matrix: facet vertex %d out of range", tri[i]);
-        hipStream_t s3 = fs_rt().stream;
-        dbuf<int32_t> d_t;
-        dbuf<double> d_h3;
-        dbuf<int> d_err3;
-        FS_CHECK(d_t.alloc(3 * n_facets));
-        FS_CHECK(d_h3.alloc(n_facets));
-        FS_CHECK(d_err3.alloc(1));
-        FS_CHECK(d_err3.zero(s3));
-        FS_CHECK(d_t.upload(tri, 3 * n_facets, s3));
-        FS_CHECK(d_h3.upload(h, n_facets, s3));
-        hipLaunchKernelGGL(k_facet_matrix_p2, dim3(fs_grid_for(6 * n_facets)), dim3(FS_BLOCK), 0, s3, sp->mesh->xyz.p, d_t.p, n_facets, d_h3.p,
-                           sp->edge_keys.p, sp->n_edges, sp->edge_grouped, sp->edge_node.p, sp->n_nodes_owned, sp->mesh->n_owned, sp->n_edges_owned,
-                           sp->slice_ptr.p, sp->sell_col.p, A->val.p, d_err3.p);
-        FS_KERNEL_CHECK();
-        int h_err3 = 0;
-        FS_CHECK(d_err3.download(&h_err3, 1, s3));
-        FS_REQUIRE(h_err3 == 0, "fs_assemble_facet_matrix: %d facet edges / entries are not in the space", h_err3);
-        return FS_OK;
-    }
-    if (sp->mesh->tdim == 2) {
-        for (int64_t i = 0; i < 2 * n_facets; ++i)
-            FS_REQUIRE(tri[i] >= 0 && tri[i] < sp->n_nodes_local, "fs_assemble_facet_matrix: edge vertex %d out of range", tri[i]);
-        hipStream_t s2 = fs_rt().stream;
-        dbuf<int32_t> d_ed;
-        dbuf<double> d_h2;
-        dbuf<int> d_err2;
-        FS_CHECK(d_ed.alloc(2 * n_facets));
-        FS_CHECK(d_h2.alloc(n_facets));
-        FS_CHECK(d_err2.alloc(1));
-        FS_CHECK(d_err2.zero(s2));
-        FS_CHECK(d_ed.upload(tri, 2 * n_facets, s2));
-        FS_CHECK(d_h2.upload(h, n_facets, s2));
-        hipLaunchKernelGGL(k_edge_matrix, dim3(fs_grid_for(4 * n_facets)), dim3(FS_BLOCK), 0, s2, sp->mesh->xyz.p, d_ed.p, n_facets, d_h2.p, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, d_err2.p);
-        FS_KERNEL_CHECK();
-        int h_err2 = 0;
-        FS_CHECK(d_err2.download(&h_err2, 1, s2));
-        FS_REQUIRE(h_err2 == 0, "fs_assemble_facet_matrix: %d edge vertex pairs are not mesh edges", h_err2);
-        return FS_OK;
-    }
-    for (int64_t i = 0; i < 3 * n_facets; ++i)
-        FS_REQUIRE(tri[i] >= 0 && tri[i] < sp->n_nodes_local, "fs_assemble_facet_matrix: facet vertex %d out of range", tri[i]);
+    const bool p2 = sp->degree == 2, edges = sp->mesh->tdim == 2;      // edges: tri holds [n_facets][2] vertex pairs
+    FS_REQUIRE(!p2 || edges || sp->mesh->tdim == 3, "fs_assemble_facet_matrix: CG2 facet matrices are built for tetrahedral meshes");
+    const int nv = edges ? 2 : 3;
+    const int64_t n_vertices = p2 ? sp->mesh->nv : sp->n_nodes_local;
+    for (int64_t i = 0; i < nv * n_facets; ++i)
+        FS_REQUIRE(tri[i] >= 0 && tri[i] < n_vertices,
+                   edges ? "fs_assemble_facet_matrix: edge vertex %d out of range" : "fs_assemble_facet_matrix: facet vertex %d out of range", tri[i]);
     hipStream_t s = fs_rt().stream;
-    dbuf<int32_t> d_tri;
-    dbuf<double> d_h;
-    dbuf<int> d_err;
-    FS_CHECK(d_tri.alloc(3 * n_facets));
-    FS_CHECK(d_h.alloc(n_facets));
-    FS_CHECK(d_err.alloc(1));
-    FS_CHECK(d_err.zero(s));
-    FS_CHECK(d_tri.upload(tri, 3 * n_facets, s));
-    FS_CHECK(d_h.upload(h, n_facets, s));
-    hipLaunchKernelGGL(k_facet_matrix, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s, sp->mesh->xyz.p, d_tri.p, n_facets, d_h.p, sp->n_nodes_owned, sp->sell_col.p, sp->slice_ptr.p, A->val.p, d_err.p);
-    FS_KERNEL_CHECK();
-    int h_err = 0;
-    FS_CHECK(d_err.download(&h_err, 1, s));
-    FS_REQUIRE(h_err == 0, "fs_assemble_facet_matrix: %d facet vertex pairs are not mesh edges", h_err);
-    return FS_OK;
+    launch_lists L;
+    FS_CHECK(L.count_errors(s));
+    FS_CHECK(L.ints(tri, nv * n_facets, s));
+    FS_CHECK(L.doubles(h, n_facets, s));
+    const double* xyz = sp->mesh->xyz.p;
+    if (p2 && edges) {
+        hipLaunchKernelGGL(k_edge_matrix_p2, dim3(fs_grid_for(3 * n_facets)), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, sp->edge_keys.p, sp->n_edges,
+                           sp->edge_grouped, sp->edge_node.p, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, L.err.p);
+        return L.check(s, "fs_assemble_facet_matrix: %d boundary edges / entries are not in the space");
+    }
+    if (p2) {
+        hipLaunchKernelGGL(k_facet_matrix_p2, dim3(fs_grid_for(6 * n_facets)), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, sp->edge_keys.p, sp->n_edges,
+                           sp->edge_grouped, sp->edge_node.p, sp->n_nodes_owned, sp->mesh->n_owned, sp->n_edges_owned, sp->slice_ptr.p, sp->sell_col.p,
+                           A->val.p, L.err.p);
+        return L.check(s, "fs_assemble_facet_matrix: %d facet edges / entries are not in the space");
+    }
+    if (edges) {
+        hipLaunchKernelGGL(k_edge_matrix, dim3(fs_grid_for(4 * n_facets)), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, sp->n_nodes_owned,
+                           sp->slice_ptr.p, sp->sell_col.p, A->val.p, L.err.p);
+        return L.check(s, "fs_assemble_facet_matrix: %d edge vertex pairs are not mesh edges");
+    }
+    hipLaunchKernelGGL(k_facet_matrix, dim3(fs_grid_for(n_facets)), dim3(FS_BLOCK), 0, s, xyz, L.idx.p, n_facets, L.val.p, sp->n_nodes_owned, sp->sell_col.p,
+                       sp->slice_ptr.p, A->val.p, L.err.p);
+    return L.check(s, "fs_assemble_facet_matrix: %d facet vertex pairs are not mesh edges");
 }
 
 extern "C" int fs_apply_dirichlet(fs_matrix_t A, fs_vector_t b, int64_t n, const int32_t* dofs, const double* vals,
@@ -3972,21 +3952,14 @@ extern "C" int fs_apply_dirichlet(fs_matrix_t A, fs_vector_t b, int64_t n, const
     FS_KERNEL_CHECK();
     if (!A) {
         hipLaunchKernelGGL(k_bc_vector, dim3(fs_grid_for(n_dofs)), dim3(FS_BLOCK), 0, s, flag.p, g.p, n_dofs, b->d.p);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipStreamSynchronize(s));
-        return FS_OK;
+    } else {
+        fs_space_s* sp = A->space;
+        double* bp = b ? b->d.p : nullptr;
+        fs_dispatch_int<1, 2, 3, 4>(A->bs, [&](auto BS) {
+            hipLaunchKernelGGL(k_dirichlet_sell<decltype(BS)::value>, dim3(fs_grid_for(sp->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned,
+                               sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, flag.p, g.p, bp, symmetric);
+        });
     }
-    fs_space_s* sp = A->space;
-    const int grid = fs_grid_for(sp->n_slices * 64, FS_BLOCK, 8192);
-    double* bp = b ? b->d.p : nullptr;
-    if (A->bs == 1)
-        hipLaunchKernelGGL(k_dirichlet_sell<1>, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, flag.p, g.p, bp, symmetric);
-    else if (A->bs == 2)
-        hipLaunchKernelGGL(k_dirichlet_sell<2>, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, flag.p, g.p, bp, symmetric);
-    else if (A->bs == 3)
-        hipLaunchKernelGGL(k_dirichlet_sell<3>, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, flag.p, g.p, bp, symmetric);
-    else
-        hipLaunchKernelGGL(k_dirichlet_sell<4>, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, flag.p, g.p, bp, symmetric);
     FS_KERNEL_CHECK();
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
@@ -4005,30 +3978,20 @@ extern "C" int fs_assemble_interior_penalty(fs_matrix_t A, int64_t n_facets, con
     for (int64_t i = 0; i < 2 * n_facets; ++i)
         FS_REQUIRE(facet_cells[i] >= 0 && facet_cells[i] < sp->mesh->nc, "fs_assemble_interior_penalty: facet %lld names cell %d", (long long)(i / 2), facet_cells[i]);
     hipStream_t s = fs_rt().stream;
-    dbuf<int32_t> dfc;
-    dbuf<int> d_err;
-    FS_CHECK(dfc.alloc(2 * n_facets));
-    FS_CHECK(d_err.alloc(1));
-    FS_CHECK(d_err.zero(s));
-    FS_CHECK(dfc.upload(facet_cells, 2 * n_facets, s));
-    if (sp->degree == 2 && sp->mesh->tdim == 2)
-        hipLaunchKernelGGL(k_interior_penalty_p2<2>, dim3(fs_grid_for(9 * n_facets, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, n_facets, dfc.p,
-                           sp->mesh->cells.p, sp->cell_dofs, sp->mesh->xyz.p, coefficient, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, d_err.p);
-    else if (sp->degree == 2)
-        hipLaunchKernelGGL(k_interior_penalty_p2<3>, dim3(fs_grid_for(14 * n_facets, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, n_facets, dfc.p,
-                           sp->mesh->cells.p, sp->cell_dofs, sp->mesh->xyz.p, coefficient, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, d_err.p);
-    else if (sp->mesh->tdim == 2)
-        hipLaunchKernelGGL(k_interior_penalty_tri, dim3(fs_grid_for(4 * n_facets, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, n_facets, dfc.p,
-                           sp->mesh->cells.p, sp->mesh->xyz.p, coefficient, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, d_err.p);
-    else
-        hipLaunchKernelGGL(k_interior_penalty, dim3(fs_grid_for(5 * n_facets, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, n_facets, dfc.p,
-                           sp->mesh->cells.p, sp->mesh->xyz.p, coefficient, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, d_err.p);
-    FS_KERNEL_CHECK();
-    int h_err = 0;
-    FS_CHECK(d_err.download(&h_err, 1, s));
-    FS_REQUIRE(h_err == 0, "fs_assemble_interior_penalty: %d entries are missing from the sparsity pattern or the cell pairs share no facet "
-               "(create the space with fs_space_create_coupled and the pairs of vertices opposite every interior facet)", h_err);
-    return FS_OK;
+    launch_lists L;
+    FS_CHECK(L.count_errors(s));
+    FS_CHECK(L.ints(facet_cells, 2 * n_facets, s));
+    // thread per (facet, node of its patch); the CG2 kernel takes the cell -> dof table after the cells
+    auto penalty = [&](auto kernel, int patch_nodes, auto... cell_dofs) {
+        hipLaunchKernelGGL(kernel, dim3(fs_grid_for(patch_nodes * n_facets, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, n_facets, L.idx.p, sp->mesh->cells.p,
+                           cell_dofs..., sp->mesh->xyz.p, coefficient, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, L.err.p);
+    };
+    if (sp->degree == 2 && sp->mesh->tdim == 2) penalty(k_interior_penalty_p2<2>, 9, sp->cell_dofs);
+    else if (sp->degree == 2) penalty(k_interior_penalty_p2<3>, 14, sp->cell_dofs);
+    else if (sp->mesh->tdim == 2) penalty(k_interior_penalty_tri, 4);
+    else penalty(k_interior_penalty, 5);
+    return L.check(s, "fs_assemble_interior_penalty: %d entries are missing from the sparsity pattern or the cell pairs share no facet "
+                      "(create the space with fs_space_create_coupled and the pairs of vertices opposite every interior facet)");
 }
 
 void fs_assemble_preload() {

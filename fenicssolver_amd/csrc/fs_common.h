@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdarg.h>
+#include <type_traits>
 #include <vector>
 #include <string>
 
@@ -354,6 +355,14 @@ static inline int fs_grid_for(int64_t work_items, int per_block = FS_BLOCK, int 
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return (int)g;
+}
+
+// Run-time flags and block sizes as template arguments: f is a generic lambda called with a std::integral_constant,
+//     fs_dispatch_bool(add, [&](auto ADD) { hipLaunchKernelGGL(k<decltype(ADD)::value>, ...); });
+// Every value that can be passed is instantiated, so nest them only where all combinations exist as kernels.
+template <class F> static inline void fs_dispatch_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int... Vs, class F> static inline bool fs_dispatch_int(int v, F&& f) {   // false: v is none of Vs
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
 // ---- cross-TU internals ------------------------------------------------------------------

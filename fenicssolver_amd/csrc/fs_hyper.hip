@@ -407,37 +407,31 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
     const double mu = form->mu, lambda = form->lambda, ms0 = 0.0;
     const bool add = form->add != 0;
     if (what & FS_HYPER_TANGENT) {
-        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-#define FS_HT3(A_, C_) hipLaunchKernelGGL((k_hyper_tangent_gather<A_, C_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
-                                          sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p, bx)
-#define FS_HT2(A_, C_) hipLaunchKernelGGL((k_hyper_tangent_tri_gather<A_, C_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
-                                          sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p)
-        if (m->tdim == 3) {
-            if (cellw) { if (add) FS_HT3(true, true); else FS_HT3(false, true); }
-            else if (add) FS_HT3(true, false); else FS_HT3(false, false);
-        } else {
-            if (cellw) { if (add) FS_HT2(true, true); else FS_HT2(false, true); }
-            else if (add) FS_HT2(true, false); else FS_HT2(false, false);
-        }
-#undef FS_HT3
-#undef FS_HT2
+        auto gather = [&](auto kernel, auto... tail) {
+            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p,
+                               m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p, tail...);
+        };
+        fs_dispatch_bool(add, [&](auto ADD) {
+            fs_dispatch_bool(cellw, [&](auto CELL) {
+                constexpr bool a = decltype(ADD)::value, c = decltype(CELL)::value;
+                if (m->tdim == 3) gather(k_hyper_tangent_gather<a, c>, bx);
+                else gather(k_hyper_tangent_tri_gather<a, c>);
+            });
+        });
         FS_KERNEL_CHECK();
     }
     if (what & FS_HYPER_FORCE) {
-        const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
-#define FS_HF3(A_, C_) hipLaunchKernelGGL((k_hyper_force_gather<A_, C_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
-                                          sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, bx, r->d.p)
-#define FS_HF2(A_, C_) hipLaunchKernelGGL((k_hyper_force_tri_gather<A_, C_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
-                                          sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, r->d.p)
-        if (m->tdim == 3) {
-            if (cellw) { if (add) FS_HF3(true, true); else FS_HF3(false, true); }
-            else if (add) FS_HF3(true, false); else FS_HF3(false, false);
-        } else {
-            if (cellw) { if (add) FS_HF2(true, true); else FS_HF2(false, true); }
-            else if (add) FS_HF2(true, false); else FS_HF2(false, false);
-        }
-#undef FS_HF3
-#undef FS_HF2
+        auto gather = [&](auto kernel, auto... tail) {
+            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p,
+                               sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, tail...);
+        };
+        fs_dispatch_bool(add, [&](auto ADD) {
+            fs_dispatch_bool(cellw, [&](auto CELL) {
+                constexpr bool a = decltype(ADD)::value, c = decltype(CELL)::value;
+                if (m->tdim == 3) gather(k_hyper_force_gather<a, c>, bx, r->d.p);
+                else gather(k_hyper_force_tri_gather<a, c>, r->d.p);
+            });
+        });
         FS_KERNEL_CHECK();
     }
     if (info) {
@@ -445,11 +439,13 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
         dbuf<double> pe, oe;
         dbuf<int64_t> part, on;
         FS_CHECK(pe.alloc(nb)); FS_CHECK(part.alloc(2 * nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
-#define FS_HC(T_, C_) hipLaunchKernelGGL((k_hyper_cells<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu, lambda, \
-                                         lc, bx, pe.p, part.p)
-        if (m->tdim == 3) { if (cellw) FS_HC(3, true); else FS_HC(3, false); }
-        else { if (cellw) FS_HC(2, true); else FS_HC(2, false); }
-#undef FS_HC
+        fs_dispatch_bool(cellw, [&](auto CELL) {
+            auto cells = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, bx, pe.p, part.p);
+            };
+            if (m->tdim == 3) cells(k_hyper_cells<3, decltype(CELL)::value>);
+            else cells(k_hyper_cells<2, decltype(CELL)::value>);
+        });
         FS_KERNEL_CHECK();
         hipLaunchKernelGGL((k_cell_tally_finish<1, true>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
         FS_KERNEL_CHECK();
