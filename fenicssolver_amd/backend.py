@@ -1193,6 +1193,12 @@ def last_iteration_form():
     return int(L.load().fs_last_iteration_form())
 
 
+def last_iteration_guard():
+    """What option "cg_guard" did in the last solve (fs_last_iteration_guard), 0 if nothing: bit 0 = guarded work vectors without the
+    edge-item path, bit 1 = own rows from the centre run (Kuhn box)."""
+    return int(L.load().fs_last_iteration_guard())
+
+
 def set_option(name, value):
     L.check(L.load().fs_set_option(name.encode(), float(value)), "fs_set_option")
 

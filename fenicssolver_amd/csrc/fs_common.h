@@ -96,12 +96,25 @@ template <typename T>
 struct dbuf {
     T* p = nullptr;
     int64_t n = 0;
+    int64_t guard = 0;      // alloc_guarded: elements of zeros in front of p[0] and behind p[n - 1]; the block starts at p - guard
     int alloc(int64_t count) {
         release();
         n = count;
         if (count == 0) return FS_OK;
         p = static_cast<T*>(fs_pool_alloc((size_t)count * sizeof(T)));
         if (!p) { n = 0; return FS_ERR_HIP; }
+        return FS_OK;
+    }
+    // count elements with g more on either side, the WHOLE block zeroed: whoever writes [0, count) only may read [-g, count + g)
+    // and finds zeros outside.  zero() and n keep meaning the count elements.
+    int alloc_guarded(int64_t count, int64_t g, hipStream_t s) {
+        release();
+        T* base = static_cast<T*>(fs_pool_alloc((size_t)(count + 2 * g) * sizeof(T)));
+        if (!base) return FS_ERR_HIP;
+        p = base + g;
+        n = count;
+        guard = g;
+        FS_HIP(hipMemsetAsync(base, 0, (size_t)(count + 2 * g) * sizeof(T), s));
         return FS_OK;
     }
     int zero(hipStream_t s) {
@@ -117,13 +130,15 @@ struct dbuf {
         return FS_OK;
     }
     void release() {
-        if (p) fs_pool_free(p);
+        if (p) fs_pool_free(p - guard);
         p = nullptr;
         n = 0;
+        guard = 0;
     }
     void swap(dbuf& o) {
         T* tp = p; p = o.p; o.p = tp;
         const int64_t tn = n; n = o.n; o.n = tn;
+        const int64_t tg = guard; guard = o.guard; o.guard = tg;
     }
     ~dbuf() { release(); }
     dbuf() = default;
@@ -296,6 +311,11 @@ struct fs_space_s {
     dbuf<int32_t> dict_plans;
     int dict_slots = 0;
     int dict_run_len = 3;         // coefficient positions per run (2: CG2 spaces, where runs of three offsets are rare)
+    // smallest and largest run start over all plans (an item's loads stay inside [first + min, first + 128 + max]: the guard bands of
+    // the one-launch iteration's vectors), and: ONE plan of one round whose slot 4 is the run (-1; 3 offsets) - the Kuhn box, where
+    // that run brings a lane's own two rows and the z run of slot 0 is not needed (k_dict_cg_iter, CENTRE)
+    int32_t dict_min_start = 0, dict_max_start = 0;
+    bool dict_centre = false;
     // hints for dict_structure_build (set by fs_lattice.hip for the lattice-ordered shadow of a CG2 box space): rows repeat their
     // offset set with this period inside mesh lines of dict_line rows (0: unknown - segments are grown from nested sets), and a
     // line is one segment whose plan is the union of its rows' sets

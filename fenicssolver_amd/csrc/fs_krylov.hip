@@ -112,8 +112,11 @@ static int g_cg_fuse_sums = 1;
 static int g_cg_graph = -1;      // -1: automatic (graphs, unless a profiler's tool library is in the process)
 static int g_update_blocks = 1024;  // (round 3, with the 16 us row-dictionary product at 1 M rows: 256 / 512 / 768 / 1024 / 2048 workgroups: 10.59 / 10.42 / 10.20 / 10.12 / 11.22 ms per step; 10 M rows: flat)
 static int g_cg_pair = getenv("FS_CG_PAIR") ? (atoi(getenv("FS_CG_PAIR")) != 0) : 1;      // option "cg_pair": the one-launch iteration updates p and x every second launch (k_dict_cg_iter, MODE); 0: in every launch
+// option "cg_guard": the LIGHT / PAIR launches run on work vectors with guard bands of zeros and without the edge-item path (k_dict_cg_iter,
+// GUARD / CENTRE); 0: the unguarded vectors and the kernels with the clamped path
+static int g_cg_guard = getenv("FS_CG_GUARD") ? (atoi(getenv("FS_CG_GUARD")) != 0) : 1;
 static int g_cg_poison_p = 0;            // option "cg_poison_p" (tests): the next CG solve finds NaN in its search-direction workspace
-static int g_last_iteration_form = 0;    // fs_last_iteration_form()
+static int g_last_iteration_form = 0;    // bits 0, 1: fs_last_iteration_form(); bits 2, 3: fs_last_iteration_guard()
 static int g_cg_fused = -1;      // one launch per CG iteration on row-dictionary operators: -1 automatic, 0 never, 1 wherever it applies
 static int g_row_dictionary = 1; // row-dictionary product where the operator allows it (0: always the streaming kernels)
 // the marching-window product of P1 box operators (fs_box.h): option "box_spmv" (0: k_dict_spmv everywhere), from "box_min_rows" rows on
@@ -149,6 +152,8 @@ extern "C" int fs_set_option(const char* name, double value) {
         g_cg_fused = value < 0.0 ? -1 : (value != 0.0);
     } else if (!strcmp(name, "cg_pair")) {
         g_cg_pair = value != 0.0;
+    } else if (!strcmp(name, "cg_guard")) {
+        g_cg_guard = value != 0.0;
     } else if (!strcmp(name, "cg_poison_p")) {
         g_cg_poison_p = value != 0.0;
     } else if (!strcmp(name, "update_blocks")) {
@@ -633,6 +638,13 @@ static int dict_structure_build(fs_space_s* sp, hipStream_t s) {
         FS_CHECK(sp->dict_plans.upload(reinterpret_cast<const int32_t*>(rounds.data()), plan_ints, s));
         sp->dict_slots = NR * RL * std::max(max_rounds, 1);
         sp->dict_run_len = RL;
+        sp->dict_min_start = 0; sp->dict_max_start = 0;
+        for (const plan_info& pi : seg_plan) {
+            sp->dict_min_start = std::min(sp->dict_min_start, pi.min_start);
+            sp->dict_max_start = std::max(sp->dict_max_start, pi.max_start);
+        }
+        sp->dict_centre = rounds.size() == 1 && NR == 8 && RL == 3 && rounds[0].start[0] == 0 && rounds[0].len[0] == 0 &&
+                          rounds[0].start[4] == -1 && rounds[0].len[4] == 3;
         // ONE segment with the offset list of a Kuhn-split box (P1 on fs_mesh_create_box / BoxMesh, one GPU): the marching-window
         // product applies (fs_box.h, k_box_spmv)
         sp->box_a = 0; sp->box_b = 0;
@@ -1831,16 +1843,24 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
     // that exchange is what the iteration uses (decided per pass below: p2p_fuse); a rank-local choice, the exchange protocol is the same
     static const bool fused_p2p_on = !(getenv("FS_CG_FUSED_P2P") && getenv("FS_CG_FUSED_P2P")[0] == '0');
     const bool fusedp_ok = fused_sized && !fuse_sums && sp->halo.active && fused_p2p_on;
-    if (fused || fusedp_ok) {
-        if (ws.z2.n != nl + 2) FS_CHECK(ws.z2.alloc(nl + 2));
-        if (ws.w2.n != nl + 2) {
-            FS_CHECK(ws.w2.alloc(nl + 2));
-            FS_CHECK(ws.s2.alloc(nl + 2));
-        }
-        if (!ws.it_ctr.p) FS_CHECK(ws.it_ctr.alloc(2));
-    }
     // k_dict_cg_iter: p and x every second launch (option "cg_pair"), dot weights from the class table where every row agrees with it
     const bool pair_form = g_cg_pair != 0, dtab_form = pair_form && g_dict.dtab_ok;
+    // ... and on one GPU the six vectors whose neighbour columns it reads with guard bands of zeros (option "cg_guard"): every run load of
+    // every item is then inside the block (a lane reads columns first + 2 lane + start + {0, 1}, lane < 64: 130 covers the item's 128
+    // values and the second value of a load; a multiple of 32 keeps row 0 on the alignment the block has), no item takes the clamped
+    // path.  The bands are zeroed with the block and nothing writes them: every kernel that gets these pointers writes rows of [0, nl + 2).
+    const bool guard_form = g_cg_guard != 0 && pair_form && fused && !BI;
+    const bool centre_form = guard_form && sp->dict_centre;
+    const int64_t guard = guard_form ? 32 * ((std::max<int64_t>(-(int64_t)sp->dict_min_start, sp->dict_max_start) + 130 + 31) / 32) : 0;
+    if (fused || fusedp_ok) {
+        dbuf<double>* const six[6] = {&ws.z, &ws.w, &ws.s, &ws.z2, &ws.w2, &ws.s2};
+        for (dbuf<double>* v : six)
+            if (v->n != nl + 2 || v->guard != guard) {
+                if (guard) FS_CHECK(v->alloc_guarded(nl + 2, guard, s));
+                else FS_CHECK(v->alloc(nl + 2));
+            }
+        if (!ws.it_ctr.p) FS_CHECK(ws.it_ctr.alloc(2));
+    }
     int iteration_form = 0;
     // A pass = fresh recurrences from the current x.  The single-reduction recurrences drift on
     // ill-conditioned operators (the recurrence residual can reach the threshold while b - A x has not):
@@ -2072,7 +2092,8 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                 // (one GPU only: behind the exchange kernel of a decomposed space the LIGHT instantiation compiles to 132 VGPRs, three
                 // waves per SIMD instead of the four the launch needs - that form keeps p and x in every launch)
                 const bool pair = pair_form && !fusedp && !BI, dtab = pair && dtab_form;
-                iteration_form = (pair ? 1 : 0) | (dtab ? 2 : 0);
+                const bool guarded = pair && guard_form, centre = pair && centre_form;
+                iteration_form = (pair ? 1 : 0) | (dtab ? 2 : 0) | (guarded ? 4 : 0) | (centre ? 8 : 0);
                 const size_t lds = (size_t)g_dict.ncls * (g_dict.S + (dtab ? 1 : 0)) * sizeof(double);
                 const double* const weights = dtab ? g_dict.dtab.p : ws.dvec.p;
                 fs_p2p_rowsred red2[2] = {};
@@ -2100,12 +2121,16 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
                         launch_exchange(par);
                         hipLaunchKernelGGL((k_dict_cg_iter<3, true>), FS_ITER_ARGS);
                     } else if (!pair) hipLaunchKernelGGL((k_dict_cg_iter<3, false>), FS_ITER_ARGS);
-                    else if (dtab) {           // (launch parity = iteration parity: it_ctr is zeroed at k = 0)
-                        if (par) hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_PAIR, true>), FS_ITER_ARGS);
-                        else hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_LIGHT, true>), FS_ITER_ARGS);
-                    } else {
-                        if (par) hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_PAIR, false>), FS_ITER_ARGS);
-                        else hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_LIGHT, false>), FS_ITER_ARGS);
+                    else {                     // (launch parity = iteration parity: it_ctr is zeroed at k = 0)
+#define FS_ITER_LAUNCH(DT, GU, CE) do { \
+                            if (par) hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_PAIR, DT, GU, CE>), FS_ITER_ARGS); \
+                            else hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_LIGHT, DT, GU, CE>), FS_ITER_ARGS); \
+                        } while (0)
+                        if (centre) { if (dtab) FS_ITER_LAUNCH(true, true, true); else FS_ITER_LAUNCH(false, true, true); }
+                        else if (guarded) { if (dtab) FS_ITER_LAUNCH(true, true, false); else FS_ITER_LAUNCH(false, true, false); }
+                        else if (dtab) FS_ITER_LAUNCH(true, false, false);
+                        else FS_ITER_LAUNCH(false, false, false);
+#undef FS_ITER_LAUNCH
                     }
 #undef FS_ITER_ARGS
                 };
@@ -2472,6 +2497,28 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
         fprintf(stderr, "[iter timing, last launch, us from the first workgroup's start] span %.2f;", (last - first) * 0.01);
         for (int k2 = 0; k2 < 8; ++k2) fprintf(stderr, " s%d mean %.2f max %.2f;", k2, mean[k2], mx[k2]);
         fprintf(stderr, "\n");
+        // stamps 5 (first item done), 6 (all items done), 7 (partials summed) apart for the workgroups whose chunks hold an edge item
+        // (the chunk walk of the kernel: xcd_chunks, or block-strided without the XCD map) and for the rest
+        std::vector<int32_t> hi((size_t)sp->n_dict_items * 4);
+        FS_CHECK(sp->dict_items.download(hi.data(), (int64_t)hi.size(), s));
+        FS_HIP(hipStreamSynchronize(s));
+        const int64_t n_chunks = (sp->n_dict_items + 3) / 4, per_xcd = (n_chunks + 7) >> 3;
+        int cnt[2] = {0, 0};
+        double gm[2][3] = {{0}}, gx[2][3] = {{0}};
+        for (int b = 0; b < igrid; ++b) {
+            int64_t cur = b, step = igrid, end = n_chunks;
+            if (dict_map_xcd()) { cur = (b & 7) * per_xcd + (b >> 3); step = igrid >> 3; end = std::min<int64_t>(((b & 7) + 1) * per_xcd, n_chunks); }
+            int e = 0;
+            for (; cur < end; cur += step)
+                for (int64_t q = 4 * cur; q < std::min<int64_t>(4 * cur + 4, sp->n_dict_items); ++q) e |= (hi[(size_t)q * 4 + 1] >> 16) & 1;
+            ++cnt[e];
+            for (int k2 = 0; k2 < 3; ++k2) { const double v = (h[8 * b + 5 + k2] - first) * 0.01; gm[e][k2] += v; gx[e][k2] = std::max(gx[e][k2], v); }
+        }
+        for (int e = 0; e < 2; ++e) {
+            fprintf(stderr, "[iter timing] %d workgroups %s an edge item:", cnt[e], e ? "with" : "without");
+            for (int k2 = 0; k2 < 3; ++k2) fprintf(stderr, " s%d mean %.2f max %.2f;", 5 + k2, cnt[e] ? gm[e][k2] / cnt[e] : 0.0, gx[e][k2]);
+            fprintf(stderr, "\n");
+        }
     }
 #endif
     ws.last_hist.resize((size_t)iters + 1);
@@ -2520,7 +2567,9 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
     return FS_OK;
 }
 
-extern "C" int fs_last_iteration_form() { return g_last_iteration_form; }
+// (the guard bits have an accessor of their own: callers of fs_last_iteration_form compare the word with PAIR | DTAB)
+extern "C" int fs_last_iteration_form() { return g_last_iteration_form & 3; }
+extern "C" int fs_last_iteration_guard() { return (g_last_iteration_form >> 2) & 3; }
 void fs_krylov_set_history(const std::vector<double>& rr) { g_ws.last_hist = rr; }
 void fs_set_last_product_kind(int kind) { g_last_product_kind = kind; }
 

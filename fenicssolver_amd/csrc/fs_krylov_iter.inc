@@ -475,8 +475,20 @@ __device__ long long g_iter_dbg[8 * 4096];
 // (COMM) the LIGHT instantiation needs 132 VGPRs - three waves per SIMD - and COMM stays on FS_ITER_EVERY.
 // DTAB: `dvec` is the table of dot weights by row class (row_dict::dtab, every row verified against it bit for bit), copied into LDS behind
 // the dictionary, instead of the 8 B per row of the weight vector.
+// GUARD (option "cg_guard", one GPU, LIGHT / PAIR launches): r, w, s of both parities have G doubles of zeros in front of row 0 and behind
+// row n + 1 (dbuf::alloc_guarded; G covers the smallest and largest run start of the space + the 128 values of an item), so every run
+// load of every item is inside the block: H.edge is ignored, no item takes the run-by-run clamped path (eight dependent round trips
+// where an ordinary item has two exposed ones), the first item's half round is always asked for before the prologue, n_cols is unused.
+// The same bits: a column outside the vector has a zero coefficient - the clamped path adds fma(+0, finite, acc), this one
+// fma(+0, 0, acc) (the recomputed residual of a band column is fma(-alpha, fma(beta, 0, 0), 0) = 0), in the same run order.
+// CENTRE (with GUARD, where the space has ONE plan of one round whose slot 4 is the run (-1; 3 offsets): the Kuhn box, fs_space_s::dict_centre):
+// that run brings x[r - 1 .. r + 2], the lane's own two rows among them, so the z run of slot 0 - whose coefficients are all zero - is
+// neither loaded nor multiplied (21 instead of 24 sixteen-byte run loads per item, 42 instead of 48 coefficient reads and fma pairs): the
+// new s, the old r and the new r of the own rows are (value.y, next lane's value.x) of slot 4, the same memory words through the same two
+// fmas.  Lane 63 has no rows of its own and loads what lane 62 needs.
+// Measured at 1 M rows: profiles/r08_cg_guard_ab.txt, r08_cg_guard_trace_*.csv, r08_iter_edge_timeline.txt (DESIGN.md section 3).
 enum { FS_ITER_EVERY = 0, FS_ITER_LIGHT = 1, FS_ITER_PAIR = 2 };
-template <int RL, bool COMM, int MODE = FS_ITER_EVERY, bool DTAB = false>
+template <int RL, bool COMM, int MODE = FS_ITER_EVERY, bool DTAB = false, bool GUARD = false, bool CENTRE = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64_t n_items, const int4* __restrict__ items,
                                                            const dict_plan_round* __restrict__ plans, const uint16_t* __restrict__ cls,
                                                            const double* __restrict__ dict, int S, int C,
@@ -541,7 +553,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     };
     // loads of runs [4 h, 4 h + 4) of round rd: scalar base (vector + run start) + one 32-bit byte offset per lane - the `saddr` form
     // of the load, no 64-bit address arithmetic or address registers per load (rows < 2^29)
-    auto load_half = [&](const item_hdr& H, int rd, int h, uint32_t boff, v2d (&A)[4], v2d (&Wb)[4], v2d (&Sb)[4]) {
+    // (skip0: slot 0 of the half round is not loaded - the z run of a CENTRE launch)
+    auto load_half = [&](const item_hdr& H, int rd, int h, uint32_t boff, v2d (&A)[4], v2d (&Wb)[4], v2d (&Sb)[4], bool skip0 = false) {
         // (measured and not kept: run starts that need no load - kernel arguments for the plan most items have, or a per-item copy beside
         // the header - and the next item's header asked for an item ahead: with nothing left between header and run loads the
         // compiler schedules 164 - 177 VGPRs (and spills SGPRs into them), two or three waves per SIMD instead of four, and the
@@ -551,6 +564,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
         for (int j = 0; j < 4; ++j) sts[j] = __builtin_amdgcn_readfirstlane(H.pl[rd].start[4 * h + j]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
+            if (skip0 && j == 0) { A[0] = Wb[0] = Sb[0] = v2d{0.0, 0.0}; continue; }
             const int32_t st = sts[j];
             A[j] = *reinterpret_cast<const v2du*>(reinterpret_cast<const char*>(r_in + st) + boff);
             Wb[j] = *reinterpret_cast<const v2du*>(reinterpret_cast<const char*>(w_in + st) + boff);
@@ -585,7 +599,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     const bool have0 = it.cur < it.end && it.cur * 4 + wave < n_items;
     if (have0) {
         H0 = decode(it.cur * 4 + wave);
-        if (!H0.edge) load_half(H0, 0, 0, (uint32_t)(H0.first + 2 * lane) * 8u, PA, PW, PS);
+        if (GUARD || !H0.edge) load_half(H0, 0, 0, (uint32_t)(H0.first + 2 * lane) * 8u, PA, PW, PS, CENTRE);
         load_own(H0, Ppp, Pxx, Pdd, Prp);
     }
     FS_STAMP(2);
@@ -681,29 +695,41 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
                 a0 = fma(w0[2], e2, a0); a1 = fma(w1[2], e3, a1);
             }
         };
-        if (!H.edge) {
+        if (GUARD || !H.edge) {
             const uint32_t boff = (uint32_t)r * 8u;
+            // (CENTRE: one round, known to the host only - with the trip count a constant the compiler schedules the PAIR launch with 172
+            // VGPRs, two waves per SIMD; as a loop 114)
             for (int rd = 0; rd < H.rounds; ++rd) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     v2d A[4], Wb[4], Sb[4];
+                    const bool skip0 = CENTRE && h == 0;        // (slot 0, the z run: neither loaded nor multiplied)
                     if (PRE && h == 0) {
                         if (rd == 0) {
 #pragma unroll
                             for (int j = 0; j < 4; ++j) { A[j] = PA[j]; Wb[j] = PW[j]; Sb[j] = PS[j]; }
                         } else load_half(H, rd, h, boff, A, Wb, Sb);
-                    } else load_half(H, rd, h, boff, A, Wb, Sb);
+                    } else load_half(H, rd, h, boff, A, Wb, Sb, skip0);
                     // the new r on these columns: r - alpha (w + beta s), two fmas per value - the owner's operations, the owner's bits
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
+                        if (skip0 && j == 0) continue;
                         v2d sn;
                         sn.x = fma(beta, Sb[j].x, Wb[j].x); sn.y = fma(beta, Sb[j].y, Wb[j].y);
-                        if (h == 0 && j == 0 && rd == 0) { sn0 = sn; ro0 = A[0]; }
+                        if (!CENTRE && h == 0 && j == 0 && rd == 0) { sn0 = sn; ro0 = A[0]; }
+                        // (CENTRE: slot 4 is the run (-1; 3) - columns r - 1, r of this lane, r + 1 the next lane's first: the own two
+                        // rows, the same memory words the z run loads, through the same two fmas)
+                        if (CENTRE && h == 1 && j == 0) {
+                            sn0.x = sn.y; sn0.y = fs_from_next_lane(sn.x);
+                            ro0.x = A[0].y; ro0.y = fs_from_next_lane(A[0].x);
+                        }
                         A[j].x = fma(nalpha, sn.x, A[j].x); A[j].y = fma(nalpha, sn.y, A[j].y);
                     }
-                    if (h == 0 && rd == 0) zi = A[0];
+                    if (!CENTRE && h == 0 && rd == 0) zi = A[0];
+                    if (CENTRE && h == 1) { zi.x = A[0].y; zi.y = fs_from_next_lane(A[0].x); }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
+                        if (skip0 && j == 0) continue;
                         run_terms(A[j], v0 + RL * (8 * rd + 4 * h + j), v1 + RL * (8 * rd + 4 * h + j));
                         asm volatile("" ::: "memory");
                     }

@@ -90,7 +90,10 @@ const char* fs_version(void);
  * "update_blocks" (grid of the fused vector-update kernel), "cg_graph" (-1 / 0 / 1: CG batches as hipGraphs by size /
  * never / always), "cg_fused" (-1 / 0 / 1: ONE launch per CG iteration on row-dictionary operators - up to 3 M rows /
  * never / wherever it applies; fs_krylov_stats.fused_iteration), "cg_pair" (1 / 0, default 1; FS_CG_PAIR in the environment: that launch
- * updates p and x every second iteration, two steps in one pass, instead of in every launch - the same bits; fs_last_iteration_form), "cg_poison_p" (tests: 1 = the next CG solve
+ * updates p and x every second iteration, two steps in one pass, instead of in every launch - the same bits; fs_last_iteration_form),
+ * "cg_guard" (1 / 0, default 1; FS_CG_GUARD in the environment: on one GPU the LIGHT / PAIR launches of "cg_pair" run on solver-owned work vectors with
+ * guard bands of zeros in front of row 0 and behind the last row, so that no work item needs the clamped edge path, and on a Kuhn box take a lane's
+ * own rows from the centre run instead of a run of their own - the same bits; fs_last_iteration_guard; 0: unguarded vectors and the kernels with the edge path), "cg_poison_p" (tests: 1 = the next CG solve
  * finds NaN in its search-direction workspace before it sets its initial state), "row_dictionary" (0 / 1: allow the row-dictionary form of the product, fs_krylov_stats.row_classes),
  * "box_snap" (0 / 1: box meshes snap their edge vectors to the grid spacing so that equal stencils are equal bit for bit),
  * "box_assembly" (1 / 0: scalar CG1 operators on fs_mesh_create_box meshes are assembled from the reference rows of the six cell types instead of
@@ -704,6 +707,10 @@ int fs_last_product_kind(void);
  * second launch (option "cg_pair"), bit 1 = the dot weights came from the table by row class (every row of the solve's weight vector
  * equalled its class's entry bit for bit) and not from the weight vector. */
 int fs_last_iteration_form(void);
+/* ... and what option "cg_guard" did in that solve, 0 if nothing: bit 0 = guarded work vectors, no edge-item path, bit 1 = with them, the own
+ * rows taken from the centre run of the space's one plan (Kuhn box) and the z run neither loaded nor multiplied.  (A word of its own:
+ * callers of fs_last_iteration_form compare that word with the two bits it has.) */
+int fs_last_iteration_guard(void);
 
 /* ---- smoothed-aggregation AMG (PETScPreconditioner("petsc_amg") + set_near_nullspace,
  *      SolverBase.py:643-672; Chebyshev/Jacobi level smoother as the PETScOptions there ask) ---- */
