@@ -452,6 +452,33 @@ class SolverBase():
             u.vector().set_local(parallel.gather_owned(x.get()[:V.n_owned], loc.owned_gids(), loc.n_global, ncomp))
         return u
 
+    def _device_solve_vectors(self, A, b, x, label, amg=False, near_nullspace=None, operator_key=None):
+        """A x = b with b and x DeviceVectors that stay on the device (one rank, a symmetric operator): CG + AMG (amg=True; the hierarchy
+        is kept under operator_key as in _device_solve) or Jacobi-CG, with the tolerances of solver_parameters.  Returns the stats of
+        the solve ('amg_reused' with a hierarchy); a solve that does not converge raises."""
+        from . import backend
+        rtol, max_iter, _ = self._krylov_options()
+        sp_ = self.solver_settings.get('solver_parameters', {}) or {}
+        norm = sp_.get('norm_type', 'preconditioned')
+        if amg:
+            hierarchy, reused = self._amg_hierarchy(A, operator_key, near_nullspace)
+            stats = hierarchy.solve(b, x, rtol=rtol, max_iter=min(max_iter, int(sp_.get('maximum_iterations', 500))), norm=norm)
+            stats['amg_reused'] = reused
+            stats['amg_setup_ms'] = hierarchy.info()['setup_ms']
+            if operator_key is None:
+                hierarchy.close()
+        else:
+            stats = backend.krylov_solve(A, b, x, rtol=rtol, max_iter=max_iter, precond='jacobi', method='cg', norm=norm)
+        self.last_solve_stats = stats
+        if stats['converged'] != 1:
+            user_tol = 'krylov_relative_tolerance' in sp_ or float(sp_.get('relative_tolerance', 1.0)) < 1e-8
+            if user_tol or stats['converged'] < 0 or not (stats['true_rel_residual'] <= 1e-8):
+                raise SolverError('{}: Krylov solver did not converge in {} iterations (||r||/||b|| = {:.3e})'.format(
+                    label, stats['iterations'], stats['true_rel_residual']))
+            self.logger.warning('%s: stopped at ||r||/||b|| = %.3e after %d iterations (default tolerance %.0e not attained)',
+                                label, stats['true_rel_residual'], stats['iterations'], rtol)
+        return stats
+
     def _amg_hierarchy(self, A, key, near_nullspace):
         """(hierarchy, reused): the smoothed-aggregation hierarchy of A, kept while the next caller names the same operator key;
         a caller with key None owns (and closes) the hierarchy it gets."""

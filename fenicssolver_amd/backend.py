@@ -780,6 +780,81 @@ def wave_advance(K, state, load_scale, dirichlet_scale, receivers=None, traces=T
     return state.advance(K, load_scale, dirichlet_scale, receivers=receivers, traces=traces, energy=energy, info=info)
 
 
+class DynamicsState(_Handle):
+    """Device state of the generalized-alpha marcher on a vector CG1 / CG2 space (fs_dyn_*): u, v, a, the work vectors p, q, M p,
+    K q, the load F, the Dirichlet dofs with their values, the constants of the scheme and the step counter n.  Arrays are in DEVICE
+    dof order.  K and M are the operators WITHOUT eliminated rows; the solve between predict() and correct() is the caller's."""
+    _destroy = "fs_dyn_state_destroy"
+
+    def __init__(self, space):
+        super().__init__()
+        self.space = space
+        self.n = int(space.n_owned)
+        L.check(L.load().fs_dyn_state_create(space.h, C.byref(self.h)), "fs_dyn_state_create")
+
+    def _field(self, a, who, name):
+        a = L.f64(a).ravel()
+        if a.size != self.n:
+            raise BackendError("DynamicsState.%s: %s has %d entries, the space has %d dofs" % (who, name, a.size, self.n))
+        return a
+
+    def configure(self, dt, alpha_m, alpha_f, beta, gamma, eta_m=0.0, eta_k=0.0, load=None, dirichlet_dofs=None, dirichlet_values=None):
+        f = None if load is None else self._field(load, "configure", "load")
+        dofs = L.i32([] if dirichlet_dofs is None else dirichlet_dofs).ravel()
+        vals = L.f64(np.broadcast_to(0.0 if dirichlet_values is None else dirichlet_values, dofs.shape))
+        L.check(L.load().fs_dyn_state_configure(self.h, float(dt), float(alpha_m), float(alpha_f), float(beta), float(gamma), float(eta_m),
+                                                float(eta_k), L.p_f64(f), dofs.size, L.p_i32(dofs), L.p_f64(vals)), "fs_dyn_state_configure")
+
+    def set(self, u, v, a, step=0):
+        u, v, a = (self._field(x, "set", nm) for x, nm in ((u, "u"), (v, "v"), (a, "a")))
+        L.check(L.load().fs_dyn_state_set(self.h, L.p_f64(u), L.p_f64(v), L.p_f64(a), int(step)), "fs_dyn_state_set")
+
+    def get(self):
+        """(u, v, a, n)"""
+        u, v, a, k = np.empty(self.n), np.empty(self.n), np.empty(self.n), C.c_int64(0)
+        L.check(L.load().fs_dyn_state_get(self.h, L.p_f64(u), L.p_f64(v), L.p_f64(a), C.byref(k)), "fs_dyn_state_get")
+        return u, v, a, k.value
+
+    def work(self):
+        """(p, q, M p, K q) of the last predict()"""
+        out = [np.empty(self.n) for _ in range(4)]
+        L.check(L.load().fs_dyn_state_get_work(self.h, *[L.p_f64(x) for x in out]), "fs_dyn_state_get_work")
+        return tuple(out)
+
+    def info(self):
+        """waits for the device: {'predict_ms', 'predict_pointwise_ms', 'correct_ms', 'n_nonfinite', 'first_nonfinite_step', 'step'}"""
+        inf = L.fs_dyn_info()
+        L.check(L.load().fs_dyn_state_info(self.h, C.byref(inf)), "fs_dyn_state_info")
+        return {k: getattr(inf, k) for k, _ in L.fs_dyn_info._fields_}
+
+    def start_rhs(self, K, M, u0, v0, load_scale0, rhs):
+        """takes (u_0, v_0); rhs (a DeviceVector) = s_f(t_0) F - C v_0 - K u_0 on the free rows, 0 on the Dirichlet rows"""
+        u0, v0 = self._field(u0, "start_rhs", "u0"), self._field(v0, "start_rhs", "v0")
+        L.check(L.load().fs_dyn_start_rhs(K.h, M.h, self.h, L.p_f64(u0), L.p_f64(v0), float(load_scale0), rhs.h), "fs_dyn_start_rhs")
+
+    def start(self, a0):
+        """a_0 (a DeviceVector, solved from start_rhs with the eliminated M): the state then holds (u_0, v_0, a_0), n = 0"""
+        L.check(L.load().fs_dyn_start(self.h, a0.h), "fs_dyn_start")
+
+    def predict(self, K, M, load_scale, dirichlet_scale_next, rhs):
+        """rhs (a DeviceVector) of the step n -> n+1; nothing returns to the host"""
+        L.check(L.load().fs_dyn_predict(K.h, M.h, self.h, float(load_scale), float(dirichlet_scale_next), rhs.h), "fs_dyn_predict")
+
+    def correct(self, x, receivers=None):
+        """x (a DeviceVector) = u_{n+1}: forms a_{n+1}, v_{n+1}; with receivers returns the samples of u_{n+1} at those dofs (and
+        waits for the device), else None"""
+        rec = L.i32([] if receivers is None else receivers).ravel()
+        out = np.empty(rec.size) if rec.size else None
+        L.check(L.load().fs_dyn_correct(self.h, x.h, rec.size, L.p_i32(rec) if rec.size else None, L.p_f64(out)), "fs_dyn_correct")
+        return out
+
+    def energy(self, K, M):
+        """(1/2 v^T M v, 1/2 u^T K u)"""
+        out = np.empty(2)
+        L.check(L.load().fs_dyn_energy(K.h, M.h, self.h, L.p_f64(out)), "fs_dyn_energy")
+        return float(out[0]), float(out[1])
+
+
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):
     """b[vertex*9 + 3i + j] = int (nu (grad u + grad u^T) - p I)_ij phi_vertex dx for a Taylor-Hood iterate w.
     viscosity_law = (p_ref, exponent): nu (p / p_ref)^exponent."""

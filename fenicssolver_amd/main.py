@@ -30,7 +30,7 @@ def load_settings(case_input):
 
 
 _SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
-            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver", "WaveSolver")
+            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver", "WaveSolver", "ElastodynamicsSolver")
 
 
 def main(case_input):
@@ -52,6 +52,8 @@ def main(case_input):
         from .ViscoelasticitySolver import ViscoelasticitySolver as cls
     elif solver_name == "WaveSolver":
         from .WaveSolver import WaveSolver as cls
+    elif solver_name == "ElastodynamicsSolver":
+        from .ElastodynamicsSolver import ElastodynamicsSolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

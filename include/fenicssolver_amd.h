@@ -536,6 +536,67 @@ int fs_wave_start(fs_matrix_t K, fs_wave_state_t state, const double* u0, const 
 int fs_wave_advance(fs_matrix_t K, fs_wave_state_t state, int64_t n_steps, const double* load_scale, const double* dirichlet_scale,
                     int64_t n_receivers, const int32_t* receiver_dofs, double* traces, double* energy, fs_wave_info* info);
 
+/* ---- Implicit structural dynamics (ElastodynamicsSolver; the reference has no transient structural solver) --------------------
+ * M a + C v + K u = s_f(t) F on a vector CG1 or CG2 space over tetrahedra or triangles (plane strain), one rank: K the isotropic
+ * elasticity operator, M the consistent mass, C = eta_M M + eta_K K, marched by the Chung-Hulbert generalized-alpha scheme.  With
+ * x_{n+1-alpha} = (1 - alpha) x_{n+1} + alpha x_n the balance of a step is
+ *   M a_{n+1-am} + C v_{n+1-af} + K u_{n+1-af} = s_f(t_n + (1 - af) dt) F,
+ *   u~ = u_n + dt v_n + dt^2 (1/2 - beta) a_n,   v~ = v_n + dt (1 - gamma) a_n,
+ *   a_{n+1} = (u_{n+1} - u~) / (beta dt^2),       v_{n+1} = v~ + gamma dt a_{n+1}.
+ * Solved for u_{n+1} a step is ONE linear solve with the fixed operator
+ *   K_eff = c_M M + c_K K,   c_M = (1 - am)/(beta dt^2) + (1 - af) gamma eta_M/(beta dt),   c_K = (1 - af)(1 + gamma eta_K/(beta dt)),
+ *   cv  = (1 - af)(v~ - gamma/(beta dt) u~) + af v_n,
+ *   p   = (1 - am) u~/(beta dt^2) - am a_n - eta_M cv - c_M g_ext,      q = -af u_n - eta_K cv - c_K g_ext,
+ *   rhs = s_f F + M p + K q on the free rows,   rhs_i = g_i s_g(t_{n+1}) on the Dirichlet rows;
+ * g_ext = the next Dirichlet values on the Dirichlet dofs, zero elsewhere (its two terms are the lifting of the Dirichlet columns).
+ * K and M are the operators WITHOUT eliminated rows.  K_eff, with its Dirichlet rows and columns eliminated, is the caller's: built
+ * once per step length and solved with (fs_amg_solve / fs_krylov_solve) between fs_dyn_predict and fs_dyn_correct.
+ * The state object holds u, v, a, the work vectors p, q, M p, K q, the load F (a Dirichlet row keeps g_i in the slot of F_i), one
+ * flag byte per row (Dirichlet bit, receiver bit), the constants of the scheme and the step counter n (-1: not started).
+ *   fs_dyn_state_create      a zero state on a vector CG space                      fs_dyn_state_destroy   frees it
+ *   fs_dyn_state_configure   dt, (alpha_m, alpha_f, beta, gamma), eta_M, eta_K, load[n_dofs] (NULL: none), the Dirichlet dofs and
+ *                            values (a dof named twice takes the last value); keeps (u, v, a) and the step counter
+ *   fs_dyn_state_set / get   (u, v, a) and the step counter from / to the host (get: any pointer may be NULL)
+ *   fs_dyn_state_get_work    p, q, M p, K q of the last fs_dyn_predict to the host (any pointer may be NULL): for checks
+ *   fs_dyn_state_info        waits for the device: the times of the last predict / correct, the non-finite rows seen since the start
+ *   fs_dyn_start_rhs         takes (u_0, v_0) and forms rhs = s_f(t_0) F - C v_0 - K u_0 on the free rows, 0 on the Dirichlet rows;
+ *   fs_dyn_start             takes a_0, solved by the caller from that right-hand side with the eliminated M (a_0 = 0 on Dirichlet
+ *                            rows): the state then holds (u_0, v_0, a_0), n = 0
+ *   fs_dyn_predict           one kernel forms p and q, two products through the dispatch of fs_spmv, one kernel forms rhs; nothing
+ *                            returns to the host.  load_scale = s_f(t_n + (1 - af) dt), dirichlet_scale_next = s_g(t_{n+1})
+ *   fs_dyn_correct           x = u_{n+1}: one kernel forms a_{n+1}, v_{n+1}, takes u_{n+1} in place (Dirichlet rows by the same
+ *                            formulas), writes the receiver samples of u_{n+1} and counts non-finite rows; n -> n+1.  It waits for
+ *                            the device only when samples is not NULL (samples[n_receivers])
+ *   fs_dyn_energy            out = (1/2 v^T M v, 1/2 u^T K u): two products, per-workgroup partials summed in a fixed order
+ * No floating-point atomics: a march gives the same bits however it is split into calls.  FS_ERR_INVALID with a message: scalar or
+ * DG spaces, several ranks, matrices of another space, dt <= 0 or not finite, parameters outside alpha_m <= alpha_f <= 1/2,
+ * beta >= 1/4 + (alpha_f - alpha_m)/2 (not unconditionally stable), eta < 0, a receiver or Dirichlet dof out of range, a state that was
+ * not configured / started; a refused call leaves the state as it was. */
+typedef struct fs_dyn_state_s* fs_dyn_state_t;
+typedef struct fs_dyn_info {
+    double predict_ms;            /* HIP-event time of the last fs_dyn_predict (both kernels and both products) */
+    double predict_pointwise_ms;  /* ... of its two kernels alone */
+    double correct_ms;            /* ... of the kernel of the last fs_dyn_correct */
+    int64_t n_nonfinite;          /* rows found non-finite by fs_dyn_correct since the start */
+    int64_t first_nonfinite_step; /* the first step n+1 that had one; -1: none */
+    int64_t step;                 /* the state's step counter n */
+} fs_dyn_info;
+int fs_dyn_state_create(fs_space_t space, fs_dyn_state_t* out);
+int fs_dyn_state_destroy(fs_dyn_state_t state);
+int fs_dyn_state_configure(fs_dyn_state_t state, double dt, double alpha_m, double alpha_f, double beta, double gamma, double eta_m,
+                           double eta_k, const double* load, int64_t n_dirichlet, const int32_t* dirichlet_dofs,
+                           const double* dirichlet_values);
+int fs_dyn_state_set(fs_dyn_state_t state, const double* u, const double* v, const double* a, int64_t step);
+int fs_dyn_state_get(fs_dyn_state_t state, double* u, double* v, double* a, int64_t* step);
+int fs_dyn_state_get_work(fs_dyn_state_t state, double* p, double* q, double* mp, double* kq);
+int fs_dyn_state_info(fs_dyn_state_t state, fs_dyn_info* info);
+int fs_dyn_start_rhs(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t state, const double* u0, const double* v0, double load_scale0,
+                     fs_vector_t rhs);
+int fs_dyn_start(fs_dyn_state_t state, fs_vector_t a0);
+int fs_dyn_predict(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t state, double load_scale, double dirichlet_scale_next, fs_vector_t rhs);
+int fs_dyn_correct(fs_dyn_state_t state, fs_vector_t x, int64_t n_receivers, const int32_t* receiver_dofs, double* samples);
+int fs_dyn_energy(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t state, double* out);
+
 /* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
  * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
  * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
