@@ -1,4 +1,5 @@
-"""ElastodynamicsSolver — implicit structural dynamics (generalized-alpha) on vector P1 / P2, GPU back end.
+"""ElastodynamicsSolver — structural dynamics on vector P1 / P2, GPU back end: implicit (generalized-alpha, the default) or explicit
+(central differences with a lumped mass, vector P1; the last paragraph).
 
 The reference has no transient structural solver: its ``solving_dynamics`` branch (kept as it is in LinearElasticitySolver) subtracts
 rho * a with a lagged finite difference inside a static solve.  This class fills the gap with the textbook model, so there is no
@@ -39,6 +40,30 @@ n_receivers, dim]; ``energy()`` [k, 3] = (step, E_kin = 1/2 v^T M v, E_pot = 1/2
 Several ranks, periodic spaces, ``transient: False``, ``temperature_distribution``, ``point_source``, ``surface_source``, a density
 <= 0, an unstable parameter set, both ``spectral_radius`` and explicit parameters and a table shorter than the run raise SolverError
 before any device call; a non-finite state after a step raises SolverError naming the step.
+
+``dynamics_settings['scheme']`` = ``'implicit'`` (the default: everything above) or ``'explicit'``: central differences with the
+LUMPED mass m = M 1 (the row sums of the consistent mass above, formed by one product with a vector of ones; > 0 on CG1) and
+C = eta_M diag(m), for impact, stress waves and short transients, where accuracy bounds the step anyway.  The state is (u_n, w_n)
+with w_n = v_{n-1/2}; with y_n = K u_n and alpha = eta_M dt / 2 a step n -> n+1 is
+    (1 + alpha) w_{n+1/2} = (1 - alpha) w_{n-1/2} + dt (s_f[n] F - y_n) / m,   u_{n+1} = u_n + dt w_{n+1/2},
+Dirichlet rows take u_{n+1} = g s_g[n+1], w_{n+1/2} = (u_{n+1} - u_n) / dt, and the start is a_0 = (s_f[0] F - y_0) / m - eta_M v_0,
+w_{1/2} = v_0 + dt/2 a_0.  A step is not a solve: one product with K and one pointwise update, and the steps of a batch run back to
+back on the device with no host round trip (fs_dyn_explicit_advance; include/fenicssolver_amd.h).  There is no K_eff and no AMG:
+``operator_assemblies`` and ``amg_setups`` stay 0.  Vector CG1 only (a row-sum lumped P2 mass is not positive), uniform steps only.
+Keys: ``rayleigh_mass`` eta_M, ``energy_freq``, ``batch_steps`` (caps the steps of one device call; a batch also ends at the next
+plot, save or energy step); ``spectral_radius``, the four generalized-alpha parameters and a ``rayleigh_stiffness`` != 0 are
+refused - stiffness-proportional damping is not offered by the explicit scheme.  TIME FACTORS DIFFER FROM THE IMPLICIT SCHEME: both
+s_f and s_g are taken at the time points t_0 .. t_N, so a 'table' for either holds N + 1 values, one per time POINT (the implicit
+scheme keeps one value per STEP for loads).  Step bounds as in WaveSolver: ``critical_time_step()`` = 2/sqrt(lambda_G), lambda_G =
+max_i sum_j |K_ij| / m_i, below which the march is stable; ``time_step_bounds()`` adds 2/sqrt(lambda_P) from 40 power iterations of
+x <- diag(1/m) K x on the rows that are not Dirichlet (products on the device): a ``time_step`` above it raises SolverError before any
+marching call, one between the two logs a warning; neither bound depends on eta_M.  Results: ``velocity()`` and ``acceleration()`` are
+the full-step v_N = (w_{N-1/2} + w+)/2 and a_N = (w+ - w_{N-1/2})/dt with w+ the recurrence's next half-step velocity under s_f[N]
+(one more product; the state is not changed; Dirichlet rows: v = w_{N-1/2}, a = 0), refreshed whenever a frame is published for plot
+or save; ``receiver_traces()`` as above; ``energy()`` [k, 3] = (n + 1, E_kin = 1/2 sum m w_{n+1/2}^2, E_pot = 1/2 u_{n+1}^T K u_n) of
+the step n -> n+1 for every ``energy_freq``-th step - the discrete energy lives on the half steps, so there is NO step-0 row under
+this scheme; ``step_stats`` one entry per batch: ``first_step``, ``steps``, ``device_ms``, ``ms_per_step``.  A non-finite step raises
+SolverError naming the step range and both step bounds.
 """
 from __future__ import annotations
 
@@ -54,7 +79,9 @@ from .LinearElasticitySolver import LinearElasticitySolver
 from .WaveSolver import tabulate_time_function, nearest_vertices
 
 _EXPLICIT = ('alpha_m', 'alpha_f', 'beta', 'gamma')
-_DYNAMICS_KEYS = set(_EXPLICIT) | {'spectral_radius', 'rayleigh_mass', 'rayleigh_stiffness', 'energy_freq'}
+_DYNAMICS_KEYS = set(_EXPLICIT) | {'spectral_radius', 'rayleigh_mass', 'rayleigh_stiffness', 'energy_freq', 'scheme', 'batch_steps'}
+_SCHEMES = ('implicit', 'explicit')
+POWER_ITERATIONS = 40
 
 
 def generalized_alpha(spectral_radius):
@@ -90,6 +117,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         self._dyn_serial = 0
         self._K = self._M = None
         self._traces = self._energy = self._velocity = self._acceleration = None
+        self._bounds = self._mass = None          # explicit scheme: (2/sqrt(lambda_G), 2/sqrt(lambda_P)), the lumped mass
 
     # ------------------------------------------------------------------ settings (host only)
     def dynamics_settings(self):
@@ -98,6 +126,39 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         if unknown:
             raise SolverError('ElastodynamicsSolver: dynamics_settings: unknown key(s) {}'.format(sorted(unknown)))
         return given
+
+    def scheme(self):
+        """'implicit' (generalized-alpha, the default) or 'explicit' (central differences with a lumped mass)"""
+        ds = self.dynamics_settings()
+        s = ds.get('scheme', 'implicit')
+        if s not in _SCHEMES:
+            raise SolverError("ElastodynamicsSolver: dynamics_settings: 'scheme' must be 'implicit' or 'explicit', got {!r}".format(s))
+        if s == 'implicit' and 'batch_steps' in ds:
+            raise SolverError("ElastodynamicsSolver: dynamics_settings: 'batch_steps' belongs to the explicit scheme (the implicit one "
+                              "solves step by step)")
+        return s
+
+    def explicit_parameters(self):
+        """{'rayleigh_mass', 'batch_steps'} of the explicit scheme, checked (SolverError on a key the scheme does not take)"""
+        ds = self.dynamics_settings()
+        taken = [k for k in ('spectral_radius',) + _EXPLICIT if k in ds]
+        if taken:
+            raise SolverError("ElastodynamicsSolver: dynamics_settings: {} belong(s) to the generalized-alpha scheme and mean(s) nothing "
+                              "under 'scheme': 'explicit'".format(taken))
+        for k in ('rayleigh_mass', 'rayleigh_stiffness'):
+            if k in ds and (isinstance(ds[k], bool) or not isinstance(ds[k], numbers.Real)):
+                raise SolverError('ElastodynamicsSolver: dynamics_settings: {} must be a number, got {!r}'.format(k, ds[k]))
+        if float(ds.get('rayleigh_stiffness', 0.0)) != 0.0:
+            raise SolverError("ElastodynamicsSolver: dynamics_settings: 'rayleigh_stiffness' = {}: stiffness-proportional damping is not "
+                              "offered by the explicit scheme (a lagged treatment needs a second field per product and changes the step "
+                              "bound); use 'rayleigh_mass' or 'scheme': 'implicit'".format(ds['rayleigh_stiffness']))
+        eta_m = float(ds.get('rayleigh_mass', 0.0))
+        if not (eta_m >= 0.0 and math.isfinite(eta_m)):
+            raise SolverError('ElastodynamicsSolver: rayleigh_mass must be >= 0, got {}'.format(eta_m))
+        bs = ds.get('batch_steps')
+        if bs is not None and (isinstance(bs, bool) or not isinstance(bs, numbers.Integral) or bs < 1):
+            raise SolverError("ElastodynamicsSolver: dynamics_settings: 'batch_steps' must be a positive number of steps, got {!r}".format(bs))
+        return {'rayleigh_mass': eta_m, 'batch_steps': None if bs is None else int(bs)}
 
     def generalized_alpha_parameters(self):
         """{'alpha_m', 'alpha_f', 'beta', 'gamma', 'rayleigh_mass', 'rayleigh_stiffness'}, checked (SolverError on a bad set)"""
@@ -166,11 +227,24 @@ class ElastodynamicsSolver(LinearElasticitySolver):
             return all(ElastodynamicsSolver._is_zero_value(c) for c in v)
         return False
 
+    def uniform_step(self):
+        """dt of the explicit scheme: every step of the run has this length"""
+        dts = self.step_lengths()
+        dt = float(dts[0])
+        if np.any(np.abs(dts - dt) > 1e-9 * dt):
+            raise SolverError("ElastodynamicsSolver: non-uniform steps ('time_series') are not supported by the explicit scheme: a uniform "
+                              "'time_step' only")
+        return dt
+
     def time_factors(self):
-        """(s_f [N] at t_n + (1 - alpha_f) dt_n, s_g [N + 1] at the time points)"""
+        """implicit: (s_f [N] at t_n + (1 - alpha_f) dt_n, s_g [N + 1] at the time points); explicit: (s_f [N + 1], s_g [N + 1]), both
+        at the time points"""
         t, dts = self.time_points(), self.step_lengths()
-        af = self.generalized_alpha_parameters()['alpha_f']
-        sf = tabulate_time_function(self.settings.get('load_time_function'), t[:-1] + (1.0 - af) * dts, 'load_time_function')
+        if self.scheme() == 'explicit':
+            sf = tabulate_time_function(self.settings.get('load_time_function'), t, 'load_time_function')
+        else:
+            af = self.generalized_alpha_parameters()['alpha_f']
+            sf = tabulate_time_function(self.settings.get('load_time_function'), t[:-1] + (1.0 - af) * dts, 'load_time_function')
         sg, owner = None, None
         for name, bc_settings in (self.boundary_conditions or {}).items():
             bc = self.get_boundary_variable(bc_settings)
@@ -211,7 +285,14 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         rho = self.material_field('density')
         if not (np.all(np.asarray(rho) > 0.0) and np.all(np.isfinite(rho))):
             raise SolverError("ElastodynamicsSolver: material 'density' must be positive")
-        self.generalized_alpha_parameters()
+        if self.scheme() == 'explicit':
+            self.explicit_parameters()
+            if V.degree() != 1:
+                raise SolverError("ElastodynamicsSolver: CG{} spaces are not supported by the explicit scheme (vector CG1 only: a row-sum "
+                                  "lumped P2 mass is not positive)".format(V.degree()))
+            self.uniform_step()
+        else:
+            self.generalized_alpha_parameters()
         self.energy_freq()
         self.time_factors()               # (the time grid and every table against the length of the run)
         self.lame_parameters()
@@ -283,7 +364,8 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         """K, M, F, the Dirichlet rows and the state object on the device.  Everything here is set-up cost."""
         from . import backend
         self._refuse_unsupported()
-        par = self.generalized_alpha_parameters()
+        explicit = self.scheme() == 'explicit'
+        par = self.explicit_parameters() if explicit else self.generalized_alpha_parameters()
         sf, sg = self.time_factors()
         u0, v0 = self.initial_fields()
         self.snap_receivers()
@@ -322,10 +404,160 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         if loc is not None and len(rec):
             rec = loc.dofs(rec, np.zeros(len(rec)))[0]
         self._K, self._M = K, M
-        self.state = backend.DynamicsState(V)
         self._dirichlet = (np.asarray(dofs, dtype=np.int32), np.asarray(vals, dtype=np.float64))
         self._load, self._par = load, par
+        if explicit:
+            self._setup_explicit(V)
+        else:
+            self.state = backend.DynamicsState(V)
         return V, u0, v0, sf, sg, rec.astype(np.int32)
+
+    # ------------------------------------------------------------------ the explicit scheme
+    def _setup_explicit(self, V):
+        """m = M 1, both step bounds and the state object of the central-difference marcher"""
+        from . import backend
+        K, M = self._K, self._M
+        n = V.n_owned
+        ones, md = backend.DeviceVector(V.n_local, np.ones(V.n_local)), backend.DeviceVector(n)
+        M.spmv(ones, md)
+        m = md.get()[:n].copy()
+        ones.close()
+        md.close()
+        M.close()                                                 # the consistent mass has done its work
+        self._M = None
+        if not (np.all(m > 0.0) and np.all(np.isfinite(m))):
+            raise SolverError('ElastodynamicsSolver: the lumped mass M 1 is not positive on every row (smallest entry {})'.format(m.min()))
+        dofs, vals = self._dirichlet
+        rp, ci, va, _ = K.to_csr()
+        lam_g = float(np.max(np.add.reduceat(np.abs(va), rp[:-1].astype(np.int64)) / m))
+        lam_p = self._power_iteration(K, m, dofs)
+        self._mass, self._bounds = m, (2.0 / math.sqrt(lam_g), 2.0 / math.sqrt(lam_p))
+        dt = self.uniform_step()
+        if dt > self._bounds[1]:
+            raise SolverError('ElastodynamicsSolver: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on '
+                              'the largest eigenvalue): the explicit march is certain to blow up; the stable bound 2/sqrt(lambda_G) is '
+                              '{:.6g}'.format(dt, self._bounds[1], self._bounds[0]))
+        if dt > self._bounds[0]:
+            self.logger.warning('ElastodynamicsSolver: time_step %.6g lies between the stable bound 2/sqrt(lambda_G) = %.6g and '
+                                '2/sqrt(lambda_P) = %.6g', dt, self._bounds[0], self._bounds[1])
+        self.state = backend.ExplicitDynamicsState(V)
+        self.state.configure(dt, self._par['rayleigh_mass'], m, load=self._load, dirichlet_dofs=dofs, dirichlet_values=vals)
+
+    def _power_iteration(self, K, m, bc_dofs):
+        """Rayleigh quotient x^T K x / x^T diag(m) x after POWER_ITERATIONS steps of x <- diag(1/m) K x on the rows that are not
+        Dirichlet: a lower bound on the largest eigenvalue of the operator the march sees.  The products run on the device."""
+        from . import backend
+        n = len(m)
+        free = np.ones(n)
+        free[np.asarray(bc_dofs, dtype=np.int64)] = 0.0
+        x = np.random.default_rng(2024).standard_normal(n) * free
+        xd, yd = backend.DeviceVector(n), backend.DeviceVector(n)
+        lam = 0.0
+        for _ in range(POWER_ITERATIONS):
+            x /= math.sqrt(float(x @ (m * x)))
+            xd.set(x)
+            K.spmv(xd, yd)
+            lam = xd.dot(yd)                    # x^T K x with x^T diag(m) x = 1
+            x = free * yd.get() / m
+        xd.close()
+        yd.close()
+        if not (lam > 0.0 and np.isfinite(lam)):
+            raise SolverError('ElastodynamicsSolver: the power iteration gave lambda_P = {}'.format(lam))
+        return lam
+
+    def _explicit_only(self, what):
+        if self.scheme() != 'explicit':
+            raise SolverError("ElastodynamicsSolver: {} belongs to 'scheme': 'explicit' (the implicit scheme is unconditionally "
+                              "stable)".format(what))
+
+    def critical_time_step(self):
+        """explicit scheme: 2 / sqrt(lambda_G), lambda_G = max_i sum_j |K_ij| / m_i: the step below which the march is stable"""
+        return self.time_step_bounds()[0]
+
+    def time_step_bounds(self):
+        """explicit scheme: (2 / sqrt(lambda_G), 2 / sqrt(lambda_P)): stable below the first, certain to blow up above the second.
+        Neither depends on eta_M.  A ``time_step`` above the second raises SolverError here as it does in solve()."""
+        self._explicit_only('a step bound')
+        if self._bounds is None:
+            self._setup()
+        return self._bounds
+
+    def _batch_end(self, n, N):
+        """the step at which the batch that starts at step n ends: the next plot / save / energy step, at most batch_steps away"""
+        end = N
+        for freq in (self.report_settings.get('plotting_freq', 0), self.report_settings.get('saving_freq', 0), self.energy_freq()):
+            if freq and freq > 0:
+                end = min(end, (n // int(freq) + 1) * int(freq))
+        bs = self._par['batch_steps']
+        return end if bs is None else min(end, n + bs)
+
+    def _blow_up_message(self, first, end):
+        return ('ElastodynamicsSolver: the state or its energy is not finite in steps {} .. {} (time_step {:.6g}; stable below '
+                '2/sqrt(lambda_G) = {:.6g}, certain to blow up above 2/sqrt(lambda_P) = {:.6g})'.format(
+                    first, end, self.uniform_step(), self._bounds[0], self._bounds[1]))
+
+    def _publish_explicit(self, sf_n):
+        u, _, _ = self.state.get()
+        v, a = self.state.full_step(self._K, sf_n)
+        self.w_current = self.result = self._function(u)
+        self._velocity, self._acceleration = self._function(v), self._function(a)
+
+    def _solve_explicit(self):
+        V, u0, v0, sf, sg, rec = self._setup()
+        t = self.time_points()
+        dt = self.uniform_step()
+        N, d = len(t) - 1, self.dimension
+        st, K, m = self.state, self._K, self._mass
+        efreq = self.energy_freq()
+        self.operator_assemblies = self.amg_setups = 0
+        self.step_stats = []
+        self._saved_frames = []
+        traces = np.zeros((N + 1, len(rec) // d, d))
+        energy = []
+        # step 0 -> 1 on the device; its energy from the fields and the product of the start (set-up cost)
+        u0d = self._to_dev(u0)
+        st.start(K, u0d, self._to_dev(v0), sf[0], sg[0], sg[1])
+        u1, w1, _ = st.get()
+        if not (np.all(np.isfinite(u1)) and np.all(np.isfinite(w1))):
+            raise SolverError(self._blow_up_message(0, 1))
+        if len(rec):
+            traces[0], traces[1] = u0d[rec].reshape(-1, d), u1[rec].reshape(-1, d)
+        if efreq == 1:
+            energy.append((1, 0.5 * float(np.sum(m * w1 * w1)), 0.5 * float(u1 @ st.work())))
+        pvd = self.report_settings.get('result_filename') or 'result_file.pvd'
+        n = 1                       # the state holds (u_n, w_n)
+        self.current_step, self.current_time = 1, float(t[1])
+        while True:
+            published = self._due('plotting_freq') or self._due('saving_freq')
+            if published:
+                self._publish_explicit(sf[n])
+                if self._due('plotting_freq'):
+                    self.plot()
+                if self._due('saving_freq'):
+                    self.save(pvd)
+            if n >= N:
+                break
+            end = self._batch_end(n, N)
+            k = end - n
+            out = st.advance(K, sf[n:end], sg[n + 1:end + 1], receivers=rec, traces=len(rec) > 0, energy=True, info=True)
+            self.step_stats.append({'first_step': n, 'steps': k, 'device_ms': out['device_ms'], 'ms_per_step': out['device_ms'] / k})
+            if out['n_nonfinite']:
+                raise SolverError(self._blow_up_message(n + out['first_nonfinite_step'], end))
+            if len(rec):
+                traces[n + 1:end + 1] = out['traces'].reshape(k, -1, d)
+            if efreq:
+                for j in range(n, end):
+                    if (j + 1) % efreq == 0:
+                        energy.append((j + 1, float(out['energy'][j - n, 0]), float(out['energy'][j - n, 1])))
+            n = end
+            self.current_step, self.current_time = n, float(t[n])
+            if efreq and n % efreq == 0:
+                self.logger.info('ElastodynamicsSolver: step %d time %g energy %.12g (%.3f ms per step)', n, self.current_time,
+                                 energy[-1][1] + energy[-1][2], self.step_stats[-1]['ms_per_step'])
+        if not published:
+            self._publish_explicit(sf[N])
+        self._traces, self._energy = traces, np.asarray(energy, dtype=np.float64).reshape(-1, 3)
+        return self.w_current
 
     def _density_spec(self, c):
         return c * float(self._rho) if np.ndim(self._rho) == 0 else ('cell', c * self._rho)
@@ -389,6 +621,8 @@ class ElastodynamicsSolver(LinearElasticitySolver):
 
     def solve_transient(self):
         from . import backend
+        if self.scheme() == 'explicit':
+            return self._solve_explicit()
         V, u0, v0, sf, sg, rec = self._setup()
         t, dts = self.time_points(), self.step_lengths()
         N, d = len(dts), self.dimension
@@ -471,11 +705,11 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         return what
 
     def velocity(self):
-        """v of the last step, a Function"""
+        """v of the last step, a Function (explicit scheme: the full-step v_N = (w_{N-1/2} + w+) / 2)"""
         return self._need(self._velocity)
 
     def acceleration(self):
-        """a of the last step, a Function"""
+        """a of the last step, a Function (explicit scheme: the full-step a_N = (w+ - w_{N-1/2}) / dt)"""
         return self._need(self._acceleration)
 
     def receiver_traces(self):
@@ -483,5 +717,6 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         return self._need(self._traces)
 
     def energy(self):
-        """[k, 3]: (step, E_kin, E_pot) at step 0 and every energy_freq-th step"""
+        """[k, 3]: (step, E_kin, E_pot) at step 0 and every energy_freq-th step; explicit scheme: (n + 1, E_kin, E_pot) of the step
+        n -> n+1 for every energy_freq-th step, and no step-0 row (the discrete energy lives on the half steps)"""
         return self._need(self._energy)

@@ -96,6 +96,10 @@ class fs_dyn_info(C.Structure):
                 ("first_nonfinite_step", C.c_int64), ("step", C.c_int64)]
 
 
+class fs_dyn_explicit_info(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("n_nonfinite", C.c_int64), ("first_nonfinite_step", C.c_int64), ("step", C.c_int64)]
+
+
 class fs_dg_form(C.Structure):
     _fields_ = [("conductivity", C.c_double), ("capacity", C.c_double), ("velocity", C.c_double * 3), ("alpha", C.c_double),
                 ("operator_scale", C.c_double), ("mass_scale", C.c_double), ("n_facets", C.c_int64), ("facet_cell", c_i32p),
@@ -277,6 +281,15 @@ SIGNATURES = {
     "fs_dyn_predict": (C.c_int, [_H, _H, _H, C.c_double, C.c_double, _H]),
     "fs_dyn_correct": (C.c_int, [_H, _H, c_i64, c_i32p, c_f64p]),
     "fs_dyn_energy": (C.c_int, [_H, _H, _H, c_f64p]),
+    "fs_dyn_explicit_state_create": (C.c_int, [_H, C.POINTER(_H)]),
+    "fs_dyn_explicit_state_destroy": (C.c_int, [_H]),
+    "fs_dyn_explicit_state_configure": (C.c_int, [_H, C.c_double, C.c_double, c_f64p, c_f64p, c_i64, c_i32p, c_f64p]),
+    "fs_dyn_explicit_state_set": (C.c_int, [_H, c_f64p, c_f64p, c_i64]),
+    "fs_dyn_explicit_state_get": (C.c_int, [_H, c_f64p, c_f64p, c_i64p]),
+    "fs_dyn_explicit_state_get_work": (C.c_int, [_H, c_f64p]),
+    "fs_dyn_explicit_start": (C.c_int, [_H, _H, c_f64p, c_f64p, C.c_double, C.c_double, C.c_double]),
+    "fs_dyn_explicit_advance": (C.c_int, [_H, _H, c_i64, c_f64p, c_f64p, c_i64, c_i32p, c_f64p, c_f64p, C.POINTER(fs_dyn_explicit_info)]),
+    "fs_dyn_explicit_full_step": (C.c_int, [_H, _H, C.c_double, c_f64p, c_f64p]),
     "fs_assemble_large_deformation":(C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),

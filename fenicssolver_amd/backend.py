@@ -855,6 +855,82 @@ class DynamicsState(_Handle):
         return float(out[0]), float(out[1])
 
 
+class ExplicitDynamicsState(_Handle):
+    """Device state of the central-difference marcher on a vector CG1 space (fs_dyn_explicit_*): u_n, w_n = v_{n-1/2}, the last
+    product y = K u, the lumped mass m, the load F, the Dirichlet dofs with their values, dt, eta_M and the step counter n.  Arrays
+    are in DEVICE dof order.  K is the operator WITHOUT eliminated rows."""
+    _destroy = "fs_dyn_explicit_state_destroy"
+
+    def __init__(self, space):
+        super().__init__()
+        self.space = space
+        self.n = int(space.n_owned)
+        L.check(L.load().fs_dyn_explicit_state_create(space.h, C.byref(self.h)), "fs_dyn_explicit_state_create")
+
+    def _field(self, a, who, name):
+        a = L.f64(a).ravel()
+        if a.size != self.n:
+            raise BackendError("ExplicitDynamicsState.%s: %s has %d entries, the space has %d dofs" % (who, name, a.size, self.n))
+        return a
+
+    def configure(self, dt, eta_m, mass, load=None, dirichlet_dofs=None, dirichlet_values=None):
+        m = self._field(mass, "configure", "mass")
+        f = None if load is None else self._field(load, "configure", "load")
+        dofs = L.i32([] if dirichlet_dofs is None else dirichlet_dofs).ravel()
+        vals = L.f64(np.broadcast_to(0.0 if dirichlet_values is None else dirichlet_values, dofs.shape))
+        L.check(L.load().fs_dyn_explicit_state_configure(self.h, float(dt), float(eta_m), L.p_f64(m), L.p_f64(f), dofs.size, L.p_i32(dofs),
+                                                         L.p_f64(vals)), "fs_dyn_explicit_state_configure")
+
+    def set(self, u, w, step):
+        u, w = self._field(u, "set", "u"), self._field(w, "set", "w")
+        L.check(L.load().fs_dyn_explicit_state_set(self.h, L.p_f64(u), L.p_f64(w), int(step)), "fs_dyn_explicit_state_set")
+
+    def get(self):
+        """(u_n, w_n = v_{n-1/2}, n)"""
+        u, w, k = np.empty(self.n), np.empty(self.n), C.c_int64(0)
+        L.check(L.load().fs_dyn_explicit_state_get(self.h, L.p_f64(u), L.p_f64(w), C.byref(k)), "fs_dyn_explicit_state_get")
+        return u, w, k.value
+
+    def work(self):
+        """y = K u of the last product"""
+        y = np.empty(self.n)
+        L.check(L.load().fs_dyn_explicit_state_get_work(self.h, L.p_f64(y)), "fs_dyn_explicit_state_get_work")
+        return y
+
+    def start(self, K, u0, v0, load_scale0=1.0, dirichlet_scale0=1.0, dirichlet_scale1=1.0):
+        """(u_1, w_{1/2}) from (u_0, v_0): n = 1"""
+        u0, v0 = self._field(u0, "start", "u0"), self._field(v0, "start", "v0")
+        L.check(L.load().fs_dyn_explicit_start(K.h, self.h, L.p_f64(u0), L.p_f64(v0), float(load_scale0), float(dirichlet_scale0),
+                                               float(dirichlet_scale1)), "fs_dyn_explicit_start")
+
+    def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
+        """len(load_scale) steps on the device without a host round trip (fs_dyn_explicit_advance); step k of the call advances
+        n -> n+1 with load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1].  Returns {'traces': [n_steps, n_receivers] or None,
+        'energy': [n_steps, 2] = (kinetic, potential) or None, and with info 'device_ms', 'n_nonfinite', 'first_nonfinite_step',
+        'step'}."""
+        sf, sg = L.f64(load_scale).ravel(), L.f64(dirichlet_scale).ravel()
+        if sf.size != sg.size:
+            raise BackendError("ExplicitDynamicsState.advance: %d load factors and %d Dirichlet factors" % (sf.size, sg.size))
+        ns = sf.size
+        rec = L.i32([] if receivers is None else receivers).ravel()
+        tr = np.empty((ns, rec.size)) if (traces and rec.size) else None
+        en = np.empty((ns, 2)) if energy else None
+        inf = L.fs_dyn_explicit_info() if info else None
+        L.check(L.load().fs_dyn_explicit_advance(K.h, self.h, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
+                                                 L.p_f64(tr), L.p_f64(en), C.byref(inf) if info else None), "fs_dyn_explicit_advance")
+        out = {"traces": tr, "energy": en}
+        if info:
+            out.update(device_ms=inf.device_ms, n_nonfinite=int(inf.n_nonfinite), first_nonfinite_step=int(inf.first_nonfinite_step),
+                       step=int(inf.step))
+        return out
+
+    def full_step(self, K, load_scale_n):
+        """(v_n, a_n) of the state's time point under s_f[n] = load_scale_n: one product, the state does not change"""
+        v, a = np.empty(self.n), np.empty(self.n)
+        L.check(L.load().fs_dyn_explicit_full_step(K.h, self.h, float(load_scale_n), L.p_f64(v), L.p_f64(a)), "fs_dyn_explicit_full_step")
+        return v, a
+
+
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):
     """b[vertex*9 + 3i + j] = int (nu (grad u + grad u^T) - p I)_ij phi_vertex dx for a Taylor-Hood iterate w.
     viscosity_law = (p_ref, exponent): nu (p / p_ref)^exponent."""

@@ -597,6 +597,61 @@ int fs_dyn_predict(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t state, double lo
 int fs_dyn_correct(fs_dyn_state_t state, fs_vector_t x, int64_t n_receivers, const int32_t* receiver_dofs, double* samples);
 int fs_dyn_energy(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t state, double* out);
 
+/* ---- Explicit structural dynamics (ElastodynamicsSolver, 'scheme': 'explicit') --------------------------------------------------
+ * M a + C v + K u = s_f(t) F on a vector CG1 space over tetrahedra or triangles (plane strain), one rank: central differences with
+ * the lumped mass m = M 1 (the row sums of the consistent mass, > 0 on CG1) and mass-proportional damping C = eta_M diag(m), so a
+ * step is ONE product with the elasticity operator K (WITHOUT eliminated rows) and one pointwise update - no solve.  The state is
+ * (u_n, w_n) with w_n = v_{n-1/2}; with y_n = K u_n and alpha = eta_M dt / 2 a step n -> n+1 (n >= 1) is, per row i,
+ *   (1 + alpha) w_{n+1/2} = (1 - alpha) w_{n-1/2} + dt (s_f[n] F - y_n) / m,      u_{n+1} = u_n + dt w_{n+1/2},
+ * and on a Dirichlet row u_{n+1} = g_i s_g[n+1], w_{n+1/2} = (u_{n+1} - u_n) / dt.
+ * Start: the Dirichlet rows of u_0 take g s_g[0]; a_0 = (s_f[0] F - y_0) / m - eta_M v_0, w_{1/2} = v_0 + dt/2 a_0, u_1 = u_0 +
+ * dt w_{1/2} (Dirichlet rows by the rule above, with s_g[1]).
+ * Discrete energy of step n -> n+1, its two halves reported separately:
+ *   E_kin = 1/2 sum_i m_i w_{n+1/2,i}^2,   E_pot = 1/2 u_{n+1}^T y_n;
+ * with F = 0 and fixed Dirichlet values E_{n+1/2} - E_{n-1/2} = -eta_M dt v_n^T diag(m) v_n exactly (constant for eta_M = 0).
+ * The state object holds u and w (updated in place), the last product y, the device copies of m, F, the Dirichlet rows and their
+ * values (a Dirichlet row keeps g_i in the slot of F_i), one flag byte per row and the step counter n (0: not started).
+ *   fs_dyn_explicit_state_create     a zero state (n = 0) on a vector CG1 space     fs_dyn_explicit_state_destroy   frees it
+ *   fs_dyn_explicit_state_configure  dt, eta_M and the arrays mass[n_dofs], load[n_dofs] (NULL: none), the Dirichlet dofs and values
+ *                                    (a dof named twice takes the last value); keeps (u, w) and the step counter
+ *   fs_dyn_explicit_state_set / get  (u_n, w_n) and the step counter n >= 1 from / to the host (get: any pointer may be NULL)
+ *   fs_dyn_explicit_state_get_work   the last y to the host: for checks
+ *   fs_dyn_explicit_start            forms (u_1, w_{1/2}) from (u_0, v_0) with s_f[0], s_g[0] and s_g[1]: n = 1
+ *   fs_dyn_explicit_full_step        v_n = (w_{n-1/2} + w+)/2 and a_n = (w+ - w_{n-1/2})/dt of the state's time point, with w+ the
+ *                                    recurrence's w_{n+1/2} under load_scale_n = s_f[n] (one product; w+ is not stored and the state
+ *                                    does not change); on Dirichlet rows v_n = w_{n-1/2}, a_n = 0.  Either output may be NULL
+ * fs_dyn_explicit_advance enqueues n_steps steps on the library's stream with no host synchronisation between them: per step the
+ * product of K through the dispatch of fs_spmv, then ONE update kernel over the rows (the formula, the Dirichlet rows, the
+ * per-workgroup partials of both energy halves, the receiver samples; 57 B per row).  Step k of the call advances n -> n+1 with
+ * load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1]; traces[k][r] = u_{n+1}[receiver_dofs[r]] and energy[k] = (E_kin, E_pot)
+ * of that step (either may be NULL).  The partials are summed in a fixed order by a finishing pass (no floating-point atomics): a
+ * repeated run gives the same bits, and so does any split of a march into calls.  A non-finite field value makes the energy of
+ * its step or of the next one non-finite: the finishing pass counts those steps on the device, read once per call.  The call
+ * waits for the device only if it hands data back (traces, energy or info).  FS_ERR_INVALID with a message: spaces other than
+ * vector CG1, several ranks, a matrix of another space, dt <= 0 or not finite, eta_M < 0, m_i <= 0, a time factor that is not
+ * finite, a receiver or Dirichlet dof out of range, a state that was not configured / started; a refused call leaves the state as
+ * it was. */
+typedef struct fs_dyn_explicit_state_s* fs_dyn_explicit_state_t;
+typedef struct fs_dyn_explicit_info {
+    double device_ms;             /* HIP-event time of the whole batch (products, updates, finishing passes) */
+    int64_t n_nonfinite;          /* steps of this call whose energy (hence: field) is not finite */
+    int64_t first_nonfinite_step; /* the first of them, as its index k in this call; -1: none */
+    int64_t step;                 /* the state's step counter n after the call */
+} fs_dyn_explicit_info;
+int fs_dyn_explicit_state_create(fs_space_t space, fs_dyn_explicit_state_t* out);
+int fs_dyn_explicit_state_destroy(fs_dyn_explicit_state_t state);
+int fs_dyn_explicit_state_configure(fs_dyn_explicit_state_t state, double dt, double eta_m, const double* mass, const double* load,
+                                    int64_t n_dirichlet, const int32_t* dirichlet_dofs, const double* dirichlet_values);
+int fs_dyn_explicit_state_set(fs_dyn_explicit_state_t state, const double* u, const double* w, int64_t step);
+int fs_dyn_explicit_state_get(fs_dyn_explicit_state_t state, double* u, double* w, int64_t* step);
+int fs_dyn_explicit_state_get_work(fs_dyn_explicit_state_t state, double* y);
+int fs_dyn_explicit_start(fs_matrix_t K, fs_dyn_explicit_state_t state, const double* u0, const double* v0, double load_scale0,
+                          double dirichlet_scale0, double dirichlet_scale1);
+int fs_dyn_explicit_advance(fs_matrix_t K, fs_dyn_explicit_state_t state, int64_t n_steps, const double* load_scale,
+                            const double* dirichlet_scale, int64_t n_receivers, const int32_t* receiver_dofs, double* traces,
+                            double* energy, fs_dyn_explicit_info* info);
+int fs_dyn_explicit_full_step(fs_matrix_t K, fs_dyn_explicit_state_t state, double load_scale_n, double* v_out, double* a_out);
+
 /* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
  * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
  * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
