@@ -77,11 +77,11 @@ from .fem import Constant, Expression, Function, interpolate
 from .SolverBase import SolverError, write_vtu
 from .LinearElasticitySolver import LinearElasticitySolver
 from .WaveSolver import tabulate_time_function, nearest_vertices
+from . import time_marching
 
 _EXPLICIT = ('alpha_m', 'alpha_f', 'beta', 'gamma')
 _DYNAMICS_KEYS = set(_EXPLICIT) | {'spectral_radius', 'rayleigh_mass', 'rayleigh_stiffness', 'energy_freq', 'scheme', 'batch_steps'}
 _SCHEMES = ('implicit', 'explicit')
-POWER_ITERATIONS = 40
 
 
 def generalized_alpha(spectral_radius):
@@ -428,10 +428,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         if not (np.all(m > 0.0) and np.all(np.isfinite(m))):
             raise SolverError('ElastodynamicsSolver: the lumped mass M 1 is not positive on every row (smallest entry {})'.format(m.min()))
         dofs, vals = self._dirichlet
-        rp, ci, va, _ = K.to_csr()
-        lam_g = float(np.max(np.add.reduceat(np.abs(va), rp[:-1].astype(np.int64)) / m))
-        lam_p = self._power_iteration(K, m, dofs)
-        self._mass, self._bounds = m, (2.0 / math.sqrt(lam_g), 2.0 / math.sqrt(lam_p))
+        self._mass, self._bounds = m, time_marching.step_bounds(self, K, m, dofs)
         dt = self.uniform_step()
         if dt > self._bounds[1]:
             raise SolverError('ElastodynamicsSolver: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on '
@@ -444,26 +441,8 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         self.state.configure(dt, self._par['rayleigh_mass'], m, load=self._load, dirichlet_dofs=dofs, dirichlet_values=vals)
 
     def _power_iteration(self, K, m, bc_dofs):
-        """Rayleigh quotient x^T K x / x^T diag(m) x after POWER_ITERATIONS steps of x <- diag(1/m) K x on the rows that are not
-        Dirichlet: a lower bound on the largest eigenvalue of the operator the march sees.  The products run on the device."""
-        from . import backend
-        n = len(m)
-        free = np.ones(n)
-        free[np.asarray(bc_dofs, dtype=np.int64)] = 0.0
-        x = np.random.default_rng(2024).standard_normal(n) * free
-        xd, yd = backend.DeviceVector(n), backend.DeviceVector(n)
-        lam = 0.0
-        for _ in range(POWER_ITERATIONS):
-            x /= math.sqrt(float(x @ (m * x)))
-            xd.set(x)
-            K.spmv(xd, yd)
-            lam = xd.dot(yd)                    # x^T K x with x^T diag(m) x = 1
-            x = free * yd.get() / m
-        xd.close()
-        yd.close()
-        if not (lam > 0.0 and np.isfinite(lam)):
-            raise SolverError('ElastodynamicsSolver: the power iteration gave lambda_P = {}'.format(lam))
-        return lam
+        """lambda_P, a lower bound on the largest eigenvalue of diag(1/m) K on the rows that are not Dirichlet"""
+        return time_marching.power_iteration(K, m, bc_dofs, 'ElastodynamicsSolver')
 
     def _explicit_only(self, what):
         if self.scheme() != 'explicit':
@@ -484,12 +463,8 @@ class ElastodynamicsSolver(LinearElasticitySolver):
 
     def _batch_end(self, n, N):
         """the step at which the batch that starts at step n ends: the next plot / save / energy step, at most batch_steps away"""
-        end = N
-        for freq in (self.report_settings.get('plotting_freq', 0), self.report_settings.get('saving_freq', 0), self.energy_freq()):
-            if freq and freq > 0:
-                end = min(end, (n // int(freq) + 1) * int(freq))
-        bs = self._par['batch_steps']
-        return end if bs is None else min(end, n + bs)
+        freqs = (self.report_settings.get('plotting_freq', 0), self.report_settings.get('saving_freq', 0), self.energy_freq())
+        return time_marching.batch_end(n, N, freqs, self._par['batch_steps'])
 
     def _blow_up_message(self, first, end):
         return ('ElastodynamicsSolver: the state or its energy is not finite in steps {} .. {} (time_step {:.6g}; stable below '

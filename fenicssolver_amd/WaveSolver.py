@@ -43,9 +43,7 @@ import numpy as np
 
 from .fem import Constant, Expression, Function, DirichletBC, PointSource, Point, nodal_values, is_constant_value
 from .SolverBase import SolverBase, SolverError
-from . import case
-
-POWER_ITERATIONS = 40
+from . import case, time_marching
 
 
 def ricker(t, frequency, delay):
@@ -282,10 +280,7 @@ class WaveSolver(SolverBase):
         if loc is not None:
             dofs, vals = loc.dofs(dofs, vals)
         # the two step bounds
-        rp, ci, va, _ = K.to_csr()
-        lam_g = float(np.max(np.add.reduceat(np.abs(va), rp[:-1].astype(np.int64)) / m))
-        lam_p = self._power_iteration(K, m, dofs)
-        self._bounds = (2.0 / math.sqrt(lam_g), 2.0 / math.sqrt(lam_p))
+        self._bounds = time_marching.step_bounds(self, K, m, dofs)
         t0, dt, N = self.time_grid()
         if dt > self._bounds[1]:
             K.close()
@@ -339,26 +334,8 @@ class WaveSolver(SolverBase):
                 PointSource(self.function_space, p[0] if isinstance(p[0], Point) else Point(*np.ravel(p[0])), p[1]) for p in ps]
 
     def _power_iteration(self, K, m, bc_dofs):
-        """Rayleigh quotient x^T K x / x^T M_L x after POWER_ITERATIONS steps of x <- M_L^-1 K x on the rows that are not Dirichlet: a
-        lower bound on the largest eigenvalue of the operator the march sees.  The products run on the device."""
-        from . import backend
-        n = len(m)
-        free = np.ones(n)
-        free[np.asarray(bc_dofs, dtype=np.int64)] = 0.0
-        x = np.random.default_rng(2024).standard_normal(n) * free
-        xd, yd = backend.DeviceVector(n), backend.DeviceVector(n)
-        lam = 0.0
-        for _ in range(POWER_ITERATIONS):
-            x /= math.sqrt(float(x @ (m * x)))
-            xd.set(x)
-            K.spmv(xd, yd)
-            lam = xd.dot(yd)                    # x^T K x with x^T M_L x = 1
-            x = free * yd.get() / m
-        xd.close()
-        yd.close()
-        if not (lam > 0.0 and np.isfinite(lam)):
-            raise SolverError('WaveSolver: the power iteration gave lambda_P = {}'.format(lam))
-        return lam
+        """lambda_P, a lower bound on the largest eigenvalue of diag(1/m) K on the rows that are not Dirichlet"""
+        return time_marching.power_iteration(K, m, bc_dofs, 'WaveSolver')
 
     def critical_time_step(self):
         """2 / sqrt(lambda_G), lambda_G = max_i sum_j |K_ij| / m_i: the step below which the march is stable"""
@@ -384,17 +361,11 @@ class WaveSolver(SolverBase):
     # ------------------------------------------------------------------ the march
     def _batch_end(self, n, N):
         """the step at which the batch that starts at step n ends: the next plot / save / energy step, at most batch_steps away"""
-        end = N
-        for key, freq in (('plotting_freq', self.report_settings.get('plotting_freq', 0)), ('saving_freq', self.report_settings.get('saving_freq', 0)),
-                          ('energy_freq', self.settings.get('energy_freq', 0))):
-            if freq and freq > 0:
-                end = min(end, (n // int(freq) + 1) * int(freq))
         bs = self.settings.get('batch_steps')
-        if bs:
-            if int(bs) < 1:
-                raise SolverError("WaveSolver: 'batch_steps' must be a positive number of steps")
-            end = min(end, n + int(bs))
-        return end
+        if bs and int(bs) < 1:
+            raise SolverError("WaveSolver: 'batch_steps' must be a positive number of steps")
+        freqs = (self.report_settings.get('plotting_freq', 0), self.report_settings.get('saving_freq', 0), self.settings.get('energy_freq', 0))
+        return time_marching.batch_end(n, N, freqs, int(bs) if bs else None)
 
     def _publish(self, u_dev):
         self.w_current.vector().set_local(self._host(u_dev))

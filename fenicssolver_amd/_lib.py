@@ -87,17 +87,16 @@ class fs_visco_info(C.Structure):
                 ("force_ms", C.c_double)]
 
 
-class fs_wave_info(C.Structure):
+class fs_march_info(C.Structure):
     _fields_ = [("device_ms", C.c_double), ("n_nonfinite", C.c_int64), ("first_nonfinite_step", C.c_int64), ("step", C.c_int64)]
+
+
+fs_wave_info = fs_dyn_explicit_info = fs_march_info
 
 
 class fs_dyn_info(C.Structure):
     _fields_ = [("predict_ms", C.c_double), ("predict_pointwise_ms", C.c_double), ("correct_ms", C.c_double), ("n_nonfinite", C.c_int64),
                 ("first_nonfinite_step", C.c_int64), ("step", C.c_int64)]
-
-
-class fs_dyn_explicit_info(C.Structure):
-    _fields_ = [("device_ms", C.c_double), ("n_nonfinite", C.c_int64), ("first_nonfinite_step", C.c_int64), ("step", C.c_int64)]
 
 
 class fs_dg_form(C.Structure):

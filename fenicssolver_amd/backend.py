@@ -711,34 +711,65 @@ def assemble_viscoelastic(space, history, material, dt, u=None, load=None, force
             "update_ms": info.update_ms, "force_ms": info.force_ms}
 
 
-class WaveState(_Handle):
-    """Device state of the explicit wave marcher on a scalar CG1 space (fs_wave_state_*): u^{n-1}, u^n and a work field, the lumped
-    mass m, the lumped boundary damping d, the load F, the Dirichlet dofs with their values, and the step counter n.  Arrays are in
-    DEVICE dof order."""
-    _destroy = "fs_wave_state_destroy"
+class _MarcherState(_Handle):
+    """What the device states of the time marchers share: creation on a space, the size check of a host field, the Dirichlet
+    arguments of configure() and the batch call of the two explicit marchers.  Arrays are in DEVICE dof order."""
+    _create = None
 
     def __init__(self, space):
         super().__init__()
         self.space = space
         self.n = int(space.n_owned)
-        L.check(L.load().fs_wave_state_create(space.h, C.byref(self.h)), "fs_wave_state_create")
+        L.check(getattr(L.load(), self._create)(space.h, C.byref(self.h)), self._create)
+
+    def _field(self, a, who, name):
+        a = L.f64(a).ravel()
+        if a.size != self.n:
+            raise BackendError("%s.%s: %s has %d entries, the space has %d dofs" % (type(self).__name__, who, name, a.size, self.n))
+        return a
+
+    @staticmethod
+    def _dirichlet(dofs, values):
+        """the Dirichlet dofs and values of a configure() call as the arrays the library takes; a scalar value serves every dof"""
+        dofs = L.i32([] if dofs is None else dofs).ravel()
+        return dofs, L.f64(np.broadcast_to(0.0 if values is None else values, dofs.shape))
+
+    def _batch_advance(self, entry, K, load_scale, dirichlet_scale, receivers, traces, energy, info):
+        """len(load_scale) steps on the device without a host round trip through the entry point `entry`; step k of the call
+        advances n -> n+1 with load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1].  Returns {'traces': [n_steps, n_receivers]
+        or None, 'energy': [n_steps, 2] = (kinetic, potential) or None, and with info 'device_ms', 'n_nonfinite',
+        'first_nonfinite_step', 'step'}."""
+        sf, sg = L.f64(load_scale).ravel(), L.f64(dirichlet_scale).ravel()
+        if sf.size != sg.size:
+            raise BackendError("%s.advance: %d load factors and %d Dirichlet factors" % (type(self).__name__, sf.size, sg.size))
+        ns = sf.size
+        rec = L.i32([] if receivers is None else receivers).ravel()
+        tr = np.empty((ns, rec.size)) if (traces and rec.size) else None
+        en = np.empty((ns, 2)) if energy else None
+        inf = L.fs_march_info() if info else None
+        L.check(getattr(L.load(), entry)(K.h, self.h, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
+                                         L.p_f64(tr), L.p_f64(en), C.byref(inf) if info else None), entry)
+        out = {"traces": tr, "energy": en}
+        if info:
+            out.update(device_ms=inf.device_ms, n_nonfinite=int(inf.n_nonfinite), first_nonfinite_step=int(inf.first_nonfinite_step),
+                       step=int(inf.step))
+        return out
+
+
+class WaveState(_MarcherState):
+    """Device state of the explicit wave marcher on a scalar CG1 space (fs_wave_state_*): u^{n-1}, u^n and a work field, the lumped
+    mass m, the lumped boundary damping d, the load F, the Dirichlet dofs with their values, and the step counter n.  Arrays are in
+    DEVICE dof order."""
+    _create, _destroy = "fs_wave_state_create", "fs_wave_state_destroy"
 
     def configure(self, dt, mass, damping=None, load=None, dirichlet_dofs=None, dirichlet_values=None):
-        m = L.f64(mass).ravel()
-        d = None if damping is None else L.f64(damping).ravel()
-        f = None if load is None else L.f64(load).ravel()
-        for name, a in (("mass", m), ("damping", d), ("load", f)):
-            if a is not None and a.size != self.n:
-                raise BackendError("WaveState.configure: %s has %d entries, the space has %d dofs" % (name, a.size, self.n))
-        dofs = L.i32([] if dirichlet_dofs is None else dirichlet_dofs).ravel()
-        vals = L.f64(np.broadcast_to(0.0 if dirichlet_values is None else dirichlet_values, dofs.shape))
+        m, d, f = (None if a is None else self._field(a, "configure", name) for a, name in ((mass, "mass"), (damping, "damping"), (load, "load")))
+        dofs, vals = self._dirichlet(dirichlet_dofs, dirichlet_values)
         L.check(L.load().fs_wave_state_configure(self.h, float(dt), L.p_f64(m), L.p_f64(d), L.p_f64(f), dofs.size, L.p_i32(dofs),
                                                  L.p_f64(vals)), "fs_wave_state_configure")
 
     def set(self, u_prev, u, step):
-        a, b = L.f64(u_prev).ravel(), L.f64(u).ravel()
-        if a.size != self.n or b.size != self.n:
-            raise BackendError("WaveState.set: fields of %d and %d entries, the space has %d dofs" % (a.size, b.size, self.n))
+        a, b = self._field(u_prev, "set", "u_prev"), self._field(u, "set", "u")
         L.check(L.load().fs_wave_state_set(self.h, L.p_f64(a), L.p_f64(b), int(step)), "fs_wave_state_set")
 
     def get(self):
@@ -749,30 +780,12 @@ class WaveState(_Handle):
 
     def start(self, K, u0, v0, load_scale0=1.0, dirichlet_scale1=1.0):
         """u^1 from (u^0, v^0): the state then holds (u^0, u^1), n = 1"""
-        a, b = L.f64(u0).ravel(), L.f64(v0).ravel()
-        if a.size != self.n or b.size != self.n:
-            raise BackendError("WaveState.start: fields of %d and %d entries, the space has %d dofs" % (a.size, b.size, self.n))
+        a, b = self._field(u0, "start", "u0"), self._field(v0, "start", "v0")
         L.check(L.load().fs_wave_start(K.h, self.h, L.p_f64(a), L.p_f64(b), float(load_scale0), float(dirichlet_scale1)), "fs_wave_start")
 
     def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
-        """len(load_scale) steps on the device without a host round trip (fs_wave_advance); step k of the call advances n -> n+1 with
-        load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1].  Returns {'traces': [n_steps, n_receivers] or None, 'energy':
-        [n_steps, 2] = (kinetic, potential) or None, and with info 'device_ms', 'n_nonfinite', 'first_nonfinite_step', 'step'}."""
-        sf, sg = L.f64(load_scale).ravel(), L.f64(dirichlet_scale).ravel()
-        if sf.size != sg.size:
-            raise BackendError("WaveState.advance: %d load factors and %d Dirichlet factors" % (sf.size, sg.size))
-        ns = sf.size
-        rec = L.i32([] if receivers is None else receivers).ravel()
-        tr = np.empty((ns, rec.size)) if (traces and rec.size) else None
-        en = np.empty((ns, 2)) if energy else None
-        inf = L.fs_wave_info() if info else None
-        L.check(L.load().fs_wave_advance(K.h, self.h, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
-                                         L.p_f64(tr), L.p_f64(en), C.byref(inf) if info else None), "fs_wave_advance")
-        out = {"traces": tr, "energy": en}
-        if info:
-            out.update(device_ms=inf.device_ms, n_nonfinite=int(inf.n_nonfinite), first_nonfinite_step=int(inf.first_nonfinite_step),
-                       step=int(inf.step))
-        return out
+        """a batch of steps through fs_wave_advance: see _MarcherState._batch_advance"""
+        return self._batch_advance("fs_wave_advance", K, load_scale, dirichlet_scale, receivers, traces, energy, info)
 
 
 def wave_advance(K, state, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
@@ -780,28 +793,15 @@ def wave_advance(K, state, load_scale, dirichlet_scale, receivers=None, traces=T
     return state.advance(K, load_scale, dirichlet_scale, receivers=receivers, traces=traces, energy=energy, info=info)
 
 
-class DynamicsState(_Handle):
+class DynamicsState(_MarcherState):
     """Device state of the generalized-alpha marcher on a vector CG1 / CG2 space (fs_dyn_*): u, v, a, the work vectors p, q, M p,
     K q, the load F, the Dirichlet dofs with their values, the constants of the scheme and the step counter n.  Arrays are in DEVICE
     dof order.  K and M are the operators WITHOUT eliminated rows; the solve between predict() and correct() is the caller's."""
-    _destroy = "fs_dyn_state_destroy"
-
-    def __init__(self, space):
-        super().__init__()
-        self.space = space
-        self.n = int(space.n_owned)
-        L.check(L.load().fs_dyn_state_create(space.h, C.byref(self.h)), "fs_dyn_state_create")
-
-    def _field(self, a, who, name):
-        a = L.f64(a).ravel()
-        if a.size != self.n:
-            raise BackendError("DynamicsState.%s: %s has %d entries, the space has %d dofs" % (who, name, a.size, self.n))
-        return a
+    _create, _destroy = "fs_dyn_state_create", "fs_dyn_state_destroy"
 
     def configure(self, dt, alpha_m, alpha_f, beta, gamma, eta_m=0.0, eta_k=0.0, load=None, dirichlet_dofs=None, dirichlet_values=None):
         f = None if load is None else self._field(load, "configure", "load")
-        dofs = L.i32([] if dirichlet_dofs is None else dirichlet_dofs).ravel()
-        vals = L.f64(np.broadcast_to(0.0 if dirichlet_values is None else dirichlet_values, dofs.shape))
+        dofs, vals = self._dirichlet(dirichlet_dofs, dirichlet_values)
         L.check(L.load().fs_dyn_state_configure(self.h, float(dt), float(alpha_m), float(alpha_f), float(beta), float(gamma), float(eta_m),
                                                 float(eta_k), L.p_f64(f), dofs.size, L.p_i32(dofs), L.p_f64(vals)), "fs_dyn_state_configure")
 
@@ -855,29 +855,16 @@ class DynamicsState(_Handle):
         return float(out[0]), float(out[1])
 
 
-class ExplicitDynamicsState(_Handle):
+class ExplicitDynamicsState(_MarcherState):
     """Device state of the central-difference marcher on a vector CG1 space (fs_dyn_explicit_*): u_n, w_n = v_{n-1/2}, the last
     product y = K u, the lumped mass m, the load F, the Dirichlet dofs with their values, dt, eta_M and the step counter n.  Arrays
     are in DEVICE dof order.  K is the operator WITHOUT eliminated rows."""
-    _destroy = "fs_dyn_explicit_state_destroy"
-
-    def __init__(self, space):
-        super().__init__()
-        self.space = space
-        self.n = int(space.n_owned)
-        L.check(L.load().fs_dyn_explicit_state_create(space.h, C.byref(self.h)), "fs_dyn_explicit_state_create")
-
-    def _field(self, a, who, name):
-        a = L.f64(a).ravel()
-        if a.size != self.n:
-            raise BackendError("ExplicitDynamicsState.%s: %s has %d entries, the space has %d dofs" % (who, name, a.size, self.n))
-        return a
+    _create, _destroy = "fs_dyn_explicit_state_create", "fs_dyn_explicit_state_destroy"
 
     def configure(self, dt, eta_m, mass, load=None, dirichlet_dofs=None, dirichlet_values=None):
         m = self._field(mass, "configure", "mass")
         f = None if load is None else self._field(load, "configure", "load")
-        dofs = L.i32([] if dirichlet_dofs is None else dirichlet_dofs).ravel()
-        vals = L.f64(np.broadcast_to(0.0 if dirichlet_values is None else dirichlet_values, dofs.shape))
+        dofs, vals = self._dirichlet(dirichlet_dofs, dirichlet_values)
         L.check(L.load().fs_dyn_explicit_state_configure(self.h, float(dt), float(eta_m), L.p_f64(m), L.p_f64(f), dofs.size, L.p_i32(dofs),
                                                          L.p_f64(vals)), "fs_dyn_explicit_state_configure")
 
@@ -904,25 +891,8 @@ class ExplicitDynamicsState(_Handle):
                                                float(dirichlet_scale1)), "fs_dyn_explicit_start")
 
     def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
-        """len(load_scale) steps on the device without a host round trip (fs_dyn_explicit_advance); step k of the call advances
-        n -> n+1 with load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1].  Returns {'traces': [n_steps, n_receivers] or None,
-        'energy': [n_steps, 2] = (kinetic, potential) or None, and with info 'device_ms', 'n_nonfinite', 'first_nonfinite_step',
-        'step'}."""
-        sf, sg = L.f64(load_scale).ravel(), L.f64(dirichlet_scale).ravel()
-        if sf.size != sg.size:
-            raise BackendError("ExplicitDynamicsState.advance: %d load factors and %d Dirichlet factors" % (sf.size, sg.size))
-        ns = sf.size
-        rec = L.i32([] if receivers is None else receivers).ravel()
-        tr = np.empty((ns, rec.size)) if (traces and rec.size) else None
-        en = np.empty((ns, 2)) if energy else None
-        inf = L.fs_dyn_explicit_info() if info else None
-        L.check(L.load().fs_dyn_explicit_advance(K.h, self.h, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
-                                                 L.p_f64(tr), L.p_f64(en), C.byref(inf) if info else None), "fs_dyn_explicit_advance")
-        out = {"traces": tr, "energy": en}
-        if info:
-            out.update(device_ms=inf.device_ms, n_nonfinite=int(inf.n_nonfinite), first_nonfinite_step=int(inf.first_nonfinite_step),
-                       step=int(inf.step))
-        return out
+        """a batch of steps through fs_dyn_explicit_advance: see _MarcherState._batch_advance"""
+        return self._batch_advance("fs_dyn_explicit_advance", K, load_scale, dirichlet_scale, receivers, traces, energy, info)
 
     def full_step(self, K, load_scale_n):
         """(v_n, a_n) of the state's time point under s_f[n] = load_scale_n: one product, the state does not change"""

@@ -23,25 +23,18 @@
 // K u_0 on the free rows and a_0 = 0 on the Dirichlet rows: fs_dyn_start_rhs forms that right-hand side, the caller solves with the
 // eliminated M, fs_dyn_start takes a_0.  Energy on request (two products): E_kin = 1/2 v^T M v, E_pot = 1/2 u^T K u.
 //
-// Kernels: one thread per row, grid-stride over a launch geometry that depends on the number of rows only (dyn_grid), 8-byte loads
+// Kernels: one thread per row, grid-stride over a launch geometry that depends on the number of rows only (fs_march_grid), 8-byte loads
 // that a wave coalesces into full lines; no floating-point atomics, so a march gives the same bits however it is split into calls.
 // Bytes per row (fp64 fields, one flag byte):
 //   k_dyn_predict   reads u, v, a and the flag, writes p, q; g only on Dirichlet rows: 24 + 1 + 16 = 41 B
 //   k_dyn_rhs       reads M p, K q, F (g on a Dirichlet row, whose products are not read) and the flag, writes rhs: 24 + 1 + 8 = 33 B
 //   k_dyn_correct   reads u, v, a, x and the flag, writes u, v, a (u~ and v~ are recomputed, not stored): 32 + 1 + 24 = 57 B;
-//                   a Dirichlet row takes the same formulas - its u is exact.  A row some receiver samples (bit 1 of the flag) searches
-//                   the receiver list; a non-finite row is counted with integer atomics (the count and the first such step do not
-//                   depend on the order).
+//                   a Dirichlet row takes the same formulas - its u is exact.  A non-finite row is counted with integer atomics (the
+//                   count and the first such step do not depend on the order).
 //   k_dyn_energy / k_dyn_energy_finish   per-workgroup partials of v . M v and u . K u, summed in a fixed order by one workgroup.
-// A Dirichlet row keeps g_i in the slot of F_i (its load is never used); bit 0 of the flag marks it.
-#include "fs_common.h"
-#include "fs_kernels.h"
-#include <math.h>
+// The row table (load, flags, receivers: a Dirichlet row keeps g_i in the slot of F_i) and the shared checks: fs_march.h.
+#include "fs_march.h"
 #include <mutex>
-
-#define FS_DYN_BLOCKS 1024               // most workgroups of a pointwise kernel (the energy partials are summed in this order)
-#define FS_DYN_DIRICHLET 1
-#define FS_DYN_RECEIVER 2
 
 // what the kernels take of the scheme: everything is derived from (dt, alpha_m, alpha_f, beta, gamma, eta_M, eta_K) on the host
 struct dyn_consts {
@@ -55,9 +48,8 @@ struct dyn_consts {
     double cm, ck;                       // the coefficients of K_eff
 };
 
-struct fs_dyn_state_s {
+struct fs_dyn_state_s : fs_march_rows, fs_march_events<6> {   // ev: predict: 0 [p, q] 1 [products] 2 [rhs] 3; correct: 4 .. 5
     fs_space_s* space = nullptr;
-    int64_t n = 0;                       // rows
     bool configured = false;
     bool pending = false;                // fs_dyn_start_rhs was called, fs_dyn_start not yet
     int64_t step = -1;                   // the n of (u_n, v_n, a_n); -1: not started
@@ -65,23 +57,11 @@ struct fs_dyn_state_s {
     dyn_consts c = {};
     dbuf<double> u, v, a;
     dbuf<double> p, q, mp, kq;           // work: p, q, M p, K q
-    dbuf<double> load;                   // F (Dirichlet rows: g)
-    dbuf<uint8_t> flag;
-    std::vector<uint8_t> flag_host;      // the Dirichlet bits; the receiver bits of `receivers` on top
-    std::vector<int32_t> receivers;      // the list whose bits the device flags carry now
-    dbuf<int32_t> rec;
-    dbuf<double> samples;
+    dbuf<double> samples;                // [n_receivers] of the last fs_dyn_correct that wanted them
     dbuf<double> part;                   // [2][grid] energy partials, then the two sums
     dbuf<unsigned long long> bad;        // (rows found non-finite since the start, the first step that had one)
-    hipEvent_t ev[6] = {};               // predict: 0 [p, q] 1 [products] 2 [rhs] 3; correct: 4 .. 5
     bool timed_predict = false, timed_correct = false;
-    ~fs_dyn_state_s() {
-        for (hipEvent_t e_ : ev)
-            if (e_) (void)hipEventDestroy(e_);
-    }
 };
-
-static int dyn_grid(int64_t n) { return fs_grid_for(n, FS_BLOCK, FS_DYN_BLOCKS); }
 
 // ---- one step: before the solve ----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FS_BLOCK) k_dyn_predict(int64_t n, const double* __restrict__ u, const double* __restrict__ v,
@@ -96,7 +76,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dyn_predict(int64_t n, const doubl
         const double cv = (1.0 - c.af) * (vt - c.gbdt * ut) + c.af * vi;
         double pi = c.um * ut - c.am * ai - c.etam * cv;
         double qi = -c.af * ui - c.etak * cv;
-        if (flag[i] & FS_DYN_DIRICHLET) {
+        if (flag[i] & FS_MARCH_DIRICHLET) {
             const double g = load[i] * sg;
             pi -= c.cm * g;
             qi -= c.ck * g;
@@ -112,7 +92,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dyn_rhs(int64_t n, const double* _
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const double fi = load[i];
-        rhs[i] = (flag[i] & FS_DYN_DIRICHLET) ? fi * sg : sf * fi + mp[i] + kq[i];
+        rhs[i] = (flag[i] & FS_MARCH_DIRICHLET) ? fi * sg : sf * fi + mp[i] + kq[i];
     }
 }
 
@@ -134,9 +114,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dyn_correct(int64_t n, double* __r
         v[i] = vn;
         a[i] = an;
         if (!(isfinite(xi) && isfinite(vn) && isfinite(an))) ++n_bad;
-        if ((flag[i] & FS_DYN_RECEIVER) && trace)
-            for (int r = 0; r < n_rec; ++r)
-                if (rec[r] == (int32_t)i) trace[r] = xi;
+        fs_march_sample(flag[i], i, xi, n_rec, rec, trace);
     }
     if (n_bad) {
         atomicAdd(&bad[0], (unsigned long long)n_bad);
@@ -161,14 +139,14 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dyn_start_rhs(int64_t n, const dou
                                                             double* __restrict__ rhs) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        rhs[i] = (flag[i] & FS_DYN_DIRICHLET) ? 0.0 : sf * load[i] - mp[i] - kq[i];
+        rhs[i] = (flag[i] & FS_MARCH_DIRICHLET) ? 0.0 : sf * load[i] - mp[i] - kq[i];
 }
 
 __global__ void __launch_bounds__(FS_BLOCK) k_dyn_take_a0(int64_t n, const double* __restrict__ a0, const uint8_t* __restrict__ flag,
                                                           double* __restrict__ a) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        a[i] = (flag[i] & FS_DYN_DIRICHLET) ? 0.0 : a0[i];
+        a[i] = (flag[i] & FS_MARCH_DIRICHLET) ? 0.0 : a0[i];
 }
 
 // ---- energy ------------------------------------------------------------------------------------------------------------------
@@ -183,12 +161,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dyn_energy(int64_t n, const double
         ek += v[i] * mv[i];
         ep += u[i] * ku[i];
     }
-    const double tk = fs_block_sum(ek, lds4);
-    const double tp = fs_block_sum(ep, lds4);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = tk;
-        part[gridDim.x + blockIdx.x] = tp;
-    }
+    fs_march_store_partials(ek, ep, lds4, part);
 }
 
 // one workgroup: out = (1/2 sum part[0][.], 1/2 sum part[1][.]) in a fixed order
@@ -214,8 +187,12 @@ static int dyn_space_ok(const fs_space_s* sp, const char* who) {
     const fs_mesh_s* m = sp->mesh;
     FS_REQUIRE((sp->degree == 1 || sp->degree == 2) && sp->ncomp == m->tdim && sp->ncomp >= 2, "%s: vector CG1 or CG2 spaces on "
                "tetrahedra or triangles only (this space: CG%d with %d component(s) on a %d-D mesh)", who, sp->degree, sp->ncomp, m->tdim);
-    FS_REQUIRE(fs_rt().n_ranks == 1 && m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local,
-               "%s: the space has ghost nodes or the communicator several ranks: not supported", who);
+    return fs_march_one_rank(sp, who);
+}
+
+static int dyn_clear_bad(fs_dyn_state_s* st, hipStream_t s) {
+    FS_HIP(hipMemsetAsync(st->bad.p, 0, sizeof(unsigned long long), s));
+    FS_HIP(hipMemsetAsync(st->bad.p + 1, 0xff, sizeof(unsigned long long), s));
     return FS_OK;
 }
 
@@ -225,34 +202,13 @@ extern "C" int fs_dyn_state_create(fs_space_t space, fs_dyn_state_t* out) {
     FS_CHECK(dyn_space_ok(space, "fs_dyn_state_create"));
     fs_dyn_state_s* st = new fs_dyn_state_s();
     st->space = space;
-    st->n = space->n_dofs_owned;
-    const int64_t n = st->n;
     hipStream_t s = fs_rt().stream;
-    int rc = FS_OK;
-    for (dbuf<double>* b : {&st->u, &st->v, &st->a, &st->p, &st->q, &st->mp, &st->kq, &st->load})
-        if ((rc = b->alloc(n)) || (rc = b->zero(s))) {
-            delete st;
-            return rc;
-        }
-    if ((rc = st->flag.alloc(n)) || (rc = st->flag.zero(s)) || (rc = st->part.alloc(2 * (int64_t)dyn_grid(n) + 2)) || (rc = st->bad.alloc(2))) {
-        delete st;
-        return rc;
-    }
-    for (hipEvent_t& e_ : st->ev)
-        if (hipEventCreate(&e_) != hipSuccess) {
-            fs_set_error("fs_dyn_state_create: hipEventCreate failed");
-            delete st;
-            return FS_ERR_HIP;
-        }
-    if (hipMemsetAsync(st->bad.p, 0, sizeof(unsigned long long), s) != hipSuccess ||
-        hipMemsetAsync(st->bad.p + 1, 0xff, sizeof(unsigned long long), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        fs_set_error("fs_dyn_state_create: clearing the state failed");
-        delete st;
-        return FS_ERR_HIP;
-    }
-    st->flag_host.assign((size_t)n, 0);
-    *out = st;
-    return FS_OK;
+    int rc = st->alloc_rows(space->n_dofs_owned, s);
+    for (dbuf<double>* b : {&st->u, &st->v, &st->a, &st->p, &st->q, &st->mp, &st->kq})
+        if (rc == FS_OK && (rc = b->alloc(st->n)) == FS_OK) rc = b->zero(s);
+    if (rc == FS_OK && (rc = st->part.alloc(2 * (int64_t)fs_march_grid(st->n) + 2)) == FS_OK && (rc = st->bad.alloc(2)) == FS_OK)
+        rc = dyn_clear_bad(st, s);
+    return fs_march_create_finish("fs_dyn_state_create", st, rc, s, out);
 }
 
 extern "C" int fs_dyn_state_destroy(fs_dyn_state_t st) {
@@ -272,27 +228,10 @@ extern "C" int fs_dyn_state_configure(fs_dyn_state_t st, double dt, double alpha
                "the scheme is not unconditionally stable", alpha_m, alpha_f, beta, gamma);
     FS_REQUIRE(eta_m >= 0.0 && eta_k >= 0.0 && isfinite(eta_m) && isfinite(eta_k), "fs_dyn_state_configure: the Rayleigh coefficients "
                "(eta_M, eta_K) = (%g, %g) must be >= 0 and finite", eta_m, eta_k);
-    FS_REQUIRE(n_dirichlet >= 0 && (n_dirichlet == 0 || (dirichlet_dofs && dirichlet_values)), "fs_dyn_state_configure: Dirichlet list: null "
-               "pointer or negative count");
-    const int64_t n = st->n;
-    if (load)
-        for (int64_t i = 0; i < n; ++i) FS_REQUIRE(isfinite(load[i]), "fs_dyn_state_configure: the load of row %lld is not finite", (long long)i);
-    std::vector<double> f(load ? load : nullptr, load ? load + n : nullptr);
-    f.resize((size_t)n, 0.0);
-    std::vector<uint8_t> fl((size_t)n, 0);
-    for (int64_t j = 0; j < n_dirichlet; ++j) {
-        const int32_t i = dirichlet_dofs[j];
-        FS_REQUIRE(i >= 0 && i < n, "fs_dyn_state_configure: Dirichlet dof %d outside the space of %lld dofs", i, (long long)n);
-        FS_REQUIRE(isfinite(dirichlet_values[j]), "fs_dyn_state_configure: the Dirichlet value of dof %d is not finite", i);
-        fl[i] = FS_DYN_DIRICHLET;
-        f[i] = dirichlet_values[j];           // (a dof named twice takes the last value)
-    }
+    FS_CHECK(fs_march_rows_ok("fs_dyn_state_configure", st->n, nullptr, nullptr, load, n_dirichlet, dirichlet_dofs, dirichlet_values));
     hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->load.upload(f.data(), n, s));
-    FS_CHECK(st->flag.upload(fl.data(), n, s));
+    FS_CHECK(st->configure("fs_dyn_state_configure", load, n_dirichlet, dirichlet_dofs, dirichlet_values, s));
     FS_HIP(hipStreamSynchronize(s));
-    st->flag_host.swap(fl);
-    st->receivers.clear();
     const double par[7] = {dt, alpha_m, alpha_f, beta, gamma, eta_m, eta_k};
     memcpy(st->par, par, sizeof(par));
     dyn_consts& c = st->c;
@@ -310,12 +249,6 @@ extern "C" int fs_dyn_state_configure(fs_dyn_state_t st, double dt, double alpha
     c.cm = (1.0 - alpha_m) / (beta * dt * dt) + (1.0 - alpha_f) * gamma * eta_m / (beta * dt);
     c.ck = (1.0 - alpha_f) * (1.0 + gamma * eta_k / (beta * dt));
     st->configured = true;
-    return FS_OK;
-}
-
-static int dyn_clear_bad(fs_dyn_state_s* st, hipStream_t s) {
-    FS_HIP(hipMemsetAsync(st->bad.p, 0, sizeof(unsigned long long), s));
-    FS_HIP(hipMemsetAsync(st->bad.p + 1, 0xff, sizeof(unsigned long long), s));
     return FS_OK;
 }
 
@@ -410,7 +343,7 @@ extern "C" int fs_dyn_start_rhs(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t st,
     FS_REQUIRE(isfinite(load_scale0), "fs_dyn_start_rhs: the load factor is not finite");
     hipStream_t s = fs_rt().stream;
     const int64_t n = st->n;
-    const int g = dyn_grid(n);
+    const int g = fs_march_grid(n);
     FS_CHECK(st->u.upload(u0, n, s));
     FS_CHECK(st->v.upload(v0, n, s));
     FS_CHECK(st->a.zero(s));
@@ -431,7 +364,7 @@ extern "C" int fs_dyn_start(fs_dyn_state_t st, fs_vector_t a0) {
     FS_REQUIRE(st->pending, "fs_dyn_start: no initial state is waiting for its acceleration (fs_dyn_start_rhs)");
     FS_REQUIRE(a0->d.n >= st->n, "fs_dyn_start: a_0 has %lld entries, the space %lld dofs", (long long)a0->d.n, (long long)st->n);
     hipStream_t s = fs_rt().stream;
-    hipLaunchKernelGGL(k_dyn_take_a0, dim3(dyn_grid(st->n)), dim3(FS_BLOCK), 0, s, st->n, a0->d.p, st->flag.p, st->a.p);
+    hipLaunchKernelGGL(k_dyn_take_a0, dim3(fs_march_grid(st->n)), dim3(FS_BLOCK), 0, s, st->n, a0->d.p, st->flag.p, st->a.p);
     FS_KERNEL_CHECK();
     FS_CHECK(dyn_clear_bad(st, s));
     FS_HIP(hipStreamSynchronize(s));
@@ -449,7 +382,7 @@ extern "C" int fs_dyn_predict(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t st, d
     FS_REQUIRE(isfinite(load_scale) && isfinite(dirichlet_scale_next), "fs_dyn_predict: a time factor is not finite");
     hipStream_t s = fs_rt().stream;
     const int64_t n = st->n;
-    const int g = dyn_grid(n);
+    const int g = fs_march_grid(n);
     FS_HIP(hipEventRecord(st->ev[0], s));
     hipLaunchKernelGGL(k_dyn_predict, dim3(g), dim3(FS_BLOCK), 0, s, n, st->u.p, st->v.p, st->a.p, st->load.p, st->flag.p, st->c,
                        dirichlet_scale_next, st->p.p, st->q.p);
@@ -464,39 +397,22 @@ extern "C" int fs_dyn_predict(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t st, d
     return FS_OK;                                   // nothing returns to the host: the solve that follows is ordered on the same stream
 }
 
-// the receiver bits of the device flags follow the list of the call (uploaded only when the list changes)
-static int dyn_set_receivers(fs_dyn_state_s* st, int64_t n_rec, const int32_t* dofs, hipStream_t s) {
-    if ((int64_t)st->receivers.size() == n_rec && (n_rec == 0 || !memcmp(st->receivers.data(), dofs, (size_t)n_rec * sizeof(int32_t))))
-        return FS_OK;
-    for (int32_t i : st->receivers) st->flag_host[i] &= (uint8_t)~FS_DYN_RECEIVER;
-    st->receivers.assign(dofs, dofs + n_rec);
-    for (int32_t i : st->receivers) st->flag_host[i] |= FS_DYN_RECEIVER;
-    FS_CHECK(st->flag.upload(st->flag_host.data(), st->n, s));
-    if (n_rec) {
-        FS_CHECK(st->rec.alloc(n_rec));
-        FS_CHECK(st->rec.upload(dofs, n_rec, s));
-        FS_CHECK(st->samples.alloc(n_rec));
-    }
-    return FS_OK;
-}
-
 extern "C" int fs_dyn_correct(fs_dyn_state_t st, fs_vector_t x, int64_t n_receivers, const int32_t* receiver_dofs, double* samples) {
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_REQUIRE(st && x, "fs_dyn_correct: null pointer");
     FS_REQUIRE(st->configured, "fs_dyn_correct: the state was not configured (fs_dyn_state_configure)");
     FS_REQUIRE(st->step >= 0, "fs_dyn_correct: the state holds no (u, v, a) yet (fs_dyn_start or fs_dyn_state_set)");
     FS_REQUIRE(x->d.n >= st->n, "fs_dyn_correct: the solution has %lld entries, the space %lld dofs", (long long)x->d.n, (long long)st->n);
-    FS_REQUIRE(n_receivers >= 0 && n_receivers <= INT32_MAX && (n_receivers == 0 || receiver_dofs), "fs_dyn_correct: receiver list: null "
-               "pointer or bad count");
     const int64_t n = st->n;
-    for (int64_t r = 0; r < n_receivers; ++r)
-        FS_REQUIRE(receiver_dofs[r] >= 0 && receiver_dofs[r] < n, "fs_dyn_correct: receiver dof %d outside the space of %lld dofs",
-                   receiver_dofs[r], (long long)n);
+    FS_CHECK(fs_march_receivers_ok("fs_dyn_correct", n, n_receivers, receiver_dofs));
     const bool want = samples && n_receivers > 0;
     hipStream_t s = fs_rt().stream;
-    if (want) FS_CHECK(dyn_set_receivers(st, n_receivers, receiver_dofs, s));
+    if (want) {
+        FS_CHECK(st->set_receivers(n_receivers, receiver_dofs, s));
+        if (st->samples.n != n_receivers) FS_CHECK(st->samples.alloc(n_receivers));
+    }
     FS_HIP(hipEventRecord(st->ev[4], s));
-    hipLaunchKernelGGL(k_dyn_correct, dim3(dyn_grid(n)), dim3(FS_BLOCK), 0, s, n, st->u.p, st->v.p, st->a.p, x->d.p, st->flag.p, st->c,
+    hipLaunchKernelGGL(k_dyn_correct, dim3(fs_march_grid(n)), dim3(FS_BLOCK), 0, s, n, st->u.p, st->v.p, st->a.p, x->d.p, st->flag.p, st->c,
                        (int)n_receivers, st->rec.p, want ? st->samples.p : nullptr, (unsigned long long)(st->step + 1), st->bad.p);
     FS_HIP(hipEventRecord(st->ev[5], s));
     FS_KERNEL_CHECK();
@@ -516,7 +432,7 @@ extern "C" int fs_dyn_energy(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t st, do
     FS_REQUIRE(out, "fs_dyn_energy: null pointer");
     hipStream_t s = fs_rt().stream;
     const int64_t n = st->n;
-    const int g = dyn_grid(n);
+    const int g = fs_march_grid(n);
     FS_CHECK(dyn_products(K, M, st, st->v.p, st->u.p, s));
     hipLaunchKernelGGL(k_dyn_energy, dim3(g), dim3(FS_BLOCK), 0, s, n, st->v.p, st->mp.p, st->u.p, st->kq.p, st->part.p);
     hipLaunchKernelGGL(k_dyn_energy_finish, dim3(1), dim3(FS_BLOCK), 0, s, g, st->part.p, st->part.p + 2 * g);

@@ -19,23 +19,13 @@
 //   k_dynx_update   one thread per row, grid-stride over a launch geometry that depends on the number of rows only, 8-byte loads
 //       that a wave coalesces into full lines: the update formula, the Dirichlet rows, the receiver samples and the per-workgroup
 //       partials of both energy halves.  Per row it reads y, u, w, m, F (8 B each) and one flag byte and writes u and w in place
-//       (a row is read and written by its own thread only): 57 B.  A Dirichlet row keeps g_i in the slot of F_i (its load is never
-//       used); bit 0 of the flag marks it, bit 1 marks a row some receiver samples - only such a row searches the receiver list.
-//   k_dynx_finish   one workgroup per step of a chunk of FS_DYNX_CHUNK steps: sums that step's partials in a fixed order into the
-//       energy table of the call and counts the steps whose energy is not finite (integer atomics: the count and the first such
-//       step do not depend on the order).  A non-finite u makes the next y and with it w and E_kin non-finite, so this is also the
-//       check of the fields.
+//       (a row is read and written by its own thread only): 57 B.  A non-finite u makes the next y and with it w and E_kin
+//       non-finite, so the finishing pass's check of the energy is also the check of the fields.
 //   k_dynx_dirichlet / k_dynx_start   the Dirichlet rows of u_0, then the first step from (u_0, v_0).
 //   k_dynx_full_step   v_n and a_n of the state's time point from (w_{n-1/2}, y_n): w+ is recomputed, nothing is stored.
-#include "fs_common.h"
-#include "fs_kernels.h"
-#include <math.h>
+// The row table (load, flags, receivers), the finishing pass, the batch driver and the shared checks: fs_march.h.
+#include "fs_march.h"
 #include <mutex>
-
-#define FS_DYNX_BLOCKS 1024              // most workgroups of the update kernel (its partials are summed in this order)
-#define FS_DYNX_CHUNK 64                 // steps between two finishing passes (the partial table holds this many steps)
-#define FS_DYNX_DIRICHLET 1
-#define FS_DYNX_RECEIVER 2
 
 // what the kernels take of the scheme, derived from (dt, eta_M) on the host: w+ = c1 w + c2 (s_f F - y) / m
 struct dynx_consts {
@@ -45,36 +35,20 @@ struct dynx_consts {
     double etam;
 };
 
-struct fs_dyn_explicit_state_s {
-    fs_space_s* space = nullptr;
-    int64_t n = 0;                       // rows
-    bool configured = false;
-    int64_t step = 0;                    // the n of (u_n, w_n = v_{n-1/2}); 0: not started
+struct fs_dyn_explicit_state_s : fs_march_batch_state {
     dynx_consts c = {};
     dbuf<double> u, w;                   // u_n, v_{n-1/2}: updated in place
     dbuf<double> y;                      // K u of the last product
-    dbuf<double> m, load;                // lumped mass, F (Dirichlet rows: g)
+    dbuf<double> m;                      // lumped mass
     dbuf<double> t0, t1;                 // fs_dyn_explicit_start: v_0; fs_dyn_explicit_full_step: v_n, a_n
-    dbuf<uint8_t> flag;
-    std::vector<uint8_t> flag_host;      // the Dirichlet bits; the receiver bits of `receivers` on top
-    std::vector<int32_t> receivers;      // the list whose bits the device flags carry now
-    dbuf<int32_t> rec;
-    dbuf<double> part;                   // [FS_DYNX_CHUNK][2][grid]
-    hipEvent_t ev[2] = {};
-    ~fs_dyn_explicit_state_s() {
-        for (hipEvent_t e_ : ev)
-            if (e_) (void)hipEventDestroy(e_);
-    }
 };
-
-static int dynx_grid(int64_t n) { return fs_grid_for(n, FS_BLOCK, FS_DYNX_BLOCKS); }
 
 // ---- the start -------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FS_BLOCK) k_dynx_dirichlet(int64_t n, const double* __restrict__ load, const uint8_t* __restrict__ flag,
                                                              double sg, double* __restrict__ u) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        if (flag[i] & FS_DYNX_DIRICHLET) u[i] = load[i] * sg;
+        if (flag[i] & FS_MARCH_DIRICHLET) u[i] = load[i] * sg;
 }
 
 // u: u_0 in, u_1 out; w: w_{1/2} out
@@ -88,7 +62,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dynx_start(int64_t n, const double
         const double a0 = (sf * fi - y[i]) / m[i] - c.etam * vi;
         double wn = vi + (0.5 * c.dt) * a0;
         double un = ui + c.dt * wn;
-        if (flag[i] & FS_DYNX_DIRICHLET) {
+        if (flag[i] & FS_MARCH_DIRICHLET) {
             un = fi * sg1;
             wn = (un - ui) * c.idt;
         }
@@ -112,7 +86,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dynx_update(int64_t n, const doubl
         const uint8_t fl = flag[i];
         double wn = c.c1 * wi + c.c2 * ((sf * fi - yi) / mi);
         double un = ui + c.dt * wn;
-        if (fl & FS_DYNX_DIRICHLET) {
+        if (fl & FS_MARCH_DIRICHLET) {
             un = fi * sg;
             wn = (un - ui) * c.idt;
         }
@@ -120,39 +94,9 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dynx_update(int64_t n, const doubl
         w[i] = wn;
         ek += 0.5 * mi * wn * wn;
         ep += 0.5 * un * yi;
-        if ((fl & FS_DYNX_RECEIVER) && trace)
-            for (int r = 0; r < n_rec; ++r)
-                if (rec[r] == (int32_t)i) trace[r] = un;
+        fs_march_sample(fl, i, un, n_rec, rec, trace);
     }
-    const double tk = fs_block_sum(ek, lds4);
-    const double tp = fs_block_sum(ep, lds4);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = tk;
-        part[gridDim.x + blockIdx.x] = tp;
-    }
-}
-
-// workgroup b: step k0 + b of the call, whose partials are part[b][2][g]; bad = (steps with a non-finite energy, the first of them)
-__global__ void __launch_bounds__(FS_BLOCK) k_dynx_finish(int g, const double* __restrict__ part, int64_t k0, double* __restrict__ energy,
-                                                          unsigned long long* __restrict__ bad) {
-    __shared__ double lds4[4];
-    const double* p = part + (int64_t)blockIdx.x * 2 * g;
-    double ek = 0.0, ep = 0.0;
-    for (int j = threadIdx.x; j < g; j += FS_BLOCK) {
-        ek += p[j];
-        ep += p[g + j];
-    }
-    const double tk = fs_block_sum(ek, lds4);
-    const double tp = fs_block_sum(ep, lds4);
-    if (threadIdx.x == 0) {
-        const int64_t k = k0 + blockIdx.x;
-        energy[2 * k] = tk;
-        energy[2 * k + 1] = tp;
-        if (!(isfinite(tk) && isfinite(tp))) {
-            atomicAdd(&bad[0], 1ull);
-            atomicMin(&bad[1], (unsigned long long)k);
-        }
-    }
+    fs_march_store_partials(ek, ep, lds4, part);
 }
 
 // ---- the full-step velocity and acceleration of the state's time point ------------------------------------------------------------
@@ -164,7 +108,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dynx_full_step(int64_t n, const do
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const double wi = w[i];
         const double wp = c.c1 * wi + c.c2 * ((sf * load[i] - y[i]) / m[i]);
-        const bool dir = flag[i] & FS_DYNX_DIRICHLET;
+        const bool dir = flag[i] & FS_MARCH_DIRICHLET;
         v[i] = dir ? wi : 0.5 * (wi + wp);
         a[i] = dir ? 0.0 : (wp - wi) * c.idt;
     }
@@ -178,9 +122,7 @@ static int dynx_space_ok(const fs_space_s* sp, const char* who) {
     FS_REQUIRE(sp->degree == 1 && sp->ncomp == m->tdim && sp->ncomp >= 2, "%s: vector CG1 spaces on tetrahedra or triangles only (this "
                "space: CG%d with %d component(s) on a %d-D mesh; a row-sum lumped P2 mass is not positive)", who, sp->degree, sp->ncomp,
                m->tdim);
-    FS_REQUIRE(fs_rt().n_ranks == 1 && m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local,
-               "%s: the space has ghost nodes or the communicator several ranks: not supported", who);
-    return FS_OK;
+    return fs_march_one_rank(sp, who);
 }
 
 extern "C" int fs_dyn_explicit_state_create(fs_space_t space, fs_dyn_explicit_state_t* out) {
@@ -189,33 +131,12 @@ extern "C" int fs_dyn_explicit_state_create(fs_space_t space, fs_dyn_explicit_st
     FS_CHECK(dynx_space_ok(space, "fs_dyn_explicit_state_create"));
     fs_dyn_explicit_state_s* st = new fs_dyn_explicit_state_s();
     st->space = space;
-    st->n = space->n_dofs_owned;
-    const int64_t n = st->n;
     hipStream_t s = fs_rt().stream;
-    int rc = FS_OK;
-    for (dbuf<double>* b : {&st->u, &st->w, &st->y, &st->m, &st->load, &st->t0, &st->t1})
-        if ((rc = b->alloc(n)) || (rc = b->zero(s))) {
-            delete st;
-            return rc;
-        }
-    if ((rc = st->flag.alloc(n)) || (rc = st->flag.zero(s)) || (rc = st->part.alloc((int64_t)FS_DYNX_CHUNK * 2 * dynx_grid(n)))) {
-        delete st;
-        return rc;
-    }
-    for (hipEvent_t& e_ : st->ev)
-        if (hipEventCreate(&e_) != hipSuccess) {
-            fs_set_error("fs_dyn_explicit_state_create: hipEventCreate failed");
-            delete st;
-            return FS_ERR_HIP;
-        }
-    if (hipStreamSynchronize(s) != hipSuccess) {
-        fs_set_error("fs_dyn_explicit_state_create: hipStreamSynchronize failed");
-        delete st;
-        return FS_ERR_HIP;
-    }
-    st->flag_host.assign((size_t)n, 0);
-    *out = st;
-    return FS_OK;
+    int rc = st->alloc_rows(space->n_dofs_owned, s);
+    for (dbuf<double>* b : {&st->u, &st->w, &st->y, &st->m, &st->t0, &st->t1})
+        if (rc == FS_OK && (rc = b->alloc(st->n)) == FS_OK) rc = b->zero(s);
+    if (rc == FS_OK) rc = st->alloc_part();
+    return fs_march_create_finish("fs_dyn_explicit_state_create", st, rc, s, out);
 }
 
 extern "C" int fs_dyn_explicit_state_destroy(fs_dyn_explicit_state_t st) {
@@ -229,31 +150,12 @@ extern "C" int fs_dyn_explicit_state_configure(fs_dyn_explicit_state_t st, doubl
     FS_REQUIRE(dt > 0.0 && isfinite(dt), "fs_dyn_explicit_state_configure: the step length is %g: dt > 0 and finite is required", dt);
     FS_REQUIRE(eta_m >= 0.0 && isfinite(eta_m), "fs_dyn_explicit_state_configure: the mass damping eta_M is %g: it must be >= 0 and finite",
                eta_m);
-    FS_REQUIRE(n_dirichlet >= 0 && (n_dirichlet == 0 || (dirichlet_dofs && dirichlet_values)), "fs_dyn_explicit_state_configure: Dirichlet "
-               "list: null pointer or negative count");
     const int64_t n = st->n;
-    for (int64_t i = 0; i < n; ++i) {
-        FS_REQUIRE(mass[i] > 0.0 && isfinite(mass[i]), "fs_dyn_explicit_state_configure: the lumped mass of row %lld is %g: m_i > 0 is "
-                   "required", (long long)i, mass[i]);
-        FS_REQUIRE(!load || isfinite(load[i]), "fs_dyn_explicit_state_configure: the load of row %lld is not finite", (long long)i);
-    }
-    std::vector<double> f(load ? load : nullptr, load ? load + n : nullptr);
-    f.resize((size_t)n, 0.0);
-    std::vector<uint8_t> fl((size_t)n, 0);
-    for (int64_t j = 0; j < n_dirichlet; ++j) {
-        const int32_t i = dirichlet_dofs[j];
-        FS_REQUIRE(i >= 0 && i < n, "fs_dyn_explicit_state_configure: Dirichlet dof %d outside the space of %lld dofs", i, (long long)n);
-        FS_REQUIRE(isfinite(dirichlet_values[j]), "fs_dyn_explicit_state_configure: the Dirichlet value of dof %d is not finite", i);
-        fl[i] = FS_DYNX_DIRICHLET;
-        f[i] = dirichlet_values[j];           // (a dof named twice takes the last value)
-    }
+    FS_CHECK(fs_march_rows_ok("fs_dyn_explicit_state_configure", n, mass, nullptr, load, n_dirichlet, dirichlet_dofs, dirichlet_values));
     hipStream_t s = fs_rt().stream;
+    FS_CHECK(st->configure("fs_dyn_explicit_state_configure", load, n_dirichlet, dirichlet_dofs, dirichlet_values, s));
     FS_CHECK(st->m.upload(mass, n, s));
-    FS_CHECK(st->load.upload(f.data(), n, s));
-    FS_CHECK(st->flag.upload(fl.data(), n, s));
     FS_HIP(hipStreamSynchronize(s));
-    st->flag_host.swap(fl);
-    st->receivers.clear();
     const double alpha = 0.5 * eta_m * dt;
     st->c.dt = dt;
     st->c.idt = 1.0 / dt;
@@ -311,7 +213,7 @@ extern "C" int fs_dyn_explicit_start(fs_matrix_t K, fs_dyn_explicit_state_t st, 
                "not finite");
     hipStream_t s = fs_rt().stream;
     const int64_t n = st->n;
-    const int g = dynx_grid(n);
+    const int g = fs_march_grid(n);
     FS_CHECK(st->u.upload(u0, n, s));
     FS_CHECK(st->t0.upload(v0, n, s));
     st->step = 0;
@@ -328,21 +230,6 @@ extern "C" int fs_dyn_explicit_start(fs_matrix_t K, fs_dyn_explicit_state_t st, 
     return FS_OK;
 }
 
-// the receiver bits of the device flags follow the list of the call (uploaded only when the list changes)
-static int dynx_set_receivers(fs_dyn_explicit_state_s* st, int64_t n_rec, const int32_t* dofs, hipStream_t s) {
-    if ((int64_t)st->receivers.size() == n_rec && (n_rec == 0 || !memcmp(st->receivers.data(), dofs, (size_t)n_rec * sizeof(int32_t))))
-        return FS_OK;
-    for (int32_t i : st->receivers) st->flag_host[i] &= (uint8_t)~FS_DYNX_RECEIVER;
-    st->receivers.assign(dofs, dofs + n_rec);
-    for (int32_t i : st->receivers) st->flag_host[i] |= FS_DYNX_RECEIVER;
-    FS_CHECK(st->flag.upload(st->flag_host.data(), st->n, s));
-    if (n_rec) {
-        FS_CHECK(st->rec.alloc(n_rec));
-        FS_CHECK(st->rec.upload(dofs, n_rec, s));
-    }
-    return FS_OK;
-}
-
 extern "C" int fs_dyn_explicit_advance(fs_matrix_t K, fs_dyn_explicit_state_t st, int64_t n_steps, const double* load_scale,
                                        const double* dirichlet_scale, int64_t n_receivers, const int32_t* receiver_dofs, double* traces,
                                        double* energy, fs_dyn_explicit_info* info) {
@@ -350,59 +237,18 @@ extern "C" int fs_dyn_explicit_advance(fs_matrix_t K, fs_dyn_explicit_state_t st
     FS_CHECK(dynx_matrix_ok(K, st, "fs_dyn_explicit_advance"));
     FS_REQUIRE(st->step >= 1, "fs_dyn_explicit_advance: the state holds no (u_n, v_{n-1/2}) yet (fs_dyn_explicit_start or "
                "fs_dyn_explicit_state_set)");
-    FS_REQUIRE(n_steps >= 0 && (n_steps == 0 || (load_scale && dirichlet_scale)), "fs_dyn_explicit_advance: %lld steps need load_scale and "
-               "dirichlet_scale of that length", (long long)n_steps);
-    FS_REQUIRE(n_receivers >= 0 && n_receivers <= INT32_MAX && (n_receivers == 0 || receiver_dofs), "fs_dyn_explicit_advance: receiver list: "
-               "null pointer or bad count");
-    const int64_t n = st->n;
-    for (int64_t r = 0; r < n_receivers; ++r)
-        FS_REQUIRE(receiver_dofs[r] >= 0 && receiver_dofs[r] < n, "fs_dyn_explicit_advance: receiver dof %d outside the space of %lld dofs",
-                   receiver_dofs[r], (long long)n);
-    for (int64_t k = 0; k < n_steps; ++k)
-        FS_REQUIRE(isfinite(load_scale[k]) && isfinite(dirichlet_scale[k]), "fs_dyn_explicit_advance: the time factors of step %lld of the "
-                   "call are not finite", (long long)k);
-    const bool want_traces = traces && n_receivers > 0;
     hipStream_t s = fs_rt().stream;
-    if (want_traces) FS_CHECK(dynx_set_receivers(st, n_receivers, receiver_dofs, s));
-    FS_CHECK(fs_spmv_prepare(K, s));
-    dbuf<double> tr, en;
-    dbuf<unsigned long long> bad;
-    FS_CHECK(en.alloc(2 * n_steps));
-    FS_CHECK(bad.alloc(2));
-    if (want_traces) FS_CHECK(tr.alloc(n_steps * n_receivers));
-    FS_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
-    FS_HIP(hipMemsetAsync(bad.p + 1, 0xff, sizeof(unsigned long long), s));
-    const int g = dynx_grid(n);
-    FS_HIP(hipEventRecord(st->ev[0], s));
-    for (int64_t k = 0; k < n_steps; ++k) {
-        const int64_t slot = k % FS_DYNX_CHUNK;
+    const int64_t n = st->n;
+    const int g = fs_march_grid(n);
+    auto enqueue = [&](int64_t k, double* trace, double* part) {
         FS_CHECK(fs_spmv_dev(K, st->u.p, st->y.p, s));
         hipLaunchKernelGGL(k_dynx_update, dim3(g), dim3(FS_BLOCK), 0, s, n, st->y.p, st->u.p, st->w.p, st->m.p, st->load.p, st->flag.p, st->c,
-                           load_scale[k], dirichlet_scale[k], (int)n_receivers, st->rec.p, want_traces ? tr.p + k * n_receivers : nullptr,
-                           st->part.p + slot * 2 * g);
+                           load_scale[k], dirichlet_scale[k], (int)n_receivers, st->rec.p, trace, part);
         ++st->step;
-        if (slot == FS_DYNX_CHUNK - 1 || k == n_steps - 1) {
-            hipLaunchKernelGGL(k_dynx_finish, dim3((int)slot + 1), dim3(FS_BLOCK), 0, s, g, st->part.p, k - slot, en.p, bad.p);
-            FS_KERNEL_CHECK();
-        }
-    }
-    FS_HIP(hipEventRecord(st->ev[1], s));
-    if (!(want_traces || energy || info)) return FS_OK;        // nothing to hand back: the batch stays in flight
-    unsigned long long bad_host[2] = {0, 0};
-    if (info) FS_CHECK(bad.download(bad_host, 2, s));
-    if (want_traces) FS_CHECK(tr.download(traces, n_steps * n_receivers, s));
-    if (energy) FS_CHECK(en.download(energy, 2 * n_steps, s));
-    FS_HIP(hipStreamSynchronize(s));
-    FS_KERNEL_CHECK();
-    if (info) {
-        float ms = 0.0f;
-        FS_HIP(hipEventElapsedTime(&ms, st->ev[0], st->ev[1]));
-        info->device_ms = ms;
-        info->n_nonfinite = (int64_t)bad_host[0];
-        info->first_nonfinite_step = bad_host[0] ? (int64_t)bad_host[1] : -1;
-        info->step = st->step;
-    }
-    return FS_OK;
+        return (int)FS_OK;
+    };
+    return fs_march_advance("fs_dyn_explicit_advance", K, st, true, n_steps, load_scale, dirichlet_scale, n_receivers, receiver_dofs, traces,
+                            energy, info, enqueue);
 }
 
 extern "C" int fs_dyn_explicit_full_step(fs_matrix_t K, fs_dyn_explicit_state_t st, double load_scale_n, double* v_out, double* a_out) {
@@ -416,7 +262,7 @@ extern "C" int fs_dyn_explicit_full_step(fs_matrix_t K, fs_dyn_explicit_state_t 
     FS_CHECK(fs_spmv_prepare(K, s));
     FS_CHECK(fs_spmv_dev(K, st->u.p, st->y.p, s));
     FS_KERNEL_CHECK();
-    hipLaunchKernelGGL(k_dynx_full_step, dim3(dynx_grid(n)), dim3(FS_BLOCK), 0, s, n, st->y.p, st->w.p, st->m.p, st->load.p, st->flag.p, st->c,
+    hipLaunchKernelGGL(k_dynx_full_step, dim3(fs_march_grid(n)), dim3(FS_BLOCK), 0, s, n, st->y.p, st->w.p, st->m.p, st->load.p, st->flag.p, st->c,
                        load_scale_n, st->t0.p, st->t1.p);
     FS_KERNEL_CHECK();
     if (v_out) FS_CHECK(st->t0.download(v_out, n, s));

@@ -520,12 +520,13 @@ int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vector_t u, fs_
  * (traces, energy or info).  FS_ERR_INVALID with a message: spaces other than scalar CG1, several ranks, a matrix of another space,
  * dt <= 0 or not finite, m_i <= 0, d_i < 0, a receiver or Dirichlet dof out of range, a state that was not configured / started. */
 typedef struct fs_wave_state_s* fs_wave_state_t;
-typedef struct fs_wave_info {
+typedef struct fs_march_info {    /* what a batch of explicit steps reports (fs_wave_advance, fs_dyn_explicit_advance) */
     double device_ms;             /* HIP-event time of the whole batch (products, updates, finishing passes) */
     int64_t n_nonfinite;          /* steps of this call whose energy (hence: field) is not finite */
     int64_t first_nonfinite_step; /* the first of them, as its index k in this call; -1: none */
     int64_t step;                 /* the state's step counter n after the call */
-} fs_wave_info;
+} fs_march_info;
+typedef fs_march_info fs_wave_info;
 int fs_wave_state_create(fs_space_t space, fs_wave_state_t* out);
 int fs_wave_state_destroy(fs_wave_state_t state);
 int fs_wave_state_configure(fs_wave_state_t state, double dt, const double* mass, const double* damping, const double* load,
@@ -632,12 +633,7 @@ int fs_dyn_energy(fs_matrix_t K, fs_matrix_t M, fs_dyn_state_t state, double* ou
  * finite, a receiver or Dirichlet dof out of range, a state that was not configured / started; a refused call leaves the state as
  * it was. */
 typedef struct fs_dyn_explicit_state_s* fs_dyn_explicit_state_t;
-typedef struct fs_dyn_explicit_info {
-    double device_ms;             /* HIP-event time of the whole batch (products, updates, finishing passes) */
-    int64_t n_nonfinite;          /* steps of this call whose energy (hence: field) is not finite */
-    int64_t first_nonfinite_step; /* the first of them, as its index k in this call; -1: none */
-    int64_t step;                 /* the state's step counter n after the call */
-} fs_dyn_explicit_info;
+typedef fs_march_info fs_dyn_explicit_info;
 int fs_dyn_explicit_state_create(fs_space_t space, fs_dyn_explicit_state_t* out);
 int fs_dyn_explicit_state_destroy(fs_dyn_explicit_state_t state);
 int fs_dyn_explicit_state_configure(fs_dyn_explicit_state_t state, double dt, double eta_m, const double* mass, const double* load,

@@ -158,6 +158,44 @@ def test_kernels_match_numpy_row_by_row(shape):
     assert info["n_nonfinite"] == 2 and info["first_nonfinite_step"] == 5 and info["step"] == 5
 
 
+def test_the_receiver_list_may_change_from_call_to_call_on_one_state():
+    """The receiver bits of the device flags follow the list of the call; a bit that is not set leaves its slot of the sample buffer
+    unwritten.  Exact: a sample of correct() is the entry of x itself."""
+    from fenicssolver_amd import backend
+    dV, d, keep = _space(("box", 2))
+    n = dV.n_owned
+    assert n == 81
+    rng = np.random.default_rng(25)
+    u, v, a, F = (rng.standard_normal(n) * s for s in (1e-2, 1e-1, 1.0, 0.5))
+    dofs, vals = np.array([0, 1, 2, 30, 31], dtype=np.int32), 0.01 * np.arange(1.0, 6.0)
+    A = np.array([5, 30, 80], dtype=np.int32)                              # one of them a Dirichlet dof
+    B = np.array([7, 1, 44], dtype=np.int32)                               # disjoint from A
+    C = np.array([80, 80], dtype=np.int32)                                 # shorter, a dof of A, named twice
+    par = (0.05,) + tuple(er.parameters(0.5)) + (0.3, 0.02)
+    st = backend.DynamicsState(dV)
+    st.configure(*par, load=F, dirichlet_dofs=dofs, dirichlet_values=vals)
+    st.set(u, v, a, step=0)
+    x = backend.DeviceVector(dV.n_local)
+
+    def step_with(rec, k):
+        x.set(rng.standard_normal(n) * 1e-2)
+        samples = st.correct(x, rec)
+        uu, _, _, step = st.get()
+        assert step == k
+        if rec is None:
+            assert samples is None
+        else:
+            assert samples.shape == (len(rec),) and np.array_equal(samples, uu[rec]), (k, rec)
+    for k, rec in enumerate((A, B, C, None, A), start=1):
+        step_with(rec, k)
+    uu, vv, aa, step = st.get()
+    st.configure(*par, load=F, dirichlet_dofs=dofs, dirichlet_values=vals)     # the flags are uploaded anew, without receiver bits
+    st.set(uu, vv, aa, step)
+    step_with(B, 6)
+    assert st.info()["n_nonfinite"] == 0
+    st.close()
+
+
 def test_start_forms_the_initial_residual_and_takes_the_acceleration():
     from fenicssolver_amd import backend
     dV, d, keep = _space(("box", 3))

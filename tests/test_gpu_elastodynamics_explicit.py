@@ -237,6 +237,43 @@ def test_a_march_gives_the_same_bits_however_it_is_split_into_calls():
     K.close()
 
 
+def test_the_receiver_list_may_change_from_call_to_call_on_one_state():
+    """The receiver bits of the device flags follow the list of the call; a bit that is not set leaves its slot of a freshly allocated
+    trace buffer unwritten.  Exact: a sample is the field value itself."""
+    from fenicssolver_amd import backend
+    dV, keep = _space(("box", 2))
+    n = dV.n_owned
+    assert n == 81
+    K, m = _operators(dV)
+    rng = np.random.default_rng(23)
+    u, w, F = rng.standard_normal(n) * 1e-2, rng.standard_normal(n) * 1e-1, rng.standard_normal(n)
+    dofs, vals = np.array([0, 1, 2, 30, 31], dtype=np.int32), 0.01 * np.arange(1.0, 6.0)
+    A = np.array([5, 30, 80], dtype=np.int32)                              # one of them a Dirichlet dof
+    B = np.array([7, 1, 44], dtype=np.int32)                               # disjoint from A
+    C = np.array([80, 80], dtype=np.int32)                                 # shorter, a dof of A, named twice
+    sf, sg = rng.standard_normal(7), rng.standard_normal(7)
+    st = backend.ExplicitDynamicsState(dV)
+    st.configure(1e-3, 0.3, m, load=F, dirichlet_dofs=dofs, dirichlet_values=vals)
+    st.set(u, w, step=1)
+
+    def step_with(rec, k):
+        out = st.advance(K, sf[k:k + 1], sg[k:k + 1], receivers=rec)
+        uu, _, step = st.get()
+        assert step == k + 1 and out["step"] == k + 1
+        if rec is None:
+            assert out["traces"] is None
+        else:
+            assert out["traces"].shape == (1, len(rec)) and np.array_equal(out["traces"][0], uu[rec]), (k, rec)
+    for k, rec in enumerate((A, B, C, None, A), start=1):
+        step_with(rec, k)
+    uu, ww, step = st.get()
+    st.configure(1e-3, 0.3, m, load=F, dirichlet_dofs=dofs, dirichlet_values=vals)      # the flags are uploaded anew, without receiver bits
+    st.set(uu, ww, step)
+    step_with(B, 6)
+    st.close()
+    K.close()
+
+
 # ---- the cases of the solver tests -----------------------------------------------------------------------------------------------
 def _xml_mesh():
     from fenicssolver_amd.fem import Mesh

@@ -39,6 +39,8 @@ def _mesh(kind):
         return RectangleMesh(Point(0, 0), Point(1.0, 0.7), 6, 5)
     if kind == "box":
         return BoxMesh(Point(0, 0, 0), Point(1.0, 0.8, 0.6), 4, 3, 3)
+    if kind == "tiny":
+        return BoxMesh(Point(0, 0, 0), Point(1.0, 0.8, 0.6), 2, 2, 2)          # 27 dofs
     return BoxMesh(Point(0, 0, 0), Point(1.0, 0.8, 0.6), 17, 13, 11)          # 3024 dofs: several workgroups, no multiple of 64
 
 
@@ -204,6 +206,37 @@ def test_get_then_set_continues_the_march_bit_for_bit(big):
     assert step == 6 and step_b == 13
     assert np.array_equal(up_a, up_b) and np.array_equal(u_a, u_b)
     assert np.array_equal(tr_a, np.concatenate([o1["traces"], o2["traces"]])) and np.array_equal(en_a, np.concatenate([o1["energy"], o2["energy"]]))
+
+
+def test_the_receiver_list_may_change_from_call_to_call_on_one_state():
+    """The receiver bits of the device flags follow the list of the call; a bit that is not set leaves its slot of a freshly allocated
+    trace buffer unwritten.  Exact: a sample is the field value itself."""
+    P = Problem("tiny")
+    assert P.n == 27
+    free = np.setdiff1d(np.arange(P.n), P.bc)
+    A = np.array([free[0], P.bc[1], free[5]], dtype=np.int32)              # one of them a Dirichlet dof
+    B = np.array([free[2], P.bc[0], free[7]], dtype=np.int32)              # disjoint from A
+    C = np.array([A[2], A[2]], dtype=np.int32)                             # shorter, a dof of A, named twice
+    rng = np.random.default_rng(21)
+    sf, sg = rng.standard_normal(7), rng.standard_normal(8)
+    st = P.state()
+    st.start(P.Kd, P.u0, P.v0, sf[0], sg[1])
+
+    def step_with(rec, n):
+        out = st.advance(P.Kd, sf[n:n + 1], sg[n + 1:n + 2], receivers=rec)
+        _, u, step = st.get()
+        assert step == n + 1 and out["step"] == n + 1
+        if rec is None:
+            assert out["traces"] is None
+        else:
+            assert out["traces"].shape == (1, len(rec)) and np.array_equal(out["traces"][0], u[rec]), (n, rec)
+    for n, rec in enumerate((A, B, C, None, A), start=1):
+        step_with(rec, n)
+    up, u, step = st.get()
+    st.configure(P.dt, P.m_dev, P.d_dev, P.F_dev, P.bc, P.g)                 # the flags are uploaded anew, without receiver bits
+    st.set(up, u, step)
+    step_with(B, 6)
+    st.close()
 
 
 def test_null_traces_and_null_energy_advance_the_state_identically(big):
