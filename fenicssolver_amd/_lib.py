@@ -138,6 +138,11 @@ class fs_saddle_opts(C.Structure):
                 ("schur_scale", C.c_double)]
 
 
+class fs_saddle_cycle_info(C.Structure):
+    _fields_ = [("restart", C.c_int), ("columns_used", C.c_int), ("second_passes", C.c_int), ("n_owned", C.c_int64),
+                ("vel_lmax", C.c_double)]
+
+
 class fs_ld_form(C.Structure):
     _fields_ = [("dt", C.c_double), ("q", C.c_double), ("mu", C.c_double), ("lambda_", C.c_double), ("body_force", C.c_double * 3),
                 ("dirichlet", C.c_void_p), ("n_facets", C.c_int64), ("facet_cell", C.c_void_p), ("facet_opposite", C.c_void_p),
@@ -239,6 +244,7 @@ SIGNATURES = {
     "fs_assemble_ns_pressure_boundary_nn": (C.c_int, [_H, _H, C.c_int64, c_i32p, c_i32p, c_f64p, C.c_double, _H, C.c_double, C.c_double,
                                                     C.c_int]),
     "fs_saddle_solve": (C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_saddle_opts), C.POINTER(fs_krylov_stats)]),
+    "fs_saddle_last_cycle": (C.c_int, [C.POINTER(fs_saddle_cycle_info), c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
     "fs_comm_get_unique_id": (C.c_int, [C.c_char_p]),
     "fs_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_char_p]),
     "fs_assemble_von_mises": (C.c_int, [_H, _H, C.c_double, C.c_double, _H, _H]),

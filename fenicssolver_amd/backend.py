@@ -1226,16 +1226,40 @@ def assemble_large_deformation(J, rhs, u, w, u0, w0, dt, q, mu, lmbda, dirichlet
     return {"residual_norm": info.residual_norm, "n_bad": int(info.n_bad), "first_bad_cell": int(info.first_bad_cell)}
 
 
-def large_deformation_solve(J, Mp, b, x, a0, schur_scale, a0_amg=None, a0_rtol=0.0, rtol=1e-10, atol=0.0, max_iter=0, restart=0):
+def large_deformation_solve(J, Mp, b, x, a0, schur_scale, a0_amg=None, a0_rtol=0.0, rtol=1e-10, atol=0.0, max_iter=0, restart=0,
+                            nonzero_guess=False):
     """FGMRES of fs_saddle_solve on the reduced large-deformation operator, right-preconditioned by the block upper triangular
-    [A J_vp; 0 S]^-1: S = schur_scale * Mp, A^-1 one V-cycle of a0_amg or Jacobi-CG on a0 to a0_rtol."""
+    [A J_vp; 0 S]^-1: S = schur_scale * Mp, A^-1 one V-cycle of a0_amg or Jacobi-CG on a0 to a0_rtol.  nonzero_guess: x holds the
+    starting vector (else it is zeroed), as in saddle_solve."""
     o = L.fs_saddle_opts()
     o.rtol, o.atol, o.max_iter, o.restart = float(rtol), float(atol), int(max_iter), int(restart)
     o.block_upper, o.a0, o.a0_rtol, o.schur_scale = 1, a0.h, float(a0_rtol), float(schur_scale)
+    o.nonzero_guess = 1 if nonzero_guess else 0
     o.a0_amg = a0_amg.h if a0_amg is not None else None
     st = L.fs_krylov_stats()
     L.check(L.load().fs_saddle_solve(J.h, None, None, Mp.h, b.h, x.h, C.byref(o), C.byref(st)), "fs_saddle_solve")
     return {k: getattr(st, k) for k, _ in L.fs_krylov_stats._fields_}
+
+
+def saddle_last_cycle():
+    """The state of the last FGMRES cycle of the most recent saddle_solve / large_deformation_solve call (fs_saddle_last_cycle, a
+    test / inspection hook), or None when that call ran no cycle.  m: restart length; kuse: columns used; V [kuse + 1, n], Z [kuse, n]
+    (owned rows); R [m + 1, m]: the rotated Hessenberg matrix; cs, sn [m]; gamma [m + 1]; y [m]: the least-squares solution (the device
+    keeps its negative); second_passes; vel_lmax.  Column kuse of R and entry kuse of cs, sn may hold an iteration that was enqueued ahead
+    and never used; it has then rotated gamma[kuse] on into gamma[kuse + 1] (include/fenicssolver_amd.h)."""
+    lib = L.load()
+    info = L.fs_saddle_cycle_info()
+    rc = lib.fs_saddle_last_cycle(C.byref(info), None, None, None, None, None, None, None)
+    if rc == L.FS_ERR_UNSUPPORTED:
+        return None
+    L.check(rc, "fs_saddle_last_cycle")
+    m, k, n = info.restart, info.columns_used, info.n_owned
+    V, Z, H = np.empty((k + 1, n)), np.empty((k, n)), np.empty((m + 1, m))
+    cs, sn, gam, y = np.empty(m), np.empty(m), np.empty(m + 1), np.empty(m)
+    L.check(lib.fs_saddle_last_cycle(C.byref(info), L.p_f64(V), L.p_f64(Z) if k else None, L.p_f64(H), L.p_f64(cs), L.p_f64(sn),
+                                     L.p_f64(gam), L.p_f64(y)), "fs_saddle_last_cycle")
+    return {"m": m, "kuse": k, "V": V, "Z": Z, "R": H, "cs": cs, "sn": sn, "gamma": gam, "y": -y,
+            "second_passes": info.second_passes, "vel_lmax": info.vel_lmax}
 
 
 def krylov_history():

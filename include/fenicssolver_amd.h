@@ -1006,6 +1006,28 @@ typedef struct fs_saddle_opts {
 int fs_saddle_solve(fs_matrix_t J, fs_matrix_t Kp, fs_amg_t Kp_amg, fs_matrix_t Mp, fs_vector_t b, fs_vector_t x,
                     const fs_saddle_opts* opts, fs_krylov_stats* stats);
 
+typedef struct fs_saddle_cycle_info {
+    int restart;            /* m: the restart length the workspace was built for */
+    int columns_used;       /* kuse: iterations of the cycle that entered the update of x */
+    int second_passes;      /* iterations of the cycle whose second Gram-Schmidt pass ran (an iteration enqueued ahead counts) */
+    int64_t n_owned;        /* owned rows of the operator: the length of every V_k and Z_k returned */
+    double vel_lmax;        /* lambda_max(D^-1 A) of the velocity block as the last velocity_sweeps > 1 solve estimated it */
+} fs_saddle_cycle_info;
+
+/* The state of the LAST FGMRES cycle of the most recent fs_saddle_solve call, copied to host arrays; every array may be
+ * NULL.  V[(columns_used + 1)][n_owned]: the Arnoldi basis; Z[columns_used][n_owned]: the preconditioned vectors, owned rows;
+ * H[(restart + 1)][restart] row-major: the Hessenberg matrix after the Givens rotations (upper triangular R in its first
+ * columns_used columns); cs, sn[restart]: the rotations; gamma[restart + 1]: the rotated right-hand side, |gamma[columns_used]|
+ * the recurrence residual the cycle stopped on; y[restart]: the NEGATIVE of the least-squares solution, as the update
+ * kernel subtracts.  Column columns_used of H and entry columns_used of cs and sn may hold the iteration that was enqueued
+ * ahead of the stopping test and never used: that iteration has then also rotated gamma[columns_used] on into
+ * gamma[columns_used + 1], and the recurrence residual is the norm of the two (a cycle that ended at max_iter or at the
+ * restart length has no such iteration).  Entries beyond are left over from earlier cycles.  Makes no launch, only
+ * device-to-host copies, and leaves the solver's state alone.  FS_ERR_UNSUPPORTED when that call ran no cycle (or none was made).
+ * Test/inspection hook. */
+int fs_saddle_last_cycle(fs_saddle_cycle_info* info, double* V, double* Z, double* H, double* cs, double* sn, double* gamma,
+                         double* y);
+
 /* ---- multi-GPU (MPI inside PETSc/DOLFIN under mpirun; SolverBase.py:102-118, 634) */
 
 #define FS_UNIQUE_ID_BYTES 128

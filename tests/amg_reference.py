@@ -200,8 +200,9 @@ def prepare(levels):
     return [L if isinstance(L, _Level) else _Level(L) for L in levels]
 
 
-def vcycle_replay(levels, r, smoother_steps=2, coarse=None):
-    """z = M r and the bound e_z of |z_device - z|.  levels[l]: {"A": A_l, "P": prolongator from level l + 1 (None on the last
+def vcycle_replay(levels, r, smoother_steps=2, coarse=None, e_r=None):
+    """z = M r and the bound e_z of |z_device - z|.  e_r: the bound that r itself arrives with where the device's right-hand side is
+    the result of earlier kernels (None: the device reads the same r, bit for bit).  levels[l]: {"A": A_l, "P": prolongator from level l + 1 (None on the last
     level), "lmax": lambda_max, "a32" / "p32": the level operator / the transfers are streamed rounded to fp32}, fp64 scipy
     matrices as AMG.level_matrix returns them, or the output of prepare().  coarse: the dense inverse applied on the last level
     (AMG.coarse_inverse()), None = Chebyshev sweeps there."""
@@ -210,7 +211,7 @@ def vcycle_replay(levels, r, smoother_steps=2, coarse=None):
     if coarse is not None:
         c = np.asarray(coarse, dtype=np.float64)
         coarse = (c.astype(LD), np.abs(c))
-    return _vcycle(lv, 0, r, np.zeros(len(r)), int(smoother_steps), coarse)
+    return _vcycle(lv, 0, r, np.zeros(len(r)) if e_r is None else np.asarray(e_r, dtype=np.float64), int(smoother_steps), coarse)
 
 
 def check_cycle(z, z_ref, e_z, what):
