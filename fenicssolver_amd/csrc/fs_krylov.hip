@@ -2487,15 +2487,15 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
     }
 #ifdef FS_ITER_TIMING
     if (fused && getenv("FS_ITER_TIMING")) {
-        std::vector<long long> h(8 * 4096);
+        std::vector<long long> h(FS_STAMPS * 4096);
         FS_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_iter_dbg), h.size() * sizeof(long long)));
         long long first = h[0], last = 0;
-        for (int b = 0; b < igrid; ++b) { first = std::min(first, h[8 * b]); last = std::max(last, h[8 * b + 7]); }
-        double mean[8] = {0}, mx[8] = {0};
+        for (int b = 0; b < igrid; ++b) { first = std::min(first, h[FS_STAMPS * b]); last = std::max(last, h[FS_STAMPS * b + 7]); }
+        double mean[9] = {0}, mx[9] = {0};
         for (int b = 0; b < igrid; ++b)
-            for (int k2 = 0; k2 < 8; ++k2) { const double v = (h[8 * b + k2] - first) * 0.01; mean[k2] += v / igrid; mx[k2] = std::max(mx[k2], v); }
+            for (int k2 = 0; k2 < 9; ++k2) { const double v = (h[FS_STAMPS * b + k2] - first) * 0.01; mean[k2] += v / igrid; mx[k2] = std::max(mx[k2], v); }
         fprintf(stderr, "[iter timing, last launch, us from the first workgroup's start] span %.2f;", (last - first) * 0.01);
-        for (int k2 = 0; k2 < 8; ++k2) fprintf(stderr, " s%d mean %.2f max %.2f;", k2, mean[k2], mx[k2]);
+        for (int k2 = 0; k2 < 9; ++k2) fprintf(stderr, " s%d mean %.2f max %.2f;", k2, mean[k2], mx[k2]);
         fprintf(stderr, "\n");
         // stamps 5 (first item done), 6 (all items done), 7 (partials summed) apart for the workgroups whose chunks hold an edge item
         // (the chunk walk of the kernel: xcd_chunks, or block-strided without the XCD map) and for the rest
@@ -2512,7 +2512,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
             for (; cur < end; cur += step)
                 for (int64_t q = 4 * cur; q < std::min<int64_t>(4 * cur + 4, sp->n_dict_items); ++q) e |= (hi[(size_t)q * 4 + 1] >> 16) & 1;
             ++cnt[e];
-            for (int k2 = 0; k2 < 3; ++k2) { const double v = (h[8 * b + 5 + k2] - first) * 0.01; gm[e][k2] += v; gx[e][k2] = std::max(gx[e][k2], v); }
+            for (int k2 = 0; k2 < 3; ++k2) { const double v = (h[FS_STAMPS * b + 5 + k2] - first) * 0.01; gm[e][k2] += v; gx[e][k2] = std::max(gx[e][k2], v); }
         }
         for (int e = 0; e < 2; ++e) {
             fprintf(stderr, "[iter timing] %d workgroups %s an edge item:", cnt[e], e ? "with" : "without");

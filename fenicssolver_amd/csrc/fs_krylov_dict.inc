@@ -379,6 +379,37 @@ __device__ __forceinline__ void fs_fill_lds(double* __restrict__ lds, const doub
     }
 }
 
+// The same copy with direct-to-LDS loads (global_load_lds_dwordx4, as fs_box.h uses them: no data registers, no ds_write pass), in two
+// halves: ISSUE, which waits for nothing, and WAIT.  The layout stays linear: lane l of wave w moves chunk 256 t + 64 w + l in trip t
+// (the LDS side of the instruction is a wave-uniform base + B l); the lanes past the end of a partial last instruction are masked
+// off.  B = 16: n even, both sides 16-byte aligned; B = 4: any n (a table of n doubles that need not be even: 2 n chunks).
+// Nothing may be scheduled in front of the issue (the wait below counts the vector loads BEHIND it).
+template <int B = 16>
+__device__ __forceinline__ void fs_fill_lds_issue(double* lds, const double* __restrict__ g, int n) {
+    static_assert(B == 16 || B == 4, "dwordx4 or dword");
+    const int nc = B == 16 ? n >> 1 : 2 * n;
+    const int lane = threadIdx.x & 63;
+    const int w64 = __builtin_amdgcn_readfirstlane((int)threadIdx.x & ~63);
+    const char* g8 = reinterpret_cast<const char*>(g);
+    char* l8 = reinterpret_cast<char*>(lds);
+    for (int base = w64; base < nc; base += FS_BLOCK)
+        if (base + lane < nc) {             // (the size is an immediate of the instruction: a literal)
+            const auto* src = (const __attribute__((address_space(1))) void*)(g8 + (int64_t)(base + lane) * B);
+            auto* dst = (__attribute__((address_space(3))) void*)(l8 + base * B);
+            if (B == 16) __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
+            else __builtin_amdgcn_global_load_lds(src, dst, 4, 0, 0);
+        }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// This wave's direct-to-LDS loads have landed: vector loads return in order, so they have once at most AFTER of the vector loads issued
+// behind them are outstanding (AFTER must not exceed the number of loads the wave has issued since; 0 is always right).  The compiler
+// does not know the LDS side of the builtin: every wave waits for its own loads before the barrier that publishes the copy, and before
+// it leaves the kernel.
+template <int AFTER>
+__device__ __forceinline__ void fs_fill_lds_wait() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AFTER) : "memory");
+}
+
 // the same by ONE wave (a class row of n2 16-byte pairs into the wave's LDS region): four loads in flight per lane and batch
 __device__ __forceinline__ void fs_wave_copy_pairs(double* __restrict__ lds, const double* __restrict__ g, int n2, int lane) {
     typedef double v2d __attribute__((ext_vector_type(2)));

@@ -450,8 +450,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_cg_update_scaled(int64_t n, int it
 // kernel, and three vectors x three mesh planes no longer fit the 4 MB L2 of an XCD.  Hence automatic only where the vectors
 // stay in the Infinity Cache (FS_CG_FUSED_MAX_ROWS, default 3 M rows).
 #ifdef FS_ITER_TIMING
-__device__ long long g_iter_dbg[8 * 4096];
-#define FS_STAMP(k) do { if (threadIdx.x == 0 && it_ctr[par] == 100) g_iter_dbg[8 * blockIdx.x + (k)] = wall_clock64(); } while (0)
+// (stamp 8 sits between 2 and 3: the prefetch is issued and the status word looked at, the sums are not yet begun)
+#define FS_STAMPS 16
+__device__ long long g_iter_dbg[FS_STAMPS * 4096];
+#define FS_STAMP(k) do { if (threadIdx.x == 0 && it_ctr[par] == 100) g_iter_dbg[FS_STAMPS * blockIdx.x + (k)] = wall_clock64(); } while (0)
 #else
 #define FS_STAMP(k) do { } while (0)
 #endif
@@ -487,7 +489,20 @@ __device__ long long g_iter_dbg[8 * 4096];
 // new s, the old r and the new r of the own rows are (value.y, next lane's value.x) of slot 4, the same memory words through the same two
 // fmas.  Lane 63 has no rows of its own and loads what lane 62 needs.
 // Measured at 1 M rows: profiles/r08_cg_guard_ab.txt, r08_cg_guard_trace_*.csv, r08_iter_edge_timeline.txt (DESIGN.md section 3).
+// PROLOGUE (every form): the dictionary and the DTAB table go into LDS by direct-to-LDS loads issued first (fs_fill_lds_issue); every wave
+// waits for its own with a counted s_waitcnt in front of the ONE barrier of the sums, which publishes them, and in front of the early
+// return.  With GUARD nothing between kernel entry and that barrier waits for the first item's run loads: the sums are reduced under
+// their flight.  Measured: profiles/r09_iter_prologue_timeline.txt, r09_cg_prologue_ab.txt, r09_cg_prologue_trace_*.csv.
 enum { FS_ITER_EVERY = 0, FS_ITER_LIGHT = 1, FS_ITER_PAIR = 2 };
+// a 16-byte pair of doubles at base + st doubles + boff bytes (8-byte aligned), through an ordinary pointer or a global-address-space one
+typedef const __attribute__((address_space(1))) double* fs_gcd;
+typedef double fs_v2du __attribute__((ext_vector_type(2), aligned(8)));
+__device__ __forceinline__ fs_v2du fs_ld_pair(const double* base, int32_t st, uint32_t boff) {
+    return *reinterpret_cast<const fs_v2du*>(reinterpret_cast<const char*>(base + st) + boff);
+}
+__device__ __forceinline__ fs_v2du fs_ld_pair(fs_gcd base, int32_t st, uint32_t boff) {
+    return *(const __attribute__((address_space(1))) fs_v2du*)((const __attribute__((address_space(1))) char*)(base + st) + boff);
+}
 template <int RL, bool COMM, int MODE = FS_ITER_EVERY, bool DTAB = false, bool GUARD = false, bool CENTRE = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64_t n_items, const int4* __restrict__ items,
                                                            const dict_plan_round* __restrict__ plans, const uint16_t* __restrict__ cls,
@@ -507,17 +522,29 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     FS_STAMP(0);
     // The launch is latency-bound at the sizes it is used for (a wave has two work items at 1 M rows), and what it reads first was
     // written by the previous launch on other XCDs - every dependent load is a round trip to the Infinity Cache (1 - 2 us).  So
-    // everything the prologue needs goes out BEFORE anything is waited for: status word, iteration number, threshold, both parities
-    // of the previous (gamma, alpha), the twelve dot partials of this thread, the first item's header -> run starts -> first
-    // twelve run loads, the dictionary.  (Timeline of the first version, tools/probes: 8.8 of 22.7 us were the prologue.)
+    // everything the prologue needs goes out BEFORE anything is waited for: the dictionary (direct-to-LDS loads: no registers, and
+    // nothing it needs depends on anything else), status word, iteration number, threshold, both parities of the previous
+    // (gamma, alpha), the twelve dot partials of this thread, the first item's header -> row-local operands, run starts -> first
+    // nine or twelve run loads.  (Timeline of the first version, tools/probes: 8.8 of 22.7 us were the prologue.)
+    // The dictionary used to go LAST, through registers, behind a wait for everything before it: a second round trip on the way to
+    // alpha and beta.  And with GUARD the first item's loads are branch-free (a wave without a first item loads the operands of item
+    // 0 - inside the guarded block like every item's - and discards them), so that the wait in front of the sums is a COUNT that
+    // leaves the run loads in flight: reduction, barrier and the two divisions run under them.
+    extern __shared__ __attribute__((aligned(16))) double sdict[];
+    fs_fill_lds_issue(sdict, dict, C * S);
+    double* const sdtab = sdict + C * S;         // (DTAB: C dot weights behind the C class rows, by the same road - as an early register
+    if (DTAB) fs_fill_lds_issue<4>(sdtab, dvec, C);     // load the compiler sinks them behind the run loads, in front of a wait for everything)
     const int st0 = status[0];
     const int iter = it_ctr[par];
     const double thresh = ctrl[0], it_max = ctrl[2];
     const double sc_g0 = scal[0], sc_a0 = scal[1], sc_g1 = scal[2], sc_a1 = scal[3];
     double sc_b0 = 0.0, sc_b1 = 0.0;
     if (MODE == FS_ITER_PAIR) { sc_b0 = scal[4]; sc_b1 = scal[5]; }
-    double dt0 = 0.0;
-    if (DTAB) dt0 = dvec[(int)threadIdx.x < C ? (int)threadIdx.x : 0];
+    // (the loads of the prologue go through copies of their pointers the compiler knows nothing about: what it loads through a
+    // read-only `restrict` argument it is free to sink behind the early return and the barrier of the sums - behind the status
+    // word's round trip, or behind alpha and beta)
+    fs_gcd part_pre = (fs_gcd)part_in, r_pre = (fs_gcd)r_in, w_pre = (fs_gcd)w_in, s_pre = (fs_gcd)s_in;
+    asm volatile("" : "+s"(part_pre), "+s"(r_pre), "+s"(w_pre), "+s"(s_pre));
     double pl[3][4];
     double sum_g = 0.0, sum_d = 0.0, sum_r = 0.0;
     if (COMM) { sum_g = sums[0]; sum_d = sums[1]; sum_r = sums[2]; }
@@ -526,14 +553,13 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
         for (int t = 0; t < 4; ++t) {
             const int i = threadIdx.x + t * FS_BLOCK;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) pl[j][t] = part_in[(int64_t)j * npart + (i < npart ? i : npart - 1)];      // (no branch: twelve loads in flight)
+            for (int j = 0; j < 3; ++j) pl[j][t] = part_pre[(int64_t)j * npart + (i < npart ? i : npart - 1)];      // (no branch: twelve loads in flight)
         }
     }
     FS_STAMP(1);
     typedef double v2d __attribute__((ext_vector_type(2)));
     typedef double v2du __attribute__((ext_vector_type(2), aligned(8)));
-    extern __shared__ __attribute__((aligned(16))) double sdict[];
-    __shared__ double lds34[3][4];
+    __shared__ double lds34[3][4], lds34e[3][4];      // (the sums of the prologue; this launch's own partials at the end)
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int64_t n_chunks = (n_items + 3) / 4;
@@ -553,8 +579,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     };
     // loads of runs [4 h, 4 h + 4) of round rd: scalar base (vector + run start) + one 32-bit byte offset per lane - the `saddr` form
     // of the load, no 64-bit address arithmetic or address registers per load (rows < 2^29)
-    // (skip0: slot 0 of the half round is not loaded - the z run of a CENTRE launch)
-    auto load_half = [&](const item_hdr& H, int rd, int h, uint32_t boff, v2d (&A)[4], v2d (&Wb)[4], v2d (&Sb)[4], bool skip0 = false) {
+    // (skip0: slot 0 of the half round is not loaded - the z run of a CENTRE launch; pre: the first item's loads in the prologue)
+    auto load_half = [&](const item_hdr& H, int rd, int h, uint32_t boff, v2d (&A)[4], v2d (&Wb)[4], v2d (&Sb)[4], bool skip0 = false, bool pre = false) {
         // (measured and not kept: run starts that need no load - kernel arguments for the plan most items have, or a per-item copy beside
         // the header - and the next item's header asked for an item ahead: with nothing left between header and run loads the
         // compiler schedules 164 - 177 VGPRs (and spills SGPRs into them), two or three waves per SIMD instead of four, and the
@@ -566,9 +592,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
         for (int j = 0; j < 4; ++j) {
             if (skip0 && j == 0) { A[0] = Wb[0] = Sb[0] = v2d{0.0, 0.0}; continue; }
             const int32_t st = sts[j];
-            A[j] = *reinterpret_cast<const v2du*>(reinterpret_cast<const char*>(r_in + st) + boff);
-            Wb[j] = *reinterpret_cast<const v2du*>(reinterpret_cast<const char*>(w_in + st) + boff);
-            Sb[j] = *reinterpret_cast<const v2du*>(reinterpret_cast<const char*>(s_in + st) + boff);
+            if (pre) { A[j] = fs_ld_pair(r_pre, st, boff); Wb[j] = fs_ld_pair(w_pre, st, boff); Sb[j] = fs_ld_pair(s_pre, st, boff); }
+            else { A[j] = fs_ld_pair(r_in, st, boff); Wb[j] = fs_ld_pair(w_in, st, boff); Sb[j] = fs_ld_pair(s_in, st, boff); }
         }
     };
     // (rp: the own rows of r_{k-1}, PAIR only)
@@ -592,30 +617,70 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
             if (!DTAB) dd.x = dvec[r];
         }
     };
+    // the same for the first item in the GUARD prologue: row by row under the lanes' masks - no two arms that write the same registers
+    // (the second arm waits for the first one's loads, and with them for everything asked for before) and no branch on `have`
+    auto load_own_pre = [&](const item_hdr& H, bool have, v2d& pp, v2d& xx, v2d& dd, v2d& rp) {
+        const int32_t r = H.first + 2 * lane;
+        pp = xx = dd = rp = v2d{0.0, 0.0};
+#ifdef FS_ITER_ABLATE_PXD
+        dd = v2d{1.0, 1.0};
+        return;
+#endif
+        if (have && 2 * lane < H.nr) {
+            if (MODE != FS_ITER_LIGHT) { pp.x = pv[r]; xx.x = xv[r]; }
+            if (MODE == FS_ITER_PAIR) rp.x = r_out[r];
+            if (!DTAB) dd.x = dvec[r];
+        }
+        if (have && 2 * lane + 1 < H.nr) {
+            if (MODE != FS_ITER_LIGHT) { pp.y = pv[r + 1]; xx.y = xv[r + 1]; }
+            if (MODE == FS_ITER_PAIR) rp.y = r_out[r + 1];
+            if (!DTAB) dd.y = dvec[r + 1];
+        }
+    };
     // Nothing the first item LOADS depends on alpha, beta: its first twelve run loads and its row-local operands are asked for
     // before the partial sums are reduced (a wave has about two items at 1 M rows; 35.3 -> 27.4 us per iteration with 1024 workgroups)
     item_hdr H0 = {};
     v2d PA[4], PW[4], PS[4], Ppp = {0.0, 0.0}, Pxx = {0.0, 0.0}, Pdd = {0.0, 0.0}, Prp = {0.0, 0.0};
     const bool have0 = it.cur < it.end && it.cur * 4 + wave < n_items;
-    if (have0) {
+    // (the vector loads the wave has certainly issued behind the dictionary's and the partials' when it comes to the sums: the run loads)
+    constexpr int RUN_LOADS0 = GUARD ? 3 * (CENTRE ? 3 : 4) : 0;
+    if (GUARD) {
+        H0 = decode(have0 ? it.cur * 4 + wave : 0);
+        load_own_pre(H0, have0, Ppp, Pxx, Pdd, Prp);        // (in front of the run loads: those are the LAST loads of every wave)
+        load_half(H0, 0, 0, (uint32_t)(H0.first + 2 * lane) * 8u, PA, PW, PS, CENTRE, true);
+    } else if (have0) {
         H0 = decode(it.cur * 4 + wave);
-        if (GUARD || !H0.edge) load_half(H0, 0, 0, (uint32_t)(H0.first + 2 * lane) * 8u, PA, PW, PS, CENTRE);
+        if (!H0.edge) load_half(H0, 0, 0, (uint32_t)(H0.first + 2 * lane) * 8u, PA, PW, PS, CENTRE, true);
         load_own(H0, Ppp, Pxx, Pdd, Prp);
     }
+    asm volatile("" ::: "memory");
     FS_STAMP(2);
-    fs_fill_lds(sdict, dict, C * S);             // (visible after the barrier of the sum below)
-    double* const sdtab = sdict + C * S;         // (DTAB: C dot weights behind the C class rows)
-    if (DTAB) {
-        if ((int)threadIdx.x < C) sdtab[threadIdx.x] = dt0;
-        for (int i = (int)threadIdx.x + FS_BLOCK; i < C; i += FS_BLOCK) sdtab[i] = dvec[i];
+    if (st0 != 0) {                             // (the no-op launches behind a converged solve: no wave leaves with a load into LDS in flight)
+        fs_fill_lds_wait<0>();
+        return;
     }
-    if (st0 != 0) return;
+    FS_STAMP(8);
+    // (a wait the compiler SEES, in front of the first use of the partials: it takes a direct-to-LDS load for one that may come back
+    // out of order, and every wait it inserts itself while it believes one in flight is vmcnt(0).  gfx9 encoding: vmcnt in bits 3:0
+    // (+ 15:14), expcnt 6:4 and lgkmcnt 11:8 left at their maxima)
+    // (... and the sums may not be begun in front of it: the partials pass through an empty statement behind it)
+    if (GUARD && !COMM) {
+        __builtin_amdgcn_s_waitcnt(0x0f70 | RUN_LOADS0);
+        asm volatile("s_nop 0");                // (the compiler merges a wait with what the NEXT instruction needs - by its book everything)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(pl[j][t]));
+        }
+    }
     // the three sums of the previous launch's partials, in the order of wg_sum_partials / fs_block_sum (same bits as the update
     // kernel of the two-launch iteration computes), with ONE barrier: a thread's partials in ascending index, the wave's by the
-    // shuffle tree, the four waves as (0 + 1) + (2 + 3) by every thread
+    // shuffle tree, the four waves as (0 + 1) + (2 + 3) by every thread.  The same barrier publishes the dictionary: every wave
+    // waits for its own direct-to-LDS loads in front of it (they went out first: at most the run loads are still outstanding).
     double sm[3];
     if (COMM) {
         sm[0] = sum_g; sm[1] = sum_d; sm[2] = sum_r;
+        fs_fill_lds_wait<0>();
         __syncthreads();                        // (the dictionary is in LDS)
     } else {                                    // (npart <= 4 x 256: the host launches this kernel with at most 1024 workgroups)
         double a[3] = {0.0, 0.0, 0.0};
@@ -631,10 +696,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
             for (int off = 32; off > 0; off >>= 1) a[j] += __shfl_down(a[j], off, 64);
             if (lane == 0) lds34[j][wave] = a[j];
         }
+        fs_fill_lds_wait<RUN_LOADS0>();
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 3; ++j) sm[j] = (lds34[j][0] + lds34[j][1]) + (lds34[j][2] + lds34[j][3]);
-        __syncthreads();                        // (lds34 is written again at the end)
     }
     FS_STAMP(3);
     const double gamma = sm[0], delta = sm[1], rho = sm[2];
@@ -803,12 +868,12 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     for (int j = 0; j < 3; ++j) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) dsum[j] += __shfl_down(dsum[j], off, 64);
-        if (lane == 0) lds34[j][wave] = dsum[j];
+        if (lane == 0) lds34e[j][wave] = dsum[j];
     }
     __syncthreads();
     FS_STAMP(7);
     if (threadIdx.x < 3) part_out[(int64_t)threadIdx.x * npart + blockIdx.x] =
-        (lds34[threadIdx.x][0] + lds34[threadIdx.x][1]) + (lds34[threadIdx.x][2] + lds34[threadIdx.x][3]);
+        (lds34e[threadIdx.x][0] + lds34e[threadIdx.x][1]) + (lds34e[threadIdx.x][2] + lds34e[threadIdx.x][3]);
 }
 
 // The step a solve of LIGHT / PAIR launches still owes x when the recurrence stops in an odd launch k (convergence, iteration limit,
