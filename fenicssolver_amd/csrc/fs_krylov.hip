@@ -15,6 +15,17 @@
 // >1 GPU) and ONE fused vector-update kernel.  alpha/beta/convergence live on the
 // device; the host only polls a status word every `batch` iterations, two batches in
 // flight, so the stream never drains.
+//
+// Parts (included below in this order, one translation unit: they share the file-scope state):
+//   fs_krylov_stream.inc    streaming products (k_sell_spmv, k_dia_pair_spmv)
+//   fs_krylov_dict.inc      row dictionary: plans, class tables, k_dict_spmv
+//   fs_box.h, fs_latmarch.h, fs_krylov_lattice.inc    marching-window and tile products of box operators
+//   fs_krylov_dict3.inc     row-dictionary product of 3 x 3 block rows
+//   fs_krylov_iter.inc      device side of the iterations: update kernels, k_dict_cg_iter, k_cg_p2p_exchange
+//   fs_krylov_boxiter.inc   k_box_cg_iter
+//   (this file)             options (fs_set_option), launch planning and launch_spmv, dict_build, lat_prepare, fs_spmv*
+//   fs_krylov_block4.inc    product of 4 x 4-block Taylor-Hood operators
+//   fs_krylov_solve.inc     host side of fs_krylov_solve: workspace, plan, pass, step functions, one-launch driver, graph cache
 #include "fs_common.h"
 #include "fs_kernels.h"
 #include <functional>
@@ -1561,1028 +1572,4 @@ extern "C" int fs_spmv_benchmark(fs_matrix_t A, fs_vector_t x, fs_vector_t y, in
     return FS_OK;
 }
 
-// persistent Krylov workspace: allocation stays out of the timed solve
-struct krylov_ws {
-    int64_t n = 0, nl = 0;
-    int hist_cap = 0;
-    dbuf<double> dinv, r, z, w, p, s, partials, sums, ctrl, scal, hist;
-    dbuf<double> rhat, t, y, partials2, bsums;   // BiCGStab only (allocated on first use)
-    dbuf<double> aval, dvec, bhat, sc_local;     // diagonally scaled CG only
-    dbuf<double> pw, pz;                         // pipelined CG only: w = A r (with ghost room: it is the exchanged vector), z = A s
-    hipEvent_t ev_upd = nullptr, ev_red = nullptr;   // pipelined CG: update done -> all-reduce on the communication stream -> sums ready
-    dbuf<int> d_err;                             // zero-diagonal counter of k_extract_dinv
-    int64_t bicg_n = -1;
-    dbuf<int> status;
-    int* h_status = nullptr;  // pinned: 2 x 4 status ints (double-buffered polls) + [8] zero-diagonal count
-    int* h_mirror = nullptr;  // pinned, written by the iteration kernel's leader lane: [0] status once stopped, [1] iteration in progress
-    int* d_mirror = nullptr;  // ... its device address
-    bool mirror_ok = true;    // false once a wait on it timed out (stores not visible on this system): the copied status word again
-    double* h_vals = nullptr; // pinned: the sums [0 .. 8) and the control block [8 .. 12) at the end of a pass
-    hipEvent_t poll[2] = {nullptr, nullptr};
-    static const int NSAMPLE = 64;
-    hipEvent_t ev[NSAMPLE][4];
-    int sample_iter[NSAMPLE];   // iteration (within its pass) a sample was taken at
-    int sample_span[NSAMPLE];   // launches a sample covers (2: a LIGHT and a PAIR launch of the one-launch iteration, their mean is reported)
-    bool sample_live[NSAMPLE];  // false: the sampled launches came after convergence (no-ops)
-    bool events = false;
-    std::vector<double> last_hist;
-    // one batch of CG iterations captured as a hipGraph (same arguments every iteration: the update kernel reads its
-    // iteration index from the device).  Re-instantiated when anything it bakes in changes.
-    dbuf<double> sg;            // s on the ghost rows, in arrival order (peer-to-peer iteration: a rank advances its ghost r, s itself)
-    hipGraphExec_t cg_graph = nullptr;
-    const void* cg_key[32] = {};
-    int64_t cg_key_i[8] = {};
-    // one-launch iteration (k_dict_cg_iter): the second set of r, w, s (double-buffered by iteration parity), the iteration
-    // counters of the device, its own captured batch
-    dbuf<double> z2, w2, s2;
-    dbuf<int> it_ctr;
-    hipGraphExec_t cgf_graph = nullptr;
-    const void* cgf_key[24] = {};
-    int64_t cgf_key_i[8] = {};
-};
-static krylov_ws g_ws;
-
-static int ws_prepare(krylov_ws& ws, int64_t n, int64_t nl, int max_iter) {
-    if (ws.n != n || ws.nl != nl) {
-        // (measured and not kept: the vectors of the update set apart by 256 B ... 1 MB so that equal
-        // indices fall on different memory channels - no effect; the 100 - 117 us spread of the update kernel at 10 M rows is
-        // the box's, not the addresses')
-        FS_CHECK(ws.dinv.alloc(n + 2));
-        FS_CHECK(ws.r.alloc(n + 2));
-        FS_CHECK(ws.z.alloc(nl + 2));
-        FS_CHECK(ws.w.alloc(nl + 2));        // (ghost room: the one-launch iteration on a decomposed space reads w and s on ghost columns)
-        FS_CHECK(ws.p.alloc(n + 2));
-        FS_CHECK(ws.s.alloc(nl + 2));
-        ws.n = n;
-        ws.nl = nl;
-    }
-    if (!ws.partials.p) {
-        FS_CHECK(ws.partials.alloc(4 * (FS_MAX_PARTIAL_BLOCKS + 8)));
-        FS_CHECK(ws.sums.alloc(8));
-        FS_CHECK(ws.ctrl.alloc(4));
-        FS_CHECK(ws.scal.alloc(8));          // ([4], [5]: beta by iteration parity, k_dict_cg_iter with LIGHT / PAIR launches)
-        FS_CHECK(ws.status.alloc(4));
-        FS_CHECK(ws.d_err.alloc(1));
-        FS_HIP(hipHostMalloc((void**)&ws.h_status, 16 * sizeof(int), hipHostMallocDefault));     // ([12 .. 16): the status word at the end of a pass)
-        FS_HIP(hipHostMalloc((void**)&ws.h_vals, 16 * sizeof(double), hipHostMallocDefault));
-        if (hipHostMalloc((void**)&ws.h_mirror, 16 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&ws.d_mirror, ws.h_mirror, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            ws.h_mirror = ws.d_mirror = nullptr;
-        }
-        FS_HIP(hipEventCreateWithFlags(&ws.poll[0], hipEventDisableTiming));
-        FS_HIP(hipEventCreateWithFlags(&ws.poll[1], hipEventDisableTiming));
-        FS_HIP(hipEventCreateWithFlags(&ws.ev_upd, hipEventDisableTiming));
-        FS_HIP(hipEventCreateWithFlags(&ws.ev_red, hipEventDisableTiming));
-        for (int i = 0; i < krylov_ws::NSAMPLE; ++i)
-            for (int j = 0; j < 4; ++j) FS_HIP(hipEventCreate(&ws.ev[i][j]));
-        ws.events = true;
-    }
-    if (ws.hist_cap < max_iter + 2) {
-        FS_CHECK(ws.hist.alloc(max_iter + 2));
-        ws.hist_cap = max_iter + 2;
-    }
-    return FS_OK;
-}
-
-extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, const fs_krylov_opts* opts,
-                               fs_krylov_stats* stats) {
-    std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
-    FS_CHECK(fs_require_init());
-    FS_REQUIRE(A && b && x && opts, "fs_krylov_solve: null pointer");
-    if (fs_is_dg(A->space)) return fs_dg_krylov_solve(A, b, x, opts, stats);
-    if (opts->method != FS_KSP_CG && opts->method != FS_KSP_BICGSTAB) {
-        fs_set_error("fs_krylov_solve: unknown Krylov method %d", opts->method);
-        return FS_ERR_UNSUPPORTED;
-    }
-    const bool bicg = opts->method == FS_KSP_BICGSTAB;
-    row_dict_scope dict_scope;           // the row dictionary describes the values of ONE solve (built below where it applies)
-    FS_REQUIRE(A->bs != 4, "fs_krylov_solve: Taylor-Hood block systems are solved by fs_saddle_solve");
-    FS_REQUIRE(opts->precond == FS_PC_NONE || opts->precond == FS_PC_JACOBI, "fs_krylov_solve: unknown preconditioner %d", opts->precond);
-    FS_REQUIRE(opts->max_iter > 0 && opts->rtol >= 0.0 && opts->atol >= 0.0, "fs_krylov_solve: bad tolerances");
-    fs_space_s* sp = A->space;
-    const int64_t n = sp->n_dofs_owned, nl = sp->n_dofs_local;
-    FS_REQUIRE(b->d.n >= n && x->d.n >= n, "fs_krylov_solve: b/x shorter than the owned dofs (%lld)", (long long)n);
-    hipStream_t s = fs_rt().stream;
-    // A scalar CG2 operator on a uniform box (one GPU) is solved in LATTICE order (fs_lattice.hip): values, b and x permuted into
-    // the solver's shadow of the space, the solve run there (this function again, on the shadow's handles), x permuted back.
-    // Automatic (option "lattice_order" = -1, the default): from FS_LATTICE_MIN_ROWS rows on, and only as long as the shadow's solves
-    // run on the tile product (a shadow whose rows do not fit the tile form - lat_prepare - is given up after its first solve).
-    if (bs_is_scalar_cg2(A) && (g_lattice > 0 || (g_lattice < 0 && sp->n_nodes_owned >= FS_LATTICE_MIN_ROWS)) && sp->lattice_state >= 0) {
-        fs_lattice_shadow* L = nullptr;
-        FS_CHECK(fs_lattice_get(sp, &L));
-        if (L) {
-            const auto t0 = std::chrono::steady_clock::now();
-            fs_matrix_s* A2 = nullptr;
-            fs_vector_s *b2 = nullptr, *x2 = nullptr;
-            FS_CHECK(fs_lattice_enter(L, A, b, x, opts->nonzero_guess != 0, &A2, &b2, &x2));
-            // (the shadow matrix has ONE serial and holds another operator's values on every call: the dictionary's marker `these rows
-            // do not repeat`, keyed on the serial, must not outlive the matrix it was set for - ADVICE r5)
-            if (g_dict.gave_up_on == A2->serial) g_dict.gave_up_on = 0;
-            g_lat.ok = false;           // (decided by THIS solve: a flag left by an earlier solve on another space says nothing)
-            g_lat.judged = false;
-            FS_CHECK(fs_krylov_solve(A2, b2, x2, opts, stats));
-            FS_CHECK(fs_lattice_leave(L, sp, x));
-            FS_HIP(hipStreamSynchronize(s));
-            if (g_lattice < 0 && g_lat.judged && !(g_lat.ok && g_lat.space_serial == A2->space->serial)) {
-                // the shadow's rows do not fit the tile form: the space's own numbering from now on, and the shadow (a second copy of
-                // the operator's structure and values: several GB at configs[3]) is given back
-                sp->lattice_state = -1;
-                fs_lattice_release(sp->lattice);
-                sp->lattice = nullptr;
-            }
-            if (stats) {
-                stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                stats->lattice_order = 1;
-            }
-            return FS_OK;
-        }
-    }
-    // FS_SOLVE_TIMING=1: wall-clock laps of the phases of a solve on stderr (each lap synchronises the stream: a diagnostic, it
-    // changes what it measures; tools/probes/first_step_probe.py uses it to split the first solve of a process)
-    static const bool lap_on = getenv("FS_SOLVE_TIMING") != nullptr;
-    auto lap_t = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!lap_on) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[fs_krylov timing] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - lap_t).count());
-        lap_t = now;
-    };
-    krylov_ws& ws = g_ws;
-    FS_CHECK(ws_prepare(ws, n, nl, opts->max_iter));
-    lap("workspace");
-    if (sp->halo.begun) {              // left over from a solve that ended in an error
-        FS_CHECK(fs_halo_end_dev(sp, fs_rt().stream));
-        sp->halo.begun = false;
-    }
-    if (bicg && (ws.bicg_n != n || ws.y.n != nl + 2)) {
-        FS_CHECK(ws.rhat.alloc(n + 2));
-        FS_CHECK(ws.t.alloc(n + 2));
-        FS_CHECK(ws.y.alloc(nl + 2));
-        FS_CHECK(ws.partials2.alloc(4 * (FS_MAX_PARTIAL_BLOCKS + 8)));
-        FS_CHECK(ws.bsums.alloc(16));
-        ws.bicg_n = n;
-    }
-    const int bs = A->bs;
-    const bool ds = !bicg && opts->precond == FS_PC_JACOBI && opts->diagonal_scale != 0;
-    if (ds) {
-        if (ws.aval.n != A->val.n) FS_CHECK(ws.aval.alloc(A->val.n));
-        if (ws.dvec.n != n + 2) {
-            FS_CHECK(ws.dvec.alloc(n + 2));
-            FS_CHECK(ws.bhat.alloc(n + 2));
-        }
-        if (ws.sc_local.n != nl + 2) FS_CHECK(ws.sc_local.alloc(nl + 2));
-    }
-    // Pipelined recurrence (k_pcg_update): only when asked for explicitly (> 0).
-    static const char* pipe_env = getenv("FS_CG_PIPELINED");
-    const int pipe_opt = pipe_env ? atoi(pipe_env) : opts->pipelined;
-    if (pipe_opt > 0 && !ds) {
-        fs_set_error("fs_krylov_solve: the pipelined recurrence needs CG + Jacobi with diagonal_scale = 1");
-        return FS_ERR_UNSUPPORTED;
-    }
-    // OPT-IN since round 4 (opts->pipelined = 1, FS_CG_PIPELINED=1): in every measurement available the recurrence lost - 69.3
-    // against 57.1 us per iteration over RCCL, 58.8 against 38.0 us over the peer-to-peer exchange at 1 M rows per rank
-    // (profiles/r03_p2p_self_halo_timings.txt): its 40 B/DOF of extra vector traffic and two more launches cost more than the
-    // 3-double all-reduce it hides.  It would pay from an all-reduce latency of about 20 us per iteration upwards (DESIGN.md
-    // section 5) - a multi-node communicator, which this library does not target.
-    const bool pipelined = ds && pipe_opt > 0;
-    if (pipelined) {
-        if (ws.pw.n != nl + 2) FS_CHECK(ws.pw.alloc(nl + 2));
-        if (ws.pz.n != n + 2) FS_CHECK(ws.pz.alloc(n + 2));
-    }
-    const bool fuse_sums = g_cg_fuse_sums && fs_rt().comm == nullptr;
-    const int vgrid = fs_grid_for(n / 2 + 1, FS_BLOCK, g_update_blocks);
-    const int pgrid = fs_grid_for(n, FS_BLOCK, FS_MAX_PARTIAL_BLOCKS);
-    if (A->bs == 1 && sp->n_pairs < 0 && spmv_use_pairs(sp, 1)) FS_CHECK(build_pair_lists(sp, s));
-    int sgrid = spmv_partials(sp, A->bs);     // dot partials per product (pairs + singles, or interior + boundary on a decomposed space)
-    const auto t_begin = std::chrono::steady_clock::now();
-
-    // Jacobi diagonal (the zero-diagonal counter is read back with the first status poll: no extra sync here)
-    {
-        FS_CHECK(ws.d_err.zero(s));
-        const int g = fs_grid_for(sp->n_nodes_owned);
-        const int jmode = ds ? 2 : (opts->precond == FS_PC_JACOBI ? 1 : 0);
-        double* dv = ds ? ws.dvec.p : nullptr;
-        if (bs == 2)
-            hipLaunchKernelGGL(k_extract_dinv<2>, dim3(g), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, jmode, ws.dinv.p, ws.d_err.p, dv);
-        else if (bs == 1)
-            hipLaunchKernelGGL(k_extract_dinv<1>, dim3(g), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, jmode, ws.dinv.p, ws.d_err.p, dv);
-        else
-            hipLaunchKernelGGL(k_extract_dinv<3>, dim3(g), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, jmode, ws.dinv.p, ws.d_err.p, dv);
-        FS_KERNEL_CHECK();
-        FS_HIP(hipMemcpyAsync(ws.h_status + 8, ws.d_err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    const bool pnorm = opts->norm_type == FS_NORM_PRECONDITIONED;
-    if (pnorm && !ds) {
-        fs_set_error("fs_krylov_solve: the preconditioned residual norm needs CG + Jacobi with diagonal_scale = 1");
-        return FS_ERR_UNSUPPORTED;
-    }
-    // ||b||^2 -> threshold.  Preconditioned norm (PETSc's KSPCG default): ||D^-1 b||^2 = sum (dinv_s^2 b)^2,
-    // where ws.dinv holds 1/sqrt(d) in scaled mode, and the residual weights become 1/d instead of d.
-    if (pnorm) {
-        hipLaunchKernelGGL(k_pointwise_mul, dim3(fs_grid_for(n)), dim3(FS_BLOCK), 0, s, ws.dinv.p, ws.dinv.p, n, ws.dvec.p);  // 1/d
-        hipLaunchKernelGGL(k_pointwise_mul, dim3(fs_grid_for(n)), dim3(FS_BLOCK), 0, s, ws.dvec.p, b->d.p, n, ws.bhat.p);    // b/d
-        hipLaunchKernelGGL(k_dot_partial, dim3(pgrid), dim3(FS_BLOCK), 0, s, ws.bhat.p, ws.bhat.p, n, ws.partials.p);
-    } else
-    hipLaunchKernelGGL(k_dot_partial, dim3(pgrid), dim3(FS_BLOCK), 0, s, b->d.p, b->d.p, n, ws.partials.p);
-    FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p, pgrid, 1, ws.sums.p + 4, s));
-    hipLaunchKernelGGL(k_set_threshold, dim3(1), dim3(64), 0, s, ws.sums.p + 4, opts->rtol, opts->atol, ws.ctrl.p);
-    const double* aval = nullptr;
-    lap("diagonal, |b|, threshold");
-    if (ds) {
-        // the scaled system needs ghost scale factors too: refresh them through the halo
-        // (no halo plan: no ghost entries - the factors are read where they are)
-        double* sc_local = sp->halo.active ? ws.sc_local.p : ws.dinv.p;
-        if (sp->halo.active) {
-            FS_HIP(hipMemcpyAsync(sc_local, ws.dinv.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            FS_CHECK(fs_halo_exchange_dev(sp, sc_local, s));
-        }
-        const int g2 = fs_grid_for(sp->n_slices * 64, FS_BLOCK, 8192);
-        const auto scale_copy1 = [&]() {
-            hipLaunchKernelGGL(k_scale_copy<1>, dim3(g2), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, sc_local, ws.aval.p);
-        };
-        // scalar operator on one GPU: the scaled copy is written only if somebody is going to read it - a matrix that the kept class
-        // table describes (verified on the fly-scaled values, dict_build) is multiplied from the table alone
-        static const bool lazy_env = !(getenv("FS_LAZY_SCALE_COPY") && getenv("FS_LAZY_SCALE_COPY")[0] == '0');
-        const bool lazy_copy = bs == 1 && !sp->halo.active && lazy_env;
-        if (bs == 2)
-            hipLaunchKernelGGL(k_scale_copy<2>, dim3(g2), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, sc_local, ws.aval.p);
-        else if (bs == 1) {
-            if (!lazy_copy) scale_copy1();
-        } else
-            hipLaunchKernelGGL(k_scale_copy<3>, dim3(g2), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->n_slices, sp->slice_ptr.p, sp->sell_col.p, A->val.p, sp->sell_entries, sc_local, ws.aval.p);
-        hipLaunchKernelGGL(k_pointwise_mul, dim3(fs_grid_for(n)), dim3(FS_BLOCK), 0, s, ws.dinv.p, b->d.p, n, ws.bhat.p);
-        FS_KERNEL_CHECK();
-        aval = ws.aval.p;
-        if (bs == 1) {
-            // a handful of distinct rows (uniform box, constant coefficient)?
-            // (with the dot weights of the solve: a table of them by class for the one-launch iteration)
-            if (lazy_copy) FS_CHECK(dict_build(A, aval, s, A->val.p, sc_local, scale_copy1, ws.dvec.p));
-            else FS_CHECK(dict_build(A, aval, s, nullptr, nullptr, nullptr, ws.dvec.p));
-            sgrid = spmv_partials(sp, bs);          // (the row-dictionary product has its own launch geometry)
-        }
-    }
-    lap("scaling + row classes");
-    // One launch per iteration (k_dict_cg_iter) where the product is the row-dictionary kernel with the whole dictionary in LDS,
-    // on one GPU.  Automatic mode: FS_CG_FUSED_MAX_ROWS rows at most (the neighbour values of three vectors instead of one have
-    // to stay in the L2 of an XCD; measured crossover in DESIGN.md section 3).
-    static const char* fused_env = getenv("FS_CG_FUSED");
-    static const int64_t fused_max_rows = getenv("FS_CG_FUSED_MAX_ROWS") ? atoll(getenv("FS_CG_FUSED_MAX_ROWS")) : (int64_t)3000000;
-    const int fused_opt = fused_env ? atoi(fused_env) : g_cg_fused;
-    const bool fused_common = ds && !pipelined && bs == 1 && fused_opt != 0 &&
-                              g_dict.bs == 1 && g_dict.built_for && g_dict.built_for == aval && sp->n_dict_items > 0 &&
-                              (size_t)g_dict.ncls * g_dict.S * sizeof(double) <= (size_t)FS_DICT_WHOLE_LDS_BYTES &&
-                              nl < ((int64_t)1 << 29) && sp->dict_run_len == 3 && sp->dict_runs == 8 && (fused_opt > 0 || n <= fused_max_rows);
-    // (round 6) P1 boxes from 400 k rows on: the iteration in marching-window form (k_box_cg_iter), with its own launch geometry
-    const box_iter_plan_s* BI = (fused_common && !sp->halo.active && fuse_sums) ? box_iter_plan_for(sp, g_dict.ncls) : nullptr;
-    const int igrid = fused_common ? (BI ? BI->g.grid : spmv_partials_unsplit(sp, bs)) : 0;        // workgroups (= dot partials) of the iteration kernel
-    const bool fused_sized = fused_common && 3 * (int64_t)igrid * 2 <= (int64_t)ws.partials.n && igrid <= 4 * FS_BLOCK;
-    const bool fused = fused_sized && fuse_sums && !sp->halo.active;
-    // a decomposed space: the same kernel after the peer-to-peer exchange kernel (two launches per iteration instead of three) - where
-    // that exchange is what the iteration uses (decided per pass below: p2p_fuse); a rank-local choice, the exchange protocol is the same
-    static const bool fused_p2p_on = !(getenv("FS_CG_FUSED_P2P") && getenv("FS_CG_FUSED_P2P")[0] == '0');
-    const bool fusedp_ok = fused_sized && !fuse_sums && sp->halo.active && fused_p2p_on;
-    // k_dict_cg_iter: p and x every second launch (option "cg_pair"), dot weights from the class table where every row agrees with it
-    const bool pair_form = g_cg_pair != 0, dtab_form = pair_form && g_dict.dtab_ok;
-    // ... and on one GPU the six vectors whose neighbour columns it reads with guard bands of zeros (option "cg_guard"): every run load of
-    // every item is then inside the block (a lane reads columns first + 2 lane + start + {0, 1}, lane < 64: 130 covers the item's 128
-    // values and the second value of a load; a multiple of 32 keeps row 0 on the alignment the block has), no item takes the clamped
-    // path.  The bands are zeroed with the block and nothing writes them: every kernel that gets these pointers writes rows of [0, nl + 2).
-    const bool guard_form = g_cg_guard != 0 && pair_form && fused && !BI;
-    const bool centre_form = guard_form && sp->dict_centre;
-    const int64_t guard = guard_form ? 32 * ((std::max<int64_t>(-(int64_t)sp->dict_min_start, sp->dict_max_start) + 130 + 31) / 32) : 0;
-    if (fused || fusedp_ok) {
-        dbuf<double>* const six[6] = {&ws.z, &ws.w, &ws.s, &ws.z2, &ws.w2, &ws.s2};
-        for (dbuf<double>* v : six)
-            if (v->n != nl + 2 || v->guard != guard) {
-                if (guard) FS_CHECK(v->alloc_guarded(nl + 2, guard, s));
-                else FS_CHECK(v->alloc(nl + 2));
-            }
-        if (!ws.it_ctr.p) FS_CHECK(ws.it_ctr.alloc(2));
-    }
-    int iteration_form = 0;
-    // A pass = fresh recurrences from the current x.  The single-reduction recurrences drift on
-    // ill-conditioned operators (the recurrence residual can reach the threshold while b - A x has not):
-    // the true residual is recomputed after every pass and, if it misses the tolerance, the solve
-    // restarts from the current x (at most 8 passes, iteration budget shared).
-    static const int env_batch = getenv("FS_CG_BATCH") ? atoi(getenv("FS_CG_BATCH")) : 0;
-    const int batch = opts->batch > 0 ? opts->batch : (env_batch > 0 ? env_batch : g_cg_batch);
-    // kernel durations (stats->spmv_ms / update_ms: the roofline of bench.py) are sampled with HIP events every
-    // sample_every-th iteration, 4 events each.  The markers are not free: on the 1 M-DOF solve (293 iterations of 45 us)
-    // sampling every 4th iteration costs 0.87 ms per solve (6 %), every 16th 0.4 ms - the default
-    static const int sample_every = getenv("FS_CG_SAMPLE_EVERY") ? std::max(1, atoi(getenv("FS_CG_SAMPLE_EVERY"))) : 16;
-    static const char* upd_nt_env = getenv("FS_UPDATE_NT");
-    const bool upd_nt = upd_nt_env ? upd_nt_env[0] == '1' : (int64_t)sp->n_dofs_owned * 72 > ((int64_t)192 << 20);   // five vectors exceed the caches
-    int total_iters = 0, n_samples = 0, n_pass = 0, n_launches = 0;
-    bool fusedp_used = false;
-    int h_status[4] = {0, 0, 0, 0};
-    bool use_guess = opts->nonzero_guess != 0;
-    double true_rr = 0.0, thresh = 0.0, bb_host = 0.0, prev_true_rr = 1e300;
-    for (;;) {
-        // initial state
-        FS_CHECK(ws.status.zero(s));
-        FS_CHECK(ws.scal.zero(s));
-        if (g_cg_poison_p) {          // (a pass sets p_{-1} = 0 itself: the LIGHT launches never write p, the first PAIR launch reads it)
-            FS_HIP(hipMemsetAsync(ws.p.p, 0xff, (size_t)ws.p.n * sizeof(double), s));
-            g_cg_poison_p = 0;
-        }
-        // p, s, z and - from a zero guess - x in one launch
-        hipLaunchKernelGGL(k_zero4, dim3(fs_grid_for(std::max<int64_t>(nl / 2, 1), FS_BLOCK, 1024)), dim3(FS_BLOCK), 0, s, ws.p.p, ws.p.n, ws.s.p, ws.s.n,
-                           ws.z.p, ws.z.n, x->d.p, use_guess ? (int64_t)0 : x->d.n);
-        if (sp->halo.active) {          // s on the ghost rows (k_cg_p2p_exchange)
-            if (ws.sg.n < nl - n + 2) FS_CHECK(ws.sg.alloc(nl - n + 2));
-            FS_CHECK(ws.sg.zero(s));
-        }
-        if (ds) {
-            // scaled unknown xhat = D^1/2 x lives in the caller's x until the final un-scaling; rhat in ws.z
-            if (use_guess) {
-                if (n_pass == 0) hipLaunchKernelGGL(k_pointwise_div, dim3(fs_grid_for(n)), dim3(FS_BLOCK), 0, s, x->d.p, ws.dinv.p, n, x->d.p);
-                FS_HIP(hipMemcpyAsync(ws.z.p, x->d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-                FS_CHECK(fs_halo_exchange_dev(sp, ws.z.p, s));
-                launch_spmv<0>(A, ws.z.p, ws.w.p, nullptr, nullptr, nullptr, s, aval);
-                hipLaunchKernelGGL(k_residual, dim3(pgrid), dim3(FS_BLOCK), 0, s, ws.bhat.p, ws.w.p, n, ws.z.p, ws.partials.p);
-            } else {
-                FS_HIP(hipMemcpyAsync(ws.z.p, ws.bhat.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            }
-        } else {
-            if (use_guess) {
-                FS_HIP(hipMemcpyAsync(ws.z.p, x->d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-                FS_CHECK(fs_halo_exchange_dev(sp, ws.z.p, s));
-                launch_spmv<0>(A, ws.z.p, ws.w.p, nullptr, nullptr, nullptr, s);
-                hipLaunchKernelGGL(k_residual, dim3(pgrid), dim3(FS_BLOCK), 0, s, b->d.p, ws.w.p, n, ws.r.p, ws.partials.p);
-            } else {
-                FS_HIP(hipMemcpyAsync(ws.r.p, b->d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            }
-            hipLaunchKernelGGL(k_pointwise_mul, dim3(fs_grid_for(n)), dim3(FS_BLOCK), 0, s, ws.dinv.p, ws.r.p, n, ws.z.p);
-        }
-        FS_KERNEL_CHECK();
-        // pipelined CG: the all-reduce of the sums runs on the communication stream of the halo plan, behind ev_upd, and the
-        // compute stream waits for ev_red only when the next update needs the sums - the product sits in between.  Without
-        // a halo plan (a replicated operator) the collective stays in-stream.
-        hipStream_t red_stream = nullptr;
-        // (the peer-to-peer all-reduce is a kernel of a few microseconds: it stays in the compute stream, a second stream's two event
-        // hops cost more than it hides)
-        if (pipelined && !fuse_sums && sp->halo.active && !fs_p2p_reduce_enabled()) FS_CHECK(fs_halo_comm_stream(sp, &red_stream));
-        auto pcg_reduce = [&](int parity) -> int {
-            hipStream_t q = red_stream ? red_stream : s;
-            if (red_stream) {
-                FS_HIP(hipEventRecord(ws.ev_upd, s));
-                FS_HIP(hipStreamWaitEvent(red_stream, ws.ev_upd, 0));
-            }
-            FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p + (int64_t)parity * 3 * vgrid, vgrid, 3, ws.sums.p, q));
-            if (red_stream) FS_HIP(hipEventRecord(ws.ev_red, red_stream));
-            return FS_OK;
-        };
-        if (pipelined) {
-            // r0 sits in ws.z; w0 = A r0, z = 0 (p, s are zero already), sums of (r0, w0)
-            FS_CHECK(ws.pz.zero(s));
-            FS_CHECK(fs_halo_exchange_dev(sp, ws.z.p, s));
-            launch_spmv<0>(A, ws.z.p, ws.pw.p, nullptr, nullptr, nullptr, s, aval);
-            hipLaunchKernelGGL(k_pcg_dots, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, ws.z.p, ws.pw.p, ws.dvec.p, ws.partials.p, vgrid);
-            FS_KERNEL_CHECK();
-            if (!fuse_sums) FS_CHECK(pcg_reduce(0));
-        }
-        if (bicg) {
-            // rhat = r0; first (rhat.r, r.r) partials; v = 0 (ws.w), p = 0, y = 0
-            FS_HIP(hipMemcpyAsync(ws.rhat.p, ws.r.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            FS_CHECK(ws.w.zero(s));
-            FS_CHECK(ws.y.zero(s));
-            hipLaunchKernelGGL(k_dot2_partial, dim3(vgrid), dim3(FS_BLOCK), 0, s, ws.rhat.p, ws.r.p, ws.r.p, ws.r.p, n, ws.partials2.p);
-            FS_KERNEL_CHECK();
-        }
-
-        // iteration pipeline
-        const int max_iter = opts->max_iter - total_iters > 0 ? opts->max_iter - total_iters : 1;
-        hipLaunchKernelGGL(k_set_iteration_limit, dim3(1), dim3(64), 0, s, ws.ctrl.p, max_iter);
-        double* const hist_p = ws.hist.p + total_iters;
-        int k = 0, slot = 0, pending = -1;
-        bool finished = false;
-        const int first_sample = n_samples;
-        // Batches after the first (which carries the event samples) go out as ONE hipGraphLaunch of 2 x batch kernel nodes
-        // on cache-resident problems: the gaps between consecutive launches (2 x 2.1 us of a 44 us iteration at 1 M DOF)
-        // shrink to the graph's own node-to-node latency.
-        static const char* graph_env = getenv("FS_CG_GRAPH");
-        // rocprofv3 (ROCm 7.2) segfaults inside hipGraphLaunch once about 10 500 kernel nodes have been replayed under
-        // --kernel-trace (168 launches of this 64-node graph; nothing to do with the graph's contents or age - renewing
-        // the executable does not help, plain launches of the same kernels trace fine).  With the profiler's tool library
-        // in the process the automatic mode therefore falls back to plain launches: the kernels and their durations are
-        // the same, only the 2 x 2 us of launch gap per iteration come back.  FS_CG_GRAPH=1 still forces graphs.
-        static const bool profiler_attached = getenv("ROCP_TOOL_LIBRARIES") != nullptr;
-        int graph_mode = graph_env ? atoi(graph_env) : g_cg_graph;
-        if (graph_mode < 0 && profiler_attached) {
-            static bool told = false;
-            if (!told) fprintf(stderr, "[libfsamd] rocprofiler tool library detected: CG batches go out as plain launches, not hipGraphs\n");
-            told = true;
-            graph_mode = 0;
-        }
-        // rows sent to the neighbours as a prefix [0, early_a) and / or a suffix [early_b, n) of the owned rows (z-slabs): see
-        // the update below.  FS_HALO_EARLY=0 keeps the exchange inside the product.
-        int64_t early_a = 0, early_b = n;
-        int p2p_fuse = 0, p2p_rows_cap = 128;
-        bool p2p_ghosts_in = false;      // fused peer-to-peer iteration: the ghosts of the next product were received by the rows kernel
-        if (ds && !bicg && !fuse_sums && sp->halo.active) {     // (a condition every rank evaluates alike; !fuse_sums: a communicator is up)
-            static const bool no_early = getenv("FS_HALO_EARLY") && getenv("FS_HALO_EARLY")[0] == '0';
-            fs_halo_plan& hp = sp->halo;
-            if (hp.early < 0) {
-                bool ok = !no_early && spmv_is_split(sp);
-                int64_t a = 0, b2 = n;
-                for (size_t i = 0; ok && i < hp.neighbors.size(); ++i) {
-                    if (hp.send_counts[i] <= 0) continue;
-                    const int64_t first = hp.send_first[i], last = first + hp.send_counts[i];
-                    if (!hp.send_contiguous[i]) ok = false;
-                    else if (first == 0) a = std::max(a, last);
-                    else if (last == n) b2 = std::min(b2, first);
-                    else ok = false;
-                }
-                a = (a + 1) & ~(int64_t)1;          // the bulk update works on 16-byte pairs
-                ok = ok && a < b2 && (a > 0 || b2 < n);
-                // every rank has to take the same path: an exchange begun by one side only would never be matched
-                // (+ 1024 per rank with the peer-to-peer exchange on: the kernel of the iteration below is gated by the status word,
-                // the separate send / receive kernels are not - a mix would leave one side waiting)
-                double flag = (ok ? 1.0 : 0.0) + (fs_p2p_fusable(sp) ? 1024.0 : 0.0);
-                FS_HIP(hipMemcpyAsync(ws.sums.p + 6, &flag, sizeof(double), hipMemcpyHostToDevice, s));
-                FS_CHECK(fs_comm_allreduce_dev(ws.sums.p + 6, 1, s));
-                FS_HIP(hipMemcpyAsync(&flag, ws.sums.p + 6, sizeof(double), hipMemcpyDeviceToHost, s));
-                FS_HIP(hipStreamSynchronize(s));
-                const int nr_all = fs_rt().n_ranks, agreed = (int)(flag + 0.5);
-                hp.early = agreed % 1024 == nr_all ? 1 : 0;
-                hp.fuse = agreed / 1024 == nr_all ? 1 : 0;
-                hp.early_a = a;
-                hp.early_b = b2;
-                if (getenv("FS_KRYLOV_DEBUG"))
-                    fprintf(stderr, "[fs_krylov] rank %d: rows [0,%lld) and [%lld,%lld) are sent; early start of the exchange: %s\n", fs_rt().rank,
-                            (long long)a, (long long)b2, (long long)n, hp.early == 1 ? "yes" : "no");
-            }
-            if (hp.early == 1) { early_a = hp.early_a; early_b = hp.early_b; }
-            // Peer-to-peer exchange on every rank: the iteration is THREE kernels of the compute stream - the plain product, the
-            // exchange kernel (k_cg_p2p_exchange: all-reduce, send, receive), the plain update - instead of seven launches on two
-            // streams (below).  FS_P2P_FUSE=0 keeps the separate send / receive / all-reduce kernels of the same transport around a
-            // split product.  Measured alternatives that lost on MI355X: ghost columns read straight from the (uncached,
-            // fine-grained) receive buffer by the boundary rows of one merged product (67 instead of 39 us per product at 1 M rows),
-            // and the sums posted by the last workgroup of the product (its agent-scope fence in every workgroup writes back the
-            // whole L2 of the XCD: + 26 us).
-            static const int fuse_env = getenv("FS_P2P_FUSE") ? atoi(getenv("FS_P2P_FUSE")) : 1;
-            static const int rows_env = getenv("FS_P2P_ROWS_BLOCKS") ? atoi(getenv("FS_P2P_ROWS_BLOCKS")) : 128;
-            p2p_rows_cap = rows_env > 0 ? rows_env : 128;
-            if (hp.fuse == 1 && !pipelined && fuse_env) p2p_fuse = 1;
-        }
-        // (the peer-to-peer iteration is three kernels and no library call, with its sequence numbers on the device: it is captured the
-        // same way; the RCCL iteration is not - ncclSend / ncclRecv / ncclAllReduce are host calls)
-        // (automatic mode: every size - the launch gaps are 10 % of an iteration at 1 M rows and still 1.5 % at 10 M)
-        const bool graph_sized = graph_mode != 0;
-        // The FIRST graph a process instantiates costs 9 ms (the runtime's graph machinery; later ones 0.1 ms), twelve times what the
-        // graphs save a 300-iteration solve at 1 M rows: the first solve of a process launches its iterations one by one - a
-        // one-shot run never pays, a time loop pays in its second step (tools/probes/first_step_probe.py; FS_CG_GRAPH=1 forces graphs)
-        // (round 6: fs_init instantiates a two-node graph on a helper thread while the code objects load - the machinery is paid for
-        // there, and the first solve of a process goes out in graphs like every other; FS_WARM=0 restores the old rule)
-        static bool first_solve_done = !(getenv("FS_WARM") && getenv("FS_WARM")[0] == '0');
-        const bool graphs_allowed = first_solve_done || graph_mode > 0;
-        struct mark_done { bool& f; ~mark_done() { f = true; } } mark_first_solve{first_solve_done};
-        const bool fusedp = fusedp_ok && p2p_fuse && !bicg;
-        if (fusedp) fusedp_used = true;
-        const bool use_graph = ds && !bicg && !pipelined && graph_sized && !fused && !fusedp &&
-                               ((fuse_sums && !sp->halo.active && bs == 1) || p2p_fuse);
-        // One-launch iteration on one GPU: the host follows the device through two words of pinned memory the kernel's leader lane
-        // writes (iteration in progress, status once stopped) and keeps between cg_ahead and cg_ahead + cg_sub launches enqueued.
-        // With batches of 32 and the status word copied back behind each, a solve of 293 iterations enqueued 352 launches - the
-        // 59 that returned on the status word cost 5.3 us each, 0.31 of a 6.8 ms solve - and ten in-stream copies.
-        static const int mirror_env = getenv("FS_CG_MIRROR") ? atoi(getenv("FS_CG_MIRROR")) : -1;
-        // (the same for the two-launch iteration on one GPU - streaming products, row-dictionary products above 3 M rows -, whose
-        // update kernel writes the words: its batches of 32 left up to 59 x 2 launches behind the last iteration)
-        const bool two_launch_1gpu = use_graph && !p2p_fuse && fuse_sums && !sp->halo.active;
-        bool mirrored = ((fused && !fusedp) || two_launch_1gpu) && ws.d_mirror && ws.mirror_ok && (mirror_env >= 0 ? mirror_env != 0 : g_cg_mirror != 0);
-        int* const mirror_dev = mirrored ? ws.d_mirror : nullptr;
-        volatile int* const hm = ws.h_mirror;
-        if (mirrored) { hm[0] = 0; hm[1] = 0; }
-        const int bsz = mirrored ? g_cg_sub : batch;
-        // the launches that carry the event samples go out one by one before the graphs take over: the first 32 iterations (samples
-        // at iterations 1 and 17), or - with the progress words - the first 16 (samples at 1 and 9)
-        const int first_plain = mirrored ? std::min(batch, 16) : batch;
-        const int sample_step = mirrored ? std::min(sample_every, 8) : sample_every;
-        int seen = 0;
-        auto t_seen = std::chrono::steady_clock::now();
-        while (!finished) {
-            if (mirrored && k > 0) {
-                if (hm[0] != 0) break;                  // the recurrence has stopped: what is enqueued returns on the status word
-                const int done = hm[1];
-                if (k - done > g_cg_ahead) {            // enough enqueued: wait for the device to get on
-                    if (done != seen) { seen = done; t_seen = std::chrono::steady_clock::now(); }
-                    else if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_seen).count() > 2.0) {
-                        // no progress seen for two seconds: the kernel's stores do not reach this host memory while it runs.  The
-                        // copied status word from here on, for the rest of the process.
-                        FS_HIP(hipStreamSynchronize(s));
-                        ws.mirror_ok = false;
-                        mirrored = false;
-                        fprintf(stderr, "[libfsamd] CG progress words in pinned memory not updated by the device: polling the status word by copies\n");
-                    }
-                    continue;
-                }
-            }
-            const int kend = (k + bsz < max_iter + 1) ? k + bsz : max_iter + 1;
-            const int k_before = k;
-            if (fused || fusedp) {
-                // launch k = update k + product k + 1; buffers [k & 1] are read, [(k + 1) & 1] written.  Decomposed space (fusedp):
-                // the exchange kernel goes first - it reduces the sums of the previous launch's partials over the ranks, stores the
-                // neighbours' w into the ghost rows of the current w and advances the ghost rows of r and s into the next buffers
-                double* const Z[2] = {ws.z.p, ws.z2.p};
-                double* const W[2] = {ws.w.p, ws.w2.p};
-                double* const SV[2] = {ws.s.p, ws.s2.p};
-                double* const PT[2] = {ws.partials.p, ws.partials.p + 3 * (int64_t)igrid};
-                // (one GPU only: behind the exchange kernel of a decomposed space the LIGHT instantiation compiles to 132 VGPRs, three
-                // waves per SIMD instead of the four the launch needs - that form keeps p and x in every launch)
-                const bool pair = pair_form && !fusedp && !BI, dtab = pair && dtab_form;
-                const bool guarded = pair && guard_form, centre = pair && centre_form;
-                iteration_form = (pair ? 1 : 0) | (dtab ? 2 : 0) | (guarded ? 4 : 0) | (centre ? 8 : 0);
-                const size_t lds = (size_t)g_dict.ncls * (g_dict.S + (dtab ? 1 : 0)) * sizeof(double);
-                const double* const weights = dtab ? g_dict.dtab.p : ws.dvec.p;
-                fs_p2p_rowsred red2[2] = {};
-                fs_p2p_sendrows snd2[2] = {};
-                if (fusedp)
-                    for (int c = 0; c < 2; ++c) FS_CHECK(fs_p2p_exchange_args(sp, PT[c], igrid, ws.sums.p, &red2[c], &snd2[c]));
-                auto launch_exchange = [&](int par) {
-                    const int64_t work = std::max(snd2[par].total_send, snd2[par].total_recv);
-                    const fs_pp_ghosts pp = {W[par], SV[par], SV[par ^ 1], Z[par], Z[par ^ 1], ws.it_ctr.p, par};
-                    hipLaunchKernelGGL((k_cg_p2p_exchange<true>), dim3(fs_grid_for(std::max<int64_t>(work, 1), FS_BLOCK, p2p_rows_cap)), dim3(FS_BLOCK), 0, s,
-                                       0, 0, ws.ctrl.p, ws.scal.p, ws.status.p, (double*)nullptr, W[par], (double*)nullptr, red2[par], snd2[par], pp);
-                };
-                auto launch_iter = [&](int par) {
-#define FS_ITER_ARGS dim3(igrid), dim3(FS_BLOCK), lds, s, sp->n_nodes_local, sp->n_dict_items, reinterpret_cast<const int4*>(sp->dict_items.p), \
-                     reinterpret_cast<const dict_plan_round*>(sp->dict_plans.p), g_dict.cls.p, g_dict.values.p, g_dict.S, g_dict.ncls, \
-                     Z[par], W[par], SV[par], Z[par ^ 1], W[par ^ 1], SV[par ^ 1], ws.p.p, x->d.p, weights, PT[par], PT[par ^ 1], igrid, \
-                     ws.ctrl.p, ws.scal.p, ws.status.p, ws.it_ctr.p, par, hist_p, dict_map_xcd(), ws.sums.p, mirror_dev
-                    if (BI && !fusedp) {
-#define FS_BOX_ITER_ARGS dim3(igrid), dim3(6 * 64), BI->lds, s, BI->g, g_dict.cls.p, g_dict.values.p, g_dict.ncls, Z[par], W[par], SV[par], Z[par ^ 1], W[par ^ 1], \
-                         SV[par ^ 1], ws.p.p, x->d.p, ws.dvec.p, PT[par], PT[par ^ 1], igrid, ws.ctrl.p, ws.scal.p, ws.status.p, ws.it_ctr.p, par, hist_p, mirror_dev
-                        if (BI->ahead == 2) hipLaunchKernelGGL((k_box_cg_iter<4, 2, 2, 2>), FS_BOX_ITER_ARGS);
-                        else hipLaunchKernelGGL((k_box_cg_iter<4, 2, 1, 2>), FS_BOX_ITER_ARGS);
-#undef FS_BOX_ITER_ARGS
-                    } else if (fusedp) {
-                        launch_exchange(par);
-                        hipLaunchKernelGGL((k_dict_cg_iter<3, true>), FS_ITER_ARGS);
-                    } else if (!pair) hipLaunchKernelGGL((k_dict_cg_iter<3, false>), FS_ITER_ARGS);
-                    else {                     // (launch parity = iteration parity: it_ctr is zeroed at k = 0)
-#define FS_ITER_LAUNCH(DT, GU, CE) do { \
-                            if (par) hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_PAIR, DT, GU, CE>), FS_ITER_ARGS); \
-                            else hipLaunchKernelGGL((k_dict_cg_iter<3, false, FS_ITER_LIGHT, DT, GU, CE>), FS_ITER_ARGS); \
-                        } while (0)
-                        if (centre) { if (dtab) FS_ITER_LAUNCH(true, true, true); else FS_ITER_LAUNCH(false, true, true); }
-                        else if (guarded) { if (dtab) FS_ITER_LAUNCH(true, true, false); else FS_ITER_LAUNCH(false, true, false); }
-                        else if (dtab) FS_ITER_LAUNCH(true, false, false);
-                        else FS_ITER_LAUNCH(false, false, false);
-#undef FS_ITER_LAUNCH
-                    }
-#undef FS_ITER_ARGS
-                };
-                if (k == 0) {
-                    // product 0 (w_0 = A r_0 and its sums) by the plain product kernel; s_{-1} = p_{-1} = 0 were set above
-                    FS_CHECK(ws.it_ctr.zero(s));
-                    if (fusedp && !p2p_ghosts_in) {          // the ghost rows of r_0: the plain send and receive kernels
-                        FS_CHECK(fs_halo_exchange_dev(sp, ws.z.p, s));
-                        p2p_ghosts_in = true;
-                    }
-                    if (BI && !fusedp) {
-                        // (the product kernel on the ITERATION's patches and chunks: one dot partial per workgroup of either kernel)
-                        box_plan_s P0;
-                        P0.g = BI->g; P0.lds = BI->lds_product; P0.shape = 0;
-                        launch_box<3>(&P0, g_dict.cls.p, g_dict.values.p, g_dict.ncls, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, 0, igrid, 1, s);
-                        g_last_product_kind = 3;
-                    } else
-                        launch_spmv<3>(A, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, s, aval, nullptr, 0, 0, 0, 0);
-                }
-                if (graph_sized && graphs_allowed && k >= first_plain && kend - k == bsz && kend <= max_iter && (bsz & 1) == 0 && (k & 1) == 0) {
-                    const void* key[24] = {A, aval, x->d.p, hist_p, ws.z.p, ws.w.p, ws.partials.p, ws.status.p, weights, ws.p.p, ws.s.p,
-                                           ws.z2.p, ws.w2.p, ws.s2.p, ws.it_ctr.p, g_dict.cls.p, g_dict.values.p, sp->dict_items.p, sp->dict_plans.p,
-                                           ws.ctrl.p, ws.scal.p, snd2[0].own_recv, red2[0].own_buf,
-                                           fusedp ? reinterpret_cast<const void*>((uintptr_t)sp->halo.p2p.generation + 1) : nullptr};
-                    const int64_t key_i[8] = {n, ((int64_t)g_dict.ncls * 256 + g_dict.S) * 4 + (fusedp ? 1 : 0) + (mirror_dev ? 2 : 0), bsz + 4096 * (BI ? BI->ahead : 0) + 65536 * iteration_form, igrid,
-                                              (int64_t)dict_map_xcd() + 16 * (int64_t)p2p_rows_cap,
-                                              (int64_t)sp->n_dict_items, (int64_t)A->serial, (int64_t)sp->serial};
-                    if (!ws.cgf_graph || memcmp(key, ws.cgf_key, sizeof(key)) || memcmp(key_i, ws.cgf_key_i, sizeof(key_i))) {
-                        if (ws.cgf_graph) { (void)hipGraphExecDestroy(ws.cgf_graph); ws.cgf_graph = nullptr; }
-                        hipGraph_t graph = nullptr;
-                        FS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                        for (int i = 0; i < bsz; ++i) launch_iter(i & 1);
-                        FS_HIP(hipStreamEndCapture(s, &graph));
-                        FS_HIP(hipGraphInstantiate(&ws.cgf_graph, graph, nullptr, nullptr, 0));
-                        (void)hipGraphDestroy(graph);
-                        memcpy(ws.cgf_key, key, sizeof(key));
-                        memcpy(ws.cgf_key_i, key_i, sizeof(key_i));
-                    }
-                    FS_HIP(hipGraphLaunch(ws.cgf_graph, s));
-                    k = kend;
-                }
-                // (LIGHT / PAIR launches: a sample is a PAIR launch and the LIGHT launch behind it, reported as their mean - avg_launch_ms
-                // stays the mean launch of the solve)
-                bool sample_open = false;
-                for (; k < kend; ++k) {
-                    const bool sample = !sample_open && (k % sample_step == 1 % sample_step) && n_samples < krylov_ws::NSAMPLE;
-                    if (sample) {
-                        ws.sample_iter[n_samples] = k;
-                        ws.sample_span[n_samples] = 0;
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][0], s));
-                        sample_open = true;
-                    }
-                    launch_iter(k & 1);
-                    if (sample_open) {
-                        ++ws.sample_span[n_samples];
-                        if (!pair || ws.sample_span[n_samples] == 2 || k + 1 == kend) {
-                            FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
-                            FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                            FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
-                            ++n_samples;
-                            sample_open = false;
-                        }
-                    }
-                }
-            }
-            if (use_graph && graphs_allowed && k >= first_plain && kend - k == bsz && kend <= max_iter) {
-                // everything the captured launches bake in: the vectors of the workspace, the operator's value and
-                // structure arrays - and the serial numbers of matrix and space, because a destroyed operator's heap
-                // and pool addresses are handed out again (another mesh with the same row count would otherwise replay
-                // this graph over column arrays that no longer exist)
-                fs_p2p_rowsred red = {};
-                fs_p2p_sendrows snd = {};
-                const int fgrid = p2p_fuse ? spmv_partials_unsplit(sp, bs) : sgrid;
-                if (p2p_fuse) FS_CHECK(fs_p2p_exchange_args(sp, ws.partials.p, fgrid, ws.sums.p, &red, &snd));
-                const bool dict_on = g_dict.built_for && g_dict.built_for == aval;
-                // (the tile product of a lattice-ordered operator bakes in the list tables, the tile table and the geometry of lat_prepare:
-                // those buffers grow - are allocated anew - when another space brings more classes or tiles)
-                const bool lat_on = dict_on && g_lat.ok && g_lat.built_for == aval && g_lat.space_serial == sp->serial;
-                const bool lm_on = lat_on && g_lm.ok && g_lat_march;          // (k_lat_march bakes in its own tables and geometry)
-                const void* key[32] = {A, aval, x->d.p, hist_p, ws.z.p, ws.w.p, ws.partials.p, ws.status.p,
-                                       ws.dvec.p, ws.p.p, ws.s.p, sp->sell_col.p, snd.own_recv, snd.peers, red.own_buf, red.peer_buf,
-                                       dict_on ? (const void*)g_dict.cls.p : nullptr, dict_on ? (const void*)g_dict.values.p : nullptr,
-                                       dict_on ? (const void*)sp->dict_items.p : nullptr, p2p_fuse ? (const void*)ws.sg.p : nullptr,
-                                       dict_on ? (const void*)sp->dict_plans.p : nullptr, dict_on ? (const void*)sp->halo.items_interior.p : nullptr,
-                                       dict_on ? (const void*)sp->halo.items_boundary.p : nullptr,
-                                       p2p_fuse ? reinterpret_cast<const void*>((uintptr_t)sp->halo.p2p.generation) : nullptr,
-                                       lat_on ? (lm_on ? (const void*)g_lm.sl_line.p : (const void*)g_lat.tile_cls.p) : nullptr, lat_on ? (const void*)g_lat.cnt.p : nullptr,
-                                       lat_on ? (const void*)g_lat.coef.p : nullptr, lat_on ? (lm_on ? (const void*)g_lm.SL.p : (const void*)g_lat.rel.p) : nullptr,
-                                       lat_on ? (const void*)g_lat.off.p : nullptr, lat_on ? (const void*)g_lat.relc.p : nullptr,
-                                       lat_on ? reinterpret_cast<const void*>((uintptr_t)g_lat.geom.n_tiles) : nullptr,
-                                       lat_on ? reinterpret_cast<const void*>(((uintptr_t)g_lat.geom.grid << 32) | (uintptr_t)(uint32_t)g_lat.geom.w_tiles) : nullptr};
-                // (+ whether the product is the row-dictionary kernel, with the class count and width its launch bakes in)
-                const int64_t dict_sig = dict_on ? ((int64_t)g_dict.ncls * 256 + g_dict.S) * 256 + g_dict.C : 0;
-                const int64_t key_i[8] = {n, (p2p_fuse ? (int64_t)p2p_rows_cap + 1 : 0) + 1024 * dict_sig, bsz, fgrid, vgrid,
-                                          (int64_t)upd_nt * 2 + (int64_t)spmv_nontemporal(sp, bs) + (mirror_dev ? 4 : 0) + (lm_on ? 8 + 16 * (int64_t)g_lm.g.PY + 1024 * (int64_t)g_lm.g.ZC : 0),
-                                          (int64_t)A->serial, (int64_t)sp->serial};
-                if (!ws.cg_graph || memcmp(key, ws.cg_key, sizeof(key)) || memcmp(key_i, ws.cg_key_i, sizeof(key_i))) {
-                    if (ws.cg_graph) { (void)hipGraphExecDestroy(ws.cg_graph); ws.cg_graph = nullptr; }
-                    hipGraph_t graph = nullptr;
-                    FS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                    int rc_cap = FS_OK;
-                    for (int i = 0; i < bsz && rc_cap == FS_OK; ++i) {
-                        // iteration index (status[2]) and iteration limit (ctrl[2]) from the device: iter = -1
-                        if (p2p_fuse) {
-                            launch_spmv<3>(A, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, s, aval);
-                            const int64_t work = std::max(snd.total_send, snd.total_recv);
-                            hipLaunchKernelGGL((k_cg_p2p_exchange<false>), dim3(fs_grid_for(std::max<int64_t>(work, 1), FS_BLOCK, p2p_rows_cap)), dim3(FS_BLOCK), 0, s,
-                                               -1, 0, ws.ctrl.p, ws.scal.p, ws.status.p, ws.z.p, ws.w.p, ws.sg.p, red, snd, fs_pp_ghosts{});
-                            if (upd_nt) hipLaunchKernelGGL((k_cg_update_scaled<false, true>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, -1, 0, ws.partials.p, fgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p);
-                            else hipLaunchKernelGGL((k_cg_update_scaled<false, false>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, -1, 0, ws.partials.p, fgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p);
-                            continue;
-                        }
-                        rc_cap = spmv_overlapped<3>(A, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, s, aval);
-                        if (upd_nt) hipLaunchKernelGGL((k_cg_update_scaled<true, true>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, -1, 0, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p, mirror_dev, g_upd_r_plain);
-                        else hipLaunchKernelGGL((k_cg_update_scaled<true, false>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, -1, 0, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p, mirror_dev, g_upd_r_plain);
-                    }
-                    const hipError_t e_end = hipStreamEndCapture(s, &graph);
-                    FS_CHECK(rc_cap);
-                    FS_HIP(e_end);
-                    FS_HIP(hipGraphInstantiate(&ws.cg_graph, graph, nullptr, nullptr, 0));
-                    (void)hipGraphDestroy(graph);
-                    memcpy(ws.cg_key, key, sizeof(key));
-                    memcpy(ws.cg_key_i, key_i, sizeof(key_i));
-                }
-                FS_HIP(hipGraphLaunch(ws.cg_graph, s));
-                k = kend;
-            }
-            for (; k < kend; ++k) {
-                const bool sample = (k % sample_step == 1 % sample_step) && n_samples < krylov_ws::NSAMPLE;
-                if (sample) { ws.sample_iter[n_samples] = k; ws.sample_span[n_samples] = 1; }
-                if (bicg) {
-                    const int co = k == max_iter ? 1 : 0;
-                    // K1: p, y
-                    if (fuse_sums) {
-                        hipLaunchKernelGGL(k_bicg_p<true>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, co, ws.partials2.p, vgrid, ws.bsums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.dinv.p, ws.r.p, ws.p.p, ws.w.p, ws.y.p);
-                    } else {
-                        FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials2.p, vgrid, 2, ws.bsums.p, s));
-                        hipLaunchKernelGGL(k_bicg_p<false>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, co, ws.partials2.p, vgrid, ws.bsums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.dinv.p, ws.r.p, ws.p.p, ws.w.p, ws.y.p);
-                    }
-                    // K2: v = A y, rhat.v
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][0], s));
-                    FS_CHECK(spmv_overlapped<2>(A, ws.y.p, ws.w.p, ws.rhat.p, ws.partials.p, ws.status.p, s));
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
-                    // K3: s, z
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                    if (fuse_sums) {
-                        hipLaunchKernelGGL(k_bicg_s<true>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, ws.partials.p, sgrid, ws.bsums.p + 4, ws.scal.p, ws.status.p, ws.dinv.p, ws.r.p, ws.w.p, ws.s.p, ws.z.p);
-                    } else {
-                        FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p, sgrid, 1, ws.bsums.p + 4, s));
-                        hipLaunchKernelGGL(k_bicg_s<false>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, ws.partials.p, sgrid, ws.bsums.p + 4, ws.scal.p, ws.status.p, ws.dinv.p, ws.r.p, ws.w.p, ws.s.p, ws.z.p);
-                    }
-                    if (sample) {
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
-                        ++n_samples;
-                    }
-                    // K4: t = A z, (t.s, t.t)
-                    FS_CHECK(spmv_overlapped<2>(A, ws.z.p, ws.t.p, ws.s.p, ws.partials.p, ws.status.p, s));
-                    // K5: x, r, next (rhat.r, r.r)
-                    if (fuse_sums) {
-                        hipLaunchKernelGGL(k_bicg_x<true>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, ws.partials.p, sgrid, ws.bsums.p + 8, ws.scal.p, ws.status.p, x->d.p, ws.y.p, ws.z.p, ws.r.p, ws.s.p, ws.t.p, ws.rhat.p, ws.partials2.p);
-                    } else {
-                        FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p, sgrid, 2, ws.bsums.p + 8, s));
-                        hipLaunchKernelGGL(k_bicg_x<false>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, ws.partials.p, sgrid, ws.bsums.p + 8, ws.scal.p, ws.status.p, x->d.p, ws.y.p, ws.z.p, ws.r.p, ws.s.p, ws.t.p, ws.rhat.p, ws.partials2.p);
-                    }
-                    continue;
-                }
-                if (pipelined) {
-                    const int co = k == max_iter ? 1 : 0;
-                    // n = A w (its halo was begun behind the previous update), under which the sums of (r, w) are reduced
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][0], s));
-                    FS_CHECK(spmv_overlapped<4>(A, ws.pw.p, ws.w.p, nullptr, nullptr, ws.status.p, s, aval));
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
-                    if (red_stream) FS_HIP(hipStreamWaitEvent(s, ws.ev_red, 0));
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                    int64_t m0 = 0, m1 = n;
-                    if (early_a > 0 || early_b < n) {
-                        hipLaunchKernelGGL(k_pcg_update_rows, dim3(fs_grid_for(early_a + (n - early_b), FS_BLOCK, 256)), dim3(FS_BLOCK), 0, s,
-                                           early_a, early_b, n, k, co, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, ws.z.p, ws.pw.p, ws.w.p, ws.p.p, ws.s.p, ws.pz.p, x->d.p);
-                        FS_CHECK(fs_halo_begin_dev(sp, ws.pw.p, s));
-                        sp->halo.begun = true;
-                        m0 = early_a; m1 = early_b;
-                    }
-#define FS_PCG_ARGS dim3(vgrid), dim3(FS_BLOCK), 0, s, n, m0, m1, k, co, ws.partials.p, vgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.dvec.p, ws.z.p, ws.pw.p, ws.w.p, ws.p.p, ws.s.p, ws.pz.p, x->d.p
-                    if (fuse_sums) {
-                        if (upd_nt) hipLaunchKernelGGL((k_pcg_update<true, true>), FS_PCG_ARGS);
-                        else hipLaunchKernelGGL((k_pcg_update<true, false>), FS_PCG_ARGS);
-                    } else {
-                        if (upd_nt) hipLaunchKernelGGL((k_pcg_update<false, true>), FS_PCG_ARGS);
-                        else hipLaunchKernelGGL((k_pcg_update<false, false>), FS_PCG_ARGS);
-                    }
-#undef FS_PCG_ARGS
-                    if (sample) {
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
-                        ++n_samples;
-                    }
-                    if (!fuse_sums) {
-                        // the halo of the new w goes first on the communication stream (the boundary rows of the next
-                        // product wait for it), the reduction of the new sums behind it
-                        // (whether a rank's product is split is a LOCAL property - a thin part may have no interior slice -
-                        // while the order of halo and reduction on the communicator must be the same everywhere: the
-                        // exchange is begun here on every rank with a plan, split or not)
-                        if (!sp->halo.begun && sp->halo.active) {
-                            FS_CHECK(fs_halo_begin_dev(sp, ws.pw.p, s));
-                            sp->halo.begun = true;
-                        }
-                        FS_CHECK(pcg_reduce((k + 1) & 1));
-                    }
-                    continue;
-                }
-                if (p2p_fuse) {
-                    const int co = k == max_iter ? 1 : 0;
-                    fs_p2p_rowsred red = {};
-                    fs_p2p_sendrows snd = {};
-                    if (!p2p_ghosts_in) {          // first iteration of a pass: the plain send and receive kernels
-                        FS_CHECK(fs_halo_exchange_dev(sp, ws.z.p, s));
-                        p2p_ghosts_in = true;
-                    }
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][0], s));
-                    launch_spmv<3>(A, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, s, aval);
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                    const int fgrid = spmv_partials_unsplit(sp, bs);
-                    FS_CHECK(fs_p2p_exchange_args(sp, ws.partials.p, fgrid, ws.sums.p, &red, &snd));
-                    const int64_t work = std::max(snd.total_send, snd.total_recv);
-                    hipLaunchKernelGGL((k_cg_p2p_exchange<false>), dim3(fs_grid_for(std::max<int64_t>(work, 1), FS_BLOCK, p2p_rows_cap)), dim3(FS_BLOCK), 0, s,
-                                       k, co, ws.ctrl.p, ws.scal.p, ws.status.p, ws.z.p, ws.w.p, ws.sg.p, red, snd, fs_pp_ghosts{});
-                    if (upd_nt) hipLaunchKernelGGL((k_cg_update_scaled<false, true>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, co, ws.partials.p, fgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p);
-                    else hipLaunchKernelGGL((k_cg_update_scaled<false, false>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, co, ws.partials.p, fgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p);
-                    if (sample) {
-                        FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
-                        ++n_samples;
-                    }
-                    continue;
-                }
-                if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][0], s));
-                if (ds) FS_CHECK(spmv_overlapped<3>(A, ws.z.p, ws.w.p, ws.dvec.p, ws.partials.p, ws.status.p, s, aval));
-                else FS_CHECK(spmv_overlapped<1>(A, ws.z.p, ws.w.p, ws.r.p, ws.partials.p, ws.status.p, s));
-                if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][1], s));
-                if (ds) {
-                    const int co = k == max_iter ? 1 : 0;
-                    if (fuse_sums) {
-                        if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                        if (upd_nt) hipLaunchKernelGGL((k_cg_update_scaled<true, true>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, co, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p, mirror_dev, g_upd_r_plain);
-                        else hipLaunchKernelGGL((k_cg_update_scaled<true, false>), dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, co, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p, mirror_dev, g_upd_r_plain);
-                    } else {
-                        FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p, sgrid, 3, ws.sums.p, s));
-                        if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                        // Slabs send a prefix and / or a suffix of their rows: those are updated first and their exchange is
-                        // started, so that it runs under the rest of the update AND the interior product of the next iteration
-                        // (the exchange alone used to start only with that product).
-                        int64_t m0 = 0, m1 = n;
-                        if (early_a > 0 || early_b < n) {
-                            hipLaunchKernelGGL(k_cg_update_scaled_rows, dim3(fs_grid_for(early_a + (n - early_b), FS_BLOCK, 256)), dim3(FS_BLOCK), 0, s,
-                                               early_a, early_b, n, k, co, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p);
-                            FS_CHECK(fs_halo_begin_dev(sp, ws.z.p, s));
-                            sp->halo.begun = true;
-                            m0 = early_a; m1 = early_b;
-                        }
-                        const int64_t nm = m1 - m0;
-                        if (upd_nt) hipLaunchKernelGGL((k_cg_update_scaled<false, true>), dim3(vgrid), dim3(FS_BLOCK), 0, s, nm, k, co, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p + m0, ws.w.p + m0, ws.p.p + m0, ws.s.p + m0, x->d.p + m0);
-                        else hipLaunchKernelGGL((k_cg_update_scaled<false, false>), dim3(vgrid), dim3(FS_BLOCK), 0, s, nm, k, co, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.z.p + m0, ws.w.p + m0, ws.p.p + m0, ws.s.p + m0, x->d.p + m0);
-                    }
-                } else if (fuse_sums) {
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                    hipLaunchKernelGGL(k_cg_update<true>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, k == max_iter ? 1 : 0, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.dinv.p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p, ws.r.p);
-                } else {
-                    FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p, sgrid, 3, ws.sums.p, s));
-                    if (sample) FS_HIP(hipEventRecord(ws.ev[n_samples][2], s));
-                    hipLaunchKernelGGL(k_cg_update<false>, dim3(vgrid), dim3(FS_BLOCK), 0, s, n, k, k == max_iter ? 1 : 0, ws.partials.p, sgrid, ws.sums.p, ws.ctrl.p, ws.scal.p, ws.status.p, hist_p, ws.dinv.p, ws.z.p, ws.w.p, ws.p.p, ws.s.p, x->d.p, ws.r.p);
-                }
-                if (sample) {
-                    FS_HIP(hipEventRecord(ws.ev[n_samples][3], s));
-                    ++n_samples;
-                }
-            }
-            FS_KERNEL_CHECK();
-            n_launches += k - k_before;
-            if (!mirrored) {
-                FS_HIP(hipMemcpyAsync(ws.h_status + 4 * slot, ws.status.p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-                FS_HIP(hipEventRecord(ws.poll[slot], s));
-                if (pending >= 0) {
-                    FS_HIP(hipEventSynchronize(ws.poll[pending]));
-                    if (ws.h_status[4 * pending] != 0) finished = true;
-                }
-                pending = slot;
-                slot ^= 1;
-            }
-            if (k > max_iter) finished = true;
-        }
-        lap("iterations of the pass");
-        if (sp->halo.begun) {          // the exchange started for a product that is not coming any more
-            FS_CHECK(fs_halo_end_dev(sp, s));
-            sp->halo.begun = false;
-        }
-        // pipelined: the reduction enqueued behind the last update still reads the partial sums on the communication stream;
-        // nothing of the workspace is touched again before it is through
-        if (red_stream) FS_HIP(hipStreamWaitEvent(s, ws.ev_red, 0));
-        // LIGHT / PAIR launches: a pass that stopped in an odd launch owes x one step (the kernel looks at the status word itself)
-        if (iteration_form & 1) {
-            hipLaunchKernelGGL(k_cg_pair_flush, dim3(fs_grid_for(n / 2 + 1, FS_BLOCK, 2048)), dim3(FS_BLOCK), 0, s, n, ws.status.p, ws.scal.p, ws.z.p, ws.p.p, x->d.p);
-            FS_KERNEL_CHECK();
-        }
-        // The end of a pass used to be six host synchronisations (stream, status word, sums, control block, the un-scaling of x,
-        // the history): 0.68 ms of fixed cost per solve at 1 M rows, a tenth of the whole solve.  Nothing of the true-residual
-        // computation depends on what the host learns from the status word, so it is enqueued first and status, sums and control
-        // block come back in ONE synchronisation.
-        // true residual b - A x (scaled mode: sum d (bhat - Ahat xhat)^2, the same number)
-        FS_HIP(hipMemcpyAsync(ws.z.p, x->d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        FS_CHECK(fs_halo_exchange_dev(sp, ws.z.p, s));
-        launch_spmv<0>(A, ws.z.p, ws.w.p, nullptr, nullptr, nullptr, s, aval);
-        if (ds) hipLaunchKernelGGL(k_residual_scaled, dim3(pgrid), dim3(FS_BLOCK), 0, s, ws.bhat.p, ws.w.p, ws.dvec.p, n, (double*)nullptr, ws.partials.p);
-        else hipLaunchKernelGGL(k_residual, dim3(pgrid), dim3(FS_BLOCK), 0, s, b->d.p, ws.w.p, n, (double*)nullptr, ws.partials.p);
-        FS_CHECK(fs_comm_sum_allreduce_dev(ws.partials.p, pgrid, 1, ws.sums.p + 5, s));
-        FS_HIP(hipMemcpyAsync(ws.h_status + 12, ws.status.p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-        FS_HIP(hipMemcpyAsync(ws.h_vals, ws.sums.p, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-        FS_HIP(hipMemcpyAsync(ws.h_vals + 8, ws.ctrl.p, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-        FS_HIP(hipStreamSynchronize(s));
-        if (fs_p2p_reduce_enabled()) FS_CHECK(fs_p2p_check(s));
-        for (int q = 0; q < 4; ++q) h_status[q] = ws.h_status[12 + q];
-        const int iters = h_status[1];
-        total_iters += iters;
-        // launches enqueued after the recurrence stopped return on the status word: their samples time no-ops
-        for (int i = first_sample; i < n_samples; ++i) ws.sample_live[i] = ws.sample_iter[i] + ws.sample_span[i] - 1 < iters;
-        if (ws.h_status[8] != 0) {
-            fs_set_error("fs_krylov_solve: %d zero%s diagonal entries (Jacobi preconditioner undefined)", ws.h_status[8], ds ? " or negative" : "");
-            return FS_ERR_NUMERIC;
-        }
-        const double* h_pass = ws.h_vals;
-        const double* h_ctrl2 = ws.h_vals + 8;
-        true_rr = h_pass[5];
-        thresh = h_ctrl2[0];
-        bb_host = h_ctrl2[1];
-        ++n_pass;
-        if (getenv("FS_KRYLOV_DEBUG"))
-            fprintf(stderr, "[fs_krylov] pass %d: status %d, %d iterations (total %d), true ||r||^2 %.3e, threshold %.3e\n",
-                    n_pass, h_status[0], h_status[1], total_iters, true_rr, thresh);
-        const bool recurrence_converged = h_status[0] == 1;
-        if (!recurrence_converged || true_rr <= thresh * 1.0201 || n_pass >= 8 || total_iters >= opts->max_iter) break;
-        if (true_rr > 0.7 * prev_true_rr) break;   // no longer improving: attainable accuracy of fp64 reached
-        prev_true_rr = true_rr;
-        use_guess = true;   // restart: r := b - A x exactly, then continue
-    }
-    if (ds) {   // x = D^-1/2 xhat (no synchronisation of its own: the download of the history below waits for it)
-        hipLaunchKernelGGL(k_pointwise_mul, dim3(fs_grid_for(n)), dim3(FS_BLOCK), 0, s, ws.dinv.p, x->d.p, n, x->d.p);
-        FS_KERNEL_CHECK();
-    }
-    const int iters = total_iters;
-    if (fs_rt().comm && getenv("FS_COMM_TIMING")) {
-        double au, hu; long ac, hc;
-        fs_comm_host_time(&au, &ac, &hu, &hc, true);
-        fprintf(stderr, "[fs_krylov] host time inside RCCL enqueue calls: all-reduce %.1f us x %ld, grouped send/recv %.1f us x %ld; %d iterations in %.1f ms\n",
-                ac ? au / ac : 0.0, ac, hc ? hu / hc : 0.0, hc, iters,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    }
-#ifdef FS_ITER_TIMING
-    if (fused && getenv("FS_ITER_TIMING")) {
-        std::vector<long long> h(FS_STAMPS * 4096);
-        FS_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_iter_dbg), h.size() * sizeof(long long)));
-        long long first = h[0], last = 0;
-        for (int b = 0; b < igrid; ++b) { first = std::min(first, h[FS_STAMPS * b]); last = std::max(last, h[FS_STAMPS * b + 7]); }
-        double mean[9] = {0}, mx[9] = {0};
-        for (int b = 0; b < igrid; ++b)
-            for (int k2 = 0; k2 < 9; ++k2) { const double v = (h[FS_STAMPS * b + k2] - first) * 0.01; mean[k2] += v / igrid; mx[k2] = std::max(mx[k2], v); }
-        fprintf(stderr, "[iter timing, last launch, us from the first workgroup's start] span %.2f;", (last - first) * 0.01);
-        for (int k2 = 0; k2 < 9; ++k2) fprintf(stderr, " s%d mean %.2f max %.2f;", k2, mean[k2], mx[k2]);
-        fprintf(stderr, "\n");
-        // stamps 5 (first item done), 6 (all items done), 7 (partials summed) apart for the workgroups whose chunks hold an edge item
-        // (the chunk walk of the kernel: xcd_chunks, or block-strided without the XCD map) and for the rest
-        std::vector<int32_t> hi((size_t)sp->n_dict_items * 4);
-        FS_CHECK(sp->dict_items.download(hi.data(), (int64_t)hi.size(), s));
-        FS_HIP(hipStreamSynchronize(s));
-        const int64_t n_chunks = (sp->n_dict_items + 3) / 4, per_xcd = (n_chunks + 7) >> 3;
-        int cnt[2] = {0, 0};
-        double gm[2][3] = {{0}}, gx[2][3] = {{0}};
-        for (int b = 0; b < igrid; ++b) {
-            int64_t cur = b, step = igrid, end = n_chunks;
-            if (dict_map_xcd()) { cur = (b & 7) * per_xcd + (b >> 3); step = igrid >> 3; end = std::min<int64_t>(((b & 7) + 1) * per_xcd, n_chunks); }
-            int e = 0;
-            for (; cur < end; cur += step)
-                for (int64_t q = 4 * cur; q < std::min<int64_t>(4 * cur + 4, sp->n_dict_items); ++q) e |= (hi[(size_t)q * 4 + 1] >> 16) & 1;
-            ++cnt[e];
-            for (int k2 = 0; k2 < 3; ++k2) { const double v = (h[FS_STAMPS * b + 5 + k2] - first) * 0.01; gm[e][k2] += v; gx[e][k2] = std::max(gx[e][k2], v); }
-        }
-        for (int e = 0; e < 2; ++e) {
-            fprintf(stderr, "[iter timing] %d workgroups %s an edge item:", cnt[e], e ? "with" : "without");
-            for (int k2 = 0; k2 < 3; ++k2) fprintf(stderr, " s%d mean %.2f max %.2f;", 5 + k2, cnt[e] ? gm[e][k2] / cnt[e] : 0.0, gx[e][k2]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    ws.last_hist.resize((size_t)iters + 1);
-    FS_CHECK(ws.hist.download(ws.last_hist.data(), iters + 1, s));
-    const auto t_end = std::chrono::steady_clock::now();
-
-    if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        const double bb = bb_host;
-        stats->iterations = iters;
-        // PETSc semantics: converged = the recurrence residual met the tolerance; the recomputed true
-        // residual is reported next to it (restarts above keep the two together whenever fp64 allows)
-        stats->converged = h_status[0] == 2 ? -1 : (h_status[0] == 1 ? 1 : 0);
-        stats->bnorm = sqrt(bb);
-        stats->rel_residual = bb > 0.0 ? sqrt(ws.last_hist[iters] / bb) : 0.0;
-        stats->true_rel_residual = bb > 0.0 ? sqrt(true_rr / bb) : sqrt(true_rr);
-        stats->solve_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
-        double t_spmv = 0.0, t_upd = 0.0;
-        int cnt = 0;
-        for (int i = 0; i < n_samples; ++i) {
-            if (!ws.sample_live[i]) continue;
-            float a = 0.f, c = 0.f;
-            if (hipEventElapsedTime(&a, ws.ev[i][0], ws.ev[i][1]) != hipSuccess) break;
-            if (hipEventElapsedTime(&c, ws.ev[i][2], ws.ev[i][3]) != hipSuccess) break;
-            t_spmv += a / (float)ws.sample_span[i];
-            t_upd += c;
-            ++cnt;
-        }
-        if (cnt) {
-            stats->spmv_ms = t_spmv / cnt;
-            stats->update_ms = t_upd / cnt;
-        }
-        stats->spmv_bytes = sp->nnz_nodes * bs * bs * 12 + n * 20;
-        stats->row_classes = g_dict.built_for ? g_dict.ncls : 0;
-        stats->fused_iteration = fusedp_used ? 2 : (fused ? 1 : 0);
-        stats->classes_kept = g_dict.built_for && g_dict.kept ? 1 : 0;
-        stats->launches = n_launches;
-        stats->product_kind = fused ? (BI ? 3 : 1) : g_last_product_kind;
-        g_last_iteration_form = (fused || fusedp_used) ? iteration_form : 0;
-        if (fused) stats->update_ms = 0.0;       // (spmv_ms is the whole iteration: one launch)
-    }
-    if (h_status[0] == 2) {
-        fs_set_error("fs_krylov_solve: %s breakdown at iteration %d (operator not SPD / rho = 0 / NaN)", bicg ? "BiCGStab" : "CG", iters);
-        return FS_ERR_NUMERIC;
-    }
-    return FS_OK;
-}
-
-// (the guard bits have an accessor of their own: callers of fs_last_iteration_form compare the word with PAIR | DTAB)
-extern "C" int fs_last_iteration_form() { return g_last_iteration_form & 3; }
-extern "C" int fs_last_iteration_guard() { return (g_last_iteration_form >> 2) & 3; }
-void fs_krylov_set_history(const std::vector<double>& rr) { g_ws.last_hist = rr; }
-void fs_set_last_product_kind(int kind) { g_last_product_kind = kind; }
-
-extern "C" int fs_krylov_history(double* out, int capacity, int* count) {
-    const int n = (int)g_ws.last_hist.size();
-    if (count) *count = n;
-    if (out)
-        for (int i = 0; i < n && i < capacity; ++i) out[i] = g_ws.last_hist[i];
-    return FS_OK;
-}
-
-void fs_krylov_preload() {
-    hipFuncAttributes attr;
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_set_threshold));
-    (void)hipGetLastError();
-}
+#include "fs_krylov_solve.inc"     // the host side of the solve: workspace, plan, pass, one step function per iteration form, the one-launch driver, the graph cache, fs_krylov_solve
