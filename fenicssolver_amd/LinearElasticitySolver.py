@@ -10,6 +10,10 @@ Modal analysis (solve_modal / solve_modal_form, :270-312): the lowest modes of K
 M = int rho phi . psi dx, by LOBPCG on the device (fs_eigen_solve; AMG-preconditioned in 3D, Jacobi in 2D).  The reference's
 stub asks SLEPc for the largest eigenvalue of K alone, a mesh-scale number of no engineering use.
 
+Linear buckling (solve_buckling; no counterpart in the reference): the static solve of the case as given, the
+geometric stiffness K_G of its per-cell stress (fs_assemble_geometric_stiffness), and the smallest factors lambda > 0 of
+(K + lambda K_G) phi = 0 by the same LOBPCG on K_G phi = nu K phi (fs_buckling_solve).  Vector P1, one rank.
+
 Reference quirk kept by default (Appendix B-Q3): body forces and tractions are ADDED to
 F (:227-228, 242-243), so they act with reversed sign; set
 ``solver.reference_load_sign = False`` for the physical convention.  The thermal term has
@@ -275,6 +279,121 @@ class LinearElasticitySolver(SolverBase):
         self.logger.info('solve_modal: %d modes in %d iterations, %.1f ms, f = %s Hz', nm, st['iterations'], st['solve_ms'],
                          np.array2string(self.natural_frequencies, precision=5))
         return self.modes[0]
+
+    # ------------------------------------------------------------------ linear buckling
+    _BUCKLING_DEFAULTS = {'number_of_modes': 4, 'tolerance': 1e-8, 'max_iterations': 500}
+
+    def buckling_settings(self):
+        """settings['solver_settings']['buckling_settings'] with its defaults, checked (SolverError on a bad value)."""
+        given = self.solver_settings.get('buckling_settings') or {}
+        unknown = set(given) - set(self._BUCKLING_DEFAULTS)
+        if unknown:
+            raise SolverError('buckling_settings: unknown key(s) {}'.format(sorted(unknown)))
+        bs = dict(self._BUCKLING_DEFAULTS, **given)
+        nm = bs['number_of_modes']
+        if isinstance(nm, bool) or not isinstance(nm, numbers.Integral) or not 1 <= nm <= 32:
+            raise SolverError('buckling_settings: number_of_modes must be an integer in 1..32, got {!r}'.format(nm))
+        for key, low in (('tolerance', 0.0), ('max_iterations', 0)):
+            if isinstance(bs[key], bool) or not isinstance(bs[key], numbers.Real) or not bs[key] > low:
+                raise SolverError('buckling_settings: {} must be positive, got {!r}'.format(key, bs[key]))
+        return {'number_of_modes': int(nm), 'tolerance': float(bs['tolerance']), 'max_iterations': int(bs['max_iterations'])}
+
+    def _refuse_buckling_space(self, what):
+        """The spaces the geometric stiffness is written for: vector CG1, one rank, not periodic (no device call is made here)."""
+        from . import parallel
+        V = self.function_space
+        if V.degree() != 1:
+            raise SolverError('{}: P2 displacement spaces are not supported - the geometric stiffness of a stress that is linear '
+                              'in the cell needs its own quadrature kernel (a follow-up); use a P1 space'.format(what))
+        if parallel.world()[1] > 1 or V.localizer() is not None:
+            raise SolverError('{} runs on one rank'.format(what))
+        if hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None:
+            raise SolverError('{} on a periodic space is not supported'.format(what))
+
+    def _geometric_stiffness(self, u, cell_stress):
+        from . import backend
+        self._refuse_buckling_space('geometric_stiffness')
+        u = self.w_current if u is None else u
+        F = forms.ElasticityForm(self.function_space)
+        F.mu, F.lmbda = self.lame_parameters()
+        V = self.function_space.device()
+        ud = backend.DeviceVector(V.n_local, u.vector()._values())
+        KG = backend.DeviceMatrix(V)
+        return KG, KG.assemble_geometric(F.lame_spec(), ud, cell_stress=cell_stress)
+
+    def geometric_stiffness(self, u=None):
+        """The geometric stiffness K_G[(a,i),(b,j)] = delta_ij sum_cells |c| grad N_a . sigma_c grad N_b of the stress sigma(u) (u: a
+        displacement Function, default the current one), as a backend.DeviceMatrix without Dirichlet rows."""
+        return self._geometric_stiffness(u, False)[0]
+
+    def solve_buckling(self):
+        """Linear (eigenvalue) buckling: the static solve of the case as given - its loads are the reference load - then the smallest
+        factors lambda > 0 with (K + lambda K_G) phi = 0, K_G the geometric stiffness of the static stress, every dof that carries
+        a displacement BC held at zero in the modes.  Sets self.buckling_factors (ascending), self.buckling_modes (Functions scaled to
+        max |component| = 1), self.prestress (per-cell stress [n_cells, 6] as xx, yy, zz, xy, xz, yz, or [n_cells, 4] as xx, yy,
+        zz, xy in plane strain) and self.buckling_stats; the static displacement stays where solve() leaves it.  Returns mode 1."""
+        import time
+        from . import backend
+        bs = self.buckling_settings()
+        what = 'solve_buckling'
+        self._refuse_buckling_space('buckling analysis')
+        if self.settings.get('temperature_distribution') is not None or getattr(self, 'temperature_distribution', None) is not None:
+            raise SolverError(what + ': a thermal prestress (temperature_distribution) is not supported')
+        if self.transient_settings['transient']:
+            raise SolverError(what + ': the reference load is a static load; transient_settings must not be transient')
+        if not any(bc.get('type') in ('Dirichlet', 'displacement') for bc in self.boundary_conditions.values()):
+            raise SolverError(what + ': no displacement boundary condition - the static solve of the reference load is singular')
+        nm = bs['number_of_modes']
+        t0 = time.perf_counter()
+        u0 = self.solve()
+        backend.synchronize()
+        t1 = time.perf_counter()
+        F, bcs = self.generate_form(0, None, None, self.w_current, self.w_prev)
+        constrained = np.unique(self._bc_arrays(bcs)[0])
+        n_free = F.space.dim() - constrained.size
+        if nm >= n_free:
+            raise SolverError('buckling_settings: {} modes asked of a space with {} free dofs'.format(nm, n_free))
+        V = F.space.device()
+        K = backend.DeviceMatrix(V)
+        K.assemble(lame=F.lame_spec())
+        KG, self.prestress = self._geometric_stiffness(u0, True)
+        K.apply_dirichlet(None, constrained, np.zeros(constrained.size), symmetric=True)
+        backend.synchronize()
+        t2 = time.perf_counter()
+        amg = None
+        if self.dimension == 3:
+            # An operator of at most 500 rows is a single level by default, whose "cycle" is the smoother alone - no better than
+            # Jacobi, and K is the B matrix here: a part that small gets a coarse level of its own.
+            sp_ = self.solver_settings.get('solver_parameters', {}) or {}
+            amg = backend.AMG(K, nullspace="rigid_body", strength_threshold=float(sp_.get('amg_strength_threshold', 0.0)),
+                              coarse_size=max(12, V.n_owned // 8) if V.n_owned <= 500 else 0)
+        backend.synchronize()
+        t3 = time.perf_counter()
+        try:
+            lam, modes, st = backend.buckling_solve(K, KG, nm, amg=amg, constrained=constrained, tol=bs['tolerance'],
+                                                    max_iter=bs['max_iterations'])
+        except backend.BackendError as e:
+            if 'buckling mode' in str(e):
+                raise SolverError(what + ': ' + str(e).split(': ', 1)[-1])
+            raise
+        finally:
+            if amg is not None:
+                amg.close()
+        st.update(static_ms=1e3 * (t1 - t0), assembly_ms=1e3 * (t2 - t1), amg_setup_ms=1e3 * (t3 - t2))
+        self.buckling_stats = st
+        if st['n_converged'] < nm:
+            raise SolverError('solve_buckling: {} of {} modes converged in {} iterations (largest relative residual {:.3e})'.format(
+                st['n_converged'], nm, st['iterations'], st['max_rel_residual']))
+        self.buckling_factors = np.asarray(lam, dtype=np.float64)
+        self.buckling_modes = []
+        for x in modes:
+            xh = x.get()[:V.n_owned]
+            f = Function(self.function_space)
+            f.vector().set_local(xh / xh[np.argmax(np.abs(xh))])
+            self.buckling_modes.append(f)
+        self.logger.info('solve_buckling: %d factors in %d iterations, %.1f ms: %s', nm, st['iterations'], st['solve_ms'],
+                         np.array2string(self.buckling_factors, precision=6))
+        return self.buckling_modes[0]
 
     def get_flux(self, u, mag_vector):
         return mag_vector

@@ -168,6 +168,16 @@ class fs_eigen_stats(C.Structure):
                 ("block_product_ms", C.c_double), ("gram_ms", C.c_double), ("precond_ms", C.c_double)]
 
 
+class fs_buckling_opts(C.Structure):
+    _fields_ = [("n_modes", C.c_int), ("block", C.c_int), ("tol", C.c_double), ("max_iter", C.c_int), ("seed", C.c_uint64),
+                ("two_pass", C.c_int)]
+
+
+class fs_buckling_stats(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("n_converged", C.c_int), ("max_rel_residual", C.c_double), ("n_negative", C.c_int),
+                ("solve_ms", C.c_double), ("block_product_ms", C.c_double), ("gram_ms", C.c_double), ("precond_ms", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fenicssolver_amd.h
 _H = C.c_void_p
 SIGNATURES = {
@@ -237,6 +247,11 @@ SIGNATURES = {
     "fs_spmv_multi": (C.c_int, [_H, C.c_int, C.POINTER(_H), C.POINTER(_H)]),
     "fs_vector_gram": (C.c_int, [C.c_int, C.POINTER(_H), C.c_int, C.POINTER(_H), c_f64p]),
     "fs_eigen_solve": (C.c_int, [_H, _H, _H, c_i64, c_i32p, C.POINTER(fs_eigen_opts), c_f64p, C.POINTER(_H), C.POINTER(fs_eigen_stats)]),
+    "fs_assemble_geometric_stiffness": (C.c_int, [_H, C.c_double, C.c_double, c_f64p, _H, _H, c_f64p]),
+    "fs_spmv_multi_pencil": (C.c_int, [_H, _H, C.c_int, C.POINTER(_H), C.POINTER(_H), C.POINTER(_H)]),
+    "fs_spmv_multi_pencil_benchmark": (C.c_int, [_H, _H, C.c_int, C.c_int, c_f64p, c_f64p]),
+    "fs_buckling_solve": (C.c_int, [_H, _H, _H, c_i64, c_i32p, C.POINTER(fs_buckling_opts), c_f64p, C.POINTER(_H),
+                                    C.POINTER(fs_buckling_stats)]),
     "fs_assemble_facet_supg": (C.c_int, [_H, _H, _H, C.c_int64, c_i32p, c_i32p, c_f64p, c_f64p, C.POINTER(fs_coef), C.c_double]),
     "fs_assemble_navier_stokes": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_ns_form)]),
     "fs_space_set_viscosity_law": (C.c_int, [_H, C.POINTER(fs_viscosity_law)]),

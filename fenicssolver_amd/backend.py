@@ -384,6 +384,24 @@ class DeviceMatrix(_Handle):
         f = _bilinear_form(keep, stiffness, mass, lame, advection, advection_scale, supg_pe)
         L.check(L.load().fs_assemble_matrix(self.h, C.byref(f), 1 if add else 0), "fs_assemble_matrix")
 
+    def assemble_geometric(self, lame, u, cell_stress=False):
+        """The geometric stiffness K_G of the linear-elastic stress of the displacement u (DeviceVector of the space's dofs) on a
+        vector CG1 space (fs_assemble_geometric_stiffness): every node-pair block is s I.  lame as assemble(lame=...): (mu, lambda)
+        numbers or ('cell', array[n_cells, 2]) in device cell order.  cell_stress=True: returns the stress per cell, array
+        [n_cells, 6] (xx, yy, zz, xy, xz, yz) or [n_cells, 4] (xx, yy, zz, xy) in plane strain, device cell order; else None."""
+        keep = []
+        mu = lm = 0.0
+        cells = None
+        nc = self.space.mesh.info()[1]
+        if _is_cell_lame(lame):
+            cells = L.p_f64(_lame_cells(lame, keep, nc))
+        else:
+            mu, lm = float(lame[0]), float(lame[1])
+        sig = np.empty((nc, 6 if self.space.ncomp == 3 else 4)) if cell_stress else None
+        L.check(L.load().fs_assemble_geometric_stiffness(self.space.h, mu, lm, cells, u.h, self.h, L.p_f64(sig)),
+                "fs_assemble_geometric_stiffness")
+        return sig
+
     def add_facet_mass(self, tri, h):
         tri = L.i32(tri)
         tri = tri.reshape(-1, 3) if tri.ndim == 1 else tri       # [nf,3] triangles (3-D) or [nf,2] edges (2-D)
@@ -1123,6 +1141,40 @@ def eigen_solve(K, M, n_modes, amg=None, constrained=None, tol=1e-8, max_iter=50
     L.check(L.load().fs_eigen_solve(K.h, M.h, amg.h if amg is not None else None, cons.size, L.p_i32(cons) if cons.size else None,
                                     C.byref(o), L.p_f64(lam), _handles(modes), C.byref(st)), "fs_eigen_solve")
     return lam, modes, {k: getattr(st, k) for k, _ in L.fs_eigen_stats._fields_}
+
+
+def spmv_multi_pencil(K, KG, X, YK, YG):
+    """YK[j] = K X[j] and YG[j] = KG X[j] for every column in one pass over the pattern per chunk of columns (fs_spmv_multi_pencil):
+    KG, whose node-pair blocks must be s I (DeviceMatrix.assemble_geometric), is read from a copy of one double per block.  YK[j]
+    equals spmv_multi(K) bit for bit, YG[j] equals spmv_multi(KG) as numbers."""
+    if not X or len(X) != len(YK) or len(X) != len(YG):
+        raise ValueError("spmv_multi_pencil: X, YK and YG must be non-empty lists of one length")
+    L.check(L.load().fs_spmv_multi_pencil(K.h, KG.h, len(X), _handles(X), _handles(YK), _handles(YG)), "fs_spmv_multi_pencil")
+
+
+def spmv_multi_pencil_benchmark(K, KG, m=8, reps=20):
+    """(fused_ms, two_pass_ms): the mean time of one fused pencil product of m columns and of the two block products it replaces
+    (HIP events after a warm-up, kernels only)."""
+    a, b = C.c_double(0.0), C.c_double(0.0)
+    L.check(L.load().fs_spmv_multi_pencil_benchmark(K.h, KG.h, int(m), int(reps), C.byref(a), C.byref(b)), "fs_spmv_multi_pencil_benchmark")
+    return a.value, b.value
+
+
+def buckling_solve(K, KG, n_modes, amg=None, constrained=None, tol=1e-8, max_iter=500, block=0, seed=2024, two_pass=False):
+    """The n_modes smallest positive factors lambda of (K + lambda KG) phi = 0 on the dofs outside `constrained` (fs_buckling_solve:
+    the LOBPCG of eigen_solve on KG phi = nu K phi, preconditioned by one V-cycle of `amg` - a hierarchy of K - per column, or by the
+    Jacobi diagonal of K).  KG as assemble_geometric leaves it, without Dirichlet rows.  two_pass=True: K S and KG S by two block
+    products instead of the fused pencil product.  Returns (factors [n_modes] ascending, modes [DeviceVector, K-orthonormal], stats
+    dict); a load with fewer than n_modes buckling modes raises BackendError (rc FS_ERR_NUMERIC, "only N buckling mode(s)")."""
+    o = L.fs_buckling_opts()
+    o.n_modes, o.block, o.tol, o.max_iter, o.seed, o.two_pass = int(n_modes), int(block), float(tol), int(max_iter), int(seed), int(bool(two_pass))
+    cons = L.i32(np.zeros(0) if constrained is None else constrained).ravel()
+    modes = [DeviceVector(K.space.n_owned) for _ in range(int(n_modes))]
+    lam = np.empty(int(n_modes))
+    st = L.fs_buckling_stats()
+    L.check(L.load().fs_buckling_solve(K.h, KG.h, amg.h if amg is not None else None, cons.size, L.p_i32(cons) if cons.size else None,
+                                       C.byref(o), L.p_f64(lam), _handles(modes), C.byref(st)), "fs_buckling_solve")
+    return lam, modes, {k: getattr(st, k) for k, _ in L.fs_buckling_stats._fields_}
 
 
 def assemble_navier_stokes(J, g, w0, w_prev=None, nu=1.0, rho=1.0, inv_dt=0.0, body_force=(0.0, 0.0, 0.0),

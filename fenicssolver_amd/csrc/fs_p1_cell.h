@@ -1,5 +1,5 @@
-// P1 cell helpers shared by the solid-mechanics kernel files (fs_hyper.hip, fs_large_deformation.hip, fs_plasticity.hip,
-// fs_viscoelasticity.hip): the gather-map source decode, the diagonal-block lookup, the gradient pick, the strain of a P1 cell,
+// P1 cell helpers shared by the solid-mechanics kernel files (fs_hyper.hip, fs_buckling.hip, fs_large_deformation.hip,
+// fs_plasticity.hip, fs_viscoelasticity.hip): the gather-map source decode, the diagonal-block lookup, the gradient pick, the strain of a P1 cell,
 // symmetric tensor times vector, the stored-stress force gather, the per-cell tally and the host pieces every such solver repeats
 // (space check, committed / trial buffer pair, first-cell number).
 //

@@ -912,6 +912,59 @@ typedef struct fs_eigen_stats {
 int fs_eigen_solve(fs_matrix_t K, fs_matrix_t M, fs_amg_t precond, int64_t n_constrained, const int32_t* constrained,
                    const fs_eigen_opts* opts, double* eigenvalues, fs_vector_t* modes, fs_eigen_stats* stats);
 
+/* ---- linear (eigenvalue) buckling --------------------------------------------------------------------------------------------
+ * No counterpart in the reference ("differs from the reference"): the factors lambda > 0 of the reference load at
+ * which (K + lambda K_G) phi = 0, K_G the geometric stiffness of the static solution's stress.  Vector CG1 spaces on tetrahedra
+ * (3 components) or on triangles in plane strain (2 components); one rank. */
+
+/* K_G[(a,i),(b,j)] = delta_ij sum_cells |c| grad N_a . sigma_c grad N_b with sigma_c = lambda tr(eps) I + 2 mu eps of the displacement
+ * u (>= n_dofs_local entries), constant per P1 cell.  Lame coefficients: (mu, lambda), or lame_cells != NULL: [n_cells][2] pairs
+ * (mu, lambda) per cell in device cell order, as FS_COEF_CELL_LAME of fs_assemble_matrix (mu and lambda are ignored then).  KG: a
+ * matrix of the space; every node-pair block becomes s I (off-diagonal block entries exactly 0.0).  No atomics: two calls give the
+ * same bits.  cell_stress_out (may be NULL): the stress per cell in device cell order, 6 doubles (xx, yy, zz, xy, xz, yz) on
+ * tetrahedra, 4 (xx, yy, zz, xy) in plane strain - sigma_zz = lambda tr(eps) there, which does not enter K_G. */
+int fs_assemble_geometric_stiffness(fs_space_t space, double mu, double lambda, const double* lame_cells, fs_vector_t u, fs_matrix_t KG,
+                                    double* cell_stress_out);
+
+/* YK[j] = K X[j] and YG[j] = KG X[j] for j < m in one pass over the pattern per chunk of columns: the column indices and X are
+ * gathered once, and KG - whose blocks must be s I, as fs_assemble_geometric_stiffness leaves them; FS_ERR_INVALID otherwise - is read
+ * from a copy of one double per node pair.  Unmasked.  YK[j] equals fs_spmv_multi(K) bit for bit; YG[j] equals fs_spmv_multi(KG)
+ * as numbers for finite X (the block product adds exact zeros, which can only change the sign of a zero). */
+int fs_spmv_multi_pencil(fs_matrix_t K, fs_matrix_t KG, int m, const fs_vector_t* X, fs_vector_t* YK, fs_vector_t* YG);
+
+/* Mean milliseconds (HIP events, after 3 warm-up launches, over reps launches) of one fused pencil product of m columns of a seeded
+ * block, and of the two fs_spmv_multi block products (K, then KG) it replaces, the kernels only. */
+int fs_spmv_multi_pencil_benchmark(fs_matrix_t K, fs_matrix_t KG, int m, int reps, double* fused_ms, double* two_pass_ms);
+
+typedef struct fs_buckling_opts {
+    int n_modes;         /* wanted buckling factors, 1 .. 32 */
+    int block;           /* block size m; 0 = min(2 n_modes, n_modes + 8); at most 40 */
+    double tol;          /* stop when every wanted column has ||K_G x - nu K x||_2 <= tol |nu| ||K x||_2 */
+    int max_iter;
+    uint64_t seed;       /* of the pseudo-random start block */
+    int two_pass;        /* 0: K S and K_G S by the fused pencil product; 1: by two block products (the kernels of fs_spmv_multi) */
+} fs_buckling_opts;
+
+typedef struct fs_buckling_stats {
+    int iterations;
+    int n_converged;            /* wanted columns that met the test, on products recomputed from X */
+    double max_rel_residual;    /* largest relative residual of the wanted columns */
+    int n_negative;             /* Ritz values nu < 0 among the block's m at the end: the buckling modes the block holds */
+    double solve_ms;            /* wall time (host clock, synchronised) */
+    double block_product_ms;    /* HIP events: products with K and K_G */
+    double gram_ms;             /* ... Gram matrices (with their download) */
+    double precond_ms;          /* ... V-cycles or Jacobi */
+} fs_buckling_stats;
+
+/* The n_modes smallest positive lambda of (K + lambda K_G) phi = 0 on the dofs outside `constrained`, by the LOBPCG of fs_eigen_solve on
+ * K_G phi = nu K phi (lambda = -1 / nu for the most negative nu).  K: Dirichlet-eliminated or not (constrained rows and columns are
+ * masked out); KG: as assembled, NOT Dirichlet-eliminated (its blocks must be s I); precond: an fs_amg_setup hierarchy of K, or NULL
+ * (the Jacobi diagonal of K).  factors[n_modes] ascending; modes[n_modes] (caller's vectors of >= n_dofs_owned entries) K-orthonormal.
+ * When the iteration converges with fewer than n_modes negative nu: FS_ERR_NUMERIC, "the reference load produces only N buckling
+ * mode(s)" (N = 0: nothing buckles under this load), with stats filled. */
+int fs_buckling_solve(fs_matrix_t K, fs_matrix_t KG, fs_amg_t precond, int64_t n_constrained, const int32_t* constrained,
+                      const fs_buckling_opts* opts, double* factors, fs_vector_t* modes, fs_buckling_stats* stats);
+
 /* ---- Taylor-Hood Navier-Stokes (CoupledNavierStokesSolver.py:288-381, 215-245, 492-528) -------------
  * Unknowns: one block (u_x, u_y, u_z, p) per CG2 node of fs_space_create(mesh, FS_FAMILY_CG, 2, 4); the
  * pressure is CG1, the pressure slot of an edge node is a dummy unknown with a unit row. */
