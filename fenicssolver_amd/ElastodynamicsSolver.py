@@ -105,6 +105,8 @@ def effective_coefficients(alpha_m, alpha_f, beta, gamma, dt, eta_m=0.0, eta_k=0
 
 
 class ElastodynamicsSolver(LinearElasticitySolver):
+    _constraint_sides = False          # 'contact' / 'sliding' sides stay with the static linear solver
+
     def __init__(self, case_settings):
         LinearElasticitySolver.__init__(self, case_settings)
         self.reference_load_sign = False          # loads with their physical sign, as in PlasticitySolver

@@ -14,6 +14,11 @@ Linear buckling (solve_buckling; no counterpart in the reference, INTEGRATION.md
 geometric stiffness K_G of its per-cell stress (fs_assemble_geometric_stiffness), and the smallest factors lambda > 0 of
 (K + lambda K_G) phi = 0 by the same LOBPCG on K_G phi = nu K phi (fs_buckling_solve).  Vector P1, one rank.
 
+Frictionless contact and sliding supports (boundary types 'contact' and 'sliding'; the reference lists the boundary condition as
+not implemented): n.u <= g against a rigid obstacle, or n.u = value, at the vertices of the marked facets, by the
+primal-dual active-set strategy in per-node Householder frames, where the constraint is a component Dirichlet condition
+(solve_contact; fs_matrix_rotate_nodes, fs_contact_update).  Vector P1, one rank, static cases.
+
 Reference quirk kept by default (Appendix B-Q3): body forces and tractions are ADDED to
 F (:227-228, 242-243), so they act with reversed sign; set
 ``solver.reference_load_sign = False`` for the physical convention.  The thermal term has
@@ -336,6 +341,7 @@ class LinearElasticitySolver(SolverBase):
         from . import backend
         bs = self.buckling_settings()
         what = 'solve_buckling'
+        self._refuse_constraint_sides(what)
         self._refuse_buckling_space('buckling analysis')
         if self.settings.get('temperature_distribution') is not None or getattr(self, 'temperature_distribution', None) is not None:
             raise SolverError(what + ': a thermal prestress (temperature_distribution) is not supported')
@@ -487,6 +493,7 @@ class LinearElasticitySolver(SolverBase):
         V = self.function_space
         bcs = []
         integrals_N = []
+        sides = []
         if 'point_source' in self.settings and self.settings['point_source']:
             # The reference reads the WRONG key here - settings['surface_source'] (LinearElasticitySolver.py:105-108) - and appends that
             # dict to the Dirichlet list, which assemble_system (:643-650 of SolverBase.py) then rejects: no elasticity case with a
@@ -560,13 +567,266 @@ class LinearElasticitySolver(SolverBase):
                     integrals_N.append(forms.FacetLoad(i, nrm @ g.values().reshape(self.dimension, self.dimension).T, 'stress(tensor.n)'))
                 else:
                     raise SolverError("boundary '{}': stress must be a constant vector or tensor".format(name))
+            elif btype in ('contact', 'sliding') and self._constraint_sides:
+                if not sides:
+                    self._refuse_contact_case()
+                sides.append((name, i, btype, bc))          # resolved below, once every displacement BC is known
             elif btype == 'Neumann':
                 raise SolverError('Neumann boundary type`{}` is not supported'.format(btype))
             elif btype == 'symmetry':
                 raise SolverError('symmetry boundary type`{}` is not supported'.format(btype))
             else:
                 raise SolverError('boundary type`{}` is not supported'.format(btype))
+        self._contact = self._contact_setup(sides, bcs) if sides else None
         return bcs, integrals_N
+
+    # ------------------------------------------------------------------ frictionless contact and sliding supports
+    # 'contact': a rigid frictionless obstacle, n.u <= g, lambda >= 0, lambda (g - n.u) = 0 at every node of the marked facets;
+    # 'sliding': the bilateral case n.u = value (oblique rollers and symmetry planes).  The five subclasses set this to False and
+    # keep refusing both types.
+    _constraint_sides = True
+    _CONTACT_DEFAULTS = {'max_iterations': 30, 'initial_active': 'all'}
+
+    def contact_settings(self):
+        """settings['solver_settings']['contact_settings'] with its defaults, checked (SolverError on a bad value)."""
+        given = self.solver_settings.get('contact_settings') or {}
+        unknown = set(given) - set(self._CONTACT_DEFAULTS)
+        if unknown:
+            raise SolverError('contact_settings: unknown key(s) {}'.format(sorted(unknown)))
+        cs = dict(self._CONTACT_DEFAULTS, **given)
+        mi = cs['max_iterations']
+        if isinstance(mi, bool) or not isinstance(mi, numbers.Integral) or mi < 1:
+            raise SolverError('contact_settings: max_iterations must be a positive integer, got {!r}'.format(mi))
+        if cs['initial_active'] not in ('all', 'none'):
+            raise SolverError("contact_settings: initial_active must be 'all' or 'none', got {!r}".format(cs['initial_active']))
+        return {'max_iterations': int(mi), 'initial_active': cs['initial_active']}
+
+    def _constraint_side_names(self):
+        return [name for name, bc in self.boundary_conditions.items()
+                if self.get_boundary_variable(bc).get('type') in ('contact', 'sliding')]
+
+    def _refuse_constraint_sides(self, what):
+        names = self._constraint_side_names() if self._constraint_sides else []
+        if names:
+            raise SolverError("{}: contact / sliding boundary conditions ({}) are not supported - the eigenproblem needs a linear "
+                              "constraint set; replace them by displacement BCs on the nodes in contact".format(what, ', '.join(names)))
+
+    def _refuse_contact_case(self):
+        """What the contact path is written for: vector CG1, one rank, not periodic, a static case (no device call is made here)."""
+        from . import parallel
+        self.contact_settings()
+        V = self.function_space
+        what = 'contact / sliding boundary conditions'
+        if V.degree() != 1:
+            raise SolverError(what + ': P2 displacement spaces are not supported - the constraint is nodal, on the vertices of the '
+                              'marked facets; use a P1 space')
+        if parallel.world()[1] > 1 or V.localizer() is not None:
+            raise SolverError(what + ' run on one rank')
+        if hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None:
+            raise SolverError(what + ' on a periodic space are not supported')
+        if self.transient_settings['transient']:
+            raise SolverError(what + ': transient_settings must not be transient (the active-set loop solves a static case)')
+
+    def _contact_setup(self, sides, bcs):
+        """The constraint nodes of the 'contact' / 'sliding' sides (host only): the vertices of the marked facets, less those that
+        carry a displacement BC (Dirichlet wins) or belong to a side listed earlier.  Returns a dict of arrays over the nodes in
+        ascending order: nodes, normals [n, d] (unit), values, bilateral, area (lumped area of the marked facets), side (index)."""
+        d = self.dimension
+        co = self.mesh.coordinates()
+        nv = co.shape[0]
+        taken = np.zeros(nv, dtype=bool)
+        dd = self._bc_arrays(bcs)[0]
+        taken[np.unique(dd // d)] = True
+        parts = []
+        for k, (name, marker, btype, bc) in enumerate(sides):
+            sel = self.boundary_facets.where(marker)
+            if len(sel) == 0:
+                raise SolverError("boundary '{}': no facet carries marker {}".format(name, marker))
+            tri, nrm, area = self._normals_of_facets(sel)
+            nodes = np.unique(tri)
+            lumped = np.zeros(nv)
+            np.add.at(lumped, tri.ravel(), np.repeat(area / tri.shape[1], tri.shape[1]))
+            if bc.get('normal') is not None:
+                n = np.asarray(self._vector_of(bc['normal'], "boundary '{}': normal".format(name)), dtype=np.float64)
+                length = np.linalg.norm(n)
+                if not np.isfinite(length) or length == 0.0:
+                    raise SolverError("boundary '{}': the normal is a zero vector".format(name))
+                normals = np.tile(n / length, (len(nodes), 1))
+            else:
+                acc = np.zeros((nv, d))
+                np.add.at(acc, tri.ravel(), np.repeat(nrm * area[:, None], tri.shape[1], axis=0))
+                normals = acc[nodes]
+                length = np.linalg.norm(normals, axis=1)
+                if np.any(length <= 1e-12 * area.max()):
+                    raise SolverError("boundary '{}': the facet normals cancel at node {} (a zero normal); give 'normal'".format(
+                        name, int(nodes[np.argmin(length)])))
+                normals = normals / length[:, None]
+            keep = ~taken[nodes]
+            dropped = int((~keep).sum())
+            if dropped:
+                self.logger.info("boundary '%s': %d of %d nodes carry a displacement BC or belong to an earlier constraint side and "
+                                 "are dropped", name, dropped, len(nodes))
+            if not keep.any():
+                raise SolverError("boundary '{}': no candidate node is left (every node of the side carries a displacement BC or "
+                                  "belongs to an earlier constraint side)".format(name))
+            nodes, normals = nodes[keep], normals[keep]
+            taken[nodes] = True
+            value = bc.get('value')
+            value = 0.0 if value is None else (Expression(value, degree=1) if isinstance(value, str) else value)
+            if is_constant_value(value):
+                vals = np.full(len(nodes), float(value))
+            elif isinstance(value, (Expression, UserExpression)):
+                vals = np.asarray(value.eval_points(co[nodes]), dtype=np.float64).reshape(len(nodes), -1)[:, 0]
+            else:
+                raise SolverError("boundary '{}': value must be a number, a Constant, an Expression or a str".format(name))
+            if not np.all(np.isfinite(vals)):
+                raise SolverError("boundary '{}': the value is not finite at node {}".format(name, int(nodes[np.argmin(np.isfinite(vals))])))
+            parts.append((nodes, normals, vals, np.full(len(nodes), btype == 'sliding'), lumped[nodes], np.full(len(nodes), k)))
+        cat = [np.concatenate([p[j] for p in parts]) for j in range(6)]
+        order = np.argsort(cat[0], kind='stable')
+        keys = ('nodes', 'normals', 'values', 'bilateral', 'area', 'side')
+        out = {key: a[order] for key, a in zip(keys, cat)}
+        out['names'] = [s[0] for s in sides]
+        return out
+
+    def solve_contact(self, F, u, bcs):
+        """The static solve with 'contact' / 'sliding' sides, by the primal-dual active-set strategy in per-node frames: K' = H K H and
+        b' = H b are built once (fs_matrix_rotate_nodes); every active set is a component Dirichlet condition on a copy of K' (the
+        user's Dirichlet dofs with the active normal dofs), solved by AMG-CG (3-D; the rigid-body modes rotated by H as near-null
+        space, a hierarchy per active set) or Jacobi-CG (2-D), warm-started; fs_contact_update gives lambda, the penetration and the
+        next set; the loop ends when no flag changes.  Only sliding sides: one solve.  u = H u' on the way out."""
+        import time
+        from . import backend
+        cs = self.contact_settings()
+        C_ = self._contact
+        d = self.dimension
+        V = F.space.device()
+        rtol, max_iter, pc = self._krylov_options()
+        sp_ = self.solver_settings.get('solver_parameters', {}) or {}
+        use_amg = d == 3 and (pc == 'amg' or 'preconditioner' not in sp_)
+        norm = sp_.get('norm_type', 'preconditioned' if pc != 'none' or use_amg else 'unpreconditioned')
+        phases = {'assembly_ms': 0.0, 'copy_dirichlet_ms': [], 'amg_setup_ms': [], 'cg_ms': [], 'update_ms': []}
+
+        def lap(t0):
+            backend.synchronize()
+            return 1e3 * (time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        K, b = self.assemble_system(F, [])
+        first = np.ones(len(C_['nodes']), dtype=np.int32) if cs['initial_active'] == 'all' else C_['bilateral'].astype(np.int32)
+        frames = backend.ContactFrames(V, C_['nodes'], C_['normals'], C_['values'], C_['bilateral'], first)
+        K.rotate_nodes(frames)
+        b.rotate_nodes(frames)
+        ns = None
+        if use_amg:
+            ns = []
+            for mode in self.build_nullspace(F.space):
+                mv = backend.DeviceVector(V.n_owned, mode)
+                mv.rotate_nodes(frames)
+                ns.append(mv.get())
+                mv.close()
+            ns = np.stack(ns)
+        x = backend.DeviceVector(V.n_local)
+        u0 = u.vector()._values()
+        warm = bool(np.any(u0 != 0.0))
+        if warm:
+            x.set(np.concatenate([u0, np.zeros(V.n_local - u0.size)]))
+            x.rotate_nodes(frames)
+        Kc = backend.DeviceMatrix(V)
+        bc_ = backend.DeviceVector(V.n_owned)
+        phases['assembly_ms'] = lap(t0)
+        user_dofs, user_vals = self._bc_arrays(bcs)
+        target = frames.sigma * frames.values                 # u'[d a + k] = sigma n . u on an active node
+        active = first.astype(bool)
+        history, cg_iterations, seen = [int(active.sum())], [], {active.tobytes()}
+        amg_setups = 0
+        for outer in range(1, cs['max_iterations'] + 1):
+            t0 = time.perf_counter()
+            Kc.copy_from(K)
+            bc_.copy_from(b)
+            dofs = np.concatenate([user_dofs, frames.normal_dofs[active]]).astype(np.int32)
+            vals = np.concatenate([user_vals, target[active]])
+            if dofs.size:
+                Kc.apply_dirichlet(bc_, dofs, vals, symmetric=True)
+                backend.set_dirichlet_values(x, dofs, vals)
+            phases['copy_dirichlet_ms'].append(lap(t0))
+            t0 = time.perf_counter()
+            if use_amg:
+                hierarchy = backend.AMG(Kc, nullspace=ns, strength_threshold=float(sp_.get('amg_strength_threshold', 0.0)))
+                amg_setups += 1
+                phases['amg_setup_ms'].append(lap(t0))
+                t0 = time.perf_counter()
+                try:
+                    st = hierarchy.solve(bc_, x, rtol=rtol, max_iter=min(max_iter, int(sp_.get('maximum_iterations', 500))),
+                                         nonzero_guess=True, norm=norm)
+                finally:
+                    hierarchy.close()
+            else:
+                phases['amg_setup_ms'].append(0.0)
+                st = backend.krylov_solve(Kc, bc_, x, rtol=rtol, max_iter=max_iter, precond='none' if pc == 'none' else 'jacobi',
+                                          method='cg', nonzero_guess=True, norm=norm)
+            phases['cg_ms'].append(lap(t0))
+            self.last_solve_stats = st
+            cg_iterations.append(int(st['iterations']))
+            if st['converged'] != 1:
+                user_tol = 'krylov_relative_tolerance' in sp_ or float(sp_.get('relative_tolerance', 1.0)) < 1e-8
+                if user_tol or st['converged'] < 0 or not (st['true_rel_residual'] <= 1e-8):
+                    raise SolverError('solve_contact: Krylov solver did not converge in {} iterations (||r||/||b|| = {:.3e}) on active '
+                                      'set {} (active counts {})'.format(st['iterations'], st['true_rel_residual'], outer, history))
+                self.logger.warning('solve_contact: stopped at ||r||/||b|| = %.3e after %d iterations (default tolerance %.0e not attained)',
+                                    st['true_rel_residual'], st['iterations'], rtol)
+            t0 = time.perf_counter()
+            changed, n_active = backend.contact_update(frames, K, x, b)
+            phases['update_ms'].append(lap(t0))
+            if changed == 0:
+                break
+            active = frames.get()[0]
+            history.append(n_active)
+            key = active.tobytes()
+            if key in seen:
+                raise SolverError('solve_contact: the active set of iteration {} repeats an earlier one - the active-set strategy cycles '
+                                  '(active counts {})'.format(outer + 1, history))
+            seen.add(key)
+        else:
+            raise SolverError('solve_contact: no fixed active set within max_iterations = {} (active counts {})'.format(
+                cs['max_iterations'], history))
+        act, lam, pen = frames.get()
+        x.rotate_nodes(frames)
+        u.vector()._adopt_device(x)
+        for h in (Kc, K, bc_, b):
+            h.close()
+        frames.close()
+        self._contact_result = {'nodes': C_['nodes'].copy(), 'active': act, 'lambda': lam, 'gap': -pen, 'area': C_['area'],
+                                'bilateral': C_['bilateral'].copy(), 'normals': C_['normals'].copy(), 'values': C_['values'].copy()}
+        self.contact_stats = dict(phases, outer_iterations=outer, active_history=history, cg_iterations=cg_iterations, amg_setups=amg_setups)
+        self.logger.info('solve_contact: %d active-set iteration(s), active counts %s, CG iterations %s', outer, history, cg_iterations)
+        return u
+
+    def _contact_solved(self):
+        res = getattr(self, '_contact_result', None)
+        if res is None:
+            raise SolverError('no contact result: solve() a case with a contact or sliding boundary condition first')
+        return res
+
+    def contact_forces(self):
+        """(node ids, lambda) after a solve: the normal force in N that the obstacle (or the sliding support, where it may have either
+        sign) exerts on every constraint node, against its normal; zero on nodes that are not in contact."""
+        res = self._contact_solved()
+        return res['nodes'].copy(), np.where(res['active'], res['lambda'], 0.0)
+
+    def contact_pressure(self):
+        """The contact pressure as a P1 scalar Function: lambda over the lumped area of the marked facets at the node, zero elsewhere."""
+        from .fem import FunctionSpace
+        res = self._contact_solved()
+        f = Function(FunctionSpace(self.mesh, 'P', 1))
+        p = np.zeros(self.mesh.num_vertices())
+        p[res['nodes']] = np.where(res['active'], res['lambda'], 0.0) / res['area']
+        f.vector().set_local(p)
+        return f
+
+    def contact_status(self):
+        """(node ids, active flags, gaps g - n.u) after a solve."""
+        res = self._contact_solved()
+        return res['nodes'].copy(), res['active'].copy(), res['gap'].copy()
 
     @staticmethod
     def _try_values(val):
@@ -625,6 +885,8 @@ class LinearElasticitySolver(SolverBase):
             F.body_force = tuple(float(x) for x in self._vector_of(bs, 'body_source'))
 
     def solve_form(self, F, u_, bcs):
+        if getattr(self, '_contact', None) is not None:
+            return self.solve_contact(F, u_, bcs)
         if self.dimension == 3:
             u_ = self.solve_amg(F, u_, bcs)
         else:
@@ -645,6 +907,7 @@ class LinearElasticitySolver(SolverBase):
     def solve_modal(self):
         """Modal analysis of the case (LinearElasticitySolver.py:270-281): the form of step 0, then solve_modal_form."""
         self.modal_settings()
+        self._refuse_constraint_sides('solve_modal')
         self.init_solver()
         F, bcs = self.generate_form(0, None, None, self.w_current, self.w_prev)
         return self.solve_modal_form(F, bcs)

@@ -31,6 +31,8 @@ from . import forms
 
 
 class NonlinearElasticitySolver(LinearElasticitySolver):
+    _constraint_sides = False          # 'contact' / 'sliding' sides stay with the static linear solver
+
     def __init__(self, case_settings):
         LinearElasticitySolver.__init__(self, case_settings)
         self.settings['mixed_variable'] = ('displacement', 'velocity', 'pressure')

@@ -39,6 +39,8 @@ from . import forms
 
 
 class PlasticitySolver(StoredStressVonMises, LinearElasticitySolver):
+    _constraint_sides = False          # 'contact' / 'sliding' sides stay with the static linear solver
+
     def __init__(self, case_settings):
         LinearElasticitySolver.__init__(self, case_settings)
         self.reference_load_sign = False          # dead loads with their physical sign, as in NonlinearElasticitySolver

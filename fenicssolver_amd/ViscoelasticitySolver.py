@@ -44,6 +44,8 @@ MAX_TERMS = 8           # FS_VISCO_MAX_TERMS of the library
 
 
 class ViscoelasticitySolver(StoredStressVonMises, LinearElasticitySolver):
+    _constraint_sides = False          # 'contact' / 'sliding' sides stay with the static linear solver
+
     def __init__(self, case_settings):
         LinearElasticitySolver.__init__(self, case_settings)
         self.reference_load_sign = False          # dead loads with their physical sign, as in PlasticitySolver

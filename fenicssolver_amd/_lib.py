@@ -252,6 +252,12 @@ SIGNATURES = {
     "fs_spmv_multi_pencil_benchmark": (C.c_int, [_H, _H, C.c_int, C.c_int, c_f64p, c_f64p]),
     "fs_buckling_solve": (C.c_int, [_H, _H, _H, c_i64, c_i32p, C.POINTER(fs_buckling_opts), c_f64p, C.POINTER(_H),
                                     C.POINTER(fs_buckling_stats)]),
+    "fs_contact_create": (C.c_int, [_H, c_i64, c_i32p, c_f64p, c_f64p, c_i32p, c_i32p, C.POINTER(_H)]),
+    "fs_contact_destroy": (C.c_int, [_H]),
+    "fs_contact_get": (C.c_int, [_H, c_i32p, c_f64p, c_f64p]),
+    "fs_matrix_rotate_nodes": (C.c_int, [_H, _H]),
+    "fs_vector_rotate_nodes": (C.c_int, [_H, _H]),
+    "fs_contact_update": (C.c_int, [_H, _H, _H, _H, c_i32p]),
     "fs_assemble_facet_supg": (C.c_int, [_H, _H, _H, C.c_int64, c_i32p, c_i32p, c_f64p, c_f64p, C.POINTER(fs_coef), C.c_double]),
     "fs_assemble_navier_stokes": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_ns_form)]),
     "fs_space_set_viscosity_law": (C.c_int, [_H, C.POINTER(fs_viscosity_law)]),

@@ -275,6 +275,10 @@ class DeviceVector(_Handle):
         L.check(L.load().fs_vector_dot(self.h, y.h, C.byref(r)), "fs_vector_dot")
         return r.value
 
+    def rotate_nodes(self, frames):
+        """self <- H self with the node reflectors of a ContactFrames (H is its own inverse: the same call leads back)."""
+        L.check(L.load().fs_vector_rotate_nodes(self.h, frames.h), "fs_vector_rotate_nodes")
+
 
 def _coef(spec, keep):
     """spec: None | number | ('cell', array) | ('nodal', array) | ('tensor', 3x3) | ('cell_tensor', [n_cells,3,3])."""
@@ -431,6 +435,11 @@ class DeviceMatrix(_Handle):
     def zero(self):
         L.check(L.load().fs_matrix_zero(self.h), "fs_matrix_zero")
 
+    def rotate_nodes(self, frames):
+        """self <- H self H in place with the node reflectors of a ContactFrames (fs_matrix_rotate_nodes): block sizes 2 and 3, the
+        pattern unchanged, blocks with neither node framed not written."""
+        L.check(L.load().fs_matrix_rotate_nodes(self.h, frames.h), "fs_matrix_rotate_nodes")
+
     def apply_dirichlet(self, b, dofs, vals, symmetric=True):
         dofs = L.i32(dofs).ravel()
         vals = L.f64(np.broadcast_to(vals, dofs.shape))
@@ -460,6 +469,48 @@ class DeviceMatrix(_Handle):
         ms = C.c_double(0.0)
         L.check(L.load().fs_spmv_benchmark(self.h, x.h, y.h, int(reps), C.byref(ms)), "fs_spmv_benchmark")
         return ms.value
+
+
+class ContactFrames(_Handle):
+    """The node frames and the active-set state of frictionless contact / sliding supports on a vector CG1 space (fs_contact_t).
+    nodes: ascending node ids; normals [n, d] (normalised by the library); values [n]: the clearance along the normal of a contact
+    node, the prescribed normal displacement of a bilateral one; bilateral [n]: sliding supports, always active; active [n]: the
+    first active set.  normal_dofs: d * node + (d - 1), the dof that holds sigma n . u in the rotated unknowns."""
+    _destroy = "fs_contact_destroy"
+
+    def __init__(self, space, nodes, normals, values=0.0, bilateral=False, active=True):
+        super().__init__()
+        self.space = space
+        nodes = L.i32(nodes).ravel()
+        d = space.ncomp
+        nrm = L.f64(normals).reshape(-1, d)
+        if nrm.shape[0] != nodes.size:
+            raise BackendError("ContactFrames: %d normals for %d nodes" % (nrm.shape[0], nodes.size))
+        self.nodes, self.n = nodes, nodes.size
+        self.bilateral = L.i32(np.broadcast_to(np.asarray(bilateral, dtype=np.int32), nodes.shape))
+        vals = L.f64(np.broadcast_to(values, nodes.shape))
+        act = L.i32(np.broadcast_to(np.asarray(active, dtype=np.int32), nodes.shape))
+        L.check(L.load().fs_contact_create(space.h, self.n, L.p_i32(nodes), L.p_f64(nrm), L.p_f64(vals), L.p_i32(self.bilateral),
+                                           L.p_i32(act), C.byref(self.h)), "fs_contact_create")
+        length = np.linalg.norm(nrm, axis=1)
+        self.normals = nrm / length[:, None]
+        self.values = vals.copy()
+        self.sigma = np.where(self.normals[:, d - 1] < 0.0, 1.0, -1.0)
+        self.normal_dofs = (d * nodes.astype(np.int64) + (d - 1)).astype(np.int32)
+
+    def get(self):
+        """(active flags, lambda, penetration) of the last contact_update (before the first: the first active set, zeros)."""
+        act, lam, pen = np.empty(self.n, dtype=np.int32), np.empty(self.n), np.empty(self.n)
+        L.check(L.load().fs_contact_get(self.h, L.p_i32(act), L.p_f64(lam), L.p_f64(pen)), "fs_contact_get")
+        return act.astype(bool), lam, pen
+
+
+def contact_update(state, Kprime, uprime, bprime):
+    """One primal-dual active-set update (fs_contact_update) from the solution u' of the system constrained on the state's active
+    set, with the unconstrained rotated K' and b'.  Returns (flags changed, flags active)."""
+    counts = np.zeros(2, dtype=np.int32)
+    L.check(L.load().fs_contact_update(state.h, Kprime.h, uprime.h, bprime.h, L.p_i32(counts)), "fs_contact_update")
+    return int(counts[0]), int(counts[1])
 
 
 def _velocity_coef(v, keep):

@@ -965,6 +965,40 @@ typedef struct fs_buckling_stats {
 int fs_buckling_solve(fs_matrix_t K, fs_matrix_t KG, fs_amg_t precond, int64_t n_constrained, const int32_t* constrained,
                       const fs_buckling_opts* opts, double* factors, fs_vector_t* modes, fs_buckling_stats* stats);
 
+/* ---- frictionless contact and sliding supports --------------------------------------------------------------------------------
+ * No counterpart in the reference, which lists the boundary condition as not implemented ("differs from the
+ * reference").  Vector CG1 spaces on tetrahedra (3 components) or on triangles in plane strain (2 components); one rank.
+ *
+ * Every framed node a has a unit normal n_a and the Householder reflector H_a = I - 2 v v^T / v^T v, v = n_a + s e_k, k the last
+ * axis, s = sgn(n_k) (sgn(0) = +1): symmetric, its own inverse, H_a e_k = sigma_a n_a with sigma_a = -s.  With H = blockdiag(H_a)
+ * (the identity on every other node) and u' = H u, the normal displacement of node a is the one dof u'[d a + k] = sigma_a n_a . u_a:
+ * the constraint n_a . u_a = value_a is a component Dirichlet condition on K' = H K H, b' = H b (fs_apply_dirichlet). */
+typedef struct fs_contact_s* fs_contact_t;
+
+/* The frames and the active-set state of n nodes (strictly ascending node ids of the space): normals [n][d] (any length > 0,
+ * normalised here; FS_ERR_INVALID on a zero or non-finite one), values [n] (the clearance g_a along n_a of a contact node, the
+ * prescribed normal displacement of a bilateral one), bilateral [n] (non-zero: a sliding support, always active), active [n] (the
+ * first active set of the contact nodes).  Held on the device: nodes, reflectors, sigma, values, the bilateral flags, the active
+ * flags, and lambda and the penetration of the last fs_contact_update. */
+int fs_contact_create(fs_space_t space, int64_t n, const int32_t* nodes, const double* normals, const double* values,
+                      const int32_t* bilateral, const int32_t* active, fs_contact_t* out);
+int fs_contact_destroy(fs_contact_t state);
+/* active [n], lambda [n], penetration [n] (each may be NULL) as the last fs_contact_update left them */
+int fs_contact_get(fs_contact_t state, int32_t* active, double* lambda, double* penetration);
+
+/* A <- H A H in place on the block values (block size 2 or 3): the owner of block (a, b) writes H_a A_ab H_b.  The pattern is
+ * unchanged, no atomics, and a block with neither node framed is not written. */
+int fs_matrix_rotate_nodes(fs_matrix_t A, fs_contact_t frames);
+/* x <- H x (>= n_dofs_owned entries): right-hand sides, initial guesses, near-null-space vectors, and the way back u = H u'. */
+int fs_vector_rotate_nodes(fs_vector_t x, fs_contact_t frames);
+
+/* One primal-dual active-set update from the solution u' (>= n_dofs_local entries) of the system constrained on the current active
+ * set, with the UNCONSTRAINED K' and b': for every node of the state rho = (K' u' - b')[d a + k] (the row of the normal dof only,
+ * summed in storage order: the same bits on every call), lambda_a = -sigma_a rho, the penetration p_a = sigma_a u'[d a + k] - value_a,
+ * and the next flag  active ? lambda_a > 0 : p_a > 0  (an exact zero releases, or stays out); bilateral nodes stay active.
+ * counts[0]: flags that changed, counts[1]: flags now active - through two words of pinned host memory, one read per call. */
+int fs_contact_update(fs_contact_t state, fs_matrix_t Kprime, fs_vector_t uprime, fs_vector_t bprime, int32_t* counts);
+
 /* ---- Taylor-Hood Navier-Stokes (CoupledNavierStokesSolver.py:288-381, 215-245, 492-528) -------------
  * Unknowns: one block (u_x, u_y, u_z, p) per CG2 node of fs_space_create(mesh, FS_FAMILY_CG, 2, 4); the
  * pressure is CG1, the pressure slot of an edge node is a dummy unknown with a unit row. */
