@@ -19,6 +19,14 @@ not implemented): n.u <= g against a rigid obstacle, or n.u = va
 primal-dual active-set strategy in per-node Householder frames, where the constraint is a component Dirichlet condition
 (solve_contact; fs_matrix_rotate_nodes, fs_contact_update).  Vector P1, one rank, static cases.
 
+Anisotropic materials (the reference lists them as a to-do, "anisotropy needs rank 4 tensor"): ``elasticity_tensor``
+(a 6x6 in the standard Voigt order 11, 22, 33, 23, 13, 12 with engineering shears) or ``orthotropic`` (E1..3, nu12 / 13 / 23,
+G12 / 13 / 23), each per region as well, with an optional ``material_orientation`` (a rotation whose columns are the material axes,
+two axes to orthonormalise, a per-region dict, or a degree-0 Expression with 9 values for per-cell frames) and a
+``thermal_expansion_coefficient`` of 3 principal values or a symmetric 3x3 in material axes.  The operator, the stress with its
+von Mises load and the eigenstrain load are kernels of their own (fs_assemble_anisotropic, fs_anisotropic_stress,
+fs_assemble_anisotropic_load).  Vector P1, one rank; no contact / sliding sides, no solving_dynamics, no buckling.
+
 Reference quirk kept by default (Appendix B-Q3): body forces and tractions are ADDED to
 F (:227-228, 242-243), so they act with reversed sign; set
 ``solver.reference_load_sign = False`` for the physical convention.  The thermal term has
@@ -46,6 +54,92 @@ from .SolverBase import SolverBase, SolverError
 from . import case, forms
 
 
+# standard Voigt order (11, 22, 33, 23, 13, 12) -> the library's tensor order (xx, yy, zz, xy, xz, yz)
+VOIGT_TO_LIBRARY = [0, 1, 2, 5, 4, 3]
+_ANISO_KEYS = ('elasticity_tensor', 'orthotropic')
+
+
+def isotropic_stiffness(E, nu):
+    """The 6x6 stiffness of an isotropic material in the standard Voigt order (11, 22, 33, 23, 13, 12), engineering shears."""
+    E, nu = float(E), float(nu)
+    mu, lmbda = E / (2.0 * (1.0 + nu)), E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+    C = np.zeros((6, 6))
+    C[:3, :3] = lmbda
+    C[np.arange(3), np.arange(3)] += 2.0 * mu
+    C[np.arange(3, 6), np.arange(3, 6)] = mu
+    return C
+
+
+def orthotropic_stiffness(E, nu, G):
+    """The 6x6 stiffness, standard Voigt order (11, 22, 33, 23, 13, 12), of an orthotropic material in its own axes from
+    E = (E1, E2, E3), nu = (nu12, nu13, nu23) and G = (G12, G13, G23): the inverse of the compliance with S_11 = 1/E1,
+    S_12 = -nu12/E1, S_13 = -nu13/E1, S_23 = -nu23/E2, S_44 = 1/G23, S_55 = 1/G13, S_66 = 1/G12."""
+    E, nu, G = (np.asarray(x, dtype=np.float64).ravel() for x in (E, nu, G))
+    if E.size != 3 or nu.size != 3 or G.size != 3:
+        raise SolverError('orthotropic material: three elastic moduli, three Poisson ratios (nu12, nu13, nu23) and three shear '
+                          'moduli (G12, G13, G23) are expected')
+    if not (np.all(np.isfinite(np.concatenate([E, nu, G]))) and np.all(E > 0.0) and np.all(G > 0.0)):
+        raise SolverError('orthotropic material: the elastic and shear moduli must be positive and finite')
+    S = np.zeros((6, 6))
+    S[0, 0], S[1, 1], S[2, 2] = 1.0 / E
+    S[0, 1] = S[1, 0] = -nu[0] / E[0]
+    S[0, 2] = S[2, 0] = -nu[1] / E[0]
+    S[1, 2] = S[2, 1] = -nu[2] / E[1]
+    S[3, 3], S[4, 4], S[5, 5] = 1.0 / G[2], 1.0 / G[1], 1.0 / G[0]
+    if abs(np.linalg.det(S[:3, :3])) == 0.0:
+        raise SolverError('orthotropic material: the compliance is singular')
+    C = np.linalg.inv(S)
+    return 0.5 * (C + C.T)
+
+
+def _rotation_from(value, what):
+    """A proper rotation [3, 3] (columns = material axes in global coordinates) from a 3x3 matrix (2x2: about z) or
+    {'axis_1': v, 'axis_2': w} (orthonormalised: e1 = v/|v|, e2 = w less its part along e1, e3 = e1 x e2)."""
+    if isinstance(value, dict):
+        if 'axis_1' not in value or 'axis_2' not in value:
+            raise SolverError("{}: a 3x3 rotation or {{'axis_1': v, 'axis_2': w}} is expected".format(what))
+        v, w = (np.asarray(value[k], dtype=np.float64).ravel() for k in ('axis_1', 'axis_2'))
+        if v.size == 2 and w.size == 2:
+            v, w = np.append(v, 0.0), np.append(w, 0.0)
+        if v.size != 3 or w.size != 3 or not np.all(np.isfinite(np.concatenate([v, w]))):
+            raise SolverError('{}: axis_1 and axis_2 must be finite vectors of 3 numbers'.format(what))
+        if np.linalg.norm(v) == 0.0:
+            raise SolverError('{}: axis_1 is a zero vector'.format(what))
+        e1 = v / np.linalg.norm(v)
+        w = w - (w @ e1) * e1
+        if np.linalg.norm(w) <= 1e-12 * max(1.0, np.linalg.norm(value['axis_2'])):
+            raise SolverError('{}: axis_2 is parallel to axis_1'.format(what))
+        e2 = w / np.linalg.norm(w)
+        return np.stack([e1, e2, np.cross(e1, e2)], axis=1)
+    try:
+        R = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SolverError('{}: a 3x3 rotation matrix is expected'.format(what))
+    if R.shape == (2, 2):
+        R3 = np.eye(3)
+        R3[:2, :2] = R
+        R = R3
+    if R.shape == (9,):
+        R = R.reshape(3, 3)
+    if R.shape != (3, 3):
+        raise SolverError('{}: a 3x3 rotation matrix is expected, got shape {}'.format(what, R.shape))
+    _check_rotations(R[None], what)
+    return R
+
+
+def _check_rotations(R, what):
+    """SolverError unless every R[c] has max|R^T R - I| <= 1e-10 and det > 0."""
+    if not np.all(np.isfinite(R)):
+        raise SolverError('{}: the rotation is not finite'.format(what))
+    err = np.abs(np.einsum('cki,ckj->cij', R, R) - np.eye(3)[None]).max(axis=(1, 2))
+    det = np.linalg.det(R)
+    bad = (err > 1e-10) | ~(det > 0.0)
+    if bad.any():
+        c = int(np.argmax(bad))
+        where = '' if len(R) == 1 else ' in cell {}'.format(c)
+        raise SolverError('{}{}: not a proper rotation (max|R^T R - I| = {:.3e}, det = {:.3g})'.format(what, where, err[c], det[c]))
+
+
 class LinearElasticitySolver(SolverBase):
     def __init__(self, case_settings):
         case_settings['vector_name'] = 'displacement'
@@ -54,10 +148,193 @@ class LinearElasticitySolver(SolverBase):
         self.solving_dynamics = False
         self.reference_load_sign = True
 
+    # ------------------------------------------------------------------ anisotropic materials
+    def is_anisotropic(self):
+        return any(k in self.material and self.material[k] is not None for k in _ANISO_KEYS)
+
+    def _no_lame(self, what):
+        return SolverError("{}: {} is defined for an isotropic material (elastic_modulus, poisson_ratio) only; the case gives "
+                           "'elasticity_tensor' / 'orthotropic', and this path does not take an anisotropic material".format(
+                               type(self).__name__, what))
+
+    def _regions_of(self, value, is_leaf):
+        """[(region name or None, leaf value, cell mask or None)] of a material entry that is a leaf or a per-region dict
+        {'name': {'subdomain_id': i, 'value': leaf}} (the leaf's own keys may also stand beside 'subdomain_id')."""
+        if is_leaf(value):
+            return [(None, value, None)]
+        if not (isinstance(value, dict) and value and all(isinstance(it, dict) and 'subdomain_id' in it for it in value.values())):
+            return None
+        if getattr(self, 'subdomains', None) is None:
+            raise SolverError('a per-region material needs the subdomain markers of the mesh')
+        ids = self.subdomains.array()
+        out = []
+        for name, item in value.items():
+            leaf = item['value'] if 'value' in item else {k: v for k, v in item.items() if k != 'subdomain_id'}
+            out.append((name, leaf, ids == item['subdomain_id']))
+        covered = np.zeros(len(ids), dtype=bool)
+        for _, _, mask in out:
+            covered |= mask
+        if not covered.all():
+            raise SolverError('multi-region value does not cover every subdomain id of the mesh')
+        return out
+
+    def _stiffness_of(self, key, leaf, region):
+        """One 6x6 in the library order from a leaf of material[key], checked for symmetry and positive definiteness."""
+        what = "material '{}'".format(key) + ('' if region is None else " of region '{}'".format(region))
+        if key == 'orthotropic':
+            if not isinstance(leaf, dict) or not all(k in leaf for k in ('elastic_moduli', 'poisson_ratios', 'shear_moduli')):
+                raise SolverError("{}: {{'elastic_moduli': [E1, E2, E3], 'poisson_ratios': [nu12, nu13, nu23], 'shear_moduli': "
+                                  "[G12, G13, G23]}} is expected".format(what))
+            try:
+                Cv = orthotropic_stiffness(leaf['elastic_moduli'], leaf['poisson_ratios'], leaf['shear_moduli'])
+            except SolverError as e:
+                raise SolverError('{}: {}'.format(what, e))
+        else:
+            try:
+                Cv = np.asarray(leaf, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise SolverError('{}: a 6x6 matrix of numbers is expected'.format(what))
+            if Cv.shape != (6, 6):
+                raise SolverError('{}: a 6x6 matrix in Voigt order (11, 22, 33, 23, 13, 12) is expected, got shape {}'.format(what, Cv.shape))
+        if not np.all(np.isfinite(Cv)):
+            raise SolverError('{}: the stiffness is not finite'.format(what))
+        scale = np.abs(Cv).max()
+        if not np.abs(Cv - Cv.T).max() <= 1e-12 * scale:
+            raise SolverError('{}: the stiffness matrix is not symmetric (max|C - C^T| = {:.3e})'.format(what, np.abs(Cv - Cv.T).max()))
+        Cv = 0.5 * (Cv + Cv.T)
+        try:
+            np.linalg.cholesky(Cv)
+        except np.linalg.LinAlgError:
+            raise SolverError('{}: the stiffness matrix is not positive definite (smallest eigenvalue {:.3e})'.format(
+                what, np.linalg.eigvalsh(Cv).min()))
+        D = Cv[np.ix_(VOIGT_TO_LIBRARY, VOIGT_TO_LIBRARY)]
+        if self.dimension == 2 and np.abs(D[:4, 4:]).max() > 1e-12 * scale:
+            raise SolverError('{}: plane strain needs a material that is monoclinic about z (no coupling between the in-plane '
+                              'strains and the out-of-plane shears); rotate the material about z only'.format(what))
+        return D
+
+    def _orientation_frames(self):
+        """None or the frames [n_cells, 3, 3] of material['material_orientation']."""
+        v = self.material.get('material_orientation')
+        if v is None:
+            return None
+        nc = self.mesh.num_cells()
+        what = "material 'material_orientation'"
+        if isinstance(v, (Expression, UserExpression)):
+            if v.value_size() != 9 or getattr(v, 'degree', 0) != 0:
+                raise SolverError(what + ': an Expression must have degree 0 and 9 values (the rotation, row-major)')
+            co = self.mesh.coordinates()
+            R = np.asarray(v.eval_points(co[self.mesh.cells().astype(np.int64)].mean(axis=1)), dtype=np.float64).reshape(nc, 3, 3)
+            _check_rotations(R, what)
+        else:
+            leaf = lambda x: not isinstance(x, dict) or 'axis_1' in x or 'axis_2' in x
+            regions = self._regions_of(v, leaf)
+            if regions is None:
+                raise SolverError(what + ": a 3x3 rotation, {'axis_1': v, 'axis_2': w}, a per-region dict of either or a degree-0 "
+                                  "Expression with 9 values is expected")
+            R = np.empty((nc, 3, 3))
+            for name, item, mask in regions:
+                Rr = _rotation_from(item, what + ('' if name is None else " of region '{}'".format(name)))
+                R[slice(None) if mask is None else mask] = Rr
+        if self.dimension == 2 and (np.abs(R[:, 2, :2]).max() > 1e-12 or np.abs(R[:, :2, 2]).max() > 1e-12 or np.abs(R[:, 2, 2] - 1.0).max() > 1e-12):
+            raise SolverError(what + ': plane strain needs rotations about z')
+        return R
+
+    def _expansion_tensors(self):
+        """alpha per cell [n_cells, 3, 3] in material axes from material['thermal_expansion_coefficient']: a number, 3 principal values
+        or a symmetric 3x3, per region as well."""
+        v = self.material['thermal_expansion_coefficient']
+        what = "material 'thermal_expansion_coefficient'"
+
+        def tensor(x, where):
+            if isinstance(x, Constant):
+                x = x.values()
+            try:
+                a = np.asarray(x, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise SolverError(where + ': a number, 3 principal values or a symmetric 3x3 is expected')
+            if a.size == 1:
+                a = float(a.ravel()[0]) * np.eye(3)
+            elif a.shape == (3,):
+                a = np.diag(a)
+            if a.shape != (3, 3) or not np.all(np.isfinite(a)) or np.abs(a - a.T).max() > 1e-12 * max(np.abs(a).max(), 1e-300):
+                raise SolverError(where + ': a number, 3 principal values or a symmetric 3x3 is expected')
+            return 0.5 * (a + a.T)
+        nc = self.mesh.num_cells()
+        regions = self._regions_of(v, lambda x: not isinstance(x, dict))
+        if regions is None:
+            raise SolverError(what + ': a number, 3 principal values, a symmetric 3x3 or a per-region dict of these is expected')
+        A = np.empty((nc, 3, 3))
+        for name, item, mask in regions:
+            A[slice(None) if mask is None else mask] = tensor(item, what + ('' if name is None else " of region '{}'".format(name)))
+        return A
+
+    def anisotropic_material(self):
+        """None for an isotropic case; else the forms.AnisotropicElasticity of material['elasticity_tensor'] / ['orthotropic'] with
+        ['material_orientation'] (host only; every distinct material checked for symmetry and positive definiteness)."""
+        if not self.is_anisotropic():
+            return None
+        given = [k for k in _ANISO_KEYS if self.material.get(k) is not None]
+        iso = [k for k in ('elastic_modulus', 'poisson_ratio') if self.material.get(k) is not None]
+        if len(given) > 1 or iso:
+            raise SolverError("material: '{}' is given together with {}; give one description of the stiffness (isotropic regions "
+                              "go under 'elasticity_tensor' as isotropic_stiffness(E, nu))".format(
+                                  given[0], ', '.join("'{}'".format(k) for k in given[1:] + iso)))
+        key = given[0]
+        v = self.material[key]
+        is_leaf = (lambda x: isinstance(x, dict) and 'elastic_moduli' in x) if key == 'orthotropic' else (lambda x: not isinstance(x, dict))
+        regions = self._regions_of(v, is_leaf)
+        if regions is None:
+            raise SolverError("material '{}': {} or a per-region dict {{'name': {{'subdomain_id': i, 'value': ...}}}} is expected".format(
+                key, 'a 6x6 matrix' if key == 'elasticity_tensor' else "{'elastic_moduli', 'poisson_ratios', 'shear_moduli'}"))
+        table = np.stack([self._stiffness_of(key, leaf, name) for name, leaf, _ in regions])
+        index = None
+        if regions[0][2] is not None:
+            index = np.zeros(self.mesh.num_cells(), dtype=np.int32)
+            for k, (_, _, mask) in enumerate(regions):
+                index[mask] = k
+        return forms.AnisotropicElasticity(table, index, self._orientation_frames())
+
+    def stiffness_tensor(self):
+        """(table [n, 6, 6], material_of_cell [n_cells] or None, frames [n_cells, 3, 3] or None) of an anisotropic case: the distinct
+        stiffness matrices in the LIBRARY's order (xx, yy, zz, xy, xz, yz; engineering shears) and material axes, the table row of
+        every cell, and the rotations whose columns are the material axes in global coordinates."""
+        mat = self.anisotropic_material()
+        if mat is None:
+            raise SolverError("stiffness_tensor: the material is isotropic (no 'elasticity_tensor' / 'orthotropic'); see lame_parameters")
+        return mat.table.copy(), None if mat.index is None else mat.index.copy(), None if mat.frames is None else mat.frames.copy()
+
+    def _refuse_anisotropic_case(self):
+        """What the anisotropic operator is written for: vector CG1, one rank, not periodic, no constraint sides, not the
+        solving_dynamics branch (no device call is made here)."""
+        from . import parallel
+        V = self.function_space
+        what = 'an anisotropic material'
+        if V.degree() != 1:
+            raise SolverError(what + ': P2 displacement spaces are not supported - the kernel integrates the constant strain of a '
+                              'P1 cell; use a P1 space')
+        if parallel.active():                    # (a file mesh that one GPU holds in locality order has a localizer too: that one is served)
+            raise SolverError(what + ' runs on one rank')
+        if hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None:
+            raise SolverError(what + ' on a periodic space is not supported')
+        names = self._constraint_side_names()
+        if names:
+            raise SolverError(what + ": 'contact' / 'sliding' boundary conditions ({}) are not supported with it".format(', '.join(names)))
+        if self.solving_dynamics:
+            raise SolverError(what + ': solving_dynamics is not supported with it')
+
+    @staticmethod
+    def _tensor_storage(T, d):
+        """[n, 3, 3] symmetric tensors -> the tensor storage [n, 6] (xx, yy, zz, xy, xz, yz) or, d == 2, [n, 4] (xx, yy, zz, xy)."""
+        cols = [T[:, 0, 0], T[:, 1, 1], T[:, 2, 2], T[:, 0, 1]] + ([T[:, 0, 2], T[:, 1, 2]] if d == 3 else [])
+        return np.stack(cols, axis=1)
+
     def material_field(self, name):
         """material[name] as a number (homogeneous: a number or a scalar Constant) or an array with one value per cell of
         self.mesh: a per-region dict, a degree-0 Expression (cell mid-points), on CG1 spaces a scalar Function or Expression
         (the mean of its vertex values - what the P1 operator integrates exactly for a linear E)."""
+        if name in ('elastic_modulus', 'poisson_ratio') and self.material.get(name) is None and self.is_anisotropic():
+            raise self._no_lame("material '{}'".format(name))
         v = self.material[name]
         if isinstance(v, numbers.Number):
             return v
@@ -97,7 +374,10 @@ class LinearElasticitySolver(SolverBase):
         return SolverError("material '{}' is out of range in cell {}".format(name, bad))
 
     def lame_parameters(self):
-        """(mu, lambda): numbers for a homogeneous material, arrays [n_cells] when E or nu vary from cell to cell."""
+        """(mu, lambda): numbers for a homogeneous material, arrays [n_cells] when E or nu vary from cell to cell.  An anisotropic
+        material has none: SolverError (what makes solve_buckling and the inelastic / dynamic subclasses refuse it)."""
+        if self.is_anisotropic():
+            raise self._no_lame('lame_parameters')
         elasticity = self.material_field('elastic_modulus')
         nu = self.material_field('poisson_ratio')
         if np.ndim(elasticity) == 0 and np.ndim(nu) == 0:
@@ -143,7 +423,11 @@ class LinearElasticitySolver(SolverBase):
 
     def sigma(self, u):
         """Cell-wise (DG0) stress tensor [nc,3,3] of a displacement Function (post-processing helper on the host; the
-        reference returns the UFL expression, LinearElasticitySolver.py:62-69)."""
+        reference returns the UFL expression, LinearElasticitySolver.py:62-69).  Anisotropic material: C : eps(u), [nc,2,2] (the
+        in-plane part) in plane strain."""
+        aniso = self.anisotropic_material()
+        if aniso is not None:
+            return self._sigma_anisotropic(u, aniso)
         mu, lmbda = self.lame_parameters()
         G = self._cell_gradients(u)
         eps = 0.5 * (G + np.transpose(G, (0, 2, 1)))
@@ -152,25 +436,53 @@ class LinearElasticitySolver(SolverBase):
             mu, lmbda = np.asarray(mu)[:, None, None], np.asarray(lmbda)[:, None, None]
         return 2.0 * mu * eps + lmbda * tr[:, None, None] * np.eye(G.shape[1])[None]
 
+    def _sigma_anisotropic(self, u, aniso):
+        G = self._cell_gradients(u)
+        d = G.shape[1]
+        E = np.zeros((len(G), 3, 3))
+        E[:, :d, :d] = 0.5 * (G + np.transpose(G, (0, 2, 1)))
+        R = aniso.frames
+        if R is not None:
+            E = np.einsum('cki,ckl,clj->cij', R, E, R)                  # R^T E R: into the material axes
+        ev = np.stack([E[:, 0, 0], E[:, 1, 1], E[:, 2, 2], 2.0 * E[:, 0, 1], 2.0 * E[:, 0, 2], 2.0 * E[:, 1, 2]], axis=1)
+        D = aniso.table[aniso.index] if aniso.index is not None else np.broadcast_to(aniso.table[0], (len(G), 6, 6))
+        sv = np.einsum('cij,cj->ci', D, ev)
+        S = np.empty((len(G), 3, 3))
+        S[:, 0, 0], S[:, 1, 1], S[:, 2, 2] = sv[:, 0], sv[:, 1], sv[:, 2]
+        S[:, 0, 1] = S[:, 1, 0] = sv[:, 3]
+        S[:, 0, 2] = S[:, 2, 0] = sv[:, 4]
+        S[:, 1, 2] = S[:, 2, 1] = sv[:, 5]
+        if R is not None:
+            S = np.einsum('cik,ckl,cjl->cij', R, S, R)
+        return S[:, :d, :d]
+
     def von_Mises(self, u):
         """project(sqrt(3/2 s:s), FunctionSpace(mesh, 'P', 1)) (:71-76): the consistent L2 projection, on the device -
-        right-hand side int vm phi_a dx (fs_assemble_von_mises), P1 mass matrix, Jacobi-CG to 1e-12."""
+        right-hand side int vm phi_a dx (fs_assemble_von_mises; anisotropic material: fs_anisotropic_stress with s the deviator
+        of C : eps(u)), P1 mass matrix, Jacobi-CG to 1e-12."""
         from .fem import FunctionSpace
         from . import backend
         V = u.function_space()
+        aniso = self.anisotropic_material()
+        if aniso is not None:
+            self._refuse_anisotropic_case()
+        else:
+            mu, lmbda = self.lame_parameters()
         P = FunctionSpace(self.mesh, 'P', 1)
         dV, dP = V.device(), P.device()
-        mu, lmbda = self.lame_parameters()
         loc, ploc = V.localizer(), P.localizer()
         uh = u.vector()._values()
         if loc is not None and not getattr(loc, 'is_identity', False):
             uh = loc.nodes(uh)                       # host field -> this rank's owned + ghost entries in device order
         ud = backend.DeviceVector(dV.n_local, uh)
         b = backend.DeviceVector(dP.n_owned)
-        if np.ndim(mu) > 0:                          # per-cell material: (mu, lambda) pairs in device cell order
-            pairs = np.stack([mu, lmbda], axis=1)
-            mu, lmbda = ('cell', pairs if loc is None else loc.cells(pairs)), None
-        backend.assemble_von_mises(dV, ud, mu, lmbda, dP, b)
+        if aniso is not None:
+            backend.anisotropic_stress(dV, ud, aniso.material(loc), p1_space=dP, vm_rhs=b)
+        else:
+            if np.ndim(mu) > 0:                      # per-cell material: (mu, lambda) pairs in device cell order
+                pairs = np.stack([mu, lmbda], axis=1)
+                mu, lmbda = ('cell', pairs if loc is None else loc.cells(pairs)), None
+            backend.assemble_von_mises(dV, ud, mu, lmbda, dP, b)
         M = backend.DeviceMatrix(dP)
         M.assemble(mass=1.0)
         x = backend.DeviceVector(dP.n_local)
@@ -256,7 +568,16 @@ class LinearElasticitySolver(SolverBase):
         shifted = None if shift == 0.0 else (shift * rho_spec if np.ndim(rho) == 0 else ('cell', shift * rho_spec[1]))
         V = F.space.device()
         K = backend.DeviceMatrix(V)
-        K.assemble(lame=F.lame_spec(), mass=shifted)              # K + shift M: one form
+        if F.anisotropic is not None:
+            if F.space.localizer() is not None:
+                # (the guard above runs before device() exists: a file mesh uploaded in locality order gets its localizer here, and
+                # the constrained dofs and the modes below are in the host's numbering)
+                raise SolverError('modal analysis with an anisotropic material: the mesh was uploaded in locality order (FS_RENUMBER=1, '
+                                  'or a tetrahedral file mesh of {} vertices or more), which solve_modal does not serve; set '
+                                  'FS_RENUMBER=0'.format(type(F.space).RENUMBER_MIN_VERTICES))
+            K.assemble_anisotropic(F.anisotropic.material(), mass=shifted)
+        else:
+            K.assemble(lame=F.lame_spec(), mass=shifted)          # K + shift M: one form
         M = backend.DeviceMatrix(V)
         M.assemble(lame=(0.0, 0.0), mass=rho_spec)
         if constrained.size:
@@ -317,6 +638,8 @@ class LinearElasticitySolver(SolverBase):
 
     def _geometric_stiffness(self, u, cell_stress):
         from . import backend
+        if self.is_anisotropic():
+            raise self._no_lame('geometric_stiffness')
         self._refuse_buckling_space('geometric_stiffness')
         u = self.w_current if u is None else u
         F = forms.ElasticityForm(self.function_space)
@@ -341,6 +664,8 @@ class LinearElasticitySolver(SolverBase):
         from . import backend
         bs = self.buckling_settings()
         what = 'solve_buckling'
+        if self.is_anisotropic():
+            raise self._no_lame(what + ' (the geometric stiffness of its prestress)')
         self._refuse_constraint_sides(what)
         self._refuse_buckling_space('buckling analysis')
         if self.settings.get('temperature_distribution') is not None or getattr(self, 'temperature_distribution', None) is not None:
@@ -840,11 +1165,15 @@ class LinearElasticitySolver(SolverBase):
     # ------------------------------------------------------------------ the form
     def generate_form(self, time_iter_, u, v, u_current, u_prev):
         F = forms.ElasticityForm(self.function_space)
+        aniso = self.anisotropic_material()
+        if aniso is not None:
+            self._refuse_anisotropic_case()
         if self.transient_settings['transient'] and self.solving_dynamics and time_iter_ >= 1:
             # F -= density * inner(accel, v) * dx (:216-220) with the explicit acceleration of SolverBase.get_acceleration
             rho = self.material_field('density')
             F.inertia = (float(rho) if np.ndim(rho) == 0 else ('cell', rho), self.get_acceleration(time_iter_))
-        F.mu, F.lmbda = self.lame_parameters()
+        if aniso is None:
+            F.mu, F.lmbda = self.lame_parameters()
         F.load_sign = -1.0 if self.reference_load_sign else 1.0
 
         bcs, integrals_F = self.update_boundary_conditions(time_iter_, u, v, Measure("ds", subdomain_data=self.boundary_facets))
@@ -865,7 +1194,19 @@ class LinearElasticitySolver(SolverBase):
                 from .fem import FunctionSpace
                 nod = nodal_values(T, FunctionSpace(self.mesh, 'P', 1))
                 Tval = float(nod[0]) if np.ptp(nod) == 0.0 else nod
-            F.thermal = (self.thermal_stress_coefficient(), Tval, T_ref)
+            if aniso is None:
+                F.thermal = (self.thermal_stress_coefficient(), Tval, T_ref)
+            else:
+                # eps* per unit temperature in global axes: R alpha R^T, alpha given in material axes
+                alpha = self._expansion_tensors()
+                if aniso.frames is not None:
+                    alpha = np.einsum('cik,ckl,cjl->cij', aniso.frames, alpha, aniso.frames)
+                if self.dimension == 2 and max(np.abs(alpha[:, 0, 2]).max(), np.abs(alpha[:, 1, 2]).max()) > 1e-12 * np.abs(alpha).max():
+                    raise SolverError("material 'thermal_expansion_coefficient': plane strain needs an expansion tensor without "
+                                      "xz / yz components")
+                aniso = forms.AnisotropicElasticity(aniso.table, aniso.index, aniso.frames,
+                                                    thermal=(self._tensor_storage(alpha, self.dimension), Tval, T_ref))
+        F.anisotropic = aniso
         return F, bcs
 
     def _set_body_force(self, F):

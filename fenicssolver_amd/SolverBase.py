@@ -723,10 +723,15 @@ class SolverBase():
                 B.spmv(tp, tmp)
                 b.axpy(1.0, tmp)
         elif isinstance(F, forms.ElasticityForm):
-            lame = F.lame_spec()
-            if F.cellwise() and loc is not None:
-                lame = ('cell', loc.cells(lame[1]))     # per-cell (mu, lambda): this rank's cells, in device cell order
-            A.assemble(lame=lame)
+            aniso = getattr(F, 'anisotropic', None)
+            if aniso is not None:
+                A.assemble_anisotropic(aniso.material(loc))     # (index and frames in device cell order: a file mesh on one GPU
+                #                                                  may be uploaded in locality order, with a one-part localizer)
+            else:
+                lame = F.lame_spec()
+                if F.cellwise() and loc is not None:
+                    lame = ('cell', loc.cells(lame[1]))     # per-cell (mu, lambda): this rank's cells, in device cell order
+                A.assemble(lame=lame)
             sgn = F.load_sign
             if F.body_force is not None:
                 backend.assemble_vector(V, b, vector_value=[sgn * x for x in F.body_force])
@@ -767,6 +772,9 @@ class SolverBase():
                         Tn = np.concatenate([Tn, np.full(F.space.num_nodes() - len(Tn), T_ref)])
                     Tn = Tn if loc is None else loc.nodes(Tn)
                     backend.assemble_vector(V, b, div_coef=("nodal", coef * (Tn - T_ref)), add=True)
+            if aniso is not None and aniso.thermal is not None:
+                # int (C : eps*) : grad v dx with eps* = R alpha R^T (T_cell - T_ref), a nodal T by its mean at the cell's vertices
+                backend.assemble_anisotropic_load(V, aniso.material(loc), aniso.eigenstrain(self.mesh.cells(), loc), b, add=True)
             if getattr(F, 'inertia', None) is not None:
                 # F -= rho inner(accel, v) dx with the known (explicit) acceleration: rhs += rho M accel
                 rho, accel = F.inertia
@@ -1597,7 +1605,8 @@ class SolverBase():
         """assemble_system + CG preconditioned by smoothed-aggregation AMG with the rigid-body near-null
         space (SolverBase.py:643-672); solver_parameters['preconditioner'] = 'jacobi' selects Jacobi-CG."""
         if isinstance(F, forms.ElasticityForm) and F.body_force is None and getattr(F, 'body_force_nodal', None) is None \
-                and not F.tractions and F.thermal is None and not any(np.any(bc.values != 0) for bc in bcs):
+                and not F.tractions and F.thermal is None and getattr(getattr(F, 'anisotropic', None), 'thermal', None) is None \
+                and not any(np.any(bc.values != 0) for bc in bcs):
             # empty right-hand side: the reference fails in assemble_system here (Appendix B-Q11)
             self.logger.warning('solve_amg: zero load and homogeneous BCs, the solution is zero')
         A, b = self.assemble_system(F, bcs, symmetric=True)
@@ -1653,6 +1662,9 @@ class SolverBase():
         if not isinstance(F, forms.ElasticityForm):
             return None
         dofs = np.concatenate([np.asarray(bc.dofs, dtype=np.int64) for bc in bcs]) if bcs else np.zeros(0, dtype=np.int64)
+        if getattr(F, 'anisotropic', None) is not None:     # a digest of table, index and frames
+            return ('elasticity', F.space.root().serial(), 'anisotropic', F.anisotropic.digest(), len(dofs),
+                    zlib.crc32(np.ascontiguousarray(dofs).tobytes()))
         if F.cellwise():        # per-cell material: a digest of the (mu, lambda) pairs
             pairs = np.ascontiguousarray(F.lame_spec()[1])
             return ('elasticity', F.space.root().serial(), 'cell', pairs.shape[0], zlib.crc32(pairs.tobytes()), len(dofs),

@@ -60,6 +60,10 @@ class fs_linear_form(C.Structure):
                 ("supg_pe", C.c_double)]
 
 
+class fs_aniso_material(C.Structure):
+    _fields_ = [("n_materials", C.c_int64), ("stiffness", c_f64p), ("material_of_cell", c_i32p), ("frame", c_f64p)]
+
+
 class fs_hyper_form(C.Structure):
     _fields_ = [("model", C.c_int), ("mu", C.c_double), ("lambda_", C.c_double), ("lame", fs_coef), ("add", C.c_int)]
 
@@ -252,6 +256,9 @@ SIGNATURES = {
     "fs_spmv_multi_pencil_benchmark": (C.c_int, [_H, _H, C.c_int, C.c_int, c_f64p, c_f64p]),
     "fs_buckling_solve": (C.c_int, [_H, _H, _H, c_i64, c_i32p, C.POINTER(fs_buckling_opts), c_f64p, C.POINTER(_H),
                                     C.POINTER(fs_buckling_stats)]),
+    "fs_assemble_anisotropic": (C.c_int, [_H, C.POINTER(fs_aniso_material), C.POINTER(fs_coef), C.c_int]),
+    "fs_anisotropic_stress": (C.c_int, [_H, _H, C.POINTER(fs_aniso_material), c_f64p, c_f64p, _H, _H]),
+    "fs_assemble_anisotropic_load": (C.c_int, [_H, C.POINTER(fs_aniso_material), c_f64p, _H, C.c_int]),
     "fs_contact_create": (C.c_int, [_H, c_i64, c_i32p, c_f64p, c_f64p, c_i32p, c_i32p, C.POINTER(_H)]),
     "fs_contact_destroy": (C.c_int, [_H]),
     "fs_contact_get": (C.c_int, [_H, c_i32p, c_f64p, c_f64p]),

@@ -388,6 +388,20 @@ class DeviceMatrix(_Handle):
         f = _bilinear_form(keep, stiffness, mass, lame, advection, advection_scale, supg_pe)
         L.check(L.load().fs_assemble_matrix(self.h, C.byref(f), 1 if add else 0), "fs_assemble_matrix")
 
+    def assemble_anisotropic(self, material, mass=None, add=False):
+        """self (+)= int eps(v) : C : eps(u) dx + mass u.v on a vector CG1 space (fs_assemble_anisotropic).  material: an
+        AnisotropicMaterial or a tuple (table[n, 6, 6] in library order, material_of_cell or None, frames or None) in device cell
+        order; mass: None, a number or ('cell', array[n_cells])."""
+        keep = []
+        nc = self.space.mesh.info()[1]
+        m = _aniso_material(material, nc, keep)
+        if isinstance(mass, tuple):
+            if mass[0] != "cell" or np.shape(mass[1]) != (nc,):
+                raise BackendError("assemble_anisotropic: mass is a number or ('cell', array[%d]), got (%r, shape %s)"
+                                   % (nc, mass[0], np.shape(mass[1])))
+        mc = _coef(mass, keep)
+        L.check(L.load().fs_assemble_anisotropic(self.h, C.byref(m), C.byref(mc), 1 if add else 0), "fs_assemble_anisotropic")
+
     def assemble_geometric(self, lame, u, cell_stress=False):
         """The geometric stiffness K_G of the linear-elastic stress of the displacement u (DeviceVector of the space's dofs) on a
         vector CG1 space (fs_assemble_geometric_stiffness): every node-pair block is s I.  lame as assemble(lame=...): (mu, lambda)
@@ -595,6 +609,99 @@ def assemble_von_mises(disp_space, u, mu, lmbda, p1_space, b):
         L.check(L.load().fs_assemble_von_mises_cells(disp_space.h, u.h, L.p_f64(a), p1_space.h, b.h), "fs_assemble_von_mises_cells")
         return
     L.check(L.load().fs_assemble_von_mises(disp_space.h, u.h, float(mu), float(lmbda), p1_space.h, b.h), "fs_assemble_von_mises")
+
+
+class AnisotropicMaterial:
+    """An anisotropic elastic material as the device layer takes it (fs_aniso_material): ``table`` [n, 6, 6] symmetric matrices in
+    the library's tensor order (xx, yy, zz, xy, xz, yz) with engineering shears, ``material_of_cell`` [n_cells] table indices in
+    device cell order (None: one material everywhere, or - with n == n_cells - one per cell) and ``frames`` [n_cells, 3, 3] rotations
+    whose columns are the material axes in global coordinates (None: the global axes)."""
+
+    def __init__(self, table, material_of_cell=None, frames=None):
+        self.table, self.material_of_cell, self.frames = table, material_of_cell, frames
+
+
+_ANISO_TRIU = np.triu_indices(6)
+
+
+def _aniso_material(material, n_cells, keep):
+    """fs_aniso_material of an AnisotropicMaterial or a tuple (table, material_of_cell, frames); wrong lengths: BackendError."""
+    if isinstance(material, AnisotropicMaterial):
+        material = (material.table, material.material_of_cell, material.frames)
+    if not isinstance(material, (tuple, list)) or len(material) != 3:
+        raise BackendError("anisotropic material: an AnisotropicMaterial or a tuple (table[n, 6, 6], material_of_cell or None, "
+                           "frames or None) is expected, got %s" % type(material).__name__)
+    table, index, frames = material
+    D = np.asarray(table, dtype=np.float64)
+    if D.ndim == 2:
+        D = D[None]
+    if D.ndim != 3 or D.shape[1:] != (6, 6) or D.shape[0] < 1:
+        raise BackendError("anisotropic material: the table must be an array [n, 6, 6], got shape %s" % (D.shape,))
+    if not np.array_equal(D, np.transpose(D, (0, 2, 1)), equal_nan=True):      # (entries that are not finite: the C call's check)
+        raise BackendError("anisotropic material: a 6x6 matrix of the table is not symmetric")
+    m = L.fs_aniso_material()
+    tri = np.ascontiguousarray(D[:, _ANISO_TRIU[0], _ANISO_TRIU[1]])
+    keep.append(tri)
+    m.n_materials = D.shape[0]
+    m.stiffness = L.p_f64(tri)
+    if index is not None:
+        idx = np.asarray(index)
+        if idx.ndim != 1 or idx.shape[0] != n_cells or not np.issubdtype(idx.dtype, np.integer):
+            raise BackendError("anisotropic material: material_of_cell must be an integer array [%d], got shape %s" % (n_cells, idx.shape))
+        idx = L.i32(idx)
+        keep.append(idx)
+        m.material_of_cell = L.p_i32(idx)
+    elif D.shape[0] not in (1, n_cells):
+        raise BackendError("anisotropic material: without material_of_cell the table holds 1 material or one per cell (%d), got %d"
+                           % (n_cells, D.shape[0]))
+    if frames is not None:
+        R = np.ascontiguousarray(frames, dtype=np.float64)
+        if R.shape != (n_cells, 3, 3) and R.shape != (n_cells, 9):
+            raise BackendError("anisotropic material: frames must be an array [%d, 3, 3], got shape %s" % (n_cells, R.shape))
+        keep.append(R)
+        m.frame = L.p_f64(R)
+    return m
+
+
+def _aniso_eigenstrain(eigenstrain, space, n_cells):
+    if eigenstrain is None:
+        return None
+    ne = 6 if space.ncomp == 3 else 4
+    e = np.ascontiguousarray(eigenstrain, dtype=np.float64)
+    if e.shape != (n_cells, ne):
+        raise BackendError("eigenstrain must be an array [%d, %d] of tensor components, got shape %s" % (n_cells, ne, e.shape))
+    return e
+
+
+def assemble_anisotropic_load(space, material, eigenstrain, b, add=True):
+    """b (+)= int (C : eps*) : grad v dx on a vector CG1 space (fs_assemble_anisotropic_load).  eigenstrain: [n_cells, 6] (xx, yy, zz,
+    xy, xz, yz) or [n_cells, 4] (xx, yy, zz, xy) in plane strain, tensor components in global axes, device cell order."""
+    keep = []
+    nc = space.mesh.info()[1]
+    m = _aniso_material(material, nc, keep)
+    e = _aniso_eigenstrain(eigenstrain, space, nc)
+    if e is None:
+        raise BackendError("assemble_anisotropic_load: an eigenstrain is required")
+    L.check(L.load().fs_assemble_anisotropic_load(space.h, C.byref(m), L.p_f64(e), b.h, 1 if add else 0), "fs_assemble_anisotropic_load")
+
+
+def anisotropic_stress(space, u, material, eigenstrain=None, cell_stress=False, p1_space=None, vm_rhs=None):
+    """sigma = C : (eps(u) - eps*) per cell on a vector CG1 space (fs_anisotropic_stress); u: DeviceVector of the space's dofs, or None.
+    cell_stress=True: returns the array [n_cells, 6] (or [n_cells, 4] in plane strain) in device cell order, else None.  p1_space and
+    vm_rhs (both or neither): vm_rhs becomes the right-hand side of the von Mises projection onto the scalar CG1 space."""
+    keep = []
+    nc = space.mesh.info()[1]
+    m = _aniso_material(material, nc, keep)
+    e = _aniso_eigenstrain(eigenstrain, space, nc)
+    if (p1_space is None) != (vm_rhs is None):
+        raise BackendError("anisotropic_stress: p1_space and vm_rhs go together")
+    if p1_space is not None:
+        _same_device_mesh(space, p1_space, "anisotropic_stress")
+    sig = np.empty((nc, 6 if space.ncomp == 3 else 4)) if cell_stress else None
+    L.check(L.load().fs_anisotropic_stress(space.h, u.h if u is not None else None, C.byref(m), L.p_f64(e), L.p_f64(sig),
+                                           p1_space.h if p1_space is not None else None, vm_rhs.h if vm_rhs is not None else None),
+            "fs_anisotropic_stress")
+    return sig
 
 
 def assemble_hyperelastic(space, u, lame, K=None, r=None, energy=False, add=False):

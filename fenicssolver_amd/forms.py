@@ -131,6 +131,7 @@ class ElasticityForm:
         self.thermal = None           # (coefficient E*alpha/(1-2nu): number or array [n_cells], T nodal array or float, T_ref)
         self.load_sign = -1.0         # reference adds the load terms to F => rhs = -loads (Appendix B-Q3)
         self.inertia = None           # (density: number or ('cell', array), acceleration dof array): rhs += rho M a (:216-220)
+        self.anisotropic = None       # AnisotropicElasticity: the operator is int eps(v) : C : eps(u) dx, mu / lmbda stay None
 
     def cellwise(self):
         return np.ndim(self.mu) > 0 or np.ndim(self.lmbda) > 0
@@ -144,7 +145,7 @@ class ElasticityForm:
                                   np.broadcast_to(np.asarray(self.lmbda, dtype=np.float64), (n,))], axis=1))
 
     def describe(self):
-        return {
+        d = {
             "type": "elasticity", "mu": _material(self.mu), "lambda": _material(self.lmbda),
             "body_force": None if self.body_force is None else tuple(float(x) for x in self.body_force),
             "tractions": [(t.marker_id, _plain(t.g), t.origin) if isinstance(t, FacetLoad) else ("nodal", len(t.dofs), t.origin)
@@ -152,6 +153,46 @@ class ElasticityForm:
             "thermal": None if self.thermal is None else (_material(self.thermal[0]), _plain(self.thermal[1]), self.thermal[2]),
             "load_sign": self.load_sign,
         }
+        if self.anisotropic is not None:      # (only then: the golden-form tests compare the dict of the isotropic forms)
+            d["anisotropic"] = self.anisotropic.describe()
+        return d
+
+
+class AnisotropicElasticity:
+    """The anisotropic material of an ElasticityForm, host cell order: ``table`` [n, 6, 6] in the library's tensor order (xx, yy, zz,
+    xy, xz, yz; engineering shears), ``index`` [n_cells] table rows (None: one material), ``frames`` [n_cells, 3, 3] rotations with
+    the material axes as columns (None: global axes), ``thermal``: None or (eps [n_cells, 6 or 4] = R alpha R^T per unit temperature
+    in the tensor storage, T nodal array or float, T_ref)."""
+
+    def __init__(self, table, index=None, frames=None, thermal=None):
+        self.table = np.ascontiguousarray(table, dtype=np.float64)
+        self.index = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        self.frames = None if frames is None else np.ascontiguousarray(frames, dtype=np.float64)
+        self.thermal = thermal
+
+    def material(self, loc=None):
+        """The argument of backend.DeviceMatrix.assemble_anisotropic, in device cell order: ``loc`` is the space's localizer (None:
+        the device numbers the cells as the host does; a mesh uploaded in locality order has one that permutes them).  The table
+        holds the distinct materials (index None: one of them everywhere) and needs no mapping."""
+        cells = (lambda a: a) if loc is None else loc.cells
+        return (self.table, None if self.index is None else cells(self.index), None if self.frames is None else cells(self.frames))
+
+    def eigenstrain(self, cells, loc=None):
+        """eps* [n_cells, 6 or 4] of the thermal load in device cell order; ``cells``: the host mesh's cell-vertex array (a nodal
+        temperature enters by its mean at the cell's vertices)."""
+        eps1, T, T_ref = self.thermal
+        dT = float(T) - T_ref if np.ndim(T) == 0 else np.asarray(T, dtype=np.float64)[np.asarray(cells, dtype=np.int64)].mean(axis=1) - T_ref
+        eps = eps1 * np.reshape(dT, (-1, 1))
+        return eps if loc is None else loc.cells(eps)
+
+    def digest(self):
+        import zlib
+        return tuple(None if a is None else (a.shape, zlib.crc32(a.tobytes())) for a in (self.table, self.index, self.frames))
+
+    def describe(self):
+        return {"materials": int(self.table.shape[0]), "table": _plain(self.table), "per_cell_index": self.index is not None,
+                "frames": self.frames is not None,
+                "thermal": None if self.thermal is None else (_plain(self.thermal[0]), _plain(self.thermal[1]), self.thermal[2])}
 
 
 class HyperelasticForm:

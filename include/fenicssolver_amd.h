@@ -965,6 +965,44 @@ typedef struct fs_buckling_stats {
 int fs_buckling_solve(fs_matrix_t K, fs_matrix_t KG, fs_amg_t precond, int64_t n_constrained, const int32_t* constrained,
                       const fs_buckling_opts* opts, double* factors, fs_vector_t* modes, fs_buckling_stats* stats);
 
+/* ---- anisotropic linear elasticity ----------------------------------------------------------------------------------------------
+ * No counterpart in the reference, whose to-do list names it ("anisotropy needs rank 4 tensor"; INTEGRATION.md, "differs from the
+ * reference").  Vector CG1 spaces on tetrahedra (3 components) or on triangles in plane strain (2 components); one rank; no DG.
+ * fs_bilinear_form is unchanged: the material has a struct of its own. */
+typedef struct fs_aniso_material {
+    int64_t n_materials;            /* >= 1 */
+    const double* stiffness;        /* [n_materials][21]: upper triangle, row-major, of the symmetric 6x6 D in the library's tensor
+                                     * order (xx, yy, zz, xy, xz, yz) acting on (e_xx, e_yy, e_zz, 2e_xy, 2e_xz, 2e_yz): D_IJ = C_ikjl */
+    const int32_t* material_of_cell;/* [n_cells], device cell order; NULL: every cell is material 0 - or, when n_materials == n_cells,
+                                     * the identity map: cell c has material c (a fully per-cell C).  Any other n_materials with a
+                                     * NULL index is refused. */
+    const double* frame;            /* [n_cells][9] row-major rotation R (columns = material axes in global coordinates),
+                                     * C_global = (R x R x R x R) C_material; NULL: identity everywhere */
+} fs_aniso_material;
+/* All arrays are host arrays.  Checked before anything is enqueued (FS_ERR_INVALID): finite entries, the range of material_of_cell,
+ * n_materials against the mesh when the index is NULL; in plane strain also that every D is monoclinic about z (D[I][xz] = D[I][yz]
+ * = 0 for I in xx, yy, zz, xy) and every frame a rotation about z.  Symmetry is in the storage; positive definiteness and the
+ * orthogonality of the frames are the caller's to check (LinearElasticitySolver does).  The kernels never rotate C: they rotate the
+ * gradients into the material axes and the block back, K_ab = R (V ghat_a . C . ghat_b) R^T with ghat = R^T g. */
+
+/* A (+)= int eps(v) : C : eps(u) dx + mass u.v; mass: NULL, FS_COEF_NONE, FS_COEF_CONST or FS_COEF_CELL, with the mass arithmetic of
+ * fs_assemble_matrix.  One thread per stored block over its sources in ascending order, no atomics: two calls give the same bits, and
+ * on a box mesh translated stencils give equal rows (the snapped geometry of the isotropic kernel).  Enqueues and does not wait, as
+ * fs_assemble_matrix. */
+int fs_assemble_anisotropic(fs_matrix_t A, const fs_aniso_material* mat, const fs_coef* mass, int add);
+
+/* sigma = C : (eps(u) - eps*) per cell in device cell order: 6 doubles (xx, yy, zz, xy, xz, yz) on tetrahedra, 4 (xx, yy, zz, xy) in
+ * plane strain.  eigenstrain: [n_cells][6 or 4] tensor components (not engineering shears) in global axes, or NULL; u (>= n_dofs_local
+ * entries) may be NULL: the stress of -eps* alone.  cell_stress_out (may be NULL): the stress, downloaded.  vm_rhs with p1_space (both
+ * or neither): the right-hand side int sqrt(3/2 s:s) phi_a dx of the von Mises L2 projection onto the scalar CG1 space of the mesh,
+ * gathered per vertex in ascending cell order as fs_assemble_von_mises does (2-D: its deviator convention, s = sigma_2x2 - tr / 3 I). */
+int fs_anisotropic_stress(fs_space_t space, fs_vector_t u, const fs_aniso_material* mat, const double* eigenstrain,
+                          double* cell_stress_out, fs_space_t p1_space, fs_vector_t vm_rhs);
+
+/* b (+)= int (C : eps*) : grad v dx (>= n_dofs_owned entries): the per-cell stress kernel of fs_anisotropic_stress into a device
+ * array, then the stored-stress force gather the inelastic solvers use. */
+int fs_assemble_anisotropic_load(fs_space_t space, const fs_aniso_material* mat, const double* eigenstrain, fs_vector_t b, int add);
+
 /* ---- frictionless contact and sliding supports --------------------------------------------------------------------------------
  * No counterpart in the reference, which lists the boundary condition as not implemented ("differs from the
  * reference").  Vector CG1 spaces on tetrahedra (3 components) or on triangles in plane strain (2 components); one rank.
