@@ -504,7 +504,7 @@ class SolverBase():
         hierarchy, solves the gathered right-hand side and keeps its own entries - the iteration count of one GPU at any
         number of parts, no communication inside the solve, the speed of one GPU (not more: the preconditioner is not
         distributed; 'amg_decomposition': 'schwarz' selects the rank-local hierarchies).  The pressure Laplacian of the
-        Navier-Stokes Schur complement is treated the same way (fs_saddle.hip)."""
+        Navier-Stokes Schur complement is treated the same way (sd_precond, fs_saddle_solve.inc)."""
         from . import backend, parallel
         if getattr(self, '_amg_distributed_off', False):
             A_local = None                  # a distribution fault was seen on this solver earlier: replicated from then on
@@ -1355,7 +1355,7 @@ class SolverBase():
                 cell_g2l = np.full(self.mesh.num_cells(), -1, dtype=np.int64)
                 cell_g2l[loc.part.cell_gids] = np.arange(len(loc.part.cell_gids))
             # several GPUs: the pressure space is small, so every rank holds the hierarchy of the GLOBAL pressure
-            # Laplacian (assembled on the global mesh) and the Schur-complement solve is replicated (fs_saddle.hip)
+            # Laplacian (assembled on the global mesh) and the Schur-complement solve is replicated (sd_precond, fs_saddle_solve.inc)
             if loc is not None:
                 if getattr(self.mesh, '_slab', None) is not None:      # distributed box: the device generates the whole box
                     nx_, ny_, nz_, p0_, p1_ = self.mesh._box

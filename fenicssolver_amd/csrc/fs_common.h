@@ -61,12 +61,12 @@ fs_runtime& fs_rt();
 // Serial numbers of spaces and matrices: heap and pool addresses are recycled after a destroy, so anything cached per
 // operator (the captured CG batch of fs_krylov.hip) is keyed on these, never on addresses alone.
 uint64_t fs_next_serial();
-// The solver workspaces (fs_krylov.hip, fs_saddle.hip) and the one compute stream belong to the process: solves are serialised
+// The solver workspaces (fs_krylov_solve.inc, fs_saddle_solve.inc) and the one compute stream belong to the process: solves are serialised
 // by this lock, so that concurrent calls from several host threads are slow rather than wrong.
 #include <mutex>
 std::recursive_mutex& fs_solve_mutex();
 struct fs_matrix_s;
-void fs_ns_reset_dummy_rows(fs_matrix_s* J, hipStream_t s);   // fs_saddle.hip: unit diagonal on the dummy pressure slots
+void fs_ns_reset_dummy_rows(fs_matrix_s* J, hipStream_t s);   // fs_saddle.hip (assembly): unit diagonal on the dummy pressure slots
 int fs_require_init();
 
 // ---- device memory -------------------------------------------------------------
@@ -468,5 +468,5 @@ static inline bool fs_is_dg(const fs_space_s* sp) { return sp && sp->family == F
     } while (0)
 #define FS_REFUSE_DG(A, name) FS_REFUSE_DG_SPACE((A) ? (A)->space : nullptr, name)
 
-// fs_saddle.hip: the law a Taylor-Hood space carries, else kind 1 from (p_ref, exponent) > 0, else Newtonian
+// fs_saddle.hip (assembly): the law a Taylor-Hood space carries, else kind 1 from (p_ref, exponent) > 0, else Newtonian
 fs_visc_dev fs_space_viscosity(const fs_space_s* sp, double legacy_pref, double legacy_exp);

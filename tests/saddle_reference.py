@@ -1,4 +1,4 @@
-"""Host replay of the two block preconditioners of fs_saddle_solve (fs_saddle.hip: sd_precond and sd_precond_ld, step for step), of
+"""Host replay of the two block preconditioners of fs_saddle_solve (fs_saddle_solve.inc: sd_precond and sd_precond_ld, step for step), of
 its eigenvalue estimate, of the small dense algebra behind its Arnoldi state and of the iteration itself (host_fgmres, plain
 float64), with a componentwise forward-error bound carried next to every vector of the preconditioners.  Shared by test_saddle_reference_host.py (the replays against explicit dense extended-precision operators on
 the CPU) and test_gpu_saddle_replay.py (the device against the replays).  Plain numpy / scipy, no GPU.

@@ -1,4 +1,4 @@
-"""fs_saddle_solve (fs_saddle.hip from k_sd_diag down: restarted FGMRES with the Arnoldi state on the device, the Cahouet-Chabard
+"""fs_saddle_solve (fs_saddle_solve.inc, part of fs_saddle.hip: restarted FGMRES with the Arnoldi state on the device, the Cahouet-Chabard
 and the block-upper preconditioner) held to a host replay of its last cycle.  The solver recomputes the true residual at every restart
 and stops on it, so a wrong preconditioner or a wrong Hessenberg column only costs iterations and every test that looks at the
 solution, `converged` and an iteration ceiling stays green.  Here every case is ONE saddle_solve / large_deformation_solve call with
@@ -64,7 +64,7 @@ least eps lmax (measured on the CPU: 0 to 1.4e-16 relative, so the tolerance is 
 # Converging runs (full GMRES on the edge-2 cube): steady1 seed 11 stops after 75 iterations at rtol 4.49e-9 (a factor 2.14 on both
 # sides), steady3 seed 11 after 51 at 3.61e-7 (2.43), transient seed 24 after 53 at 2.47e-11 (2.04; seeds 11 to 23 offer at most
 # 1.95); device and host agree in the count and in the residual to the digits printed.
-# Three deliberate mistakes in scratch builds of fs_saddle.hip, each against this file and against tests/test_gpu_navier_stokes.py,
+# Three deliberate mistakes in scratch builds of fs_saddle.hip (the solve is now fs_saddle_solve.inc), each against this file and against tests/test_gpu_navier_stokes.py,
 # test_gpu_navier_stokes_2d.py and test_gpu_large_deformation.py (55 tests):
 #   rho_new * rho_new for rho_new * rho_c in the Mp     here: (a) in all 15 Taylor-Hood cases, 63 / 124 / 29 pressure rows outside the bound
 #   Chebyshev of sd_precond                             (err / e_z 5.6e6 to 2.3e11); the 55 existing tests: all pass
