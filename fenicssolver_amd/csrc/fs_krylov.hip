@@ -121,6 +121,7 @@ static int g_cg_batch = 32;
 static int g_cg_sub = 16, g_cg_ahead = 6, g_cg_mirror = 1;      // (tools/probes/cg_tail_probe.py: 6.80 -> 6.44 ms per solve at 1 M rows)
 static int g_cg_fuse_sums = 1;
 static int g_cg_graph = -1;      // -1: automatic (graphs, unless a profiler's tool library is in the process)
+#define FS_MAX_UPDATE_BLOCKS 2048    // option "update_blocks": every value measured below; what the dot partials of an update kernel have room for, see fs_set_option
 static int g_update_blocks = 1024;  // (round 3, with the 16 us row-dictionary product at 1 M rows: 256 / 512 / 768 / 1024 / 2048 workgroups: 10.59 / 10.42 / 10.20 / 10.12 / 11.22 ms per step; 10 M rows: flat)
 static int g_cg_pair = getenv("FS_CG_PAIR") ? (atoi(getenv("FS_CG_PAIR")) != 0) : 1;      // option "cg_pair": the one-launch iteration updates p and x every second launch (k_dict_cg_iter, MODE); 0: in every launch
 // option "cg_guard": the LIGHT / PAIR launches run on work vectors with guard bands of zeros and without the edge-item path (k_dict_cg_iter,
@@ -168,7 +169,10 @@ extern "C" int fs_set_option(const char* name, double value) {
     } else if (!strcmp(name, "cg_poison_p")) {
         g_cg_poison_p = value != 0.0;
     } else if (!strcmp(name, "update_blocks")) {
-        FS_REQUIRE(value >= 1 && value <= 65535, "update_blocks must be in [1,65535]");
+        // (every workgroup of the grid leaves dot partials: the pipelined update 2 x 3 per workgroup in krylov_ws::partials, BiCGStab 2 in
+        // partials2, each 4 (FS_MAX_PARTIAL_BLOCKS + 8) doubles - room for 2736 and 8208 workgroups)
+        static_assert(2 * 3 * FS_MAX_UPDATE_BLOCKS <= 4 * (FS_MAX_PARTIAL_BLOCKS + 8), "the partials of the pipelined update do not fit");
+        FS_REQUIRE(value >= 1 && value <= FS_MAX_UPDATE_BLOCKS, "update_blocks must be in [1,%d]", FS_MAX_UPDATE_BLOCKS);
         g_update_blocks = (int)value;
     } else if (!strcmp(name, "box_iter")) {
         g_box_iter = value != 0.0;

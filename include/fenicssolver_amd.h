@@ -87,7 +87,7 @@ const char* fs_version(void);
  * through pinned host memory and the host keeps "cg_ahead" to "cg_ahead" + "cg_sub" launches enqueued, instead of batches of
  * "cg_batch" with the status word copied back behind each),
  * "cg_fuse_sums" (0/1: sum the dot partials inside the update kernel on one GPU),
- * "update_blocks" (grid of the fused vector-update kernel), "cg_graph" (-1 / 0 / 1: CG batches as hipGraphs by size /
+ * "update_blocks" (grid of the fused vector-update kernel, 1 to 2048: every workgroup leaves dot partials in a fixed buffer), "cg_graph" (-1 / 0 / 1: CG batches as hipGraphs by size /
  * never / always), "cg_fused" (-1 / 0 / 1: ONE launch per CG iteration on row-dictionary operators - up to 3 M rows /
  * never / wherever it applies; fs_krylov_stats.fused_iteration), "cg_pair" (1 / 0, default 1; FS_CG_PAIR in the environment: that launch
  * updates p and x every second iteration, two steps in one pass, instead of in every launch - the same bits; fs_last_iteration_form),

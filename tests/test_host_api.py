@@ -160,6 +160,25 @@ def test_every_tunable_is_documented_in_the_header():
     assert len(names) >= 15 and not [n for n in names if '"%s"' % n not in header]
 
 
+def test_update_blocks_stops_at_what_the_dot_partials_hold():
+    """Every workgroup of an update kernel leaves dot partials - the pipelined update 2 x 3, BiCGStab 2 - in buffers of
+    4 (FS_MAX_PARTIAL_BLOCKS + 8) doubles: room for 2736 and 8208 workgroups.  The option is refused beyond 2048 (it took 65535)."""
+    import re
+    from fenicssolver_amd import backend
+    src = open(os.path.join(ROOT, "fenicssolver_amd", "csrc", "fs_common.h")).read()
+    room = 4 * (int(re.search(r"#define FS_MAX_PARTIAL_BLOCKS (\d+)", src).group(1)) + 8)
+    assert room // 6 == 2736 and room // 2 == 8208
+    try:
+        for bad in (0, -3, 2049, 2737, 8209, 65535):
+            with pytest.raises(backend.BackendError, match=r"update_blocks must be in \[1,2048\]"):
+                backend.set_option("update_blocks", bad)
+        for ok in (1, 2048):
+            assert 6 * ok <= room
+            backend.set_option("update_blocks", ok)
+    finally:
+        backend.set_option("update_blocks", 1024)
+
+
 def test_product_fails_loudly_without_gpu(data_dir):
     from fenicssolver_amd import backend
     if backend.device_count() > 0:
