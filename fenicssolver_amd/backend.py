@@ -1210,6 +1210,24 @@ class AMG(_Handle):
         return {"n_nodes": nn.value, "block_size": bs.value, "nnz_blocks": nz.value, "p_nnz_blocks": pn.value,
                 "p_block_cols": pc.value, "lambda_max": lm.value}
 
+    def level_aggregates(self, level):
+        """The aggregate (node of level+1) of every node of a level with a prolongator, int32, -1 = in none."""
+        out = np.empty(self.level_info(level)["n_nodes"], dtype=np.int32)
+        L.check(L.load().fs_amg_level_get(self.h, int(level), 4, None, L.p_i32(out), None), "fs_amg_level_get")
+        return out
+
+    def level_blocks(self, level, which="A"):
+        """The raw block CSR of a level operator ('A') or of the prolongator from level+1 ('P'): (rowptr, col, val[nnz, br, bc]),
+        the structural blocks in the library's order, zeros included."""
+        li = self.level_info(level)
+        nnz, bc = (li["nnz_blocks"], li["block_size"]) if which == "A" else (li["p_nnz_blocks"], li["p_block_cols"])
+        rp = np.empty(li["n_nodes"] + 1, dtype=np.int32)
+        ci = np.empty(nnz, dtype=np.int32)
+        va = np.empty(nnz * li["block_size"] * bc)
+        L.check(L.load().fs_amg_level_get(self.h, int(level), 0 if which == "A" else 1, L.p_i32(rp), L.p_i32(ci),
+                                          L.p_f64(va)), "fs_amg_level_get")
+        return rp, ci, va.reshape(nnz, li["block_size"], bc)
+
     def level_matrix(self, level, which="A"):
         """scipy BSR copy of a level operator ('A') or of the prolongator from level+1 ('P')."""
         import scipy.sparse as sp

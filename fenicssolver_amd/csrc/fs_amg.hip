@@ -45,6 +45,7 @@ struct amg_level {
     bcsr A;
     bcsr P;               // nn x n_agg, blocks bs x nb
     int64_t n_agg = 0;
+    dbuf<int32_t> agg;    // [nn] aggregate of every node, -1 = in none (no strong coupling); inspection hook (fs_amg_level_get, which = 4)
     dbuf<int32_t> pt_ptr, pt_entry, pt_row;   // transpose index of P (entries sorted by column)
     dbuf<double> rt_val;  // R = P^T blocks [nb][bs] in pt order: the restriction streams them contiguously
     dbuf<float> rt_val32; // rounded to fp32 (the SAME rounded numbers as P.val32: R stays the exact transpose of P)
@@ -233,36 +234,8 @@ __device__ __forceinline__ void fs_atomic_max_positive(unsigned long long* word,
     if ((threadIdx.x & 63) == 0 && bits > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, bits);
 }
 
-// per node: 1/diag, identity-row flags, Gershgorin ratio (max over the block row, atomically maxed), block norm
-__global__ void k_amg_diag(int64_t nn, int bs, const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                           const double* __restrict__ val, double* __restrict__ dinv, uint8_t* __restrict__ ident,
-                           double* __restrict__ dnorm, unsigned long long* __restrict__ gersh_bits) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    double gmax = 0.0;
-    for (; i < nn; i += stride) {
-        double dn = 0.0;
-        for (int r = 0; r < bs; ++r) {
-            double d = 0.0, off = 0.0;
-            for (int32_t e = rp[i]; e < rp[i + 1]; ++e) {
-                const double* blk = val + ((int64_t)e * bs + r) * bs;
-                const bool diag = ci[e] == (int32_t)i;
-                for (int c = 0; c < bs; ++c) {
-                    if (diag && c == r) d = blk[c]; else off += fabs(blk[c]);
-                    if (diag) dn += blk[c] * blk[c];
-                }
-            }
-            dinv[i * bs + r] = d != 0.0 ? 1.0 / d : 1.0;
-            ident[i * bs + r] = off == 0.0 ? 1 : 0;
-            if (d != 0.0) gmax = fmax(gmax, (fabs(d) + off) / fabs(d));
-        }
-        dnorm[i] = sqrt(dn);
-    }
-    // positive doubles order like their bit patterns
-    fs_atomic_max_positive(gersh_bits, gmax);
-}
-
-// the same with 16 lanes per node striding over the values of its block row (contiguous in memory); bs <= 6
+// per node: 1/diag, identity-row flags, Gershgorin ratio (max over the block row, atomically maxed), block norm:
+// 16 lanes per node striding over the values of its block row (contiguous in memory); bs <= 6 (1, 3 or 6 on every level)
 __global__ void __launch_bounds__(FS_BLOCK) k_amg_diag_grp(int64_t nn, int bs, const int32_t* __restrict__ rp,
                                                            const int32_t* __restrict__ ci, const double* __restrict__ val,
                                                            double* __restrict__ dinv, uint8_t* __restrict__ ident,
@@ -1506,10 +1479,8 @@ static int coarsen(fs_amg_s* M, amg_level* L, double theta, int eig_steps, amg_l
     FS_CHECK(gbits.zero(s));
     FS_CHECK(L->dinv.alloc(L->n));
     FS_CHECK(L->ident.alloc(L->n));
-    if (bs <= 6)
-        hipLaunchKernelGGL(k_amg_diag_grp, dim3(fs_grid_for(nn * 16, FS_BLOCK, 65536)), dim3(FS_BLOCK), 0, s, nn, bs, L->A.rowptr.p, L->A.col.p, L->A.val.p, L->dinv.p, L->ident.p, dnorm.p, gbits.p);
-    else
-        hipLaunchKernelGGL(k_amg_diag, dim3(g), dim3(FS_BLOCK), 0, s, nn, bs, L->A.rowptr.p, L->A.col.p, L->A.val.p, L->dinv.p, L->ident.p, dnorm.p, gbits.p);
+    FS_REQUIRE(bs <= 6, "AMG setup: block size %d (the diagonal kernel keeps six rows per lane)", bs);
+    hipLaunchKernelGGL(k_amg_diag_grp, dim3(fs_grid_for(nn * 16, FS_BLOCK, 65536)), dim3(FS_BLOCK), 0, s, nn, bs, L->A.rowptr.p, L->A.col.p, L->A.val.p, L->dinv.p, L->ident.p, dnorm.p, gbits.p);
     FS_KERNEL_CHECK();
     unsigned long long hb = 0;
     FS_HIP(hipMemcpyAsync(&hb, gbits.p, 8, hipMemcpyDeviceToHost, s));
@@ -1631,6 +1602,7 @@ static int coarsen(fs_amg_s* M, amg_level* L, double theta, int eig_steps, amg_l
     FS_KERNEL_CHECK();
     FS_CHECK(level_operator_to_f32(C, s));
     FS_HIP(hipStreamSynchronize(s));
+    L->agg.swap(agg);
     *out = C;
     return FS_OK;
 }
@@ -1934,6 +1906,12 @@ extern "C" int fs_amg_level_get(fs_amg_t M, int level, int which, int32_t* rowpt
         }
         return val ? M->cinv.download(val, M->nc * M->nc, s) : FS_OK;
     }
+    if (which == 4) {       // the aggregate of every node of a level with a prolongator, -1 = in none
+        FS_REQUIRE(col, "fs_amg_level_get: null pointer");
+        FS_REQUIRE(L->P.nnz > 0 && L->agg.p, "fs_amg_level_get: level %d has no prolongator, hence no aggregates", level);
+        return L->agg.download(col, L->nn, s);
+    }
+    FS_REQUIRE(which == 0 || which == 1, "fs_amg_level_get: which = %d (0 to 4)", which);
     FS_REQUIRE(X.nnz > 0, "fs_amg_level_get: level %d has no such operator", level);
     if (rowptr) FS_CHECK(X.rowptr.download(rowptr, X.nrows + 1, s));
     if (col) FS_CHECK(X.col.download(col, X.nnz, s));

@@ -866,7 +866,9 @@ int fs_amg_level_info(fs_amg_t amg, int level, int64_t* n_nodes, int* block_size
  * that the V-cycle applies there ([n_dofs][n_dofs] row-major, val only, level = the last one;
  * FS_ERR_UNSUPPORTED when the hierarchy has none: a single level, or more than 2500 rows on the
  * coarsest, where the cycle runs Chebyshev sweeps instead; val == NULL only asks whether there is
- * one).  Test/inspection hook. */
+ * one), 4 = the aggregate of every node of a level with a prolongator (col only: n_nodes int32, the
+ * block column of the tentative prolongator, -1 = in no aggregate because the node has no strong
+ * coupling; an error on a level without a prolongator).  Test/inspection hook. */
 int fs_amg_level_get(fs_amg_t amg, int level, int which, int32_t* rowptr, int32_t* col, double* val);
 /* z = M r: one V-cycle from a zero guess (PCApply). */
 int fs_amg_apply(fs_amg_t amg, fs_vector_t r, fs_vector_t z);

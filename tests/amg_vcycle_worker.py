@@ -216,22 +216,23 @@ def run(name, make):
         h.close()
 
 
-for name, make in CASES.items():
-    if ONLY is None or name in ONLY:
-        try:
-            run(name, make)
-        except Exception:
-            if not MEASURE:
-                raise
-            import traceback
-            say("case failed", name, traceback.format_exc())
-if ONLY is None and NODE_WAVES and ROW_GROUPS and FP32 and not any(k in os.environ for k in ("FS_AMG_SPGEMM_BLOCK", "FS_AMG_SERIAL_QR")):
-    # the edge of the cube is the smallest whose level 1 has more than 2500 rows: one less, and the dense inverse is back
-    co, ce = fo.box_mesh((0, 0, 0), (1, 1, 1), CUBE_EDGE - 1, CUBE_EDGE - 1, CUBE_EDGE - 1)
-    V, A, K = scalar_p1(co, ce, 2, 2)
-    amg = B.AMG(A, max_levels=2)
-    say("cube", CUBE_EDGE - 1, "level 1 rows", amg.level_info(1)["n_nodes"])
-    assert amg.coarse_inverse() is not None and amg.level_info(1)["n_nodes"] <= 2500
-np.savez(sys.argv[1], **out)
-say("seconds", round(time.time() - T0, 1))
-say("ok")
+if __name__ == "__main__":          # (amg_setup_worker.py imports the builders above)
+    for name, make in CASES.items():
+        if ONLY is None or name in ONLY:
+            try:
+                run(name, make)
+            except Exception:
+                if not MEASURE:
+                    raise
+                import traceback
+                say("case failed", name, traceback.format_exc())
+    if ONLY is None and NODE_WAVES and ROW_GROUPS and FP32 and not any(k in os.environ for k in ("FS_AMG_SPGEMM_BLOCK", "FS_AMG_SERIAL_QR")):
+        # the edge of the cube is the smallest whose level 1 has more than 2500 rows: one less, and the dense inverse is back
+        co, ce = fo.box_mesh((0, 0, 0), (1, 1, 1), CUBE_EDGE - 1, CUBE_EDGE - 1, CUBE_EDGE - 1)
+        V, A, K = scalar_p1(co, ce, 2, 2)
+        amg = B.AMG(A, max_levels=2)
+        say("cube", CUBE_EDGE - 1, "level 1 rows", amg.level_info(1)["n_nodes"])
+        assert amg.coarse_inverse() is not None and amg.level_info(1)["n_nodes"] <= 2500
+    np.savez(sys.argv[1], **out)
+    say("seconds", round(time.time() - T0, 1))
+    say("ok")
