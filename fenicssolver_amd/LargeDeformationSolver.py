@@ -34,6 +34,7 @@ import numpy as np
 
 from .fem import Constant, Function, is_constant_value
 from .SolverBase import SolverError, write_vtu
+from .LinearElasticitySolver import LinearElasticitySolver
 from .NonlinearElasticitySolver import NonlinearElasticitySolver
 from .mixed import LargeDeformationSpace, split_large_deformation
 
@@ -53,6 +54,7 @@ class LargeDeformationSolver(NonlinearElasticitySolver):
     KRYLOV_RTOL = 1e-10
     KRYLOV_MAX_IT = 600
     KRYLOV_STALL_RTOL = 1e-8
+    von_Mises = LinearElasticitySolver.von_Mises      # as before: the Cauchy-stress results of the parent read a plain displacement space
 
     def __init__(self, case_settings):
         NonlinearElasticitySolver.__init__(self, case_settings)

@@ -1012,9 +1012,12 @@ class SolverBase():
                       '(a per-step sequence or a callable of time - constant values repeat the full load at every step)')
         gdofs, gvals = self._bc_arrays(bcs)
         dofs = gdofs if loc is None else loc.dofs(gdofs, gvals)[0]
-        lame = F.lame_spec()
+        model, lame, params = F.model_spec()             # the energy and its material: Lame parameters or a parameter table
         if F.cellwise() and loc is not None:
-            lame = ('cell', loc.cells(lame[1]))
+            if params is None:
+                lame = ('cell', loc.cells(lame[1]))
+            else:
+                params = ('cell', loc.cells(params[1]))
         f_ext = self._hyperelastic_external_loads(F, V, loc)
         K = backend.DeviceMatrix(V)
         r = backend.DeviceVector(V.n_owned)
@@ -1025,7 +1028,7 @@ class SolverBase():
             iterate); (info, ||r|| with the Dirichlet rows zeroed) - None for a state with an inverted cell.  K and r then belong to
             the last state evaluated: the tangent of a rejected trial is overwritten by the next one."""
             ud.set(to_dev(xh))
-            info = backend.assemble_hyperelastic(V, ud, lame, K=K, r=r)
+            info = backend.assemble_hyperelastic(V, ud, lame, K=K, r=r, model=model, params=params)
             if info['n_inverted']:
                 return info, None
             r.axpy(-1.0, f_ext)

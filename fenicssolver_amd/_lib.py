@@ -19,7 +19,8 @@ FS_OK = 0
 FS_ERR_UNSUPPORTED, FS_ERR_COMM, FS_ERR_NUMERIC, FS_ERR_P2P_TIMEOUT = -4, -5, -6, -7      # include/fenicssolver_amd.h
 FS_COEF_NONE, FS_COEF_CONST, FS_COEF_CELL, FS_COEF_TENSOR, FS_COEF_NODAL, FS_COEF_CELL_ROW, FS_COEF_CELL_TENSOR, FS_COEF_CELL_QP = 0, 1, 2, 3, 4, 5, 6, 7
 FS_COEF_CELL_LAME = 8
-FS_HYPER_NEO_HOOKEAN = 0
+FS_HYPER_NEO_HOOKEAN, FS_HYPER_ST_VENANT_KIRCHHOFF, FS_HYPER_MOONEY_RIVLIN, FS_HYPER_YEOH = 0, 1, 2, 3
+FS_COEF_CELL_HYPER = 11
 FS_HYPER_TANGENT, FS_HYPER_FORCE, FS_HYPER_ENERGY = 1, 2, 4
 FS_COEF_CELL_PLASTIC = 9
 FS_PLASTIC_TANGENT, FS_PLASTIC_FORCE = 1, 2
@@ -65,7 +66,8 @@ class fs_aniso_material(C.Structure):
 
 
 class fs_hyper_form(C.Structure):
-    _fields_ = [("model", C.c_int), ("mu", C.c_double), ("lambda_", C.c_double), ("lame", fs_coef), ("add", C.c_int)]
+    _fields_ = [("model", C.c_int), ("mu", C.c_double), ("lambda_", C.c_double), ("lame", fs_coef), ("add", C.c_int),
+                ("params", C.c_double * 4), ("cell_params", fs_coef)]
 
 
 class fs_hyper_info(C.Structure):
@@ -281,6 +283,7 @@ SIGNATURES = {
     "fs_assemble_dg_transport": (C.c_int, [_H, _H, C.POINTER(fs_dg_form)]),
     "fs_assemble_dg_projection": (C.c_int, [_H, _H, _H, _H]),
     "fs_assemble_hyperelastic": (C.c_int, [_H, _H, _H, _H, C.POINTER(fs_hyper_form), C.c_int, C.POINTER(fs_hyper_info)]),
+    "fs_hyper_stress": (C.c_int, [_H, _H, C.POINTER(fs_hyper_form), c_f64p, C.POINTER(fs_hyper_info)]),
     "fs_plastic_state_create": (C.c_int, [_H, C.POINTER(_H)]),
     "fs_plastic_state_destroy": (C.c_int, [_H]),
     "fs_plastic_state_reset": (C.c_int, [_H]),

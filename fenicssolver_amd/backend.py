@@ -704,26 +704,76 @@ def anisotropic_stress(space, u, material, eigenstrain=None, cell_stress=False, 
     return sig
 
 
-def assemble_hyperelastic(space, u, lame, K=None, r=None, energy=False, add=False):
-    """Neo-Hookean tangent K, internal force r and energy at the displacement u (DeviceVector of the space's dofs) on a vector CG1
-    space (fs_assemble_hyperelastic).  lame: (mu, lambda) numbers or ('cell', array[n_cells, 2]) in device cell order.  K / r: the
-    DeviceMatrix / DeviceVector to fill (None: not computed).  Returns {'energy', 'n_inverted', 'first_inverted_cell'}; the
-    energy is computed only with energy=True (0.0 otherwise)."""
-    keep = []
+HYPER_MODELS = {"neo_hookean": L.FS_HYPER_NEO_HOOKEAN, "st_venant_kirchhoff": L.FS_HYPER_ST_VENANT_KIRCHHOFF,
+                "mooney_rivlin": L.FS_HYPER_MOONEY_RIVLIN, "yeoh": L.FS_HYPER_YEOH}
+_HYPER_PARAMS = {"mooney_rivlin": 3, "yeoh": 4}           # numbers in the parameter row: (c10, c01, kappa), (c10, c20, c30, kappa)
+
+
+def _hyper_form(who, space, lame, model, params, add, keep):
+    """The fs_hyper_form of a model: neo_hookean / st_venant_kirchhoff read `lame`, mooney_rivlin / yeoh read `params`."""
+    if model not in HYPER_MODELS:
+        raise BackendError("%s: unknown energy model %r (one of %s)" % (who, model, ", ".join(sorted(HYPER_MODELS))))
     f = L.fs_hyper_form()
-    f.model = L.FS_HYPER_NEO_HOOKEAN
-    if _is_cell_lame(lame):
+    f.model = HYPER_MODELS[model]
+    f.add = 1 if add else 0
+    nc = space.mesh.info()[1]
+    if model in _HYPER_PARAMS:
+        n = _HYPER_PARAMS[model]
+        if params is None:
+            raise BackendError("%s: the %s energy needs params (%d numbers, or ('cell', array[n_cells, %d]))" % (who, model, n, n))
+        if _is_cell_lame(params):
+            if params[0] != "cell":
+                raise BackendError("%s: params are numbers or ('cell', array), got kind %r" % (who, params[0]))
+            a = np.asarray(params[1], dtype=np.float64)
+            if a.ndim != 2 or a.shape[0] != nc or a.shape[1] not in (n, 4):
+                raise BackendError("%s: per-cell %s parameters must be an array [%d, %d], got shape %s" % (who, model, nc, n, a.shape))
+            rows = np.zeros((nc, 4))
+            rows[:, :n] = a[:, :n]
+            keep.append(rows)
+            f.cell_params.mode = L.FS_COEF_CELL_HYPER
+            f.cell_params.data = L.p_f64(rows)
+        else:
+            vals = [float(x) for x in params]
+            if len(vals) not in (n, 4):
+                raise BackendError("%s: the %s energy takes %d parameters, got %d" % (who, model, n, len(vals)))
+            for k in range(n):
+                f.params[k] = vals[k]
+    elif lame is None:
+        raise BackendError("%s: the %s energy needs the Lame parameters" % (who, model))
+    elif _is_cell_lame(lame):
         f.lame.mode = L.FS_COEF_CELL_LAME
-        f.lame.data = L.p_f64(_lame_cells(lame, keep, space.mesh.info()[1]))
+        f.lame.data = L.p_f64(_lame_cells(lame, keep, nc))
     else:
         f.mu, f.lambda_ = float(lame[0]), float(lame[1])
-    f.add = 1 if add else 0
+    return f
+
+
+def assemble_hyperelastic(space, u, lame, K=None, r=None, energy=False, add=False, model='neo_hookean', params=None):
+    """Tangent K, internal force r and energy of a hyperelastic material at the displacement u (DeviceVector of the space's dofs) on a
+    vector CG1 space (fs_assemble_hyperelastic).  model: 'neo_hookean' (default) or 'st_venant_kirchhoff' with lame = (mu, lambda)
+    numbers or ('cell', array[n_cells, 2]); 'mooney_rivlin' with params = (c10, c01, kappa) or 'yeoh' with params = (c10, c20, c30,
+    kappa), numbers or ('cell', array[n_cells, 3 or 4]) - lame is not read then.  Per-cell arrays are in device cell order.  K / r:
+    the DeviceMatrix / DeviceVector to fill (None: not computed).  Returns {'energy', 'n_inverted', 'first_inverted_cell'}; the
+    energy is computed only with energy=True (0.0 otherwise)."""
+    keep = []
+    f = _hyper_form("assemble_hyperelastic", space, lame, model, params, add, keep)
     what = (L.FS_HYPER_TANGENT if K is not None else 0) | (L.FS_HYPER_FORCE if r is not None else 0) | (L.FS_HYPER_ENERGY if energy else 0)
     info = L.fs_hyper_info()
     L.check(L.load().fs_assemble_hyperelastic(space.h, K.h if K is not None else None, r.h if r is not None else None, u.h,
                                               C.byref(f), int(what), C.byref(info)), "fs_assemble_hyperelastic")
     return {"energy": info.energy if energy else 0.0, "n_inverted": int(info.n_inverted),
             "first_inverted_cell": int(info.first_inverted_cell)}
+
+
+def hyperelastic_stress(space, u, lame, model='neo_hookean', params=None):
+    """Cauchy stress sigma = P F^T / J per cell at the displacement u (fs_hyper_stress), for every model of assemble_hyperelastic with
+    the same lame / params: array [n_cells, 6] (xx, yy, zz, xy, xz, yz), in plane strain [n_cells, 4] (xx, yy, zz, xy), device cell
+    order.  A state with an inverted cell raises BackendError naming the first one."""
+    keep = []
+    f = _hyper_form("hyperelastic_stress", space, lame, model, params, False, keep)
+    sig = np.empty((space.mesh.info()[1], 6 if space.ncomp == 3 else 4))
+    L.check(L.load().fs_hyper_stress(space.h, u.h, C.byref(f), L.p_f64(sig), None), "fs_hyper_stress")
+    return sig
 
 
 class _CellHistory(_Handle):

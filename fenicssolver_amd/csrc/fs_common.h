@@ -454,6 +454,9 @@ int fs_dg_spmv(fs_matrix_s* A, fs_vector_s* x, fs_vector_s* y);
 int fs_dg_spmv_dev(fs_matrix_s* A, const double* x, double* y, hipStream_t s);
 int64_t fs_dg_spmv_bytes(const fs_space_s* sp);
 int fs_dg_krylov_solve(fs_matrix_s* A, fs_vector_s* b, fs_vector_s* x, const fs_krylov_opts* opts, fs_krylov_stats* stats);
+// fs_hyper_models.hip: fs_assemble_hyperelastic for every energy but the neo-Hookean one (handles and `what` checked by the caller)
+int fs_hyper_models_assemble(fs_space_s* sp, fs_matrix_s* K, fs_vector_s* r, fs_vector_s* u, const fs_hyper_form* form, int what,
+                             fs_hyper_info* info);
 // fs_krylov.hip: what fs_krylov_history / fs_last_product_kind report
 void fs_krylov_set_history(const std::vector<double>& rr);
 void fs_set_last_product_kind(int kind);

@@ -1,5 +1,7 @@
 // Compressible neo-Hookean hyperelasticity on vector CG1 spaces (tetrahedra, and triangles in plane strain): the tangent
-// stiffness, the internal force and the stored energy at a displaced state, on the device.
+// stiffness, the internal force and the stored energy at a displaced state, on the device.  The other energies of
+// fs_assemble_hyperelastic (St Venant-Kirchhoff, Mooney-Rivlin, Yeoh) and the Cauchy stress of all four are in fs_hyper_models.hip;
+// this file keeps the neo-Hookean expression order and with it the bits.
 //
 // Stands in for the two UFL derivatives of FenicsSolver/NonlinearElasticitySolver.py:41-98 that solve(F == 0, u, bcs, J=J)
 // assembles at every Newton iterate:
@@ -373,7 +375,9 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
     FS_REFUSE_DG_SPACE(space, "fs_assemble_hyperelastic"); FS_REFUSE_DG(K, "fs_assemble_hyperelastic");
     FS_REQUIRE(space && u && form, "fs_assemble_hyperelastic: null pointer");
     FS_REQUIRE((what & ~(FS_HYPER_TANGENT | FS_HYPER_FORCE | FS_HYPER_ENERGY)) == 0, "fs_assemble_hyperelastic: unknown bits in what (%d)", what);
-    FS_REQUIRE(form->model == FS_HYPER_NEO_HOOKEAN, "fs_assemble_hyperelastic: unknown energy model %d (FS_HYPER_NEO_HOOKEAN only)", form->model);
+    FS_REQUIRE(form->model == FS_HYPER_NEO_HOOKEAN || form->model == FS_HYPER_ST_VENANT_KIRCHHOFF || form->model == FS_HYPER_MOONEY_RIVLIN ||
+                   form->model == FS_HYPER_YEOH,
+               "fs_assemble_hyperelastic: unknown energy model %d (FS_HYPER_NEO_HOOKEAN, _ST_VENANT_KIRCHHOFF, _MOONEY_RIVLIN, _YEOH)", form->model);
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
     FS_CHECK(fs_require_vector_cg1(sp, "fs_assemble_hyperelastic"));
@@ -383,6 +387,7 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
     FS_REQUIRE(!(what & FS_HYPER_FORCE) || (r && r->d.n >= sp->n_dofs_owned), "fs_assemble_hyperelastic: the internal force needs a vector of "
                "the space's owned dofs");
     FS_REQUIRE(!(what & FS_HYPER_ENERGY) || info, "fs_assemble_hyperelastic: the energy needs an info struct");
+    if (form->model != FS_HYPER_NEO_HOOKEAN) return fs_hyper_models_assemble(sp, K, r, u, form, what, info);      // fs_hyper_models.hip
     FS_REQUIRE(form->lame.mode == FS_COEF_NONE || form->lame.mode == FS_COEF_CELL_LAME,
                "fs_assemble_hyperelastic: the Lame coefficient is FS_COEF_NONE (mu / lambda) or FS_COEF_CELL_LAME");
     FS_REQUIRE(form->lame.mode == FS_COEF_CELL_LAME || (form->mu > 0.0 && form->lambda >= 0.0 && isfinite(form->mu) && isfinite(form->lambda)),

@@ -1,0 +1,558 @@
+// St Venant-Kirchhoff, Mooney-Rivlin and Yeoh hyperelasticity on vector CG1 spaces (tetrahedra, and triangles in true plane strain):
+// tangent, internal force, energy and inverted-cell tally behind fs_assemble_hyperelastic for every model but the neo-Hookean one
+// (fs_hyper.hip keeps that: its expression order and its bits), and the Cauchy stress per cell of all four (fs_hyper_stress).
+// None of the three has a counterpart in FenicsSolver/NonlinearElasticitySolver.py.
+//
+// The material is written once, in invariant form psi = W(I1, I2, J), I1 = tr C, I2 = 1/2 (I1^2 - tr C^2), J = det F.  With
+//   dI1/dF = 2 F,   dI2/dF = 2 (I1 F - B F),   dJ/dF = cof F            (B = F F^T)
+// and g_a the reference gradient of the barycentric function a, the three vectors a_p = (dI_p/dF) g_a (b_p for g_b) give
+//   force     f_a[i]     = V (W_1 a_1 + W_2 a_2 + W_J a_3)[i]
+//   tangent   K_ab[i][k] = V ( sum_pq W_pq a_p[i] b_q[k]
+//                              + W_1 2 (g_a.g_b) d_ik
+//                              + W_2 (4 Fa_i Fb_k - 2 Fb_i Fa_k + (2 I1 g_a.g_b - 2 Fa.Fb) d_ik - 2 B_ik g_a.g_b)      Fa = F g_a
+//                              + W_J eps_ikm (F (g_a x g_b))_m )
+//   Cauchy    sigma      = (2/J) (W_1 + W_2 I1) B - (2/J) W_2 B^2 + W_J I
+// A model is a device functor that returns the nine numbers W_1, W_2, W_J, W_11, W_12, W_1J, W_22, W_2J, W_JJ (and psi); it is a
+// TEMPLATE parameter of every kernel, as ADD and CELL are, so the parameter row stays in registers (a run-time switch over rows
+// indexed at run time would put them in scratch).  Parameter row p[4] (constant, or one row per cell in device cell order):
+//   m_svk   (mu, lambda, -, -)       psi = lambda/2 (tr E)^2 + mu E:E = lambda/8 (I1 - 3)^2 + mu/4 (I1^2 - 2 I2 - 2 I1 + 3)
+//   m_mooney(c10, c01, kappa, -)     psi = c10 (J^-2/3 I1 - 3) + c01 (J^-4/3 I2 - 3) + kappa/2 (J - 1)^2
+//   m_yeoh  (c10, c20, c30, kappa)   psi = sum_k ck0 (J^-2/3 I1 - 3)^k + kappa/2 (J - 1)^2
+//   m_neo   (mu, lambda, -, -)       stress only: W_1 = mu/2, W_J = (lambda ln J - mu) / J
+// 2-D is plane strain: F is embedded in 3 x 3 with F33 = 1 and g_a[2] = 0, the same code runs with TD = 2 and the compiler folds the
+// constants; only the in-plane rows and columns of the block are formed.  psi(I) = 0 in both dimensions.
+//
+// Kernels (no atomics; the rules of fs_hyper.hip): the gathers RECOMPUTE the cell state per source, as the neo-Hookean gathers do.
+// A per-cell pre-pass would have to store F, B, cof F and the nine W (36 doubles, 288 B) for every source to read, against the
+// 4 vertex records, 4 displacements and the cell record (64 B + the parameter row) the recomputation reads; that variant was not
+// built, so the choice rests on this count and not on a measured comparison.
+//   k_hm_tangent<M, TD, ADD, CELL>  thread per stored block over the sources of the inverse slot table, ascending
+//   k_hm_force<M, TD, ADD, CELL>    thread per owned node over the sources of its diagonal block
+//   k_hm_cells<M, TD, CELL, false>  V psi and the cells with J <= 0 or J not finite -> p1_cell_tally, k_cell_tally_finish
+//   k_hm_cells<M, TD, CELL, true>   sigma per cell (6 or 4 values, tensor storage of fs_p1_cell.h) and the same tally
+// Resource use on gfx950 (-Rpass-analysis=kernel-resource-usage): 0 bytes of scratch and no AGPRs in every instantiation.  VGPRs
+// (waves per SIMD), the range over ADD and CELL:
+//                 tangent TD = 3    tangent TD = 2     force TD = 3    force TD = 2    cells TD = 3     cells TD = 2
+//   m_svk         102 - 126 (4)     92 - 94 (5)        84 - 90 (5)     54 (8)          82 - 88 (5)      48 - 55 (8)
+//   m_mooney      108 - 126 (4)     78 - 94 (5 - 6)    82 - 90 (5)     58 - 64 (8)     80 - 90 (5 - 6)  56 - 62 (8)
+//   m_yeoh        126 (4)           90 - 94 (5)        92 - 94 (5)     58 - 62 (8)     80 - 92 (5 - 6)  54 - 62 (8)
+//   m_neo         -                 -                  -               -               90 - 102 (4 - 5) 60 - 66 (7 - 8)
+#include "fs_common.h"
+#include "fs_kernels.h"
+#include "fs_p1_cell.h"
+#include <math.h>
+#include <type_traits>
+#include <vector>
+
+#define FS_HM_CELL_BLOCKS 1024      // workgroups of the per-cell passes (their partials are summed in this order)
+
+struct hm_par { double p[4]; };
+struct hm_w { double w1, w2, wj, w11, w12, w1j, w22, w2j, wjj; };
+
+// ---- the models ------------------------------------------------------------------------------------------------------------------
+struct m_svk {
+    static __device__ __forceinline__ void eval(const hm_par& q, double I1, double I2, double J, hm_w& w, double& psi) {
+        const double mu = q.p[0], lm = q.p[1];
+        psi = 0.125 * lm * (I1 - 3.0) * (I1 - 3.0) + 0.25 * mu * (I1 * I1 - 2.0 * I2 - 2.0 * I1 + 3.0);
+        w.w1 = 0.25 * lm * (I1 - 3.0) + 0.5 * mu * (I1 - 1.0);
+        w.w2 = -0.5 * mu;
+        w.w11 = 0.25 * lm + 0.5 * mu;
+        w.wj = w.w12 = w.w1j = w.w22 = w.w2j = w.wjj = 0.0;
+    }
+};
+
+struct m_neo {          // the Cauchy stress of the neo-Hookean energy (its tangent, force and energy are fs_hyper.hip's)
+    static __device__ __forceinline__ void eval(const hm_par& q, double I1, double I2, double J, hm_w& w, double& psi) {
+        const double mu = q.p[0], lm = q.p[1], lj = log(J);
+        psi = 0.5 * mu * (I1 - 3.0) - mu * lj + 0.5 * lm * lj * lj;
+        w.w1 = 0.5 * mu;
+        w.wj = (lm * lj - mu) / J;
+        w.wjj = (lm * (1.0 - lj) + mu) / (J * J);
+        w.w2 = w.w11 = w.w12 = w.w1j = w.w22 = w.w2j = 0.0;
+    }
+};
+
+// a = J^-2/3 and its first two derivatives with respect to J
+__device__ __forceinline__ void hm_jm23(double J, double& a, double& a1, double& a2, double& iJ) {
+    const double cj = cbrt(J);
+    a = 1.0 / (cj * cj);
+    iJ = 1.0 / J;
+    a1 = -(2.0 / 3.0) * a * iJ;
+    a2 = (10.0 / 9.0) * a * iJ * iJ;
+}
+
+struct m_mooney {
+    static __device__ __forceinline__ void eval(const hm_par& q, double I1, double I2, double J, hm_w& w, double& psi) {
+        const double c10 = q.p[0], c01 = q.p[1], kap = q.p[2];
+        double a, a1, a2, iJ;
+        hm_jm23(J, a, a1, a2, iJ);
+        const double b = a * a, b1 = -(4.0 / 3.0) * b * iJ, b2 = (28.0 / 9.0) * b * iJ * iJ;      // J^-4/3
+        psi = c10 * (a * I1 - 3.0) + c01 * (b * I2 - 3.0) + 0.5 * kap * (J - 1.0) * (J - 1.0);
+        w.w1 = c10 * a;
+        w.w2 = c01 * b;
+        w.wj = c10 * I1 * a1 + c01 * I2 * b1 + kap * (J - 1.0);
+        w.w1j = c10 * a1;
+        w.w2j = c01 * b1;
+        w.wjj = c10 * I1 * a2 + c01 * I2 * b2 + kap;
+        w.w11 = w.w12 = w.w22 = 0.0;
+    }
+};
+
+struct m_yeoh {
+    static __device__ __forceinline__ void eval(const hm_par& q, double I1, double I2, double J, hm_w& w, double& psi) {
+        const double c10 = q.p[0], c20 = q.p[1], c30 = q.p[2], kap = q.p[3];
+        double a, a1, a2, iJ;
+        hm_jm23(J, a, a1, a2, iJ);
+        const double x = a * I1 - 3.0, xj = I1 * a1;
+        const double f1 = c10 + x * (2.0 * c20 + 3.0 * c30 * x), f2 = 2.0 * c20 + 6.0 * c30 * x;
+        psi = x * (c10 + x * (c20 + x * c30)) + 0.5 * kap * (J - 1.0) * (J - 1.0);
+        w.w1 = f1 * a;
+        w.wj = f1 * xj + kap * (J - 1.0);
+        w.w11 = f2 * a * a;
+        w.w1j = f2 * a * xj + f1 * a1;
+        w.wjj = f2 * xj * xj + f1 * I1 * a2 + kap;
+        w.w2 = w.w12 = w.w22 = w.w2j = 0.0;
+    }
+};
+
+// ---- kinematics --------------------------------------------------------------------------------------------------------------------
+// F = I + sum_a u_a g_a^T of the cell c (plane strain: embedded, F33 = 1), its volume (area), g_a and (PAIR) g_b with a zero third
+// component in 2-D.  The gradient picks are select chains on a local geometry (fs_p1_cell.h): never an index into a register array.
+template <int TD, bool PAIR>
+__device__ __forceinline__ void hm_cell_load(int4 v4, const double* __restrict__ xyz4, const double* __restrict__ u, const box_snap& bx,
+                                             int a, int b, double (&F)[3][3], double (&ga)[3], double (&gb)[3], double& vol) {
+    if constexpr (TD == 3) {
+        const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
+        const tet_geom t = tet_geometry_box(xyz4, v, bx);
+        vol = t.adet * (1.0 / 6.0);
+        double uv[4][3];
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) uv[n][k] = u[3 * (int64_t)v[n] + k];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                F[i][j] = (i == j ? 1.0 : 0.0) + (((uv[0][i] * t.g[0][j] + uv[1][i] * t.g[1][j]) + uv[2][i] * t.g[2][j]) + uv[3][i] * t.g[3][j]);
+        P1_GRAD_TET(t, a, ga);
+        if (PAIR) P1_GRAD_TET(t, b, gb);
+    } else {
+        const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
+        vol = t.area;
+        const double2 u0 = reinterpret_cast<const double2*>(u)[v4.x], u1 = reinterpret_cast<const double2*>(u)[v4.y],
+                      u2 = reinterpret_cast<const double2*>(u)[v4.z];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            F[0][j] = (j == 0 ? 1.0 : 0.0) + ((u0.x * t.g[0][j] + u1.x * t.g[1][j]) + u2.x * t.g[2][j]);
+            F[1][j] = (j == 1 ? 1.0 : 0.0) + ((u0.y * t.g[0][j] + u1.y * t.g[1][j]) + u2.y * t.g[2][j]);
+        }
+        F[0][2] = F[1][2] = F[2][0] = F[2][1] = 0.0;
+        F[2][2] = 1.0;
+        double g2[2];
+        p1_grad(t, a, g2);
+        ga[0] = g2[0]; ga[1] = g2[1]; ga[2] = 0.0;
+        if (PAIR) {
+            p1_grad(t, b, g2);
+            gb[0] = g2[0]; gb[1] = g2[1]; gb[2] = 0.0;
+        }
+    }
+}
+
+// cof F, B = F F^T, I1, I2, J
+struct hm_state { double cof[3][3], B[3][3], I1, I2, J; };
+__device__ __forceinline__ void hm_invariants(const double (&F)[3][3], hm_state& s) {
+    s.cof[0][0] = F[1][1] * F[2][2] - F[1][2] * F[2][1];
+    s.cof[0][1] = F[1][2] * F[2][0] - F[1][0] * F[2][2];
+    s.cof[0][2] = F[1][0] * F[2][1] - F[1][1] * F[2][0];
+    s.cof[1][0] = F[0][2] * F[2][1] - F[0][1] * F[2][2];
+    s.cof[1][1] = F[0][0] * F[2][2] - F[0][2] * F[2][0];
+    s.cof[1][2] = F[0][1] * F[2][0] - F[0][0] * F[2][1];
+    s.cof[2][0] = F[0][1] * F[1][2] - F[0][2] * F[1][1];
+    s.cof[2][1] = F[0][2] * F[1][0] - F[0][0] * F[1][2];
+    s.cof[2][2] = F[0][0] * F[1][1] - F[0][1] * F[1][0];
+    s.J = F[0][0] * s.cof[0][0] + F[0][1] * s.cof[0][1] + F[0][2] * s.cof[0][2];
+    double bb = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            s.B[i][j] = F[i][0] * F[j][0] + F[i][1] * F[j][1] + F[i][2] * F[j][2];
+            bb += s.B[i][j] * s.B[i][j];
+        }
+    s.I1 = s.B[0][0] + s.B[1][1] + s.B[2][2];
+    s.I2 = 0.5 * (s.I1 * s.I1 - bb);
+}
+
+__device__ __forceinline__ void hm_mul(const double (&A)[3][3], const double (&x)[3], double (&y)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) y[i] = A[i][0] * x[0] + A[i][1] * x[1] + A[i][2] * x[2];
+}
+
+// a_1, a_2, a_3 = (dI1/dF, dI2/dF, dJ/dF) g and Fg = F g
+__device__ __forceinline__ void hm_dvec(const double (&F)[3][3], const hm_state& s, const double (&g)[3], double (&Fg)[3], double (&a1)[3],
+                                        double (&a2)[3], double (&a3)[3]) {
+    double BFg[3];
+    hm_mul(F, g, Fg);
+    hm_mul(s.B, Fg, BFg);
+    hm_mul(s.cof, g, a3);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        a1[i] = 2.0 * Fg[i];
+        a2[i] = 2.0 * (s.I1 * Fg[i] - BFg[i]);
+    }
+}
+
+__device__ __forceinline__ hm_par hm_row(const double2* __restrict__ rows, int64_t c) {
+    const double2 x = rows[2 * c], y = rows[2 * c + 1];
+    hm_par q;
+    q.p[0] = x.x; q.p[1] = x.y; q.p[2] = y.x; q.p[3] = y.y;
+    return q;
+}
+
+// ---- tangent ---------------------------------------------------------------------------------------------------------------------
+template <class M, int TD, bool ADD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hm_tangent(int64_t n_entries, const int32_t* __restrict__ ptr, const int32_t* __restrict__ src,
+                                                         const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
+                                                         const double* __restrict__ u, const hm_par par, const double2* __restrict__ rows,
+                                                         int64_t plane, double* __restrict__ val, const box_snap bx) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; e < n_entries; e += stride) {
+        double acc[TD][TD];
+#pragma unroll
+        for (int i = 0; i < TD; ++i)
+#pragma unroll
+            for (int k = 0; k < TD; ++k) acc[i][k] = 0.0;
+        const int32_t q1 = ptr[e + 1];
+        for (int32_t q = ptr[e]; q < q1; ++q) {
+            int64_t c;
+            int a, b;
+            p1_source<TD>(src[q], c, a, b);
+            const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+            const hm_par mat = CELL ? hm_row(rows, c) : par;
+            double F[3][3], ga[3], gb[3], vol;
+            hm_cell_load<TD, true>(v4, xyz4, u, bx, a, b, F, ga, gb, vol);
+            hm_state s;
+            hm_invariants(F, s);
+            hm_w w;
+            double psi;
+            M::eval(mat, s.I1, s.I2, s.J, w, psi);
+            double Fa[3], Fb[3], a1[3], a2[3], a3[3], b1[3], b2[3], b3[3];
+            hm_dvec(F, s, ga, Fa, a1, a2, a3);
+            hm_dvec(F, s, gb, Fb, b1, b2, b3);
+            const double gg = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
+            const double ff = Fa[0] * Fb[0] + Fa[1] * Fb[1] + Fa[2] * Fb[2];
+            const double cr[3] = {ga[1] * gb[2] - ga[2] * gb[1], ga[2] * gb[0] - ga[0] * gb[2], ga[0] * gb[1] - ga[1] * gb[0]};
+            double wv[3];
+            hm_mul(F, cr, wv);
+            const double dg = 2.0 * w.w1 * gg + w.w2 * (2.0 * s.I1 * gg - 2.0 * ff);
+#pragma unroll
+            for (int i = 0; i < TD; ++i) {
+                const double u1 = w.w11 * a1[i] + w.w12 * a2[i] + w.w1j * a3[i];
+                const double u2 = w.w12 * a1[i] + w.w22 * a2[i] + w.w2j * a3[i];
+                const double u3 = w.w1j * a1[i] + w.w2j * a2[i] + w.wjj * a3[i];
+#pragma unroll
+                for (int k = 0; k < TD; ++k) {
+                    double x = u1 * b1[k] + u2 * b2[k] + u3 * b3[k];
+                    x += w.w2 * (4.0 * Fa[i] * Fb[k] - 2.0 * Fb[i] * Fa[k] - 2.0 * gg * s.B[i][k]);
+                    if (i == k) x += dg;
+                    else x += w.wj * (((k - i + 3) % 3 == 1) ? wv[3 - i - k] : -wv[3 - i - k]);      // eps_ikm w_m, m = 3 - i - k
+                    acc[i][k] += vol * x;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TD; ++i)
+#pragma unroll
+            for (int k = 0; k < TD; ++k) {
+                const int64_t idx = (int64_t)(i * TD + k) * plane + e;
+                val[idx] = ADD ? val[idx] + acc[i][k] : acc[i][k];
+            }
+    }
+}
+
+// ---- internal force ----------------------------------------------------------------------------------------------------------------
+template <class M, int TD, bool ADD, bool CELL>
+__global__ void __launch_bounds__(FS_BLOCK) k_hm_force(int64_t n_rows, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ sell_col,
+                                                       const int32_t* __restrict__ gptr, const int32_t* __restrict__ gsrc,
+                                                       const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
+                                                       const double* __restrict__ u, const hm_par par, const double2* __restrict__ rows,
+                                                       const box_snap bx, double* __restrict__ f) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; r < n_rows; r += stride) {
+        const int64_t e = p1_diag_entry(r, slice_ptr, sell_col);
+        double acc[TD];
+#pragma unroll
+        for (int i = 0; i < TD; ++i) acc[i] = 0.0;
+        if (e >= 0) {
+            const int32_t q1 = gptr[e + 1];
+            for (int32_t q = gptr[e]; q < q1; ++q) {
+                int64_t c;
+                int a, b;
+                p1_source<TD>(gsrc[q], c, a, b);
+                const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+                const hm_par mat = CELL ? hm_row(rows, c) : par;
+                double F[3][3], ga[3], gb[3], vol;
+                hm_cell_load<TD, false>(v4, xyz4, u, bx, a, b, F, ga, gb, vol);
+                hm_state s;
+                hm_invariants(F, s);
+                hm_w w;
+                double psi;
+                M::eval(mat, s.I1, s.I2, s.J, w, psi);
+                double Fa[3], a1[3], a2[3], a3[3];
+                hm_dvec(F, s, ga, Fa, a1, a2, a3);
+#pragma unroll
+                for (int i = 0; i < TD; ++i) acc[i] += vol * (w.w1 * a1[i] + w.w2 * a2[i] + w.wj * a3[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TD; ++i) f[TD * r + i] = ADD ? f[TD * r + i] + acc[i] : acc[i];
+    }
+}
+
+// ---- energy, Cauchy stress and inverted cells -------------------------------------------------------------------------------------
+// STRESS false: part_e gets the energy partials.  STRESS true: sig[c][6 or 4] = sigma (zeros in an inverted cell; the host refuses
+// the result then).  A cell counts as inverted when J <= 0 or J is not finite.
+template <class M, int TD, bool CELL, bool STRESS>
+__global__ void __launch_bounds__(FS_BLOCK) k_hm_cells(int64_t nc, const int32_t* __restrict__ cells, const double* __restrict__ xyz4,
+                                                       const double* __restrict__ u, const hm_par par, const double2* __restrict__ rows,
+                                                       const box_snap bx, double* __restrict__ part_e, int64_t* __restrict__ part,
+                                                       double* __restrict__ sig) {
+    constexpr int NE = TD == 3 ? 6 : 4;
+    double en = 0.0;
+    int64_t n_bad[1] = {0}, first = INT64_MAX;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += stride) {
+        const int4 v4 = reinterpret_cast<const int4*>(cells)[c];
+        const hm_par mat = CELL ? hm_row(rows, c) : par;
+        double F[3][3], ga[3], gb[3], vol;
+        hm_cell_load<TD, false>(v4, xyz4, u, bx, 0, 0, F, ga, gb, vol);
+        hm_state s;
+        hm_invariants(F, s);
+        const bool bad = !(s.J > 0.0) || !isfinite(s.J);
+        if (bad) {
+            ++n_bad[0];
+            first = c < first ? c : first;
+        }
+        hm_w w;
+        double psi;
+        M::eval(mat, s.I1, s.I2, bad ? 1.0 : s.J, w, psi);
+        if (STRESS) {
+            const double k1 = bad ? 0.0 : 2.0 / s.J * (w.w1 + w.w2 * s.I1), k2 = bad ? 0.0 : 2.0 / s.J * w.w2, k3 = bad ? 0.0 : w.wj;
+            double B2[3][3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) B2[i][j] = s.B[i][0] * s.B[0][j] + s.B[i][1] * s.B[1][j] + s.B[i][2] * s.B[2][j];
+            double* o = sig + NE * c;
+            o[0] = k1 * s.B[0][0] - k2 * B2[0][0] + k3;
+            o[1] = k1 * s.B[1][1] - k2 * B2[1][1] + k3;
+            o[2] = k1 * s.B[2][2] - k2 * B2[2][2] + k3;
+            o[3] = k1 * s.B[0][1] - k2 * B2[0][1];
+            if (TD == 3) {
+                o[4] = k1 * s.B[0][2] - k2 * B2[0][2];
+                o[5] = k1 * s.B[1][2] - k2 * B2[1][2];
+            }
+        } else if (!bad) {
+            en += vol * psi;
+        }
+    }
+    p1_cell_tally<1, !STRESS>(n_bad, first, en, part, part_e);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+static const char* hm_name(int model) {
+    return model == FS_HYPER_NEO_HOOKEAN ? "neo-Hookean" : model == FS_HYPER_ST_VENANT_KIRCHHOFF ? "St Venant-Kirchhoff"
+           : model == FS_HYPER_MOONEY_RIVLIN ? "Mooney-Rivlin" : "Yeoh";
+}
+
+// one parameter row against the refusals of its model; cell < 0: the constant row
+static int hm_check_row(int model, const double* p, const char* who, int64_t cell) {
+    char where[64] = "the material";
+    if (cell >= 0) snprintf(where, sizeof where, "cell %lld (device order)", (long long)cell);
+    const bool fin = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && isfinite(p[3]);
+    if (model == FS_HYPER_NEO_HOOKEAN || model == FS_HYPER_ST_VENANT_KIRCHHOFF) {
+        FS_REQUIRE(fin && p[0] > 0.0 && p[1] >= 0.0, "%s: %s has mu = %g, lambda = %g: mu > 0 and lambda >= 0 are required (%s)", who, where, p[0],
+                   p[1], hm_name(model));
+    } else if (model == FS_HYPER_MOONEY_RIVLIN) {
+        FS_REQUIRE(fin && p[0] >= 0.0 && p[1] >= 0.0 && p[0] + p[1] > 0.0 && p[2] > 0.0,
+                   "%s: %s has c10 = %g, c01 = %g, kappa = %g: c10 >= 0, c01 >= 0, c10 + c01 > 0 and kappa > 0 are required (Mooney-Rivlin)", who,
+                   where, p[0], p[1], p[2]);
+    } else {
+        FS_REQUIRE(fin && p[0] > 0.0 && p[3] > 0.0,
+                   "%s: %s has c10 = %g, c20 = %g, c30 = %g, kappa = %g: finite values with c10 > 0 and kappa > 0 are required (Yeoh)", who, where,
+                   p[0], p[1], p[2], p[3]);
+    }
+    return FS_OK;
+}
+
+// the parameter row of the form (par), or its per-cell rows [nc][4] (rows non-empty), checked
+static int hm_material(const fs_hyper_form* form, int64_t nc, const char* who, hm_par& par, std::vector<double>& rows) {
+    const int model = form->model;
+    FS_REQUIRE(model == FS_HYPER_NEO_HOOKEAN || model == FS_HYPER_ST_VENANT_KIRCHHOFF || model == FS_HYPER_MOONEY_RIVLIN || model == FS_HYPER_YEOH,
+               "%s: unknown energy model %d (FS_HYPER_NEO_HOOKEAN, _ST_VENANT_KIRCHHOFF, _MOONEY_RIVLIN, _YEOH)", who, model);
+    rows.clear();
+    for (int k = 0; k < 4; ++k) par.p[k] = 0.0;
+    if (model == FS_HYPER_NEO_HOOKEAN || model == FS_HYPER_ST_VENANT_KIRCHHOFF) {
+        FS_REQUIRE(form->lame.mode == FS_COEF_NONE || form->lame.mode == FS_COEF_CELL_LAME,
+                   "%s: the Lame coefficient is FS_COEF_NONE (mu / lambda) or FS_COEF_CELL_LAME", who);
+        if (form->lame.mode == FS_COEF_CELL_LAME) {
+            FS_REQUIRE(form->lame.data, "%s: per-cell Lame data pointer is null", who);
+            rows.assign((size_t)(4 * nc), 0.0);
+            for (int64_t c = 0; c < nc; ++c) {
+                rows[4 * c] = form->lame.data[2 * c];
+                rows[4 * c + 1] = form->lame.data[2 * c + 1];
+            }
+        } else {
+            par.p[0] = form->mu;
+            par.p[1] = form->lambda;
+        }
+    } else {
+        FS_REQUIRE(form->cell_params.mode == FS_COEF_NONE || form->cell_params.mode == FS_COEF_CELL_HYPER,
+                   "%s: the %s parameters are FS_COEF_NONE (params) or FS_COEF_CELL_HYPER (cell_params)", who, hm_name(model));
+        if (form->cell_params.mode == FS_COEF_CELL_HYPER) {
+            FS_REQUIRE(form->cell_params.data, "%s: per-cell parameter data pointer is null", who);
+            rows.assign(form->cell_params.data, form->cell_params.data + 4 * nc);
+        } else {
+            for (int k = 0; k < 4; ++k) par.p[k] = form->params[k];
+        }
+    }
+    if (rows.empty()) return hm_check_row(model, par.p, who, -1);
+    for (int64_t c = 0; c < nc; ++c) FS_CHECK(hm_check_row(model, &rows[4 * c], who, c));
+    return FS_OK;
+}
+
+template <class F> static inline void hm_dispatch_model(int model, F&& f) {
+    if (model == FS_HYPER_ST_VENANT_KIRCHHOFF) f(m_svk{});
+    else if (model == FS_HYPER_MOONEY_RIVLIN) f(m_mooney{});
+    else if (model == FS_HYPER_YEOH) f(m_yeoh{});
+    else f(m_neo{});
+}
+
+// the per-cell pass (energy or stress) and its tally; sig_dev: device [nc][6 or 4] for the stress
+template <class M>
+static int hm_cells_pass(fs_space_s* sp, fs_vector_s* u, const hm_par& par, const double2* rows, bool stress, double* sig_dev,
+                         fs_hyper_info* info) {
+    fs_mesh_s* m = sp->mesh;
+    hipStream_t s = fs_rt().stream;
+    const box_snap bx = make_box_snap(m);
+    const int nb = FS_HM_CELL_BLOCKS;
+    dbuf<double> pe, oe;
+    dbuf<int64_t> part, on;
+    FS_CHECK(pe.alloc(nb)); FS_CHECK(part.alloc(2 * nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
+    fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
+        fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
+            fs_dispatch_bool(stress, [&](auto ST) {
+                hipLaunchKernelGGL((k_hm_cells<M, decltype(T3)::value ? 3 : 2, decltype(CELL)::value, decltype(ST)::value>), dim3(nb),
+                                   dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, par, rows, bx, pe.p, part.p, sig_dev);
+            });
+        });
+    });
+    FS_KERNEL_CHECK();
+    if (stress) hipLaunchKernelGGL((k_cell_tally_finish<1, false>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
+    else hipLaunchKernelGGL((k_cell_tally_finish<1, true>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
+    FS_KERNEL_CHECK();
+    double e_host = 0.0;
+    int64_t n_host[2] = {0, 0};
+    if (!stress) FS_CHECK(oe.download(&e_host, 1, s));
+    FS_CHECK(on.download(n_host, 2, s));
+    FS_HIP(hipStreamSynchronize(s));
+    info->energy = e_host;
+    info->n_inverted = n_host[0];
+    info->first_inverted_cell = fs_first_cell(m, n_host[0], n_host[1]);
+    return FS_OK;
+}
+
+template <class M>
+static int hm_assemble(fs_space_s* sp, fs_matrix_s* K, fs_vector_s* r, fs_vector_s* u, const hm_par& par, const double2* rows, bool add,
+                       int what, fs_hyper_info* info) {
+    fs_mesh_s* m = sp->mesh;
+    hipStream_t s = fs_rt().stream;
+    const box_snap bx = make_box_snap(m);
+    if (what & FS_HYPER_TANGENT) {
+        fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
+            fs_dispatch_bool(add, [&](auto ADD) {
+                fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
+                    hipLaunchKernelGGL((k_hm_tangent<M, decltype(T3)::value ? 3 : 2, decltype(ADD)::value, decltype(CELL)::value>),
+                                       dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p,
+                                       sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, par, rows, sp->sell_entries, K->val.p, bx);
+                });
+            });
+        });
+        FS_KERNEL_CHECK();
+    }
+    if (what & FS_HYPER_FORCE) {
+        fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
+            fs_dispatch_bool(add, [&](auto ADD) {
+                fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
+                    hipLaunchKernelGGL((k_hm_force<M, decltype(T3)::value ? 3 : 2, decltype(ADD)::value, decltype(CELL)::value>),
+                                       dim3(fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p,
+                                       sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, par, rows, bx, r->d.p);
+                });
+            });
+        });
+        FS_KERNEL_CHECK();
+    }
+    if (info) FS_CHECK((hm_cells_pass<M>(sp, u, par, rows, false, nullptr, info)));
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}
+
+// fs_assemble_hyperelastic for every model but the neo-Hookean one (the caller has checked the handles and `what`)
+int fs_hyper_models_assemble(fs_space_s* sp, fs_matrix_s* K, fs_vector_s* r, fs_vector_s* u, const fs_hyper_form* form, int what,
+                             fs_hyper_info* info) {
+    const char* who = "fs_assemble_hyperelastic";
+    fs_mesh_s* m = sp->mesh;
+    hm_par par;
+    std::vector<double> host_rows;
+    FS_CHECK(hm_material(form, m->nc, who, par, host_rows));
+    FS_REQUIRE(form->model != FS_HYPER_NEO_HOOKEAN, "%s: the neo-Hookean energy is assembled by its own kernels", who);
+    hipStream_t s = fs_rt().stream;
+    dbuf<double> rstore;
+    if (!host_rows.empty()) {
+        FS_CHECK(rstore.alloc(4 * m->nc));
+        FS_CHECK(rstore.upload(host_rows.data(), 4 * m->nc, s));
+    }
+    const double2* rows = host_rows.empty() ? nullptr : reinterpret_cast<const double2*>(rstore.p);
+    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    int rc = FS_OK;
+    hm_dispatch_model(form->model, [&](auto M) {
+        using model_t = decltype(M);
+        if constexpr (!std::is_same<model_t, m_neo>::value) rc = hm_assemble<model_t>(sp, K, r, u, par, rows, form->add != 0, what, info);
+    });
+    return rc;
+}
+
+extern "C" int fs_hyper_stress(fs_space_t space, fs_vector_t u, const fs_hyper_form* form, double* sigma, fs_hyper_info* info) {
+    const char* who = "fs_hyper_stress";
+    FS_REFUSE_DG_SPACE(space, who);
+    FS_REQUIRE(space && u && form && sigma, "%s: null pointer", who);
+    fs_space_s* sp = space;
+    fs_mesh_s* m = sp->mesh;
+    FS_CHECK(fs_require_vector_cg1(sp, who));
+    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "%s: displacement vector shorter than the space's dofs", who);
+    hm_par par;
+    std::vector<double> host_rows;
+    FS_CHECK(hm_material(form, m->nc, who, par, host_rows));
+    hipStream_t s = fs_rt().stream;
+    const int ne = m->tdim == 3 ? 6 : 4;
+    dbuf<double> rstore, sig;
+    if (!host_rows.empty()) {
+        FS_CHECK(rstore.alloc(4 * m->nc));
+        FS_CHECK(rstore.upload(host_rows.data(), 4 * m->nc, s));
+    }
+    const double2* rows = host_rows.empty() ? nullptr : reinterpret_cast<const double2*>(rstore.p);
+    FS_CHECK(sig.alloc((int64_t)ne * m->nc));
+    fs_hyper_info local;
+    int rc = FS_OK;
+    hm_dispatch_model(form->model, [&](auto M) { rc = hm_cells_pass<decltype(M)>(sp, u, par, rows, true, sig.p, &local); });
+    FS_CHECK(rc);
+    if (info) *info = local;
+    FS_REQUIRE(local.n_inverted == 0, "%s: %lld cell(s) are inverted (J <= 0 or not finite), first cell %lld: the Cauchy stress is not defined there",
+               who, (long long)local.n_inverted, (long long)local.first_inverted_cell);
+    FS_CHECK(sig.download(sigma, (int64_t)ne * m->nc, s));
+    FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}

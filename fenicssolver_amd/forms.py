@@ -195,30 +195,57 @@ class AnisotropicElasticity:
                 "thermal": None if self.thermal is None else (_plain(self.thermal[0]), _plain(self.thermal[1]), self.thermal[2])}
 
 
+HYPER_PARAMETER_NAMES = {"mooney_rivlin": ("c10", "c01", "bulk_modulus"), "yeoh": ("c10", "c20", "c30", "bulk_modulus")}
+
+
 class HyperelasticForm:
-    """Pi = int psi(F) dx - int B.u dx - loads.u ds, psi the compressible neo-Hookean energy (NonlinearElasticitySolver.py:41-98);
-    the Newton iteration solves dPi/du = 0 (SolverBase._hyperelastic_newton).  The loads are dead loads with their PHYSICAL sign
-    (the reference subtracts them from Pi; no reversed-sign quirk here)."""
+    """Pi = int psi(F) dx - int B.u dx - loads.u ds; the Newton iteration solves dPi/du = 0 (SolverBase._hyperelastic_newton).
+    ``model``: 'neo_hookean' (the compressible neo-Hookean energy of NonlinearElasticitySolver.py:41-98) or 'st_venant_kirchhoff',
+    both with the Lame parameters mu / lmbda; 'mooney_rivlin' or 'yeoh' with the parameter table ``params``.  Only the first has a
+    counterpart upstream.  The loads are dead loads with their PHYSICAL sign (the reference subtracts them from Pi; no
+    reversed-sign quirk here)."""
 
     def __init__(self, space):
         self.space = space
         self.model = "neo_hookean"
         self.mu = None                # numbers (homogeneous) or arrays [n_cells] (per-cell material, host cell order)
         self.lmbda = None
+        self.params = None            # mooney_rivlin (c10, c01, kappa, 0) / yeoh (c10, c20, c30, kappa): one row of 4 numbers,
+                                      # or an array [n_cells, 4] of rows in host cell order
         self.body_force = None        # (fx, fy[, fz]) or None
         self.body_force_nodal = None  # [n_nodes, dim]: a body force FIELD by its nodal values (consistent-mass load)
         self.tractions = []           # [FacetLoad] with vector g, or [NodalLoad] (surface_source, varying pressure)
 
-    cellwise = ElasticityForm.cellwise
     lame_spec = ElasticityForm.lame_spec
 
+    def cellwise(self):
+        if self.model in HYPER_PARAMETER_NAMES:
+            return np.ndim(self.params) > 1
+        return ElasticityForm.cellwise(self)
+
+    def model_spec(self):
+        """(model, lame, params) as backend.assemble_hyperelastic takes them, per-cell arrays in HOST cell order: lame = (mu, lambda)
+        or ('cell', [n_cells, 2]) and params None for the two Lame models; lame None and params a row of 4 numbers or
+        ('cell', [n_cells, 4]) for the others."""
+        if self.model not in HYPER_PARAMETER_NAMES:
+            return (self.model, self.lame_spec(), None)
+        if self.cellwise():
+            return (self.model, None, ("cell", np.ascontiguousarray(self.params, dtype=np.float64)))
+        return (self.model, None, tuple(float(x) for x in self.params))
+
     def describe(self):
-        return {
+        d = {
             "type": "hyperelasticity", "model": self.model, "mu": _material(self.mu), "lambda": _material(self.lmbda),
             "body_force": None if self.body_force is None else tuple(float(x) for x in self.body_force),
             "tractions": [(t.marker_id, _plain(t.g), t.origin) if isinstance(t, FacetLoad) else ("nodal", len(t.dofs), t.origin)
                           for t in self.tractions],
         }
+        if self.model in HYPER_PARAMETER_NAMES:      # (only then: the neo-Hookean description stays as it was)
+            names = HYPER_PARAMETER_NAMES[self.model]
+            p = np.asarray(self.params, dtype=np.float64)
+            cols = (0, 1, 2) if self.model == "mooney_rivlin" else (0, 1, 2, 3)
+            d["parameters"] = {n: _material(p[..., k] if p.ndim > 1 else float(p[k])) for n, k in zip(names, cols)}
+        return d
 
 
 class PlasticForm:

@@ -23,9 +23,12 @@ class StoredStressVonMises:
         """The consistent L2 projection onto CG1 of the von Mises value of the RETURNED stress (the inherited method would project
         the elastic stress of u, which is wrong once a cell has yielded): right-hand side int vm phi_a dx with the per-cell value,
         P1 mass matrix, Jacobi-CG to 1e-12 on the device.  ``u`` is accepted for the inherited signature and not used."""
+        return self._project_cells(self.von_Mises_cells())
+
+    def _project_cells(self, vm):
+        """The consistent L2 projection onto CG1 of one value per cell (host cell order)."""
         from .fem import FunctionSpace
         from . import backend
-        vm = self.von_Mises_cells()
         P = FunctionSpace(self.mesh, 'P', 1)
         dP = P.device()
         ploc = P.localizer()

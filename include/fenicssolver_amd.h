@@ -353,28 +353,55 @@ int fs_assemble_dg_transport(fs_matrix_t A, fs_vector_t b, const fs_dg_form* for
 int fs_assemble_dg_projection(fs_space_t V_dg, fs_vector_t x, fs_space_t V_cg1, fs_vector_t b);
 
 /* ---- Hyperelasticity (NonlinearElasticitySolver.py:41-98) -------------------------------------------------------------------
- * Compressible neo-Hookean energy  psi = mu/2 (tr F^T F - 3) - mu ln J + lambda/2 (ln J)^2,  F = I + grad u,  J = det F
- * (2-D, plane strain: F is 2 x 2 and the reference's "- 3" is kept).  fs_assemble_hyperelastic evaluates at the displacement u,
- * on a vector CG1 space over tetrahedra or triangles (one rank):
+ * F = I + grad u, C = F^T F, J = det F, I1 = tr C, I2 = 1/2 (I1^2 - tr C^2), Ibar1 = J^(-2/3) I1, Ibar2 = J^(-4/3) I2.  Energies:
+ *   FS_HYPER_NEO_HOOKEAN          psi = mu/2 (I1 - 3) - mu ln J + lambda/2 (ln J)^2                    (the reference's energy)
+ *   FS_HYPER_ST_VENANT_KIRCHHOFF  psi = lambda/2 (tr E)^2 + mu E:E,  E = (C - I)/2
+ *   FS_HYPER_MOONEY_RIVLIN        psi = c10 (Ibar1 - 3) + c01 (Ibar2 - 3) + kappa/2 (J - 1)^2
+ *   FS_HYPER_YEOH                 psi = c10 (Ibar1 - 3) + c20 (Ibar1 - 3)^2 + c30 (Ibar1 - 3)^3 + kappa/2 (J - 1)^2
+ * The last three have no counterpart in the reference.  Parameters: neo-Hookean and St Venant-Kirchhoff take mu / lambda (or the
+ * per-cell pairs of `lame`); Mooney-Rivlin takes params = (c10, c01, kappa, -) and Yeoh params = (c10, c20, c30, kappa), or one such
+ * row per cell in `cell_params`.
+ * 2-D is plane strain.  For the three new energies F is the 3 x 3 matrix with the in-plane 2 x 2 block and F33 = 1, the invariants are
+ * the 3-D ones and psi = 0 at u = 0.  The 2-D neo-Hookean energy keeps the reference's form: F is 2 x 2 and the "- 3" stays, which
+ * shifts the energy by -mu/2 per unit area and changes nothing else.
+ * fs_assemble_hyperelastic evaluates at the displacement u, on a vector CG1 space over tetrahedra or triangles (one rank):
  *   FS_HYPER_TANGENT  K = d^2 Pi / du^2, the tangent stiffness (pattern of the space, no Dirichlet rows);
  *   FS_HYPER_FORCE    r = d Pi / du, the internal force int P : grad v dx (owned dofs);
  *   FS_HYPER_ENERGY   info->energy = int psi dx.
  * External loads do not depend on u: they are assembled with fs_assemble_vector / fs_assemble_facet_vector.
  * u: dof vector (node-interleaved, >= n_dofs_local entries).  K and r are overwritten, or added to with form->add.  Every result is
- * deterministic (no atomics; the energy is summed in a fixed order).  At u = 0 the tangent equals fs_assemble_matrix of the linear
- * elasticity operator with the same (mu, lambda) bit for bit.
+ * deterministic (no atomics; the energy is summed in a fixed order).  At u = 0 the neo-Hookean tangent equals fs_assemble_matrix of
+ * the linear elasticity operator with the same (mu, lambda) bit for bit; the tangent of the other energies equals the operator of
+ * their small-strain moduli (mu0 = mu, 2 (c10 + c01), 2 c10; lambda0 = lambda, kappa - 2 mu0 / 3) to rounding.
  * info (optional unless FS_HYPER_ENERGY): the energy, the number of cells with J <= 0 or J not finite (where the tangent, the force
  * and the energy are meaningless) and one of them, in the caller's cell numbering (-1: none).  info is filled whatever `what`
- * holds.  Other spaces, several ranks, mu <= 0 or lambda < 0 (constant or in any cell): FS_ERR_INVALID with a message. */
+ * holds.
+ * Refused with FS_ERR_INVALID and a message (naming the cell, in device order, for per-cell data): other spaces, several ranks, an
+ * unknown model, any parameter that is not finite, and
+ *   neo-Hookean, St Venant-Kirchhoff: mu <= 0 or lambda < 0;
+ *   Mooney-Rivlin: c10 < 0, c01 < 0, c10 + c01 <= 0 or kappa <= 0;
+ *   Yeoh: c10 <= 0 or kappa <= 0 (c20 and c30 may have either sign: fitted c20 are usually negative).
+ * St Venant-Kirchhoff loses ellipticity under strong compression; nothing here guards against that.
+ *
+ * fs_hyper_stress: the Cauchy stress sigma = P F^T / J per cell for all four energies, into the HOST array sigma[n_cells][6] =
+ * (xx, yy, zz, xy, xz, yz), in plane strain sigma[n_cells][4] = (xx, yy, zz, xy) with sigma_zz kept - tensor components, cells in
+ * device cell order, as fs_anisotropic_stress.  `add` is ignored.  A state with an inverted cell is refused (FS_ERR_INVALID, the
+ * message names the count and the first cell in the caller's numbering; info, if given, holds them) and sigma is left untouched. */
 #define FS_HYPER_NEO_HOOKEAN 0
+#define FS_HYPER_ST_VENANT_KIRCHHOFF 1
+#define FS_HYPER_MOONEY_RIVLIN 2
+#define FS_HYPER_YEOH 3
 #define FS_HYPER_TANGENT 1
 #define FS_HYPER_FORCE 2
 #define FS_HYPER_ENERGY 4
+#define FS_COEF_CELL_HYPER 11 /* fs_hyper_form.cell_params only: data[n_cells][4], one parameter row per cell in device cell order */
 typedef struct fs_hyper_form {
-    int model;           /* FS_HYPER_NEO_HOOKEAN */
-    double mu, lambda;   /* Lame parameters when lame.mode == FS_COEF_NONE */
+    int model;           /* FS_HYPER_NEO_HOOKEAN, _ST_VENANT_KIRCHHOFF, _MOONEY_RIVLIN or _YEOH */
+    double mu, lambda;   /* neo-Hookean, St Venant-Kirchhoff: Lame parameters when lame.mode == FS_COEF_NONE */
     fs_coef lame;        /* FS_COEF_NONE or FS_COEF_CELL_LAME: data[n_cells][2] = (mu, lambda), host, device cell order */
     int add;             /* 0: overwrite K / r; 1: add to them */
+    double params[4];    /* Mooney-Rivlin (c10, c01, kappa, -), Yeoh (c10, c20, c30, kappa) when cell_params.mode == FS_COEF_NONE */
+    fs_coef cell_params; /* FS_COEF_NONE or FS_COEF_CELL_HYPER: data[n_cells][4], rows as params, host, device cell order */
 } fs_hyper_form;
 typedef struct fs_hyper_info {
     double energy;
@@ -383,6 +410,7 @@ typedef struct fs_hyper_info {
 } fs_hyper_info;
 int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vector_t r, fs_vector_t u, const fs_hyper_form* form, int what,
                              fs_hyper_info* info);
+int fs_hyper_stress(fs_space_t space, fs_vector_t u, const fs_hyper_form* form, double* sigma, fs_hyper_info* info);
 
 /* ---- Small-strain J2 plasticity (PlasticitySolver; the reference names the class in its Readme and never delivers it) ----------
  * Rate-independent von Mises plasticity with linear isotropic hardening on a vector CG1 space over tetrahedra or triangles (plane
