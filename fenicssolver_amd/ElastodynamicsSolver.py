@@ -120,6 +120,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         self._K = self._M = None
         self._traces = self._energy = self._velocity = self._acceleration = None
         self._bounds = self._mass = None          # explicit scheme: (2/sqrt(lambda_G), 2/sqrt(lambda_P)), the lumped mass
+        self.nonfinite_steps = None               # explicit scheme, after a march that failed: (steps the library counted, the first)
 
     # ------------------------------------------------------------------ settings (host only)
     def dynamics_settings(self):
@@ -400,11 +401,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
             A_.close()
         load = b.get()[:V.n_owned]
         b.close()
-        d = self.dimension
-        rv = np.asarray(self.receiver_vertices, dtype=np.int64)
-        rec = (rv[:, None] * d + np.arange(d)[None, :]).ravel()
-        if loc is not None and len(rec):
-            rec = loc.dofs(rec, np.zeros(len(rec)))[0]
+        rec = self._receiver_dofs(loc)
         self._K, self._M = K, M
         self._dirichlet = (np.asarray(dofs, dtype=np.int32), np.asarray(vals, dtype=np.float64))
         self._load, self._par = load, par
@@ -412,39 +409,58 @@ class ElastodynamicsSolver(LinearElasticitySolver):
             self._setup_explicit(V)
         else:
             self.state = backend.DynamicsState(V)
-        return V, u0, v0, sf, sg, rec.astype(np.int32)
+        return V, u0, v0, sf, sg, rec
+
+    def _receiver_dofs(self, loc):
+        """the dofs (device order, every component) of the snapped receiver vertices"""
+        d = self.dimension
+        rv = np.asarray(self.receiver_vertices, dtype=np.int64)
+        rec = (rv[:, None] * d + np.arange(d)[None, :]).ravel()
+        if loc is not None and len(rec):
+            rec = loc.dofs(rec, np.zeros(len(rec)))[0]
+        return rec.astype(np.int32)
 
     # ------------------------------------------------------------------ the explicit scheme
-    def _setup_explicit(self, V):
-        """m = M 1, both step bounds and the state object of the central-difference marcher"""
+    def _lumped_mass(self, V, M):
+        """m = M 1 (device dof order); M is closed: the consistent mass has done its work"""
         from . import backend
-        K, M = self._K, self._M
         n = V.n_owned
         ones, md = backend.DeviceVector(V.n_local, np.ones(V.n_local)), backend.DeviceVector(n)
         M.spmv(ones, md)
         m = md.get()[:n].copy()
         ones.close()
         md.close()
-        M.close()                                                 # the consistent mass has done its work
-        self._M = None
+        M.close()
         if not (np.all(m > 0.0) and np.all(np.isfinite(m))):
-            raise SolverError('ElastodynamicsSolver: the lumped mass M 1 is not positive on every row (smallest entry {})'.format(m.min()))
-        dofs, vals = self._dirichlet
-        self._mass, self._bounds = m, time_marching.step_bounds(self, K, m, dofs)
-        dt = self.uniform_step()
+            raise SolverError('{}: the lumped mass M 1 is not positive on every row (smallest entry {})'.format(type(self).__name__, m.min()))
+        return m
+
+    def _check_step(self, dt):
+        """a step above the second bound is refused, one between the two is logged"""
+        who = type(self).__name__
         if dt > self._bounds[1]:
-            raise SolverError('ElastodynamicsSolver: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on '
+            raise SolverError('{}: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on '
                               'the largest eigenvalue): the explicit march is certain to blow up; the stable bound 2/sqrt(lambda_G) is '
-                              '{:.6g}'.format(dt, self._bounds[1], self._bounds[0]))
+                              '{:.6g}'.format(who, dt, self._bounds[1], self._bounds[0]))
         if dt > self._bounds[0]:
-            self.logger.warning('ElastodynamicsSolver: time_step %.6g lies between the stable bound 2/sqrt(lambda_G) = %.6g and '
-                                '2/sqrt(lambda_P) = %.6g', dt, self._bounds[0], self._bounds[1])
+            self.logger.warning('%s: time_step %.6g lies between the stable bound 2/sqrt(lambda_G) = %.6g and '
+                                '2/sqrt(lambda_P) = %.6g', who, dt, self._bounds[0], self._bounds[1])
+
+    def _setup_explicit(self, V):
+        """m = M 1, both step bounds and the state object of the central-difference marcher"""
+        from . import backend
+        m = self._lumped_mass(V, self._M)
+        self._M = None
+        dofs, vals = self._dirichlet
+        self._mass, self._bounds = m, time_marching.step_bounds(self, self._K, m, dofs)
+        dt = self.uniform_step()
+        self._check_step(dt)
         self.state = backend.ExplicitDynamicsState(V)
         self.state.configure(dt, self._par['rayleigh_mass'], m, load=self._load, dirichlet_dofs=dofs, dirichlet_values=vals)
 
     def _power_iteration(self, K, m, bc_dofs):
         """lambda_P, a lower bound on the largest eigenvalue of diag(1/m) K on the rows that are not Dirichlet"""
-        return time_marching.power_iteration(K, m, bc_dofs, 'ElastodynamicsSolver')
+        return time_marching.power_iteration(K, m, bc_dofs, type(self).__name__)
 
     def _explicit_only(self, what):
         if self.scheme() != 'explicit':
@@ -468,10 +484,23 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         freqs = (self.report_settings.get('plotting_freq', 0), self.report_settings.get('saving_freq', 0), self.energy_freq())
         return time_marching.batch_end(n, N, freqs, self._par['batch_steps'])
 
+    _not_finite = 'the state or its energy is not finite'
+
     def _blow_up_message(self, first, end):
-        return ('ElastodynamicsSolver: the state or its energy is not finite in steps {} .. {} (time_step {:.6g}; stable below '
+        return ('{}: {} in steps {} .. {} (time_step {:.6g}; stable below '
                 '2/sqrt(lambda_G) = {:.6g}, certain to blow up above 2/sqrt(lambda_P) = {:.6g})'.format(
-                    first, end, self.uniform_step(), self._bounds[0], self._bounds[1]))
+                    type(self).__name__, self._not_finite, first, end, self.uniform_step(), self._bounds[0], self._bounds[1]))
+
+    # what a step of the explicit march asks of the device state: the subclass with another force term overrides these four
+    def _march_start(self, u0d, v0d, sf0, sg0, sg1):
+        self.state.start(self._K, u0d, v0d, sf0, sg0, sg1)
+
+    def _march_advance(self, sf, sg, rec):
+        return self.state.advance(self._K, sf, sg, receivers=rec, traces=len(rec) > 0, energy=True, info=True)
+
+    def _first_step_potential(self, u1):
+        """the potential half of the energy row of the step 0 -> 1"""
+        return 0.5 * float(u1 @ self.state.work())
 
     def _publish_explicit(self, sf_n):
         u, _, _ = self.state.get()
@@ -480,27 +509,27 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         self._velocity, self._acceleration = self._function(v), self._function(a)
 
     def _solve_explicit(self):
+        self.operator_assemblies = self.amg_setups = 0
         V, u0, v0, sf, sg, rec = self._setup()
         t = self.time_points()
         dt = self.uniform_step()
         N, d = len(t) - 1, self.dimension
-        st, K, m = self.state, self._K, self._mass
+        st, m = self.state, self._mass
         efreq = self.energy_freq()
-        self.operator_assemblies = self.amg_setups = 0
         self.step_stats = []
         self._saved_frames = []
         traces = np.zeros((N + 1, len(rec) // d, d))
         energy = []
         # step 0 -> 1 on the device; its energy from the fields and the product of the start (set-up cost)
         u0d = self._to_dev(u0)
-        st.start(K, u0d, self._to_dev(v0), sf[0], sg[0], sg[1])
+        self._march_start(u0d, self._to_dev(v0), sf[0], sg[0], sg[1])
         u1, w1, _ = st.get()
         if not (np.all(np.isfinite(u1)) and np.all(np.isfinite(w1))):
             raise SolverError(self._blow_up_message(0, 1))
         if len(rec):
             traces[0], traces[1] = u0d[rec].reshape(-1, d), u1[rec].reshape(-1, d)
         if efreq == 1:
-            energy.append((1, 0.5 * float(np.sum(m * w1 * w1)), 0.5 * float(u1 @ st.work())))
+            energy.append((1, 0.5 * float(np.sum(m * w1 * w1)), self._first_step_potential(u1)))
         pvd = self.report_settings.get('result_filename') or 'result_file.pvd'
         n = 1                       # the state holds (u_n, w_n)
         self.current_step, self.current_time = 1, float(t[1])
@@ -516,9 +545,10 @@ class ElastodynamicsSolver(LinearElasticitySolver):
                 break
             end = self._batch_end(n, N)
             k = end - n
-            out = st.advance(K, sf[n:end], sg[n + 1:end + 1], receivers=rec, traces=len(rec) > 0, energy=True, info=True)
+            out = self._march_advance(sf[n:end], sg[n + 1:end + 1], rec)
             self.step_stats.append({'first_step': n, 'steps': k, 'device_ms': out['device_ms'], 'ms_per_step': out['device_ms'] / k})
             if out['n_nonfinite']:
+                self.nonfinite_steps = (out['n_nonfinite'], n + out['first_nonfinite_step'])      # what the library counted
                 raise SolverError(self._blow_up_message(n + out['first_nonfinite_step'], end))
             if len(rec):
                 traces[n + 1:end + 1] = out['traces'].reshape(k, -1, d)

@@ -1,7 +1,8 @@
 """fenicssolver_amd — MI355X-native assemble + Krylov-solve pipeline behind the
 FenicsSolver Python API (SolverBase / ScalarTransportSolver / ScalarTransportDGSolver /
 LinearElasticitySolver / NonlinearElasticitySolver / LargeDeformationSolver / PlasticitySolver /
-ViscoelasticitySolver / WaveSolver / ElastodynamicsSolver, JSON case settings).
+ViscoelasticitySolver / WaveSolver / ElastodynamicsSolver / HyperelasticDynamicsSolver, JSON case
+settings).
 
 Mirrors FenicsSolver/__init__.py:9-13 of the reference, except that importing
 the package never starts a solve by itself (the reference runs ``main(sys.argv)``

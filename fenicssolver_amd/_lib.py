@@ -326,6 +326,16 @@ SIGNATURES = {
     "fs_dyn_explicit_start": (C.c_int, [_H, _H, c_f64p, c_f64p, C.c_double, C.c_double, C.c_double]),
     "fs_dyn_explicit_advance": (C.c_int, [_H, _H, c_i64, c_f64p, c_f64p, c_i64, c_i32p, c_f64p, c_f64p, C.POINTER(fs_dyn_explicit_info)]),
     "fs_dyn_explicit_full_step": (C.c_int, [_H, _H, C.c_double, c_f64p, c_f64p]),
+    "fs_hyper_dyn_state_create": (C.c_int, [_H, C.POINTER(_H)]),
+    "fs_hyper_dyn_state_destroy": (C.c_int, [_H]),
+    "fs_hyper_dyn_state_configure": (C.c_int, [_H, C.c_double, C.c_double, c_f64p, c_f64p, c_i64, c_i32p, c_f64p]),
+    "fs_hyper_dyn_state_set": (C.c_int, [_H, c_f64p, c_f64p, c_i64]),
+    "fs_hyper_dyn_state_get": (C.c_int, [_H, c_f64p, c_f64p, c_i64p]),
+    "fs_hyper_dyn_start": (C.c_int, [_H, C.POINTER(fs_hyper_form), c_f64p, c_f64p, C.c_double, C.c_double, C.c_double]),
+    "fs_hyper_dyn_advance": (C.c_int, [_H, C.POINTER(fs_hyper_form), c_i64, c_f64p, c_f64p, c_i64, c_i32p, c_f64p, c_f64p,
+                                       C.POINTER(fs_march_info)]),
+    "fs_hyper_dyn_full_step": (C.c_int, [_H, C.POINTER(fs_hyper_form), C.c_double, c_f64p, c_f64p]),
+    "fs_hyper_dyn_internal_force": (C.c_int, [_H, C.POINTER(fs_hyper_form), c_f64p, c_f64p]),
     "fs_assemble_large_deformation":(C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
     "fs_assemble_viscous_stress_nn": (C.c_int, [_H, _H, C.c_double, _H, _H, C.c_double, C.c_double]),

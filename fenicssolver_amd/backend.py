@@ -960,8 +960,9 @@ class _MarcherState(_Handle):
         dofs = L.i32([] if dofs is None else dofs).ravel()
         return dofs, L.f64(np.broadcast_to(0.0 if values is None else values, dofs.shape))
 
-    def _batch_advance(self, entry, K, load_scale, dirichlet_scale, receivers, traces, energy, info):
-        """len(load_scale) steps on the device without a host round trip through the entry point `entry`; step k of the call
+    def _batch_advance(self, entry, head, load_scale, dirichlet_scale, receivers, traces, energy, info):
+        """len(load_scale) steps on the device without a host round trip through the entry point `entry`, whose leading arguments
+        (the matrix and the state, or the state and its material) are `head`; step k of the call
         advances n -> n+1 with load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1].  Returns {'traces': [n_steps, n_receivers]
         or None, 'energy': [n_steps, 2] = (kinetic, potential) or None, and with info 'device_ms', 'n_nonfinite',
         'first_nonfinite_step', 'step'}."""
@@ -973,7 +974,7 @@ class _MarcherState(_Handle):
         tr = np.empty((ns, rec.size)) if (traces and rec.size) else None
         en = np.empty((ns, 2)) if energy else None
         inf = L.fs_march_info() if info else None
-        L.check(getattr(L.load(), entry)(K.h, self.h, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
+        L.check(getattr(L.load(), entry)(*head, ns, L.p_f64(sf), L.p_f64(sg), rec.size, L.p_i32(rec) if rec.size else None,
                                          L.p_f64(tr), L.p_f64(en), C.byref(inf) if info else None), entry)
         out = {"traces": tr, "energy": en}
         if info:
@@ -1011,7 +1012,7 @@ class WaveState(_MarcherState):
 
     def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
         """a batch of steps through fs_wave_advance: see _MarcherState._batch_advance"""
-        return self._batch_advance("fs_wave_advance", K, load_scale, dirichlet_scale, receivers, traces, energy, info)
+        return self._batch_advance("fs_wave_advance", (K.h, self.h), load_scale, dirichlet_scale, receivers, traces, energy, info)
 
 
 def wave_advance(K, state, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
@@ -1118,13 +1119,67 @@ class ExplicitDynamicsState(_MarcherState):
 
     def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
         """a batch of steps through fs_dyn_explicit_advance: see _MarcherState._batch_advance"""
-        return self._batch_advance("fs_dyn_explicit_advance", K, load_scale, dirichlet_scale, receivers, traces, energy, info)
+        return self._batch_advance("fs_dyn_explicit_advance", (K.h, self.h), load_scale, dirichlet_scale, receivers, traces, energy, info)
 
     def full_step(self, K, load_scale_n):
         """(v_n, a_n) of the state's time point under s_f[n] = load_scale_n: one product, the state does not change"""
         v, a = np.empty(self.n), np.empty(self.n)
         L.check(L.load().fs_dyn_explicit_full_step(K.h, self.h, float(load_scale_n), L.p_f64(v), L.p_f64(a)), "fs_dyn_explicit_full_step")
         return v, a
+
+
+class HyperelasticDynamicsState(_MarcherState):
+    """Device state of the explicit finite-strain marcher on a vector CG1 space (fs_hyper_dyn_*): u_n (double-buffered inside the
+    library), w_n = v_{n-1/2}, the lumped mass m, the load F, the Dirichlet dofs with their values, dt, eta_M, the step counter n
+    and the device copy of the material.  Arrays are in DEVICE dof order.  The material is given once, as for
+    assemble_hyperelastic (per-cell arrays in device cell order); there is no matrix: every step evaluates the internal force."""
+    _create, _destroy = "fs_hyper_dyn_state_create", "fs_hyper_dyn_state_destroy"
+
+    def __init__(self, space, lame=None, model='neo_hookean', params=None):
+        super().__init__(space)
+        self._keep = []
+        self._form = _hyper_form("HyperelasticDynamicsState", space, lame, model, params, False, self._keep)
+
+    def configure(self, dt, eta_m, mass, load=None, dirichlet_dofs=None, dirichlet_values=None):
+        m = self._field(mass, "configure", "mass")
+        f = None if load is None else self._field(load, "configure", "load")
+        dofs, vals = self._dirichlet(dirichlet_dofs, dirichlet_values)
+        L.check(L.load().fs_hyper_dyn_state_configure(self.h, float(dt), float(eta_m), L.p_f64(m), L.p_f64(f), dofs.size, L.p_i32(dofs),
+                                                      L.p_f64(vals)), "fs_hyper_dyn_state_configure")
+
+    def set(self, u, w, step):
+        u, w = self._field(u, "set", "u"), self._field(w, "set", "w")
+        L.check(L.load().fs_hyper_dyn_state_set(self.h, L.p_f64(u), L.p_f64(w), int(step)), "fs_hyper_dyn_state_set")
+
+    def get(self):
+        """(u_n, w_n = v_{n-1/2}, n)"""
+        u, w, k = np.empty(self.n), np.empty(self.n), C.c_int64(0)
+        L.check(L.load().fs_hyper_dyn_state_get(self.h, L.p_f64(u), L.p_f64(w), C.byref(k)), "fs_hyper_dyn_state_get")
+        return u, w, k.value
+
+    def start(self, u0, v0, load_scale0=1.0, dirichlet_scale0=1.0, dirichlet_scale1=1.0):
+        """(u_1, w_{1/2}) from (u_0, v_0): n = 1"""
+        u0, v0 = self._field(u0, "start", "u0"), self._field(v0, "start", "v0")
+        L.check(L.load().fs_hyper_dyn_start(self.h, C.byref(self._form), L.p_f64(u0), L.p_f64(v0), float(load_scale0),
+                                            float(dirichlet_scale0), float(dirichlet_scale1)), "fs_hyper_dyn_start")
+
+    def advance(self, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
+        """a batch of steps through fs_hyper_dyn_advance: see _MarcherState._batch_advance; energy[k] = (E_kin(w_{n+1/2}), Pi(u_n))"""
+        return self._batch_advance("fs_hyper_dyn_advance", (self.h, C.byref(self._form)), load_scale, dirichlet_scale, receivers, traces,
+                                   energy, info)
+
+    def full_step(self, load_scale_n):
+        """(v_n, a_n) of the state's time point under s_f[n] = load_scale_n: the force is recomputed, the state does not change"""
+        v, a = np.empty(self.n), np.empty(self.n)
+        L.check(L.load().fs_hyper_dyn_full_step(self.h, C.byref(self._form), float(load_scale_n), L.p_f64(v), L.p_f64(a)),
+                "fs_hyper_dyn_full_step")
+        return v, a
+
+    def internal_force(self):
+        """(f_int(u_n), Pi(u_n)) of the held state"""
+        f, e = np.empty(self.n), C.c_double(0.0)
+        L.check(L.load().fs_hyper_dyn_internal_force(self.h, C.byref(self._form), L.p_f64(f), C.byref(e)), "fs_hyper_dyn_internal_force")
+        return f, e.value
 
 
 def assemble_viscous_stress(th_space, w, nu, p1_space, b, viscosity_law=None):

@@ -1,4 +1,4 @@
-// Scaffolding shared by the per-row time marchers (fs_wave.hip, fs_dynamics_explicit.hip, fs_dynamics.hip): everything of a marcher
+// Scaffolding shared by the per-row time marchers (fs_wave.hip, fs_dynamics_explicit.hip, fs_dynamics.hip, fs_hyper_dynamics.hip): everything of a marcher
 // that is not its update formula.  Header-only; every translation unit keeps its own copy of the one kernel.
 //
 //   row table      F with the Dirichlet values g in the slots of the Dirichlet rows, one flag byte per row (bit 0: Dirichlet row, bit 1: a
@@ -211,7 +211,7 @@ static inline int fs_march_advance(const char* who, fs_matrix_s* K, fs_march_bat
     const bool want_traces = traces && n_receivers > 0;
     hipStream_t s = fs_rt().stream;
     if (want_traces) FS_CHECK(st->set_receivers(n_receivers, receiver_dofs, s));
-    FS_CHECK(fs_spmv_prepare(K, s));
+    if (K) FS_CHECK(fs_spmv_prepare(K, s));                    // (nullptr: a marcher whose step has no product)
     dbuf<double> tr, en;
     dbuf<unsigned long long> bad;
     FS_CHECK(en.alloc(2 * n_steps));

@@ -30,7 +30,8 @@ def load_settings(case_input):
 
 
 _SOLVERS = ("CoupledNavierStokesSolver", "ScalarTransportSolver", "ScalarTransportDGSolver", "LinearElasticitySolver",
-            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver", "WaveSolver", "ElastodynamicsSolver")
+            "NonlinearElasticitySolver", "LargeDeformationSolver", "PlasticitySolver", "ViscoelasticitySolver", "WaveSolver", "ElastodynamicsSolver",
+            "HyperelasticDynamicsSolver")
 
 
 def main(case_input):
@@ -54,6 +55,8 @@ def main(case_input):
         from .WaveSolver import WaveSolver as cls
     elif solver_name == "ElastodynamicsSolver":
         from .ElastodynamicsSolver import ElastodynamicsSolver as cls
+    elif solver_name == "HyperelasticDynamicsSolver":
+        from .HyperelasticDynamicsSolver import HyperelasticDynamicsSolver as cls
     elif solver_name == "CoupledNavierStokesSolver":
         from .CoupledNavierStokesSolver import CoupledNavierStokesSolver as cls
     else:

@@ -676,6 +676,58 @@ int fs_dyn_explicit_advance(fs_matrix_t K, fs_dyn_explicit_state_t state, int64_
                             double* energy, fs_dyn_explicit_info* info);
 int fs_dyn_explicit_full_step(fs_matrix_t K, fs_dyn_explicit_state_t state, double load_scale_n, double* v_out, double* a_out);
 
+/* ---- Explicit finite-strain dynamics (HyperelasticDynamicsSolver; no counterpart in the reference) ------------------------------
+ * M a + C v + f_int(u) = s_f(t) F on a vector CG1 space over tetrahedra or triangles (true plane strain), one rank: the scheme of
+ * fs_dyn_explicit_* with the product K u_n replaced by the internal force f_int(u_n) = dPi/du of one of the four energies of
+ * fs_hyper_form, evaluated at the current displacement in every step.  Lumped mass m = M 1 of the reference configuration,
+ * C = eta_M diag(m), alpha = eta_M dt / 2; the state is (u_n, w_n) with w_n = v_{n-1/2} and a step n -> n+1 (n >= 1) is, per row i,
+ *   (1 + alpha) w_{n+1/2} = (1 - alpha) w_{n-1/2} + dt (s_f[n] F - f_int(u_n)) / m,      u_{n+1} = u_n + dt w_{n+1/2},
+ * and on a Dirichlet row u_{n+1} = g_i s_g[n+1], w_{n+1/2} = (u_{n+1} - u_n) / dt.  Start: the Dirichlet rows of u_0 take g s_g[0];
+ * a_0 = (s_f[0] F - f_int(u_0)) / m - eta_M v_0, w_{1/2} = v_0 + dt/2 a_0, u_1 = u_0 + dt w_{1/2} (Dirichlet rows by the rule above,
+ * with s_g[1]).  Loads are dead loads.  Energy of the step n -> n+1, its two halves reported separately:
+ *   E_kin = 1/2 sum_i m_i w_{n+1/2,i}^2,   Pi(u_n) = int psi(F(u_n)) dx
+ * - the potential half is taken at t_n, where the force is evaluated (fs_dyn_explicit_advance reports 1/2 u_{n+1}^T K u_n).  psi = 0
+ * at rest for all four energies in both dimensions: in plane strain the neo-Hookean energy is taken with F embedded in 3 x 3 like
+ * the other three (the "- 3" shift of the 2-D energy of fs_assemble_hyperelastic does not appear here).
+ * A step is ONE kernel launch: one thread per node gathers the force and its share of Pi over the incident cells and applies the
+ * update, the Dirichlet rows, the receiver samples and the energy partials.  u is double-buffered inside the state (the gather reads
+ * the neighbours' u_n while their threads write u_{n+1}); the buffers swap per step and the calls below always see u_n.
+ *   fs_hyper_dyn_state_create     a zero state (n = 0) on a vector CG1 space     fs_hyper_dyn_state_destroy   frees it
+ *   fs_hyper_dyn_state_configure  dt, eta_M and the arrays mass[n_dofs], load[n_dofs] (NULL: none), the Dirichlet dofs and values
+ *                                 (a dof named twice takes the last value); keeps (u, w) and the step counter
+ *   fs_hyper_dyn_state_set / get  (u_n, w_n) and the step counter n >= 1 from / to the host (get: any pointer may be NULL)
+ *   fs_hyper_dyn_start            forms (u_1, w_{1/2}) from (u_0, v_0) with s_f[0], s_g[0] and s_g[1]: n = 1
+ *   fs_hyper_dyn_advance          n_steps steps enqueued back to back with no host synchronisation between them; step k of the call
+ *                                 advances n -> n+1 with load_scale[k] = s_f[n] and dirichlet_scale[k] = s_g[n+1];
+ *                                 traces[k][r] = u_{n+1}[receiver_dofs[r]], energy[k] = (E_kin(w_{n+1/2}), Pi(u_n)) (either may be NULL)
+ *   fs_hyper_dyn_full_step        v_n = (w_{n-1/2} + w+)/2 and a_n = (w+ - w_{n-1/2})/dt of the state's time point, w+ the recurrence's
+ *                                 w_{n+1/2} under load_scale_n = s_f[n] (the force is recomputed, nothing is stored, the state does
+ *                                 not change); on Dirichlet rows v_n = w_{n-1/2}, a_n = 0.  Either output may be NULL
+ *   fs_hyper_dyn_internal_force   f_int(u_n)[n_dofs] and Pi(u_n) of the held state (either may be NULL)
+ * form: the material, constant parameters or per-cell rows as for fs_assemble_hyperelastic (`add` is ignored); it is checked at every
+ * call and uploaded only when it differs from what the state holds - never per step.
+ * A cell with J <= 0 or J not finite makes Pi of its step NaN (for every energy: St Venant-Kirchhoff itself stays finite there), so
+ * the finishing pass of the batch counts that step in info->n_nonfinite / first_nonfinite_step, as it counts a non-finite field.
+ * The energy partials are summed in a fixed order (no floating-point atomics): a repeated run gives the same bits, and so does any
+ * split of a march into calls.  The call waits for the device only if it hands data back (traces, energy or info).
+ * FS_ERR_INVALID with a message: DG, CG2 or scalar spaces, several ranks, dt <= 0 or not finite, eta_M < 0, m_i <= 0, an unknown
+ * model or a parameter row its model refuses (fs_assemble_hyperelastic), a time factor that is not finite, a receiver or Dirichlet
+ * dof out of range, a state that was not configured / started. */
+typedef struct fs_hyper_dyn_state_s* fs_hyper_dyn_state_t;
+int fs_hyper_dyn_state_create(fs_space_t space, fs_hyper_dyn_state_t* out);
+int fs_hyper_dyn_state_destroy(fs_hyper_dyn_state_t state);
+int fs_hyper_dyn_state_configure(fs_hyper_dyn_state_t state, double dt, double eta_m, const double* mass, const double* load,
+                                 int64_t n_dirichlet, const int32_t* dirichlet_dofs, const double* dirichlet_values);
+int fs_hyper_dyn_state_set(fs_hyper_dyn_state_t state, const double* u, const double* w, int64_t step);
+int fs_hyper_dyn_state_get(fs_hyper_dyn_state_t state, double* u, double* w, int64_t* step);
+int fs_hyper_dyn_start(fs_hyper_dyn_state_t state, const fs_hyper_form* form, const double* u0, const double* v0, double load_scale0,
+                       double dirichlet_scale0, double dirichlet_scale1);
+int fs_hyper_dyn_advance(fs_hyper_dyn_state_t state, const fs_hyper_form* form, int64_t n_steps, const double* load_scale,
+                         const double* dirichlet_scale, int64_t n_receivers, const int32_t* receiver_dofs, double* traces,
+                         double* energy, fs_march_info* info);
+int fs_hyper_dyn_full_step(fs_hyper_dyn_state_t state, const fs_hyper_form* form, double load_scale_n, double* v_out, double* a_out);
+int fs_hyper_dyn_internal_force(fs_hyper_dyn_state_t state, const fs_hyper_form* form, double* f_out, double* energy_out);
+
 /* ---- Large-deformation elasticity (LargeDeformationSolver.py:80-135) ---------------------------------------------------------
  * Mixed CG1 (u, v, p), one Crank-Nicolson step (q; dt), F = I + grad u, J = det F, S = J (-p I + mu (B - I)) F^-T, pp = p/lambda +
  * J^2 - 1, follower loads J F^-T g on boundary facets.  The u rows are linear, du = dt (q dv - r_u) with r_u = (u - u0)/dt - q v -
