@@ -242,6 +242,7 @@ SIGNATURES = {
     "fs_last_product_kind": (C.c_int, []),
     "fs_last_iteration_form": (C.c_int, []),
     "fs_last_iteration_guard": (C.c_int, []),
+    "fs_last_iteration_runs": (C.c_int, []),
     "fs_amg_setup": (C.c_int, [_H, C.c_int, c_f64p, C.POINTER(fs_amg_opts), C.POINTER(_H)]),
     "fs_amg_attach_distributed_fine": (C.c_int, [_H, _H, c_i64, c_i32p]),
     "fs_amg_destroy": (C.c_int, [_H]),

@@ -1677,6 +1677,12 @@ def last_iteration_guard():
     return int(L.load().fs_last_iteration_guard())
 
 
+def last_iteration_runs():
+    """How many of a Kuhn-box row's seven runs the one-launch CG iteration of the last solve left out because every row class of the
+    operator held nothing above 2^-53 of its unit diagonal there (fs_last_iteration_runs, option "cg_zero_runs"): 0 or 2."""
+    return int(L.load().fs_last_iteration_runs())
+
+
 def set_option(name, value):
     L.check(L.load().fs_set_option(name.encode(), float(value)), "fs_set_option")
 

@@ -61,6 +61,7 @@ struct row_dict {
     dbuf<double> slot_d, dtab;
     bool dtab_valid = false;                // the kept tables come with a dtab
     bool dtab_ok = false;                   // ... and every row of THIS call's weight vector equals its class's entry
+    int nz_slots = ~0;                      // bit j: some class row of the tables holds a coefficient above 2^-53 in run j of its plan (k_dict_compact: info[5]; kept with the tables)
     int ncls = 0, S = 0, C = 0, bs = 1;     // classes, doubles per class row, most classes of any item, block size of the matrix
     const double* built_for = nullptr;      // the value array the classes describe (nullptr: plain form in use)
     uint64_t space_serial = 0;              // ... of this space
@@ -127,6 +128,14 @@ static int g_cg_pair = getenv("FS_CG_PAIR") ? (atoi(getenv("FS_CG_PAIR")) != 0) 
 // option "cg_guard": the LIGHT / PAIR launches run on work vectors with guard bands of zeros and without the edge-item path (k_dict_cg_iter,
 // GUARD / CENTRE); 0: the unguarded vectors and the kernels with the clamped path
 static int g_cg_guard = getenv("FS_CG_GUARD") ? (atoi(getenv("FS_CG_GUARD")) != 0) : 1;
+// option "cg_zero_runs": on a Kuhn box whose class rows hold nothing above 2^-53 (of a unit diagonal) in the runs of slots 1 and 7 - pure
+// diffusion on orthogonal edges, the 7-point stencil - the LIGHT / PAIR launches neither load nor multiply those runs (k_dict_cg_iter,
+// ZRUNS): -1 automatic (from "cg_zero_runs_min_rows" rows on), 0 never, 1 wherever it applies.  Iterates equal the seven-run form's to
+// rounding, not bit for bit - hence never below 100 000 rows in automatic mode: the bit-for-bit tests of the forms run below that
+static int g_cg_zero_runs = getenv("FS_CG_ZERO_RUNS") ? atoi(getenv("FS_CG_ZERO_RUNS")) : -1;
+#define FS_CG_ZERO_RUNS_FLOOR_ROWS 100000
+static int64_t g_cg_zero_runs_min_rows = FS_CG_ZERO_RUNS_FLOOR_ROWS;       // (faster at every cube measured from n = 49 on: profiles/r10_cg_zero_runs_sizes.txt)
+static int g_last_iteration_runs = 0;    // fs_last_iteration_runs()
 static int g_cg_poison_p = 0;            // option "cg_poison_p" (tests): the next CG solve finds NaN in its search-direction workspace
 static int g_last_iteration_form = 0;    // bits 0, 1: fs_last_iteration_form(); bits 2, 3: fs_last_iteration_guard()
 static int g_cg_fused = -1;      // one launch per CG iteration on row-dictionary operators: -1 automatic, 0 never, 1 wherever it applies
@@ -166,6 +175,11 @@ extern "C" int fs_set_option(const char* name, double value) {
         g_cg_pair = value != 0.0;
     } else if (!strcmp(name, "cg_guard")) {
         g_cg_guard = value != 0.0;
+    } else if (!strcmp(name, "cg_zero_runs")) {
+        g_cg_zero_runs = value < 0.0 ? -1 : (value != 0.0);
+    } else if (!strcmp(name, "cg_zero_runs_min_rows")) {
+        FS_REQUIRE(value >= FS_CG_ZERO_RUNS_FLOOR_ROWS, "cg_zero_runs_min_rows must be >= %d (below, the automatic mode keeps all seven runs, whose iterates are bit-identical to the two-launch iteration)", FS_CG_ZERO_RUNS_FLOOR_ROWS);
+        g_cg_zero_runs_min_rows = (int64_t)value;
     } else if (!strcmp(name, "cg_poison_p")) {
         g_cg_poison_p = value != 0.0;
     } else if (!strcmp(name, "update_blocks")) {
@@ -783,7 +797,8 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
     FS_HIP(hipMemsetAsync(D.slot_vals.p, 0, (size_t)FS_DICT_CAP * S * sizeof(double), s));
     hipLaunchKernelGGL(k_dict_insert, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_dict_items, items, plans, sp->slice_ptr.p, sp->dia_ptr.p, sp->dia_off.p,
                        val, nq, sp->sell_entries, S, sp->dict_run_len, D.keys.p, D.keys.p, D.slot_vals.p, D.cls_slot.p, D.info.p, sp->dict_runs, dvec, D.slot_d.p);
-    hipLaunchKernelGGL(k_dict_compact, dim3(1), dim3(1024), 0, s, D.keys.p, D.slot_vals.p, S, D.slot2cls.p, D.values.p, D.nnz.p, dvec ? D.slot_d.p : nullptr, D.dtab.p);
+    hipLaunchKernelGGL(k_dict_compact, dim3(1), dim3(1024), 0, s, D.keys.p, D.slot_vals.p, S, D.slot2cls.p, D.values.p, D.nnz.p, dvec ? D.slot_d.p : nullptr, D.dtab.p,
+                       D.info.p, nq * sp->dict_run_len);
     hipLaunchKernelGGL(k_dict_finish, dim3(grid), dim3(FS_BLOCK), 0, s, sp->n_dict_items, items, plans, sp->slice_ptr.p, sp->dia_ptr.p, sp->dia_off.p,
                        val, nq, sp->sell_entries, S, sp->dict_run_len, D.slot2cls.p, D.values.p, D.nnz.p, D.cls_slot.p, D.cls.p, D.info.p, nullptr, sp->dict_runs,
                        dvec, D.dtab.p);
@@ -801,6 +816,18 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
         ++D.n_failed;
         return FS_OK;
     }
+    if (getenv("FS_KRYLOV_DEBUG") && A->bs == 1 && S >= 24 && h[0] > 0 && h[0] <= FS_DICT_MAX) {     // (the largest coefficient of each run over all class rows)
+        std::vector<double> hv((size_t)h[0] * S);
+        FS_CHECK(D.values.download(hv.data(), (int64_t)hv.size(), s));
+        fprintf(stderr, "[fs_krylov] row dictionary: runs with a coefficient above 2^-53: mask 0x%x; largest |coefficient| by run:", h[5]);
+        for (int j = 0; j < S / sp->dict_run_len; ++j) {
+            double m = 0.0;
+            for (int c = 0; c < h[0]; ++c)
+                for (int t = 0; t < sp->dict_run_len; ++t) m = std::max(m, std::fabs(hv[(size_t)c * S + j * sp->dict_run_len + t]));
+            fprintf(stderr, " %.3e", m);
+        }
+        fprintf(stderr, "\n");
+    }
     adopt(h, h[0]);
     D.kept = false;
     D.tables_space = sp->serial;
@@ -810,6 +837,7 @@ static int dict_build_impl(fs_matrix_s* A, const double* val, hipStream_t s, con
     // (rows of one class with different weights - classes are keyed on the SCALED rows, the weights are 1 / a_ii of the unscaled matrix:
     // the iteration kernel keeps its weight stream for this operator)
     D.dtab_valid = D.dtab_ok = dvec != nullptr && h[4] == 0;
+    D.nz_slots = h[5];
     ++D.n_built;
     return FS_OK;
 }

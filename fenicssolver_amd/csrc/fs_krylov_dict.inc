@@ -259,9 +259,13 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_insert(int64_t n_items, const
 }
 
 // number the occupied slots; values[id][S] = the class rows in plan layout, nnz[id] = their nonzero positions
+// info[5] (run_width > 0): bit j set = some class row holds a coefficient above 2^-53 in magnitude in run j of its plan (run_width doubles
+// per run; runs from 30 on share bit 30).  The class rows of a scalar operator are rows of D^-1/2 A D^-1/2, unit diagonal: a run whose bit
+// stays clear adds less than half an ulp of the diagonal term to any row's product (k_dict_cg_iter, ZRUNS)
 __global__ void __launch_bounds__(1024) k_dict_compact(const unsigned long long* __restrict__ keys, const double* __restrict__ slot_vals,
                                                        int S, int32_t* __restrict__ slot2cls, double* __restrict__ values, int32_t* __restrict__ nnz,
-                                                       const double* __restrict__ slot_d = nullptr, double* __restrict__ dtab = nullptr) {
+                                                       const double* __restrict__ slot_d = nullptr, double* __restrict__ dtab = nullptr,
+                                                       int* __restrict__ info = nullptr, int run_width = 0) {
     constexpr int PER = FS_DICT_CAP / 1024;       // consecutive slots per thread
     __shared__ int cnt[1024];
     const int t = threadIdx.x;
@@ -281,13 +285,15 @@ __global__ void __launch_bounds__(1024) k_dict_compact(const unsigned long long*
         const bool used = keys[slot] != 0ull;
         slot2cls[slot] = used ? id : -1;
         if (used && id < FS_DICT_MAX) {
-            int nz = 0;
+            int nz = 0, runs = 0;
             for (int k = 0; k < S; ++k) {
                 const double v = slot_vals[(int64_t)slot * S + k];
                 values[(int64_t)id * S + k] = v;
                 nz += v != 0.0;
+                if (run_width > 0 && fabs(v) > 0x1p-53) runs |= 1 << (k / run_width < 30 ? k / run_width : 30);
             }
             nnz[id] = nz;
+            if (runs) atomicOr(&info[5], runs);
             if (slot_d) dtab[id] = slot_d[slot];
         }
         id += used;

@@ -460,6 +460,14 @@ __device__ long long g_iter_dbg[FS_STAMPS * 4096];
 // -DFS_ITER_ABLATE_PXD (probe builds only, wrong numerics): the kernel without the loads and stores of p, x and the dot weights - what
 // the launch costs without the 40 B per row that do nothing for the recurrence (tools/probes/fused_iter_probe.py with FS_PROBE_LIB;
 // profiles/r07_cg_pair_ablation.txt: 18.8 against 21.7 us per launch at 1 M rows)
+// -DFS_ITER_ABLATE_RUNS (probe builds only; wrong numerics wherever those runs carry a coefficient): EVERY CENTRE launch drops the runs of
+// slots 1 and 7 as ZRUNS does - 2 of the 7 runs a Kuhn-box row multiplies, 29 % of the run loads and of the recomputed-residual fma
+// pairs.  Timing ablation of profiles/r10_cg_lines_ablation.txt (tools/probes/fused_iter_probe.py with FS_PROBE_LIB).
+#ifdef FS_ITER_ABLATE_RUNS
+#define FS_ABLATE_RUNS true
+#else
+#define FS_ABLATE_RUNS false
+#endif
 // COMM: a decomposed space - the three sums come reduced over the ranks from `sums` (k_cg_p2p_exchange<true> before this launch put
 // them there, stored the neighbours' w into the ghost rows of w_in and advanced the ghost rows of r_out / s_out); the neighbour
 // columns of an item may then be ghost columns: n_cols counts them.
@@ -489,6 +497,15 @@ __device__ long long g_iter_dbg[FS_STAMPS * 4096];
 // new s, the old r and the new r of the own rows are (value.y, next lane's value.x) of slot 4, the same memory words through the same two
 // fmas.  Lane 63 has no rows of its own and loads what lane 62 needs.
 // Measured at 1 M rows: profiles/r08_cg_guard_ab.txt, r08_cg_guard_trace_*.csv, r08_iter_edge_timeline.txt (DESIGN.md section 3).
+// ZRUNS (with CENTRE and DTAB, option "cg_zero_runs"; the host takes it where NO class row of the solve's dictionary holds a coefficient
+// above 2^-53 at any position of slots 1 and 7 - row_dict::nz_slots, found from the class table itself): the runs (-(a + b + 1); 2) and
+// (a + b; 2) are neither loaded nor multiplied - 15 instead of 21 run loads per item, 30 instead of 42 coefficient reads and fma pairs.
+// They are the (0, 1, 1) and (1, 1, 1) diagonals of the Kuhn split, whose P1 stiffness entries vanish on a box with orthogonal edges:
+// the pure diffusion operator is the 7-point stencil, and what the assembly leaves there is the rounding of sums that cancel (1.9e-17
+// at most on the unit cube, against a unit diagonal).  The two runs are each other's transposes: the operator stays symmetric.  NOT the
+// same bits: a row's product loses terms below half an ulp of its diagonal term; iterates equal the seven-run form's to rounding, the
+// true residual at the end of a pass is taken with the whole operator.  A mass or reaction term fills those entries and the host keeps
+// the seven runs.
 // PROLOGUE (every form): the dictionary and the DTAB table go into LDS by direct-to-LDS loads issued first (fs_fill_lds_issue); every wave
 // waits for its own with a counted s_waitcnt in front of the ONE barrier of the sums, which publishes them, and in front of the early
 // return.  With GUARD nothing between kernel entry and that barrier waits for the first item's run loads: the sums are reduced under
@@ -503,7 +520,7 @@ __device__ __forceinline__ fs_v2du fs_ld_pair(const double* base, int32_t st, ui
 __device__ __forceinline__ fs_v2du fs_ld_pair(fs_gcd base, int32_t st, uint32_t boff) {
     return *(const __attribute__((address_space(1))) fs_v2du*)((const __attribute__((address_space(1))) char*)(base + st) + boff);
 }
-template <int RL, bool COMM, int MODE = FS_ITER_EVERY, bool DTAB = false, bool GUARD = false, bool CENTRE = false>
+template <int RL, bool COMM, int MODE = FS_ITER_EVERY, bool DTAB = false, bool GUARD = false, bool CENTRE = false, bool ZRUNS = false>
 __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64_t n_items, const int4* __restrict__ items,
                                                            const dict_plan_round* __restrict__ plans, const uint16_t* __restrict__ cls,
                                                            const double* __restrict__ dict, int S, int C,
@@ -519,6 +536,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     // the iteration this launch is working on - written by one lane with relaxed system-scope stores (no fence: nothing is ordered
     // against them).  The host enqueues the next launches from what it reads there (fs_krylov_solve) instead of copying the status
     // word back behind every batch, and stops within a few launches of the end instead of a batch and a half after it.
+    static_assert(!ZRUNS || (CENTRE && DTAB && RL == 3), "ZRUNS: the Kuhn box with the class table of dot weights");
+    // (run j of half round h is dropped: slots 1 and 7)
+    constexpr bool DROP17 = ZRUNS || (FS_ABLATE_RUNS && CENTRE);
+    auto dropped = [](int h, int j) { return DROP17 && ((h == 0 && j == 1) || (h == 1 && j == 3)); };
     FS_STAMP(0);
     // The launch is latency-bound at the sizes it is used for (a wave has two work items at 1 M rows), and what it reads first was
     // written by the previous launch on other XCDs - every dependent load is a round trip to the Infinity Cache (1 - 2 us).  So
@@ -590,7 +611,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
         for (int j = 0; j < 4; ++j) sts[j] = __builtin_amdgcn_readfirstlane(H.pl[rd].start[4 * h + j]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (skip0 && j == 0) { A[0] = Wb[0] = Sb[0] = v2d{0.0, 0.0}; continue; }
+            if ((skip0 && j == 0) || dropped(h, j)) { A[j] = Wb[j] = Sb[j] = v2d{0.0, 0.0}; continue; }
             const int32_t st = sts[j];
             if (pre) { A[j] = fs_ld_pair(r_pre, st, boff); Wb[j] = fs_ld_pair(w_pre, st, boff); Sb[j] = fs_ld_pair(s_pre, st, boff); }
             else { A[j] = fs_ld_pair(r_in, st, boff); Wb[j] = fs_ld_pair(w_in, st, boff); Sb[j] = fs_ld_pair(s_in, st, boff); }
@@ -643,7 +664,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
     v2d PA[4], PW[4], PS[4], Ppp = {0.0, 0.0}, Pxx = {0.0, 0.0}, Pdd = {0.0, 0.0}, Prp = {0.0, 0.0};
     const bool have0 = it.cur < it.end && it.cur * 4 + wave < n_items;
     // (the vector loads the wave has certainly issued behind the dictionary's and the partials' when it comes to the sums: the run loads)
-    constexpr int RUN_LOADS0 = GUARD ? 3 * (CENTRE ? 3 : 4) : 0;
+    constexpr int RUN_LOADS0 = GUARD ? 3 * ((CENTRE ? 3 : 4) - (DROP17 ? 1 : 0)) : 0;
     if (GUARD) {
         H0 = decode(have0 ? it.cur * 4 + wave : 0);
         load_own_pre(H0, have0, Ppp, Pxx, Pdd, Prp);        // (in front of the run loads: those are the LAST loads of every wave)
@@ -778,7 +799,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
                     // the new r on these columns: r - alpha (w + beta s), two fmas per value - the owner's operations, the owner's bits
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        if (skip0 && j == 0) continue;
+                        if ((skip0 && j == 0) || dropped(h, j)) continue;
                         v2d sn;
                         sn.x = fma(beta, Sb[j].x, Wb[j].x); sn.y = fma(beta, Sb[j].y, Wb[j].y);
                         if (!CENTRE && h == 0 && j == 0 && rd == 0) { sn0 = sn; ro0 = A[0]; }
@@ -794,7 +815,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_dict_cg_iter(int64_t n_cols, int64
                     if (CENTRE && h == 1) { zi.x = A[0].y; zi.y = fs_from_next_lane(A[0].x); }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        if (skip0 && j == 0) continue;
+                        if ((skip0 && j == 0) || dropped(h, j)) continue;
                         run_terms(A[j], v0 + RL * (8 * rd + 4 * h + j), v1 + RL * (8 * rd + 4 * h + j));
                         asm volatile("" ::: "memory");
                     }

@@ -176,7 +176,7 @@ struct solve_plan {
     const box_iter_plan_s* BI = nullptr;    // the one-launch iteration in marching-window form (k_box_cg_iter)
     bool fused = false;                     // one launch per iteration on one GPU
     bool fusedp_ok = false;                 // ... behind the exchange kernel on a decomposed space, where the pass uses that exchange
-    bool pair_form = false, dtab_form = false, guard_form = false, centre_form = false;
+    bool pair_form = false, dtab_form = false, guard_form = false, centre_form = false, zruns_form = false;
     int64_t guard = 0;                      // zeros in front of and behind the six vectors of the guarded form
     std::chrono::steady_clock::time_point t_begin;
 };
@@ -226,7 +226,7 @@ struct pass_state {
     // carried from pass to pass
     int total_iters = 0, n_pass = 0, n_launches = 0;
     bool use_guess = false, fusedp_used = false;
-    int iteration_form = 0;
+    int iteration_form = 0, iteration_runs = 0;
     int h_status[4] = {0, 0, 0, 0};
     double true_rr = 0.0, thresh = 0.0, bb_host = 0.0, prev_true_rr = 1e300;
     // set by begin_pass
@@ -447,6 +447,10 @@ static int choose_iteration_form(solve_plan& P, krylov_ws& ws) {
     // path.  The bands are zeroed with the block and nothing writes them: every kernel that gets these pointers writes rows of [0, nl + 2).
     P.guard_form = g_cg_guard != 0 && P.pair_form && P.fused && !P.BI;
     P.centre_form = P.guard_form && sp->dict_centre;
+    // ... without the runs of slots 1 and 7 where no class row of this solve's dictionary holds a coefficient above 2^-53 there (option
+    // "cg_zero_runs"; automatic mode: from cg_zero_runs_min_rows rows on, never below 100 000 - iterates equal to rounding only)
+    P.zruns_form = P.centre_form && P.dtab_form && (g_dict.nz_slots & ((1 << 1) | (1 << 7))) == 0 && g_cg_zero_runs != 0 &&
+                   (g_cg_zero_runs > 0 || P.n >= std::max<int64_t>(g_cg_zero_runs_min_rows, FS_CG_ZERO_RUNS_FLOOR_ROWS));
     P.guard = P.guard_form ? 32 * ((std::max<int64_t>(-(int64_t)sp->dict_min_start, sp->dict_max_start) + 130 + 31) / 32) : 0;
     if (P.fused || P.fusedp_ok) {
         dbuf<double>* const six[6] = {&ws.z, &ws.w, &ws.s, &ws.z2, &ws.w2, &ws.s2};
@@ -891,7 +895,7 @@ static int run_graph_batch(const solve_plan& P, pass_state& ps, krylov_ws& ws, i
 // stores the neighbours' w into the ghost rows of the current w and advances the ghost rows of r and s into the next buffers
 struct one_launch {
     double *Z[2], *W[2], *SV[2], *PT[2];
-    bool pair, dtab, guarded, centre;
+    bool pair, dtab, guarded, centre, zruns;
     size_t lds;
     const double* weights;
     fs_p2p_rowsred red2[2];
@@ -909,6 +913,8 @@ static int one_launch_setup(const solve_plan& P, pass_state& ps, krylov_ws& ws, 
     L.dtab = L.pair && P.dtab_form;
     L.guarded = L.pair && P.guard_form;
     L.centre = L.pair && P.centre_form;
+    L.zruns = L.centre && L.dtab && P.zruns_form;
+    ps.iteration_runs = L.zruns ? 2 : 0;
     ps.iteration_form = (L.pair ? 1 : 0) | (L.dtab ? 2 : 0) | (L.guarded ? 4 : 0) | (L.centre ? 8 : 0);
     L.lds = (size_t)g_dict.ncls * (g_dict.S + (L.dtab ? 1 : 0)) * sizeof(double);
     L.weights = L.dtab ? g_dict.dtab.p : ws.dvec.p;
@@ -927,10 +933,10 @@ static void launch_dict_iter(const solve_plan& P, const pass_state& ps, krylov_w
                        ws.ctrl.p, ws.scal.p, ws.status.p, ws.it_ctr.p, par, ps.hist_p, dict_map_xcd(), ws.sums.p, ps.mirror_dev);
 }
 // the LIGHT (even) or PAIR (odd) launch (launch parity = iteration parity: it_ctr is zeroed at k = 0)
-template <bool DT, bool GU, bool CE>
+template <bool DT, bool GU, bool CE, bool ZR = false>
 static void launch_dict_pair(const solve_plan& P, const pass_state& ps, krylov_ws& ws, const one_launch& L, int par) {
-    if (par) launch_dict_iter<false, FS_ITER_PAIR, DT, GU, CE>(P, ps, ws, L, par);
-    else launch_dict_iter<false, FS_ITER_LIGHT, DT, GU, CE>(P, ps, ws, L, par);
+    if (par) launch_dict_iter<false, FS_ITER_PAIR, DT, GU, CE, ZR>(P, ps, ws, L, par);
+    else launch_dict_iter<false, FS_ITER_LIGHT, DT, GU, CE, ZR>(P, ps, ws, L, par);
 }
 
 template <int AHEAD>
@@ -956,6 +962,7 @@ static void launch_iter(const solve_plan& P, const pass_state& ps, krylov_ws& ws
         launch_exchange(P, ps, ws, L, par);
         launch_dict_iter<true>(P, ps, ws, L, par);
     } else if (!L.pair) launch_dict_iter<false>(P, ps, ws, L, par);
+    else if (L.zruns) launch_dict_pair<true, true, true, true>(P, ps, ws, L, par);
     else if (L.centre) { if (L.dtab) launch_dict_pair<true, true, true>(P, ps, ws, L, par); else launch_dict_pair<false, true, true>(P, ps, ws, L, par); }
     else if (L.guarded) { if (L.dtab) launch_dict_pair<true, true, false>(P, ps, ws, L, par); else launch_dict_pair<false, true, false>(P, ps, ws, L, par); }
     else if (L.dtab) launch_dict_pair<true, false, false>(P, ps, ws, L, par);
@@ -998,7 +1005,7 @@ static int one_launch_batch(const solve_plan& P, pass_state& ps, krylov_ws& ws, 
         key.snd_own_recv = L.snd2[0].own_recv; key.red_own_buf = L.red2[0].own_buf;
         if (ps.fusedp) { key.p2p_on = 1; key.p2p_generation = (int64_t)sp->halo.p2p.generation; }
         key.p2p_rows_cap = ps.p2p_rows_cap;
-        key.bsz = bsz; key.box_ahead = P.BI ? P.BI->ahead : 0; key.iteration_form = ps.iteration_form; key.igrid = P.igrid;
+        key.bsz = bsz; key.box_ahead = P.BI ? P.BI->ahead : 0; key.iteration_form = ps.iteration_form | ps.iteration_runs << 8; key.igrid = P.igrid;
         key.mirror = ps.mirror_dev != nullptr;
         FS_CHECK(ws.cgf_graph.replay(key, bsz, P.s, [&](int i) { launch_iter(P, ps, ws, L, i & 1); return FS_OK; }));
         ps.k = kend;
@@ -1211,6 +1218,7 @@ static void fill_stats(const solve_plan& P, const pass_state& ps, const krylov_w
     stats->launches = ps.n_launches;
     stats->product_kind = P.fused ? (P.BI ? 3 : 1) : g_last_product_kind;
     g_last_iteration_form = (P.fused || ps.fusedp_used) ? ps.iteration_form : 0;
+    g_last_iteration_runs = (P.fused || ps.fusedp_used) ? ps.iteration_runs : 0;
     if (P.fused) stats->update_ms = 0.0;       // (spmv_ms is the whole iteration: one launch)
 }
 
@@ -1278,6 +1286,7 @@ extern "C" int fs_krylov_solve(fs_matrix_t A, fs_vector_t b, fs_vector_t x, cons
 // (the guard bits have an accessor of their own: callers of fs_last_iteration_form compare the word with PAIR | DTAB)
 extern "C" int fs_last_iteration_form() { return g_last_iteration_form & 3; }
 extern "C" int fs_last_iteration_guard() { return (g_last_iteration_form >> 2) & 3; }
+extern "C" int fs_last_iteration_runs() { return g_last_iteration_runs; }
 void fs_krylov_set_history(const std::vector<double>& rr) { g_ws.last_hist = rr; }
 void fs_set_last_product_kind(int kind) { g_last_product_kind = kind; }
 

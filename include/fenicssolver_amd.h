@@ -93,7 +93,11 @@ const char* fs_version(void);
  * updates p and x every second iteration, two steps in one pass, instead of in every launch - the same bits; fs_last_iteration_form),
  * "cg_guard" (1 / 0, default 1; FS_CG_GUARD in the environment: on one GPU the LIGHT / PAIR launches of "cg_pair" run on solver-owned work vectors with
  * guard bands of zeros in front of row 0 and behind the last row, so that no work item needs the clamped edge path, and on a Kuhn box take a lane's
- * own rows from the centre run instead of a run of their own - the same bits; fs_last_iteration_guard; 0: unguarded vectors and the kernels with the edge path), "cg_poison_p" (tests: 1 = the next CG solve
+ * own rows from the centre run instead of a run of their own - the same bits; fs_last_iteration_guard; 0: unguarded vectors and the kernels with the edge path),
+ * "cg_zero_runs" (-1 / 0 / 1, default -1; FS_CG_ZERO_RUNS in the environment: on a Kuhn box those launches neither load nor multiply the two runs of a row in which no
+ * row class of the scaled operator holds a coefficient above 2^-53 - the (0, 1, 1) and (1, 1, 1) diagonals of a pure diffusion operator on orthogonal edges, where the
+ * assembly leaves the rounding of sums that cancel; iterates equal to rounding, not bit for bit - from "cg_zero_runs_min_rows" rows on (default and floor 100 000) / never /
+ * wherever it applies; fs_last_iteration_runs), "cg_poison_p" (tests: 1 = the next CG solve
  * finds NaN in its search-direction workspace before it sets its initial state), "row_dictionary" (0 / 1: allow the row-dictionary form of the product, fs_krylov_stats.row_classes),
  * "box_snap" (0 / 1: box meshes snap their edge vectors to the grid spacing so that equal stencils are equal bit for bit),
  * "box_assembly" (1 / 0: scalar CG1 operators on fs_mesh_create_box meshes are assembled from the reference rows of the six cell types instead of
@@ -903,6 +907,9 @@ int fs_last_iteration_form(void);
  * rows taken from the centre run of the space's one plan (Kuhn box) and the z run neither loaded nor multiplied.  (A word of its own:
  * callers of fs_last_iteration_form compare that word with the two bits it has.) */
 int fs_last_iteration_guard(void);
+/* ... and how many of the seven runs of a Kuhn-box row its LIGHT / PAIR launches left out because every class row of the solve's dictionary
+ * held nothing above 2^-53 of its unit diagonal there (option "cg_zero_runs"): 0 or 2.  A word of its own: the two above keep their values. */
+int fs_last_iteration_runs(void);
 
 /* ---- smoothed-aggregation AMG (PETScPreconditioner("petsc_amg") + set_near_nullspace,
  *      SolverBase.py:643-672; Chebyshev/Jacobi level smoother as the PETScOptions there ask) ---- */
