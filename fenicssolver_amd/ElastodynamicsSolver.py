@@ -437,14 +437,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
 
     def _check_step(self, dt):
         """a step above the second bound is refused, one between the two is logged"""
-        who = type(self).__name__
-        if dt > self._bounds[1]:
-            raise SolverError('{}: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on '
-                              'the largest eigenvalue): the explicit march is certain to blow up; the stable bound 2/sqrt(lambda_G) is '
-                              '{:.6g}'.format(who, dt, self._bounds[1], self._bounds[0]))
-        if dt > self._bounds[0]:
-            self.logger.warning('%s: time_step %.6g lies between the stable bound 2/sqrt(lambda_G) = %.6g and '
-                                '2/sqrt(lambda_P) = %.6g', who, dt, self._bounds[0], self._bounds[1])
+        time_marching.check_step(type(self).__name__, dt, self._bounds, self.logger, march='the explicit march')
 
     def _setup_explicit(self, V):
         """m = M 1, both step bounds and the state object of the central-difference marcher"""

@@ -282,14 +282,11 @@ class WaveSolver(SolverBase):
         # the two step bounds
         self._bounds = time_marching.step_bounds(self, K, m, dofs)
         t0, dt, N = self.time_grid()
-        if dt > self._bounds[1]:
+        try:
+            time_marching.check_step('WaveSolver', dt, self._bounds, self.logger)
+        except SolverError:
             K.close()
-            raise SolverError('WaveSolver: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on the largest '
-                              'eigenvalue): the march is certain to blow up; the stable bound 2/sqrt(lambda_G) is {:.6g}'.format(
-                                  dt, self._bounds[1], self._bounds[0]))
-        if dt > self._bounds[0]:
-            self.logger.warning('WaveSolver: time_step %.6g lies between the stable bound 2/sqrt(lambda_G) = %.6g and 2/sqrt(lambda_P) = %.6g',
-                                dt, self._bounds[0], self._bounds[1])
+            raise
         self._K = K
         self.state = backend.WaveState(V)
         self.state.configure(dt, m, d, F, dofs, vals)

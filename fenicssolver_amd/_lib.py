@@ -318,24 +318,7 @@ SIGNATURES = {
     "fs_dyn_predict": (C.c_int, [_H, _H, _H, C.c_double, C.c_double, _H]),
     "fs_dyn_correct": (C.c_int, [_H, _H, c_i64, c_i32p, c_f64p]),
     "fs_dyn_energy": (C.c_int, [_H, _H, _H, c_f64p]),
-    "fs_dyn_explicit_state_create": (C.c_int, [_H, C.POINTER(_H)]),
-    "fs_dyn_explicit_state_destroy": (C.c_int, [_H]),
-    "fs_dyn_explicit_state_configure": (C.c_int, [_H, C.c_double, C.c_double, c_f64p, c_f64p, c_i64, c_i32p, c_f64p]),
-    "fs_dyn_explicit_state_set": (C.c_int, [_H, c_f64p, c_f64p, c_i64]),
-    "fs_dyn_explicit_state_get": (C.c_int, [_H, c_f64p, c_f64p, c_i64p]),
     "fs_dyn_explicit_state_get_work": (C.c_int, [_H, c_f64p]),
-    "fs_dyn_explicit_start": (C.c_int, [_H, _H, c_f64p, c_f64p, C.c_double, C.c_double, C.c_double]),
-    "fs_dyn_explicit_advance": (C.c_int, [_H, _H, c_i64, c_f64p, c_f64p, c_i64, c_i32p, c_f64p, c_f64p, C.POINTER(fs_dyn_explicit_info)]),
-    "fs_dyn_explicit_full_step": (C.c_int, [_H, _H, C.c_double, c_f64p, c_f64p]),
-    "fs_hyper_dyn_state_create": (C.c_int, [_H, C.POINTER(_H)]),
-    "fs_hyper_dyn_state_destroy": (C.c_int, [_H]),
-    "fs_hyper_dyn_state_configure": (C.c_int, [_H, C.c_double, C.c_double, c_f64p, c_f64p, c_i64, c_i32p, c_f64p]),
-    "fs_hyper_dyn_state_set": (C.c_int, [_H, c_f64p, c_f64p, c_i64]),
-    "fs_hyper_dyn_state_get": (C.c_int, [_H, c_f64p, c_f64p, c_i64p]),
-    "fs_hyper_dyn_start": (C.c_int, [_H, C.POINTER(fs_hyper_form), c_f64p, c_f64p, C.c_double, C.c_double, C.c_double]),
-    "fs_hyper_dyn_advance": (C.c_int, [_H, C.POINTER(fs_hyper_form), c_i64, c_f64p, c_f64p, c_i64, c_i32p, c_f64p, c_f64p,
-                                       C.POINTER(fs_march_info)]),
-    "fs_hyper_dyn_full_step": (C.c_int, [_H, C.POINTER(fs_hyper_form), C.c_double, c_f64p, c_f64p]),
     "fs_hyper_dyn_internal_force": (C.c_int, [_H, C.POINTER(fs_hyper_form), c_f64p, c_f64p]),
     "fs_assemble_large_deformation":(C.c_int, [_H, _H, _H, _H, _H, _H, C.POINTER(fs_ld_form), C.POINTER(fs_ld_info)]),
     "fs_assemble_viscous_stress": (C.c_int, [_H, _H, C.c_double, _H, _H]),
@@ -353,6 +336,25 @@ SIGNATURES = {
     "fs_space_enable_p2p_halo": (C.c_int, [_H, C.c_int]),
     "fs_comm_benchmark": (C.c_int, [_H, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
+
+
+def _leapfrog_rows(api, head):
+    """the entry points the two central-difference marchers share (csrc/fs_leapfrog.h); head: the leading arguments of a marching call
+    (the matrix and the state, or the state and its material)"""
+    return {
+        api + "_state_create": (C.c_int, [_H, C.POINTER(_H)]),
+        api + "_state_destroy": (C.c_int, [_H]),
+        api + "_state_configure": (C.c_int, [_H, C.c_double, C.c_double, c_f64p, c_f64p, c_i64, c_i32p, c_f64p]),
+        api + "_state_set": (C.c_int, [_H, c_f64p, c_f64p, c_i64]),
+        api + "_state_get": (C.c_int, [_H, c_f64p, c_f64p, c_i64p]),
+        api + "_start": (C.c_int, head + [c_f64p, c_f64p, C.c_double, C.c_double, C.c_double]),
+        api + "_advance": (C.c_int, head + [c_i64, c_f64p, c_f64p, c_i64, c_i32p, c_f64p, c_f64p, C.POINTER(fs_march_info)]),
+        api + "_full_step": (C.c_int, head + [C.c_double, c_f64p, c_f64p]),
+    }
+
+
+SIGNATURES.update(_leapfrog_rows("fs_dyn_explicit", [_H, _H]))
+SIGNATURES.update(_leapfrog_rows("fs_hyper_dyn", [_H, C.POINTER(fs_hyper_form)]))
 
 _lib = None
 

@@ -1082,103 +1082,104 @@ class DynamicsState(_MarcherState):
         return float(out[0]), float(out[1])
 
 
-class ExplicitDynamicsState(_MarcherState):
-    """Device state of the central-difference marcher on a vector CG1 space (fs_dyn_explicit_*): u_n, w_n = v_{n-1/2}, the last
-    product y = K u, the lumped mass m, the load F, the Dirichlet dofs with their values, dt, eta_M and the step counter n.  Arrays
-    are in DEVICE dof order.  K is the operator WITHOUT eliminated rows."""
-    _create, _destroy = "fs_dyn_explicit_state_create", "fs_dyn_explicit_state_destroy"
+class _LeapfrogState(_MarcherState):
+    """What the device states of the two central-difference ("leapfrog") marchers share: every call but the ones that are a
+    marcher's own.  _api is the prefix of the entry points, _head(K) their leading arguments: the matrix and the state, or the
+    state and its material.  The state is (u_n, w_n = v_{n-1/2}, n)."""
+    _api = None
+
+    def _call(self, name, *args):
+        entry = "%s_%s" % (self._api, name)
+        L.check(getattr(L.load(), entry)(*args), entry)
 
     def configure(self, dt, eta_m, mass, load=None, dirichlet_dofs=None, dirichlet_values=None):
         m = self._field(mass, "configure", "mass")
         f = None if load is None else self._field(load, "configure", "load")
         dofs, vals = self._dirichlet(dirichlet_dofs, dirichlet_values)
-        L.check(L.load().fs_dyn_explicit_state_configure(self.h, float(dt), float(eta_m), L.p_f64(m), L.p_f64(f), dofs.size, L.p_i32(dofs),
-                                                         L.p_f64(vals)), "fs_dyn_explicit_state_configure")
+        self._call("state_configure", self.h, float(dt), float(eta_m), L.p_f64(m), L.p_f64(f), dofs.size, L.p_i32(dofs), L.p_f64(vals))
 
     def set(self, u, w, step):
         u, w = self._field(u, "set", "u"), self._field(w, "set", "w")
-        L.check(L.load().fs_dyn_explicit_state_set(self.h, L.p_f64(u), L.p_f64(w), int(step)), "fs_dyn_explicit_state_set")
+        self._call("state_set", self.h, L.p_f64(u), L.p_f64(w), int(step))
 
     def get(self):
         """(u_n, w_n = v_{n-1/2}, n)"""
         u, w, k = np.empty(self.n), np.empty(self.n), C.c_int64(0)
-        L.check(L.load().fs_dyn_explicit_state_get(self.h, L.p_f64(u), L.p_f64(w), C.byref(k)), "fs_dyn_explicit_state_get")
+        self._call("state_get", self.h, L.p_f64(u), L.p_f64(w), C.byref(k))
         return u, w, k.value
+
+    def _start(self, K, u0, v0, load_scale0, dirichlet_scale0, dirichlet_scale1):
+        u0, v0 = self._field(u0, "start", "u0"), self._field(v0, "start", "v0")
+        self._call("start", *self._head(K), L.p_f64(u0), L.p_f64(v0), float(load_scale0), float(dirichlet_scale0), float(dirichlet_scale1))
+
+    def _advance(self, K, load_scale, dirichlet_scale, receivers, traces, energy, info):
+        return self._batch_advance(self._api + "_advance", self._head(K), load_scale, dirichlet_scale, receivers, traces, energy, info)
+
+    def _full_step(self, K, load_scale_n):
+        v, a = np.empty(self.n), np.empty(self.n)
+        self._call("full_step", *self._head(K), float(load_scale_n), L.p_f64(v), L.p_f64(a))
+        return v, a
+
+
+class ExplicitDynamicsState(_LeapfrogState):
+    """Device state of the central-difference marcher on a vector CG1 space (fs_dyn_explicit_*): u_n, w_n = v_{n-1/2}, the last
+    product y = K u, the lumped mass m, the load F, the Dirichlet dofs with their values, dt, eta_M and the step counter n.  Arrays
+    are in DEVICE dof order.  K is the operator WITHOUT eliminated rows."""
+    _create, _destroy, _api = "fs_dyn_explicit_state_create", "fs_dyn_explicit_state_destroy", "fs_dyn_explicit"
+
+    def _head(self, K):
+        return K.h, self.h
 
     def work(self):
         """y = K u of the last product"""
         y = np.empty(self.n)
-        L.check(L.load().fs_dyn_explicit_state_get_work(self.h, L.p_f64(y)), "fs_dyn_explicit_state_get_work")
+        self._call("state_get_work", self.h, L.p_f64(y))
         return y
 
     def start(self, K, u0, v0, load_scale0=1.0, dirichlet_scale0=1.0, dirichlet_scale1=1.0):
         """(u_1, w_{1/2}) from (u_0, v_0): n = 1"""
-        u0, v0 = self._field(u0, "start", "u0"), self._field(v0, "start", "v0")
-        L.check(L.load().fs_dyn_explicit_start(K.h, self.h, L.p_f64(u0), L.p_f64(v0), float(load_scale0), float(dirichlet_scale0),
-                                               float(dirichlet_scale1)), "fs_dyn_explicit_start")
+        self._start(K, u0, v0, load_scale0, dirichlet_scale0, dirichlet_scale1)
 
     def advance(self, K, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
         """a batch of steps through fs_dyn_explicit_advance: see _MarcherState._batch_advance"""
-        return self._batch_advance("fs_dyn_explicit_advance", (K.h, self.h), load_scale, dirichlet_scale, receivers, traces, energy, info)
+        return self._advance(K, load_scale, dirichlet_scale, receivers, traces, energy, info)
 
     def full_step(self, K, load_scale_n):
         """(v_n, a_n) of the state's time point under s_f[n] = load_scale_n: one product, the state does not change"""
-        v, a = np.empty(self.n), np.empty(self.n)
-        L.check(L.load().fs_dyn_explicit_full_step(K.h, self.h, float(load_scale_n), L.p_f64(v), L.p_f64(a)), "fs_dyn_explicit_full_step")
-        return v, a
+        return self._full_step(K, load_scale_n)
 
 
-class HyperelasticDynamicsState(_MarcherState):
+class HyperelasticDynamicsState(_LeapfrogState):
     """Device state of the explicit finite-strain marcher on a vector CG1 space (fs_hyper_dyn_*): u_n (double-buffered inside the
     library), w_n = v_{n-1/2}, the lumped mass m, the load F, the Dirichlet dofs with their values, dt, eta_M, the step counter n
     and the device copy of the material.  Arrays are in DEVICE dof order.  The material is given once, as for
     assemble_hyperelastic (per-cell arrays in device cell order); there is no matrix: every step evaluates the internal force."""
-    _create, _destroy = "fs_hyper_dyn_state_create", "fs_hyper_dyn_state_destroy"
+    _create, _destroy, _api = "fs_hyper_dyn_state_create", "fs_hyper_dyn_state_destroy", "fs_hyper_dyn"
 
     def __init__(self, space, lame=None, model='neo_hookean', params=None):
         super().__init__(space)
         self._keep = []
         self._form = _hyper_form("HyperelasticDynamicsState", space, lame, model, params, False, self._keep)
 
-    def configure(self, dt, eta_m, mass, load=None, dirichlet_dofs=None, dirichlet_values=None):
-        m = self._field(mass, "configure", "mass")
-        f = None if load is None else self._field(load, "configure", "load")
-        dofs, vals = self._dirichlet(dirichlet_dofs, dirichlet_values)
-        L.check(L.load().fs_hyper_dyn_state_configure(self.h, float(dt), float(eta_m), L.p_f64(m), L.p_f64(f), dofs.size, L.p_i32(dofs),
-                                                      L.p_f64(vals)), "fs_hyper_dyn_state_configure")
-
-    def set(self, u, w, step):
-        u, w = self._field(u, "set", "u"), self._field(w, "set", "w")
-        L.check(L.load().fs_hyper_dyn_state_set(self.h, L.p_f64(u), L.p_f64(w), int(step)), "fs_hyper_dyn_state_set")
-
-    def get(self):
-        """(u_n, w_n = v_{n-1/2}, n)"""
-        u, w, k = np.empty(self.n), np.empty(self.n), C.c_int64(0)
-        L.check(L.load().fs_hyper_dyn_state_get(self.h, L.p_f64(u), L.p_f64(w), C.byref(k)), "fs_hyper_dyn_state_get")
-        return u, w, k.value
+    def _head(self, K=None):
+        return self.h, C.byref(self._form)
 
     def start(self, u0, v0, load_scale0=1.0, dirichlet_scale0=1.0, dirichlet_scale1=1.0):
         """(u_1, w_{1/2}) from (u_0, v_0): n = 1"""
-        u0, v0 = self._field(u0, "start", "u0"), self._field(v0, "start", "v0")
-        L.check(L.load().fs_hyper_dyn_start(self.h, C.byref(self._form), L.p_f64(u0), L.p_f64(v0), float(load_scale0),
-                                            float(dirichlet_scale0), float(dirichlet_scale1)), "fs_hyper_dyn_start")
+        self._start(None, u0, v0, load_scale0, dirichlet_scale0, dirichlet_scale1)
 
     def advance(self, load_scale, dirichlet_scale, receivers=None, traces=True, energy=True, info=True):
         """a batch of steps through fs_hyper_dyn_advance: see _MarcherState._batch_advance; energy[k] = (E_kin(w_{n+1/2}), Pi(u_n))"""
-        return self._batch_advance("fs_hyper_dyn_advance", (self.h, C.byref(self._form)), load_scale, dirichlet_scale, receivers, traces,
-                                   energy, info)
+        return self._advance(None, load_scale, dirichlet_scale, receivers, traces, energy, info)
 
     def full_step(self, load_scale_n):
         """(v_n, a_n) of the state's time point under s_f[n] = load_scale_n: the force is recomputed, the state does not change"""
-        v, a = np.empty(self.n), np.empty(self.n)
-        L.check(L.load().fs_hyper_dyn_full_step(self.h, C.byref(self._form), float(load_scale_n), L.p_f64(v), L.p_f64(a)),
-                "fs_hyper_dyn_full_step")
-        return v, a
+        return self._full_step(None, load_scale_n)
 
     def internal_force(self):
         """(f_int(u_n), Pi(u_n)) of the held state"""
         f, e = np.empty(self.n), C.c_double(0.0)
-        L.check(L.load().fs_hyper_dyn_internal_force(self.h, C.byref(self._form), L.p_f64(f), C.byref(e)), "fs_hyper_dyn_internal_force")
+        self._call("internal_force", *self._head(), L.p_f64(f), C.byref(e))
         return f, e.value
 
 

@@ -1,13 +1,11 @@
 // Explicit finite-strain dynamics on vector CG1 spaces (tetrahedra, triangles in true plane strain): the central-difference marcher
 // of HyperelasticDynamicsSolver, on the device.  Neither the reference nor its NonlinearElasticitySolver has a transient form.
 //
-// The scheme is fs_dynamics_explicit.hip's with y_n = K u_n replaced by the internal force f_int(u_n) = dPi/du of a hyperelastic
-// energy (neo-Hookean, St Venant-Kirchhoff, Mooney-Rivlin, Yeoh: the invariant-form functors of fs_hyper_energy.h): the LUMPED
-// mass m = M 1 of the reference configuration, C = eta_M diag(m), alpha = eta_M dt / 2 and, per dof,
-//   (1 + alpha) w_{n+1/2} = (1 - alpha) w_{n-1/2} + dt (s_f[n] F - f_int(u_n)) / m,      u_{n+1} = u_n + dt w_{n+1/2},
-// on a Dirichlet row u_{n+1} = g s_g[n+1], w_{n+1/2} = (u_{n+1} - u_n) / dt; the start is
-//   a_0 = (s_f[0] F - f_int(u_0)) / m - eta_M v_0,   w_{1/2} = v_0 + dt/2 a_0,   u_1 = u_0 + dt w_{1/2}
-// (the Dirichlet rows of u_0 take g s_g[0] first).  The energy of the step n -> n+1 is reported as
+// The scheme is the leapfrog of fs_leapfrog.h - the one fs_dynamics_explicit.hip marches with y_n = K u_n; the formulas of the step,
+// of the start and of the Dirichlet rows, the constants and the per-row helpers are there - with y_n = f_int(u_n) = dPi/du, the
+// internal force of a hyperelastic energy (neo-Hookean, St Venant-Kirchhoff, Mooney-Rivlin, Yeoh: the invariant-form functors of
+// fs_hyper_energy.h), the LUMPED mass m = M 1 of the reference configuration and C = eta_M diag(m).  The energy of the step
+// n -> n+1 is reported as
 //   E_kin = 1/2 sum_i m_i w_{n+1/2,i}^2,   Pi(u_n) = sum_cells V psi(F(u_n)):
 // the potential half is taken at t_n, where the force is evaluated (the linear marcher reports 1/2 u_{n+1}^T K u_n).  All four
 // energies have psi = 0 at rest in both dimensions: the neo-Hookean one is m_neo's, with F embedded in 3 x 3 in plane strain (the
@@ -30,7 +28,8 @@
 //       stays finite at J <= 0 -, so the finishing pass that counts non-finite energies reports the step (n_nonfinite,
 //       first_nonfinite_step).  This is arithmetic only: no gather index depends on u.
 //     MODE = HDYN_STEP   the step above
-//            HDYN_START  the first step from (u_0, v_0)
+//            HDYN_START  the first step from (u_0, v_0); k_leapfrog_dirichlet (fs_leapfrog.h) has put g s_g[0] into the Dirichlet rows
+//                        of u_0 before it, on the same stream
 //            HDYN_FULL   v_n and a_n of the state's time point: w+ is recomputed, nothing is stored
 //            HDYN_FORCE  f_int and Pi of the held state, for checks and for internal_force()
 //   Per node and step: one source per incident cell (24 at an interior node of a box mesh, 6 in a rectangle mesh), each with the cell
@@ -46,23 +45,16 @@
 // The sources are walked in groups of four with the cell records of a group fetched before its arithmetic (the PF = 4 of
 // k_hyper_force_gather).  Without the groups the kernel needs 68 - 120 VGPRs (4 - 7 waves) and takes twice as long on the 80^3-cell
 // box (565 against 266 us, Mooney-Rivlin): the walk is bound by the chain source -> cell record -> vertices, not by occupancy.
-// The row table (load, flags, receivers), the finishing pass and the batch driver: fs_march.h.
+// The row table (load, flags, receivers), the finishing pass and the batch driver: fs_march.h.  The state object and the checks the
+// two leapfrog marchers share: fs_leapfrog.h.
 #include "fs_hyper_energy.h"
-#include "fs_march.h"
+#include "fs_leapfrog.h"
 #include <mutex>
 
 #define HDYN_STEP 0
 #define HDYN_START 1
 #define HDYN_FULL 2
 #define HDYN_FORCE 3
-
-// what the kernel takes of the scheme, derived from (dt, eta_M) on the host: w+ = c1 w + c2 (s_f F - f_int) / m
-struct hdyn_consts {
-    double dt, idt;
-    double c1;                           // (1 - alpha) / (1 + alpha)
-    double c2;                           // dt / (1 + alpha)
-    double etam;
-};
 
 // the rows of a launch; what a mode does not use is nullptr
 struct hdyn_rows {
@@ -81,15 +73,9 @@ struct hdyn_rows {
     double* part;                        // this launch's [2][gridDim.x] partials
 };
 
-struct fs_hyper_dyn_state_s : fs_march_batch_state {
-    hdyn_consts c = {};
+struct fs_hyper_dyn_state_s : fs_leapfrog_state {
     dbuf<double> u[2];                   // u_n is u[cur]; a step writes u[1 - cur]
     int cur = 0;
-    dbuf<double> w;                      // v_{n-1/2}: updated in place
-    dbuf<double> m;                      // lumped mass
-    dbuf<double> t0, t1;                 // fs_hyper_dyn_start: v_0; _full_step: v_n, a_n; _internal_force: f_int
-    std::vector<int32_t> dir_dofs;       // the Dirichlet list of the last configure (the start applies it to u_0 on the host)
-    std::vector<double> dir_vals;
     // the material on the device: uploaded when it changes, never per step
     int model = -1;
     hm_par par = {};
@@ -97,6 +83,7 @@ struct fs_hyper_dyn_state_s : fs_march_batch_state {
     dbuf<double> rows;
     dbuf<double> en;                     // _internal_force: (-, Pi)
     dbuf<unsigned long long> bad;
+    fs_hyper_dyn_state_s() : fs_leapfrog_state("fs_hyper_dyn") {}
 };
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------
@@ -105,7 +92,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hdyn_step(int64_t n_nodes, const i
                                                         const int32_t* __restrict__ gptr, const int32_t* __restrict__ gsrc,
                                                         const int32_t* __restrict__ cells, const double* __restrict__ xyz4, const hm_par par,
                                                         const double2* __restrict__ rows, const box_snap bx, const hdyn_rows R,
-                                                        const hdyn_consts c, double sf, double sg) {
+                                                        const fs_leapfrog_consts c, double sf, double sg) {
     __shared__ double lds4[4];
     const double* __restrict__ u = R.ua;
     double ek = 0.0, ep = 0.0;
@@ -169,29 +156,18 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hdyn_step(int64_t n_nodes, const i
             const bool dir = R.flag[row] & FS_MARCH_DIRICHLET;
             if (MODE == HDYN_FULL) {
                 const double wi = R.w[row];
-                const double wp = c.c1 * wi + c.c2 * ((sf * fi - acc[i]) / mi);
-                R.o0[row] = dir ? wi : 0.5 * (wi + wp);
-                R.o1[row] = dir ? 0.0 : (wp - wi) * c.idt;
+                const double wp = fs_leapfrog_w(c, wi, acc[i], mi, fi, sf);
+                R.o0[row] = fs_leapfrog_v(wi, wp, dir);
+                R.o1[row] = fs_leapfrog_a(c, wi, wp, dir);
                 continue;
             }
             const double ui = u[row];
-            double wn;
-            if (MODE == HDYN_START) {
-                const double vi = R.v0[row];
-                const double a0 = (sf * fi - acc[i]) / mi - c.etam * vi;
-                wn = vi + (0.5 * c.dt) * a0;
-            } else {
-                wn = c.c1 * R.w[row] + c.c2 * ((sf * fi - acc[i]) / mi);
-            }
-            double un = ui + c.dt * wn;
-            if (dir) {
-                un = fi * sg;
-                wn = (un - ui) * c.idt;
-            }
-            R.ub[row] = un;
-            R.w[row] = wn;
-            ek += 0.5 * mi * wn * wn;
-            if (MODE == HDYN_STEP) fs_march_sample(R.flag[row], row, un, R.n_rec, R.rec, R.trace);
+            const fs_leapfrog_row n = MODE == HDYN_START ? fs_leapfrog_start_row(c, ui, R.v0[row], acc[i], mi, fi, sf, sg, dir)
+                                                         : fs_leapfrog_step_row(c, ui, R.w[row], acc[i], mi, fi, sf, sg, dir);
+            R.ub[row] = n.u;
+            R.w[row] = n.w;
+            ek += fs_leapfrog_ekin(mi, n.w);
+            if (MODE == HDYN_STEP) fs_march_sample(R.flag[row], row, n.u, R.n_rec, R.rec, R.trace);
         }
     }
     fs_march_store_partials(ek, ep, lds4, R.part);
@@ -258,9 +234,7 @@ static hdyn_rows hdyn_rows_of(fs_hyper_dyn_state_s* st) {
 static int hdyn_ready(const fs_hyper_dyn_state_s* st, const char* who, bool started) {
     FS_REQUIRE(st, "%s: null pointer", who);
     FS_CHECK(hdyn_space_ok(st->space, who));
-    FS_REQUIRE(st->configured, "%s: the state was not configured (fs_hyper_dyn_state_configure)", who);
-    FS_REQUIRE(!started || st->step >= 1, "%s: the state holds no (u_n, v_{n-1/2}) yet (fs_hyper_dyn_start or fs_hyper_dyn_state_set)", who);
-    return FS_OK;
+    return st->ready(who, started);
 }
 
 // ---- the state object --------------------------------------------------------------------------------------------------------------
@@ -271,10 +245,7 @@ extern "C" int fs_hyper_dyn_state_create(fs_space_t space, fs_hyper_dyn_state_t*
     fs_hyper_dyn_state_s* st = new fs_hyper_dyn_state_s();
     st->space = space;
     hipStream_t s = fs_rt().stream;
-    int rc = st->alloc_rows(space->n_dofs_owned, s);
-    for (dbuf<double>* b : {&st->u[0], &st->u[1], &st->w, &st->m, &st->t0, &st->t1})
-        if (rc == FS_OK && (rc = b->alloc(st->n)) == FS_OK) rc = b->zero(s);
-    if (rc == FS_OK) rc = st->alloc_part();
+    int rc = st->alloc(space->n_dofs_owned, {&st->u[0], &st->u[1]}, s);
     if (rc == FS_OK) rc = st->en.alloc(2);
     if (rc == FS_OK) rc = st->bad.alloc(2);
     return fs_march_create_finish("fs_hyper_dyn_state_create", st, rc, s, out);
@@ -287,47 +258,18 @@ extern "C" int fs_hyper_dyn_state_destroy(fs_hyper_dyn_state_t st) {
 
 extern "C" int fs_hyper_dyn_state_configure(fs_hyper_dyn_state_t st, double dt, double eta_m, const double* mass, const double* load,
                                             int64_t n_dirichlet, const int32_t* dirichlet_dofs, const double* dirichlet_values) {
-    const char* who = "fs_hyper_dyn_state_configure";
-    FS_REQUIRE(st && mass, "%s: null pointer", who);
-    FS_REQUIRE(dt > 0.0 && isfinite(dt), "%s: the step length is %g: dt > 0 and finite is required", who, dt);
-    FS_REQUIRE(eta_m >= 0.0 && isfinite(eta_m), "%s: the mass damping eta_M is %g: it must be >= 0 and finite", who, eta_m);
-    const int64_t n = st->n;
-    FS_CHECK(fs_march_rows_ok(who, n, mass, nullptr, load, n_dirichlet, dirichlet_dofs, dirichlet_values));
-    hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->configure(who, load, n_dirichlet, dirichlet_dofs, dirichlet_values, s));
-    FS_CHECK(st->m.upload(mass, n, s));
-    FS_HIP(hipStreamSynchronize(s));
-    st->dir_dofs.assign(dirichlet_dofs, dirichlet_dofs + n_dirichlet);
-    st->dir_vals.assign(dirichlet_values, dirichlet_values + n_dirichlet);
-    const double alpha = 0.5 * eta_m * dt;
-    st->c.dt = dt;
-    st->c.idt = 1.0 / dt;
-    st->c.c1 = (1.0 - alpha) / (1.0 + alpha);
-    st->c.c2 = dt / (1.0 + alpha);
-    st->c.etam = eta_m;
-    st->configured = true;
-    return FS_OK;
+    FS_REQUIRE(st, "fs_hyper_dyn_state_configure: null pointer");
+    return st->configure("fs_hyper_dyn_state_configure", dt, eta_m, mass, load, n_dirichlet, dirichlet_dofs, dirichlet_values);
 }
 
 extern "C" int fs_hyper_dyn_state_set(fs_hyper_dyn_state_t st, const double* u, const double* w, int64_t step) {
-    FS_REQUIRE(st && u && w, "fs_hyper_dyn_state_set: null pointer");
-    FS_REQUIRE(step >= 1, "fs_hyper_dyn_state_set: the step counter is %lld: (u_n, v_{n-1/2}) needs n >= 1", (long long)step);
-    hipStream_t s = fs_rt().stream;
-    FS_CHECK(st->u[st->cur].upload(u, st->n, s));
-    FS_CHECK(st->w.upload(w, st->n, s));
-    FS_HIP(hipStreamSynchronize(s));
-    st->step = step;
-    return FS_OK;
+    FS_REQUIRE(st, "fs_hyper_dyn_state_set: null pointer");
+    return st->set("fs_hyper_dyn_state_set", st->u[st->cur], u, w, step);
 }
 
 extern "C" int fs_hyper_dyn_state_get(fs_hyper_dyn_state_t st, double* u, double* w, int64_t* step) {
     FS_REQUIRE(st, "fs_hyper_dyn_state_get: null pointer");
-    hipStream_t s = fs_rt().stream;
-    if (u) FS_CHECK(st->u[st->cur].download(u, st->n, s));
-    if (w) FS_CHECK(st->w.download(w, st->n, s));
-    FS_HIP(hipStreamSynchronize(s));
-    if (step) *step = st->step;
-    return FS_OK;
+    return st->get(st->u[st->cur], u, w, step);
 }
 
 // ---- the march -------------------------------------------------------------------------------------------------------------------
@@ -336,17 +278,10 @@ extern "C" int fs_hyper_dyn_start(fs_hyper_dyn_state_t st, const fs_hyper_form* 
     const char* who = "fs_hyper_dyn_start";
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(hdyn_ready(st, who, false));
-    FS_REQUIRE(u0 && v0, "%s: null pointer", who);
-    FS_REQUIRE(isfinite(load_scale0) && isfinite(dirichlet_scale0) && isfinite(dirichlet_scale1), "%s: a time factor is not finite", who);
+    FS_CHECK(st->start_ok(who, u0, v0, load_scale0, dirichlet_scale0, dirichlet_scale1));
     hipStream_t s = fs_rt().stream;
     FS_CHECK(hdyn_material(st, form, who, s));
-    const int64_t n = st->n;
-    std::vector<double> u(u0, u0 + n);                       // the Dirichlet rows of u_0 take g s_g[0] (a dof named twice: the last value)
-    for (size_t j = 0; j < st->dir_dofs.size(); ++j) u[st->dir_dofs[j]] = st->dir_vals[j] * dirichlet_scale0;
-    FS_CHECK(st->u[st->cur].upload(u.data(), n, s));
-    FS_CHECK(st->t0.upload(v0, n, s));
-    FS_HIP(hipStreamSynchronize(s));
-    st->step = 0;
+    FS_CHECK(st->start_fields(st->u[st->cur], u0, v0, dirichlet_scale0, s));   // the kernel below reads u[cur] behind it on s
     hdyn_rows R = hdyn_rows_of(st);
     R.v0 = st->t0.p;
     hdyn_launch<HDYN_START>(st, R, load_scale0, dirichlet_scale1, s);
@@ -387,17 +322,12 @@ extern "C" int fs_hyper_dyn_full_step(fs_hyper_dyn_state_t st, const fs_hyper_fo
     FS_REQUIRE(isfinite(load_scale_n), "%s: the load factor is not finite", who);
     hipStream_t s = fs_rt().stream;
     FS_CHECK(hdyn_material(st, form, who, s));
-    const int64_t n = st->n;
     hdyn_rows R = hdyn_rows_of(st);
     R.o0 = st->t0.p;
     R.o1 = st->t1.p;
     hdyn_launch<HDYN_FULL>(st, R, load_scale_n, 0.0, s);
     FS_KERNEL_CHECK();
-    if (v_out) FS_CHECK(st->t0.download(v_out, n, s));
-    if (a_out) FS_CHECK(st->t1.download(a_out, n, s));
-    FS_HIP(hipStreamSynchronize(s));
-    FS_KERNEL_CHECK();
-    return FS_OK;
+    return st->full_step_out(v_out, a_out, s);
 }
 
 extern "C" int fs_hyper_dyn_internal_force(fs_hyper_dyn_state_t st, const fs_hyper_form* form, double* f_out, double* energy_out) {

@@ -1,5 +1,6 @@
 """Host pieces the explicit time marchers share (WaveSolver, ElastodynamicsSolver with 'scheme': 'explicit'): the two bounds on the
-time step of a central-difference march with the operator K and the lumped mass m, and the end of a batch of device steps."""
+time step of a central-difference march with the operator K and the lumped mass m, the check of a step against them, and the end of a
+batch of device steps."""
 
 from __future__ import annotations
 
@@ -44,6 +45,18 @@ def step_bounds(solver, K, m, bc_dofs):
     lam_g = float(np.max(np.add.reduceat(np.abs(va), rp[:-1].astype(np.int64)) / m))
     lam_p = solver._power_iteration(K, m, bc_dofs)
     return 2.0 / math.sqrt(lam_g), 2.0 / math.sqrt(lam_p)
+
+
+def check_step(who, dt, bounds, logger, march='the march'):
+    """a step above the second bound of step_bounds is refused, one between the two is logged.  who: the solver the messages name;
+    march: what the refusal calls the march"""
+    if dt > bounds[1]:
+        raise SolverError('{}: time_step {:.6g} exceeds 2/sqrt(lambda_P) = {:.6g} (power iteration, a lower bound on the largest '
+                          'eigenvalue): {} is certain to blow up; the stable bound 2/sqrt(lambda_G) is {:.6g}'.format(
+                              who, dt, bounds[1], march, bounds[0]))
+    if dt > bounds[0]:
+        logger.warning('%s: time_step %.6g lies between the stable bound 2/sqrt(lambda_G) = %.6g and 2/sqrt(lambda_P) = %.6g', who, dt,
+                       bounds[0], bounds[1])
 
 
 def batch_end(n, N, freqs, batch_steps):
