@@ -77,7 +77,7 @@ from .fem import Constant, Expression, Function, interpolate
 from .SolverBase import SolverError, write_vtu
 from .LinearElasticitySolver import LinearElasticitySolver
 from .WaveSolver import tabulate_time_function, nearest_vertices
-from . import time_marching
+from . import solid_steps, time_marching
 
 _EXPLICIT = ('alpha_m', 'alpha_f', 'beta', 'gamma')
 _DYNAMICS_KEYS = set(_EXPLICIT) | {'spectral_radius', 'rayleigh_mass', 'rayleigh_stiffness', 'energy_freq', 'scheme', 'batch_steps'}
@@ -271,20 +271,13 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         return float(tabulate_time_function(spec, self.time_points()[:1], 'load_time_function')[0])
 
     def _refuse_unsupported(self):
-        from . import parallel
         V = self.function_space
-        if parallel.world()[1] > 1:
-            raise SolverError('ElastodynamicsSolver runs on one rank')
-        if (hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None) or self.settings.get('periodic_boundary'):
-            raise SolverError('ElastodynamicsSolver: periodic spaces are not supported')
-        if V.degree() not in (1, 2) or getattr(V, '_ncomp', 1) != self.dimension:
-            raise SolverError('ElastodynamicsSolver: vector CG1 or CG2 spaces only')
-        T = getattr(self, 'temperature_distribution', None) or self.settings.get('temperature_distribution')
-        if T is not None and not (isinstance(T, (int, float)) and T == 0):
-            raise SolverError('ElastodynamicsSolver: temperature_distribution is not supported (no thermal strain in the model)')
-        for key in ('point_source', 'surface_source'):
-            if self.settings.get(key):
-                raise SolverError('ElastodynamicsSolver: {} is not supported'.format(key))
+
+        def space_check():
+            if V.degree() not in (1, 2) or getattr(V, '_ncomp', 1) != self.dimension:
+                raise SolverError('ElastodynamicsSolver: vector CG1 or CG2 spaces only')
+        solid_steps.refuse_unsupported(self, 'ElastodynamicsSolver', ' (no thermal strain in the model)',
+                                       ('point_source', 'surface_source'), space_check)
         rho = self.material_field('density')
         if not (np.all(np.asarray(rho) > 0.0) and np.all(np.isfinite(rho))):
             raise SolverError("ElastodynamicsSolver: material 'density' must be positive")
@@ -382,9 +375,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         u0 = u0.copy()
         u0[gdofs.astype(np.int64)] = gvals * sg[0]                # the initial displacement takes the Dirichlet values of t_0
         dofs, vals = (gdofs, gvals) if loc is None else loc.dofs(gdofs, gvals)
-        lame = form.lame_spec()
-        if form.cellwise() and loc is not None:
-            lame = ('cell', loc.cells(lame[1]))
+        lame = solid_steps.localized(form.lame_spec(), loc)
         rho = self.material_field('density')
         if np.ndim(rho) > 0:
             rho = np.asarray(rho, dtype=np.float64)
@@ -395,7 +386,7 @@ class ElastodynamicsSolver(LinearElasticitySolver):
         M = backend.DeviceMatrix(V)
         M.assemble(lame=(0.0, 0.0), mass=self._density_spec(1.0))
         if self.function_space.degree() == 1:
-            b = self._hyperelastic_external_loads(form, V, loc)   # per dof in a fixed order: the same bits from run to run
+            b = solid_steps.external_loads(self, form, V, loc)    # per dof in a fixed order: the same bits from run to run
         else:
             A_, b = self.assemble_system(form, [])                # (CG2 facet loads: the consistent P2 weights)
             A_.close()

@@ -50,7 +50,7 @@ import numpy as np
 from .SolverBase import SolverError
 from .NonlinearElasticitySolver import NonlinearElasticitySolver
 from .ElastodynamicsSolver import ElastodynamicsSolver
-from . import time_marching
+from . import solid_steps, time_marching
 
 
 class HyperelasticDynamicsSolver(NonlinearElasticitySolver, ElastodynamicsSolver):
@@ -72,21 +72,14 @@ class HyperelasticDynamicsSolver(NonlinearElasticitySolver, ElastodynamicsSolver
         return 'explicit'
 
     def _refuse_unsupported(self):
-        from . import parallel
         V = self.function_space
         who = 'HyperelasticDynamicsSolver'
-        if parallel.world()[1] > 1:
-            raise SolverError(who + ' runs on one rank')
-        if (hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None) or self.settings.get('periodic_boundary'):
-            raise SolverError(who + ': periodic spaces are not supported')
-        if V.degree() != 1 or getattr(V, '_ncomp', 1) != self.dimension:
-            raise SolverError(who + ': CG{} spaces with {} component(s) are not supported (vector CG1 only: the P2 integrand is not '
-                              'polynomial and a row-sum lumped P2 mass is not positive)'.format(V.degree(), getattr(V, '_ncomp', 1)))
-        T = getattr(self, 'temperature_distribution', None) or self.settings.get('temperature_distribution')
-        if T is not None and not (isinstance(T, (int, float)) and T == 0):
-            raise SolverError(who + ': temperature_distribution is not supported (the energies have no thermal term)')
-        if self.settings.get('point_source'):
-            raise SolverError(who + ': point_source is not supported')
+
+        def space_check():
+            if V.degree() != 1 or getattr(V, '_ncomp', 1) != self.dimension:
+                raise SolverError(who + ': CG{} spaces with {} component(s) are not supported (vector CG1 only: the P2 integrand is not '
+                                  'polynomial and a row-sum lumped P2 mass is not positive)'.format(V.degree(), getattr(V, '_ncomp', 1)))
+        solid_steps.refuse_unsupported(self, who, ' (the energies have no thermal term)', ('point_source',), space_check)
         rho = self.material_field('density')
         if not (np.all(np.asarray(rho) > 0.0) and np.all(np.isfinite(rho))):
             raise SolverError(who + ": material 'density' must be positive")
@@ -105,7 +98,7 @@ class HyperelasticDynamicsSolver(NonlinearElasticitySolver, ElastodynamicsSolver
         from . import backend
         V = self.function_space.device()
         lame, model, params = self._hyper
-        ud = backend.DeviceVector(V.n_local, np.concatenate([u_dev, np.zeros(V.n_local - len(u_dev))]))
+        ud = backend.DeviceVector(V.n_local, solid_steps.to_device_dofs(V, None, u_dev))      # (u_dev is in device order already)
         K = backend.DeviceMatrix(V)
         try:
             info = backend.assemble_hyperelastic(V, ud, lame, K=K, model=model, params=params)
@@ -137,8 +130,7 @@ class HyperelasticDynamicsSolver(NonlinearElasticitySolver, ElastodynamicsSolver
         u0[gdofs.astype(np.int64)] = gvals * sg[0]                # the initial displacement takes the Dirichlet values of t_0
         dofs, vals = (gdofs, gvals) if loc is None else loc.dofs(gdofs, gvals)
         model, lame, params = form.model_spec()
-        if form.cellwise() and loc is not None:
-            lame, params = (('cell', loc.cells(lame[1])), None) if params is None else (None, ('cell', loc.cells(params[1])))
+        lame, params = solid_steps.localized(lame, loc), solid_steps.localized(params, loc)
         self._hyper = (lame, model, params)
         rho = self.material_field('density')
         if np.ndim(rho) > 0:
@@ -148,7 +140,7 @@ class HyperelasticDynamicsSolver(NonlinearElasticitySolver, ElastodynamicsSolver
         M = backend.DeviceMatrix(V)
         M.assemble(lame=(0.0, 0.0), mass=self._density_spec(1.0))
         self._mass = self._lumped_mass(V, M)
-        b = self._hyperelastic_external_loads(form, V, loc)       # per dof in a fixed order: the same bits from run to run
+        b = solid_steps.external_loads(self, form, V, loc)        # per dof in a fixed order: the same bits from run to run
         self._load = b.get()[:V.n_owned]
         b.close()
         self._dirichlet = (np.asarray(dofs, dtype=np.int32), np.asarray(vals, dtype=np.float64))

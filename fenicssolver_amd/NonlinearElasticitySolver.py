@@ -8,7 +8,7 @@ constant 3 is kept: it shifts the energy by -mu/2 per unit area and changes noth
 
 The tangent, the internal force and the energy are assembled on the device at every iterate (fs_assemble_hyperelastic); the
 loads are dead loads (force, pressure and stress act on the reference configuration's normals and areas) and are assembled
-once per load step.  The Newton loop (SolverBase._hyperelastic_newton) uses DOLFIN's defaults and stopping test; each step is
+once per load step.  The Newton loop (solid_steps.hyperelastic_newton) uses DOLFIN's defaults and stopping test; each step is
 CG + AMG with the rigid-body near-null space in 3-D and Jacobi-CG in 2-D.  A trial step that inverts a cell is halved.
 
 Energies beyond the reference's (``material['hyperelastic_model']``, one type per solve; none of them exists upstream):
@@ -38,7 +38,7 @@ from .fem import Measure, is_constant_value
 from .SolverBase import SolverError
 from .LinearElasticitySolver import LinearElasticitySolver
 from .stored_stress import StoredStressVonMises
-from . import forms
+from . import forms, solid_steps
 
 _LAME_MODELS = ('neo_hookean', 'st_venant_kirchhoff')
 _MODEL_KEYS = {'neo_hookean': (), 'st_venant_kirchhoff': (), 'mooney_rivlin': ('c10', 'c01', 'bulk_modulus'),
@@ -57,19 +57,12 @@ class NonlinearElasticitySolver(StoredStressVonMises, LinearElasticitySolver):
         self.newton_history = []
 
     def _refuse_unsupported(self):
-        from . import parallel
         V = self.function_space
         if V.degree() != 1:
             raise SolverError('NonlinearElasticitySolver: CG{} displacements are not supported (vector CG1 only: the P2 integrand '
                               'is not polynomial)'.format(V.degree()))
-        if parallel.world()[1] > 1:
-            raise SolverError('NonlinearElasticitySolver runs on one rank')
-        if (hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None) or self.settings.get('periodic_boundary'):
-            raise SolverError('NonlinearElasticitySolver: periodic spaces are not supported')
-        T = getattr(self, 'temperature_distribution', None) or self.settings.get('temperature_distribution')
-        if T is not None and not (isinstance(T, (int, float)) and T == 0):
-            raise SolverError('NonlinearElasticitySolver: temperature_distribution is not supported - the neo-Hookean energy has no '
-                              'thermal term (the reference ignores the setting)')
+        solid_steps.refuse_unsupported(self, 'NonlinearElasticitySolver',
+                                       ' - the neo-Hookean energy has no thermal term (the reference ignores the setting)')
 
     def update_boundary_conditions(self, time_iter_, u, v, ds):
         """The linear class's boundary conditions (loads without a sign: Pi subtracts them), plus surface_source with the
@@ -269,15 +262,10 @@ class NonlinearElasticitySolver(StoredStressVonMises, LinearElasticitySolver):
         model, lame, params = F.model_spec()
         V = self.function_space
         dV, loc = V.device(), V.localizer()
-        uh = u.vector()._values()
-        if loc is not None:
-            uh = loc.nodes(uh)
-            if F.cellwise():
-                lame, params = (('cell', loc.cells(lame[1])), None) if params is None else (None, ('cell', loc.cells(params[1])))
-        if len(uh) < dV.n_local:
-            uh = np.concatenate([uh, np.zeros(dV.n_local - len(uh))])
+        lame, params = solid_steps.localized(lame, loc), solid_steps.localized(params, loc)
+        ud = backend.DeviceVector(dV.n_local, solid_steps.to_device_dofs(dV, loc, u.vector()._values()))
         try:
-            sig = backend.hyperelastic_stress(dV, backend.DeviceVector(dV.n_local, uh), lame, model=model, params=params)
+            sig = backend.hyperelastic_stress(dV, ud, lame, model=model, params=params)
         except backend.BackendError as e:
             if 'inverted' in str(e):
                 raise SolverError('cauchy_stress: the displacement inverts cells - {}'.format(e)) from e
@@ -295,7 +283,4 @@ class NonlinearElasticitySolver(StoredStressVonMises, LinearElasticitySolver):
     def von_Mises(self, u=None):
         """The consistent L2 projection onto CG1 of sqrt(3/2 dev sigma : dev sigma) of the CAUCHY stress of u (default: the
         solution), by the projection the other solid classes use (the linear class's von_Mises means nothing at finite strain)."""
-        s = self.cauchy_stress(u)
-        m = s[:, :3].mean(axis=1)
-        dev2 = ((s[:, :3] - m[:, None]) ** 2).sum(axis=1) + 2.0 * (s[:, 3:] ** 2).sum(axis=1)
-        return self._project_cells(np.sqrt(1.5 * dev2))
+        return self._project_cells(self.von_Mises_cells(self.cauchy_stress(u)))

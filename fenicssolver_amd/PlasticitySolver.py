@@ -11,7 +11,7 @@ Model: eps = sym grad u, one integration point per cell (CG1: constant strain); 
 plastic strain p.  Trial stress sigma_tr = K tr(eps - eps_p) I + 2 G dev(eps - eps_p), q = sqrt(3/2) |dev sigma_tr|,
 f = q - (yield_stress + hardening_modulus p); f <= 0 is elastic, f > 0 the radial return with the consistent tangent.  Return
 mapping, tangent and internal force are evaluated on the device at every iterate (fs_assemble_plasticity); the Newton loop
-(SolverBase._plastic_newton) uses DOLFIN's defaults and stopping test; each step is CG + AMG with the rigid-body near-null space in
+(solid_steps.plastic_newton) uses DOLFIN's defaults and stopping test; each step is CG + AMG with the rigid-body near-null space in
 3-D and Jacobi-CG in 2-D.  The history is committed when a load step has converged.
 
 Settings: material ``yield_stress`` (> 0, required) and ``hardening_modulus`` (H = d sigma_y / dp >= 0, default 0; the uniaxial
@@ -35,7 +35,7 @@ from .fem import Measure
 from .SolverBase import SolverError
 from .LinearElasticitySolver import LinearElasticitySolver
 from .stored_stress import StoredStressVonMises
-from . import forms
+from . import forms, solid_steps
 
 
 class PlasticitySolver(StoredStressVonMises, LinearElasticitySolver):
@@ -53,21 +53,11 @@ class PlasticitySolver(StoredStressVonMises, LinearElasticitySolver):
 
     # ------------------------------------------------------------------ settings
     def _refuse_unsupported(self):
-        from . import parallel
         V = self.function_space
         if V.degree() != 1:
             raise SolverError('PlasticitySolver: CG{} displacements are not supported (vector CG1 only: a P2 strain varies over the '
                               'cell and needs a history per quadrature point)'.format(V.degree()))
-        if parallel.world()[1] > 1:
-            raise SolverError('PlasticitySolver runs on one rank')
-        if (hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None) or self.settings.get('periodic_boundary'):
-            raise SolverError('PlasticitySolver: periodic spaces are not supported')
-        T = getattr(self, 'temperature_distribution', None) or self.settings.get('temperature_distribution')
-        if T is not None and not (isinstance(T, (int, float)) and T == 0):
-            raise SolverError('PlasticitySolver: temperature_distribution is not supported (no thermal strain in the model)')
-        for key in ('point_source', 'surface_source'):
-            if self.settings.get(key):
-                raise SolverError('PlasticitySolver: {} is not supported'.format(key))
+        solid_steps.refuse_unsupported(self, 'PlasticitySolver', ' (no thermal strain in the model)', ('point_source', 'surface_source'))
 
     def plastic_parameters(self):
         """(mu, lambda, yield_stress, hardening_modulus): numbers for a homogeneous material, arrays [n_cells] where a value varies

@@ -34,7 +34,7 @@ import numpy as np
 
 from .fem import (SolverError, Mesh, MeshFunction, FunctionSpace, VectorFunctionSpace, Function, Constant,
                   Expression, DirichletBC, interpolate, project, nodal_values, is_constant_value)
-from . import forms, case
+from . import forms, case, solid_steps
 
 __all__ = ["SolverError", "SolverBase", "default_report_settings", "default_solver_parameters",
            "default_case_settings"]
@@ -717,8 +717,7 @@ class SolverBase():
                 if loc is None or getattr(loc, 'is_identity', False):
                     tp = F.T_prev.vector()._device(V.n_local)          # the previous solve left it in HBM
                 else:
-                    tp_host = loc.nodes(F.T_prev.vector()._values())
-                    tp = backend.DeviceVector(V.n_local, np.concatenate([tp_host, np.zeros(V.n_local - len(tp_host))]))
+                    tp = backend.DeviceVector(V.n_local, solid_steps.to_device_dofs(V, loc, F.T_prev.vector()._values()))
                 tmp = backend.DeviceVector(V.n_owned)
                 B.spmv(tp, tmp)
                 b.axpy(1.0, tmp)
@@ -739,8 +738,7 @@ class SolverBase():
                 Mb = backend.DeviceMatrix(V)
                 Mb.assemble(lame=(0.0, 0.0), mass=1.0)
                 fh = np.ascontiguousarray(F.body_force_nodal, dtype=np.float64).reshape(-1)
-                fh = fh if loc is None else loc.nodes(fh)
-                fd = backend.DeviceVector(V.n_local, np.concatenate([fh, np.zeros(V.n_local - len(fh))]))
+                fd = backend.DeviceVector(V.n_local, solid_steps.to_device_dofs(V, loc, fh))
                 tmpb = backend.DeviceVector(V.n_owned)
                 Mb.spmv(fd, tmpb)
                 b.axpy(sgn, tmpb)
@@ -780,9 +778,7 @@ class SolverBase():
                 rho, accel = F.inertia
                 Mv = backend.DeviceMatrix(V)
                 Mv.assemble(lame=(0.0, 0.0), mass=L_(rho))
-                ah = accel.vector()._values()
-                ah = ah if loc is None else loc.nodes(ah)
-                ad = backend.DeviceVector(V.n_local, np.concatenate([ah, np.zeros(V.n_local - len(ah))]))
+                ad = backend.DeviceVector(V.n_local, solid_steps.to_device_dofs(V, loc, accel.vector()._values()))
                 tmp = backend.DeviceVector(V.n_owned)
                 Mv.spmv(ad, tmp)
                 b.axpy(1.0, tmp)
@@ -809,6 +805,14 @@ class SolverBase():
         method = "cg" if getattr(F, "symmetric", True) else "bicgstab"
         return self._device_solve(A, b, u, 'solve_linear_problem', method=method)
 
+    def _newton_settings(self):
+        """solver_parameters['newton_solver'] with DOLFIN's NewtonSolver defaults, and solver_parameters['monitor_convergence']"""
+        sp = self.solver_settings.get('solver_parameters', {}) or {}
+        newton = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
+        return solid_steps.NewtonSettings(float(newton.get('relative_tolerance', 1e-9)), float(newton.get('absolute_tolerance', 1e-10)),
+                                          int(newton.get('maximum_iterations', 50)), float(newton.get('relaxation_parameter', 1.0)),
+                                          sp.get('monitor_convergence'))
+
     def solve_nonlinear_problem(self, F, u_current, Dirichlet_bcs, J):
         """NonlinearVariationalSolver.solve() (SolverBase.py:615-626): Newton iteration with DOLFIN's
         NewtonSolver defaults (relative 1e-9 / absolute 1e-10 on the residual norm, 50 iterations, no
@@ -820,18 +824,14 @@ class SolverBase():
         if isinstance(F, forms.NavierStokesForm):
             return self._navier_stokes_newton(F, u_current, Dirichlet_bcs)
         if isinstance(F, forms.HyperelasticForm):
-            return self._hyperelastic_newton(F, u_current, Dirichlet_bcs)
+            return solid_steps.hyperelastic_newton(self, F, u_current, Dirichlet_bcs)
         if isinstance(F, forms.PlasticForm):
-            return self._plastic_newton(F, u_current, Dirichlet_bcs)
+            return solid_steps.plastic_newton(self, F, u_current, Dirichlet_bcs)
         if not isinstance(F, forms.ScalarForm):
             raise SolverError('nonlinear solves are built for scalar transport and Navier-Stokes only')
         per = F.space.periodic_pairs()
         from . import parallel
-        sp = self.solver_settings.get('solver_parameters', {}) or {}
-        newton = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
-        rtol = float(newton.get('relative_tolerance', 1e-9))
-        atol = float(newton.get('absolute_tolerance', 1e-10))
-        max_it = int(newton.get('maximum_iterations', 50))
+        rtol, atol, max_it, _, monitor = self._newton_settings()
         V = F.space.device()
         loc = F.space.localizer()          # several GPUs: the iterate stays global on the host, rows are local
         n = V.n_owned
@@ -903,7 +903,7 @@ class SolverBase():
             rnorm = float(np.sqrt(rn2))
             if r0 is None:
                 r0 = rnorm
-            if sp.get('monitor_convergence'):
+            if monitor:
                 self.logger.info("Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = %.3e (tol = %.3e)",
                                  it, rnorm, atol, rnorm / r0 if r0 > 0 else 0.0, rtol)
             if rnorm < atol or (r0 > 0 and rnorm / r0 < rtol):
@@ -931,373 +931,6 @@ class SolverBase():
             T = T + d
             self.newton_iterations = it + 1
         u_current.vector().set_local(T)
-        return u_current
-
-    # ---- hyperelasticity (NonlinearElasticitySolver) ------------------------------------------------
-    def _hyperelastic_external_loads(self, F, V, loc):
-        """f_ext = int B.v dx + the boundary loads (dead loads, physical sign) on the device: assembled once per load step."""
-        from . import backend
-        b = backend.DeviceVector(V.n_owned)
-        b.fill(0.0)
-        if F.body_force is not None:
-            backend.assemble_vector(V, b, vector_value=list(F.body_force))
-        if F.body_force_nodal is not None:
-            Mb = backend.DeviceMatrix(V)
-            Mb.assemble(lame=(0.0, 0.0), mass=1.0)
-            fh = np.ascontiguousarray(F.body_force_nodal, dtype=np.float64).reshape(-1)
-            fh = fh if loc is None else loc.nodes(fh)
-            fd = backend.DeviceVector(V.n_local, np.concatenate([fh, np.zeros(V.n_local - len(fh))]))
-            tmp = backend.DeviceVector(V.n_owned)
-            Mb.spmv(fd, tmp)
-            b.axpy(1.0, tmp)
-        # boundary loads: summed per dof on the host in a fixed order and added once per dof - the facet kernels scatter with atomics,
-        # whose order would make f_ext, and with it every Newton iterate, differ in the last bits from run to run
-        d = self.dimension
-        n_dofs = F.space.dim()
-        co = self.mesh.coordinates()[:, :d]
-        dof_l, val_l = [], []
-        for t in F.tractions:
-            if isinstance(t, forms.NodalLoad):
-                dof_l.append(np.asarray(t.dofs, dtype=np.int64))
-                val_l.append(np.asarray(t.values, dtype=np.float64))
-                continue
-            tri = np.asarray(self._facets_of(t.marker_id), dtype=np.int64)
-            if not len(tri):
-                continue
-            p = co[tri]
-            if tri.shape[1] == 2:                       # boundary edges of a triangle mesh
-                size = np.linalg.norm(p[:, 1] - p[:, 0], axis=1)
-            else:
-                size = 0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
-            g = np.broadcast_to(np.asarray(t.g, dtype=np.float64), (len(tri), d))
-            w = size / tri.shape[1]                     # int lambda_a ds = |facet| / (number of its vertices)
-            dof_l.append((tri[:, :, None] * d + np.arange(d)[None, None, :]).ravel())
-            val_l.append(np.broadcast_to((w[:, None] * g)[:, None, :], (len(tri), tri.shape[1], d)).ravel())
-        if dof_l:
-            total = np.bincount(np.concatenate(dof_l), weights=np.concatenate(val_l), minlength=n_dofs)
-            nd_ = np.nonzero(total)[0]
-            nv_ = total[nd_]
-            if loc is not None:
-                nd_, nv_ = loc.dofs(nd_, nv_)
-            if len(nd_):
-                b.add_entries(nd_, nv_)
-        return b
-
-    def _hyperelastic_newton(self, F, u_current, bcs):
-        """solve(F == 0, u, bcs, J=J) of NonlinearElasticitySolver (:90-98): Newton on r(u) = f_int(u) - f_ext = 0 with DOLFIN's
-        NewtonSolver defaults and stopping test (the norm of r with the Dirichlet rows zeroed, absolute 1e-10 / relative 1e-9,
-        50 iterations, relaxation 1).  The boundary values are imposed on the first iterate; every correction is zero on the
-        Dirichlet dofs.  Tangent, internal force and inverted cells are assembled on the device in one call per iterate
-        (fs_assemble_hyperelastic; the tangent of the converged iterate is the one unused assembly); each linear step is CG + AMG
-        (3-D, rigid-body near-null space, a hierarchy per tangent) or Jacobi-CG (2-D).  A trial iterate with an inverted cell
-        (J <= 0) or a non-finite residual is halved, at most 10 times."""
-        from . import backend, parallel
-        from .fem import Function
-        if parallel.world()[1] > 1:
-            raise SolverError('hyperelastic Newton solves run on one rank')
-        sp = self.solver_settings.get('solver_parameters', {}) or {}
-        newton = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
-        rtol = float(newton.get('relative_tolerance', 1e-9))
-        atol = float(newton.get('absolute_tolerance', 1e-10))
-        max_it = int(newton.get('maximum_iterations', 50))
-        relax = float(newton.get('relaxation_parameter', 1.0))
-        V = F.space.device()
-        loc = F.space.localizer()          # a mesh file uploaded in locality order: host arrays map through it
-
-        def to_dev(xh):
-            xd = xh if loc is None else loc.nodes(xh)
-            return np.concatenate([xd, np.zeros(V.n_local - len(xd))]) if len(xd) < V.n_local else xd
-
-        steps_hint = ('apply the load in steps: transient_settings with boundary values and loads that change from step to step '
-                      '(a per-step sequence or a callable of time - constant values repeat the full load at every step)')
-        gdofs, gvals = self._bc_arrays(bcs)
-        dofs = gdofs if loc is None else loc.dofs(gdofs, gvals)[0]
-        model, lame, params = F.model_spec()             # the energy and its material: Lame parameters or a parameter table
-        if F.cellwise() and loc is not None:
-            if params is None:
-                lame = ('cell', loc.cells(lame[1]))
-            else:
-                params = ('cell', loc.cells(params[1]))
-        f_ext = self._hyperelastic_external_loads(F, V, loc)
-        K = backend.DeviceMatrix(V)
-        r = backend.DeviceVector(V.n_owned)
-        ud = backend.DeviceVector(V.n_local)
-
-        def evaluate(xh):
-            """Tangent, internal force minus loads and inverted cells at xh in ONE call (a per-cell material is uploaded once per
-            iterate); (info, ||r|| with the Dirichlet rows zeroed) - None for a state with an inverted cell.  K and r then belong to
-            the last state evaluated: the tangent of a rejected trial is overwritten by the next one."""
-            ud.set(to_dev(xh))
-            info = backend.assemble_hyperelastic(V, ud, lame, K=K, r=r, model=model, params=params)
-            if info['n_inverted']:
-                return info, None
-            r.axpy(-1.0, f_ext)
-            if dofs.size:
-                backend.set_dirichlet_values(r, dofs, 0.0)
-            rn = float(np.sqrt(r.dot(r)))
-            return info, (rn if np.isfinite(rn) else None)
-
-        x = u_current.vector()._values().copy()
-        if gdofs.size:
-            x[gdofs] = gvals                                # the first iterate carries the boundary values
-        info, rnorm = evaluate(x)
-        if rnorm is None:
-            if info['n_inverted']:
-                raise SolverError('hyperelastic Newton: the initial iterate (previous solution with the boundary values imposed) inverts '
-                                  '{} cell(s), first cell {}: {}'.format(info['n_inverted'], info['first_inverted_cell'], steps_hint))
-            raise SolverError('hyperelastic Newton: the residual of the initial iterate is not finite')
-        r0 = rnorm
-        self.newton_iterations = 0
-        self.newton_history = [rnorm]
-        self.newton_stats = []
-        self.newton_steps = []                              # the step length taken at each iteration (relaxation, halvings)
-        du = Function(self.function_space)
-        for it in range(max_it + 1):
-            if sp.get('monitor_convergence'):
-                self.logger.info("Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = %.3e (tol = %.3e)",
-                                 it, rnorm, atol, rnorm / r0 if r0 > 0 else 0.0, rtol)
-            if rnorm < atol or (r0 > 0 and rnorm / r0 < rtol):
-                break
-            if it == max_it:
-                raise SolverError('Newton solver did not converge in {} iterations (residual {:.3e})'.format(max_it, rnorm))
-            rhs = backend.DeviceVector(V.n_owned)
-            rhs.axpy(-1.0, r)
-            if dofs.size:
-                K.apply_dirichlet(rhs, dofs, 0.0, symmetric=True)     # the correction is zero on the Dirichlet boundary
-            try:
-                if self.dimension == 3:
-                    self._device_solve(K, rhs, du, 'hyperelastic Newton step', amg=True, near_nullspace="rigid_body", operator_key=None)
-                else:
-                    self._device_solve(K, rhs, du, 'hyperelastic Newton step')
-            except (SolverError, backend.BackendError) as e:
-                st = self.last_solve_stats or {}
-                if isinstance(e, backend.BackendError) and getattr(e, 'rc', None) == -6 or \
-                        (isinstance(e, SolverError) and st.get('converged', 0) < 0):      # FS_ERR_NUMERIC: CG breakdown
-                    raise SolverError('hyperelastic Newton: CG broke down at iteration {} - the tangent is not positive definite there '
-                                      '(a material instability, or a load step too large: {})'.format(it, steps_hint)) from e
-                raise
-            st = self.last_solve_stats
-            self.newton_stats.append({'krylov_iterations': st['iterations'], 'solve_ms': st['solve_ms'],
-                                      'amg_setup_ms': st.get('amg_setup_ms', 0.0)})
-            d = du.vector()._values()
-            if not np.all(np.isfinite(d)):
-                raise SolverError('hyperelastic Newton: the correction of iteration {} is not finite'.format(it))
-            step = relax
-            for cut in range(11):
-                x_try = x + step * d
-                info, rn_try = evaluate(x_try)
-                if rn_try is not None:
-                    break
-                if cut == 10:
-                    what = ('inverts {} cell(s), first cell {}'.format(info['n_inverted'], info['first_inverted_cell'])
-                            if info['n_inverted'] else 'gives a non-finite residual')
-                    raise SolverError('hyperelastic Newton: at iteration {} the step, halved 10 times, still {}: {}'.format(
-                        it, what, steps_hint))
-                step *= 0.5
-            if step != relax:
-                self.logger.info('hyperelastic Newton: step of iteration %d cut to %g (inverted cells at the full step)', it, step)
-            x = x_try
-            rnorm = rn_try
-            self.newton_steps.append(step)
-            self.newton_history.append(rnorm)
-            self.newton_iterations = it + 1
-        u_current.vector().set_local(x)
-        return u_current
-
-    # ---- J2 plasticity (PlasticitySolver) -----------------------------------------------------------------
-    def _plastic_newton(self, F, u_current, bcs):
-        """One load step of PlasticitySolver: Newton on r(u) = f_int(u; committed history) - f_ext = 0 with the stopping test, the
-        defaults and the linear solvers of _hyperelastic_newton (DOLFIN's NewtonSolver; CG + AMG with the rigid-body near-null space
-        and a hierarchy per tangent in 3-D, Jacobi-CG in 2-D).  Return mapping, consistent tangent and internal force are evaluated
-        on the device in one call per iterate (fs_assemble_plasticity) from the history committed by the previous step; this loop only
-        decides about convergence.  A trial iterate with a non-finite residual is halved, at most 10 times.  The history is committed
-        when the step has converged and not otherwise: an error leaves the committed state as it was."""
-        from . import backend, parallel
-        from .fem import Function
-        if parallel.world()[1] > 1:
-            raise SolverError('plastic Newton solves run on one rank')
-        sp = self.solver_settings.get('solver_parameters', {}) or {}
-        newton = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
-        rtol = float(newton.get('relative_tolerance', 1e-9))
-        atol = float(newton.get('absolute_tolerance', 1e-10))
-        max_it = int(newton.get('maximum_iterations', 50))
-        relax = float(newton.get('relaxation_parameter', 1.0))
-        V = F.space.device()
-        loc = F.space.localizer()
-
-        def to_dev(xh):
-            xd = xh if loc is None else loc.nodes(xh)
-            return np.concatenate([xd, np.zeros(V.n_local - len(xd))]) if len(xd) < V.n_local else xd
-
-        steps_hint = ('apply the load in smaller steps (transient_settings with boundary values and loads that change from step to '
-                      'step), or give the material a hardening_modulus > 0')
-        gdofs, gvals = self._bc_arrays(bcs)
-        dofs = gdofs if loc is None else loc.dofs(gdofs, gvals)[0]
-        material = F.material_spec()
-        if F.cellwise() and loc is not None:
-            material = ('cell', loc.cells(material[1]))
-        history = F.history
-        f_ext = self._hyperelastic_external_loads(F, V, loc)
-        K = backend.DeviceMatrix(V)
-        r = backend.DeviceVector(V.n_owned)
-        ud = backend.DeviceVector(V.n_local)
-
-        def evaluate(xh):
-            """Trial history, tangent and internal force minus loads at xh in ONE call; (info, ||r|| with the Dirichlet rows zeroed) -
-            None for a non-finite state.  K, r and the trial history then belong to the last state evaluated."""
-            ud.set(to_dev(xh))
-            info = backend.assemble_plasticity(V, ud, history, material, K=K, r=r)
-            if info['n_nonfinite']:
-                return info, None
-            r.axpy(-1.0, f_ext)
-            if dofs.size:
-                backend.set_dirichlet_values(r, dofs, 0.0)
-            rn = float(np.sqrt(r.dot(r)))
-            return info, (rn if np.isfinite(rn) else None)
-
-        x = u_current.vector()._values().copy()
-        if gdofs.size:
-            x[gdofs] = gvals                                # the first iterate carries the boundary values
-        info, rnorm = evaluate(x)
-        if rnorm is None:
-            raise SolverError('plastic Newton: the residual of the initial iterate is not finite')
-        r0 = rnorm
-        self.newton_iterations = 0
-        self.newton_history = [rnorm]
-        self.newton_stats = []
-        self.newton_steps = []
-        du = Function(self.function_space)
-        for it in range(max_it + 1):
-            if sp.get('monitor_convergence'):
-                self.logger.info("Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = %.3e (tol = %.3e), %d cells yielding",
-                                 it, rnorm, atol, rnorm / r0 if r0 > 0 else 0.0, rtol, info['n_yielded'])
-            if rnorm < atol or (r0 > 0 and rnorm / r0 < rtol):
-                break
-            if it == max_it:
-                raise SolverError('Newton solver did not converge in {} iterations (residual {:.3e}): {}'.format(max_it, rnorm, steps_hint))
-            rhs = backend.DeviceVector(V.n_owned)
-            rhs.axpy(-1.0, r)
-            if dofs.size:
-                K.apply_dirichlet(rhs, dofs, 0.0, symmetric=True)     # the correction is zero on the Dirichlet boundary
-            try:
-                if self.dimension == 3:
-                    self._device_solve(K, rhs, du, 'plastic Newton step', amg=True, near_nullspace="rigid_body", operator_key=None)
-                else:
-                    self._device_solve(K, rhs, du, 'plastic Newton step')
-            except (SolverError, backend.BackendError) as e:
-                st = self.last_solve_stats or {}
-                if isinstance(e, backend.BackendError) and getattr(e, 'rc', None) == -6 or \
-                        (isinstance(e, SolverError) and st.get('converged', 0) < 0):      # FS_ERR_NUMERIC: CG breakdown
-                    raise SolverError('plastic Newton: CG broke down at iteration {} - the consistent tangent is singular there (a limit '
-                                      'load with hardening_modulus = 0): {}'.format(it, steps_hint)) from e
-                raise
-            st = self.last_solve_stats
-            self.newton_stats.append({'krylov_iterations': st['iterations'], 'solve_ms': st['solve_ms'],
-                                      'amg_setup_ms': st.get('amg_setup_ms', 0.0)})
-            d = du.vector()._values()
-            if not np.all(np.isfinite(d)):
-                raise SolverError('plastic Newton: the correction of iteration {} is not finite: {}'.format(it, steps_hint))
-            step = relax
-            for cut in range(11):
-                x_try = x + step * d
-                info, rn_try = evaluate(x_try)
-                if rn_try is not None:
-                    break
-                if cut == 10:
-                    raise SolverError('plastic Newton: at iteration {} the step, halved 10 times, still gives a non-finite residual: {}'.format(
-                        it, steps_hint))
-                step *= 0.5
-            if step != relax:
-                self.logger.info('plastic Newton: step of iteration %d cut to %g (non-finite residual at the full step)', it, step)
-            x = x_try
-            rnorm = rn_try
-            self.newton_steps.append(step)
-            self.newton_history.append(rnorm)
-            self.newton_iterations = it + 1
-        history.commit()                                    # the last evaluation was at the converged iterate
-        self.yielded_last_step = info['n_yielded']
-        u_current.vector().set_local(x)
-        return u_current
-
-    # ---- Prony-series viscoelasticity (ViscoelasticitySolver) ------------------------------------------------
-    def _viscoelastic_step(self, F, u_current, bcs):
-        """One step of ViscoelasticitySolver, a single linear solve: (1) the history load -int B^T s_hist dx from the COMMITTED
-        history (fs_assemble_viscoelastic), (2) K(mu_eff, lambda_eff) u = f_ext + history load with the Dirichlet values imposed -
-        CG + AMG with the rigid-body near-null space in 3-D, Jacobi-CG in 2-D, (3) the per-cell update at u, (4) commit.  A solve that
-        does not converge raises before (3): the committed history stays as it was.  The effective operator depends on the step
-        length and the material only, so it is assembled once and kept while both (and the set of Dirichlet dofs) are unchanged,
-        and with it the AMG hierarchy (the operator key of _device_solve): ``operator_assemblies`` and ``amg_setups`` count the
-        builds.  F.steady: the long-term equilibrium - the same solve with mu = G0 g_inf and no history load."""
-        from . import backend, parallel
-        if parallel.world()[1] > 1:
-            raise SolverError('viscoelastic steps run on one rank')
-        V = F.space.device()
-        loc = F.space.localizer()
-
-        def to_dev(xh):
-            xd = xh if loc is None else loc.nodes(xh)
-            return np.concatenate([xd, np.zeros(V.n_local - len(xd))]) if len(xd) < V.n_local else xd
-
-        def cell_spec(spec):
-            return ('cell', loc.cells(spec[1])) if isinstance(spec[0], str) and loc is not None else spec
-
-        gdofs, gvals = self._bc_arrays(bcs)
-        dofs, vals = (gdofs, gvals) if loc is None else loc.dofs(gdofs, gvals)
-        dt = 1.0 if F.steady else float(F.dt)
-        history = F.history
-        # the effective operator and everything derived from the material: once per (dt, material, Dirichlet set).  Forms of one
-        # solve() carry the material under one token, so a step that changes nothing costs no host work per cell here.
-        dof_bytes = np.asarray(dofs, dtype=np.int64).tobytes()
-        ctx = getattr(self, '_visco_ctx', None)
-        token = getattr(F, 'material_token', None)
-        if ctx is None or token is None or ctx['token'] is not token or ctx['steady'] != bool(F.steady) or ctx['dt'] != dt \
-                or ctx['dofs'] != dof_bytes or ctx['space'] is not V:
-            mu_e, lm_e = F.effective_lame(None if F.steady else F.dt)
-            cellwise = np.ndim(mu_e) > 0 or np.ndim(lm_e) > 0
-            lame_host = np.stack(np.broadcast_arrays(np.asarray(mu_e, dtype=np.float64), np.asarray(lm_e, dtype=np.float64)), axis=-1)
-            if F.steady:                                # an elastic material with the long-term moduli, no series
-                material = ('cell', lame_host) if cellwise else (float(mu_e), float(lm_e), [])
-            else:
-                material = F.material_spec()
-            K_raw = backend.DeviceMatrix(V)
-            K_raw.assemble(lame=cell_spec(('cell', lame_host)) if cellwise else (float(mu_e), float(lm_e)))
-            self.operator_assemblies = getattr(self, 'operator_assemblies', 0) + 1
-            self._visco_serial = getattr(self, '_visco_serial', 0) + 1          # never reused: the key of the AMG hierarchy
-            ctx = {'token': token, 'steady': bool(F.steady), 'dt': dt, 'dofs': dof_bytes, 'space': V, 'material': cell_spec(material),
-                   'K_raw': K_raw, 'K': backend.DeviceMatrix(V), 'key': ('viscoelastic', self._visco_serial)}
-            self._visco_ctx = ctx
-        material = ctx['material']
-        # 1. right-hand side: loads plus the history load
-        rhs = self._hyperelastic_external_loads(F, V, loc)
-        times = {'history_load_ms': 0.0}
-        if not F.steady and history.n_terms:
-            info = backend.assemble_viscoelastic(V, history, material, dt, load=rhs, add=True)
-            times['history_load_ms'] = info['load_ms']
-        # 2. the solve; the Dirichlet rows and the lifting of their values go into a copy of the kept operator
-        K = ctx['K']
-        K.copy_from(ctx['K_raw'])
-        if len(dofs):
-            K.apply_dirichlet(rhs, dofs, vals, symmetric=True)
-        if self.dimension == 3:
-            self._device_solve(K, rhs, u_current, 'viscoelastic step', amg=True, near_nullspace="rigid_body", operator_key=ctx['key'])
-        else:
-            self._device_solve(K, rhs, u_current, 'viscoelastic step')
-        st = self.last_solve_stats
-        if 'amg_reused' in st and not st['amg_reused']:
-            self.amg_setups = getattr(self, 'amg_setups', 0) + 1
-        x = u_current.vector()._values()
-        if not np.all(np.isfinite(x)):
-            raise SolverError('viscoelastic step: the displacement is not finite')
-        # 3. the update, 4. commit
-        ud = backend.DeviceVector(V.n_local, to_dev(x))
-        info = backend.assemble_viscoelastic(V, history, material, dt, u=ud)
-        if info['n_nonfinite']:
-            raise SolverError('viscoelastic step: the updated stress is not finite in {} cell(s), first cell {}'.format(
-                info['n_nonfinite'], info['first_nonfinite_cell']))
-        history.commit()
-        times.update({'update_ms': info['update_ms'], 'solve_ms': st['solve_ms'], 'krylov_iterations': st['iterations'],
-                      'amg_setup_ms': st.get('amg_setup_ms', 0.0) if not st.get('amg_reused', True) else 0.0})
-        self.step_stats.append(times)
         return u_current
 
     # ---- Taylor-Hood Navier-Stokes (CoupledNavierStokesSolver) -----------------------------------------
@@ -1473,11 +1106,7 @@ class SolverBase():
         V, ctx, dofs, vals, loc = self._navier_stokes_context(F, bcs)
         gdofs, gvals = self._bc_arrays(bcs)
         sp = self.solver_settings.get('solver_parameters', {}) or {}
-        ns = sp.get('newton_solver', {}) if isinstance(sp.get('newton_solver', {}), dict) else {}
-        rtol = float(ns.get('relative_tolerance', 1e-9))
-        atol = float(ns.get('absolute_tolerance', 1e-10))
-        max_it = int(ns.get('maximum_iterations', 50))
-        relax = float(ns.get('relaxation_parameter', 1.0))
+        rtol, atol, max_it, relax, _ = self._newton_settings()
         lin_rtol = float(sp.get('krylov_relative_tolerance', 1e-6))
         adaptive = 'krylov_relative_tolerance' not in sp     # inexact Newton: see forcing() below
         w = u_current.vector().get_local()

@@ -10,7 +10,7 @@ deviatoric response relaxes:
 A step of length dt uses the recursion that is exact for a strain history linear within the step (x_k = dt/tau_k, a_k = exp(-x_k),
 b_k = -expm1(-x_k)/x_k, h_k <- a_k h_k + b_k (e_new - e_old)), so every step is ONE linear solve with the elasticity operator of
 the effective moduli mu_eff = G0 (g_inf + sum g_k b_k), lambda_eff = K - 2/3 mu_eff and a history load on the right-hand side
-(SolverBase._viscoelastic_step, fs_assemble_viscoelastic).  The history per cell is e, h_k and the stress; it starts from zero at the
+(solid_steps.viscoelastic_step, fs_assemble_viscoelastic).  The history per cell is e, h_k and the stress; it starts from zero at the
 starting time, and the first step ramps from the zero state to that step's loads: an "instant" load is a very short first step
 through ``time_series``.  The effective operator and its AMG hierarchy are built once per step length (``operator_assemblies``,
 ``amg_setups``); each solve is CG + AMG with the rigid-body near-null space in 3-D and Jacobi-CG in 2-D (plane strain).
@@ -38,7 +38,7 @@ from .fem import Measure
 from .SolverBase import SolverError
 from .LinearElasticitySolver import LinearElasticitySolver
 from .stored_stress import StoredStressVonMises
-from . import case, forms
+from . import case, forms, solid_steps
 
 MAX_TERMS = 8           # FS_VISCO_MAX_TERMS of the library
 
@@ -57,21 +57,11 @@ class ViscoelasticitySolver(StoredStressVonMises, LinearElasticitySolver):
 
     # ------------------------------------------------------------------ settings
     def _refuse_unsupported(self):
-        from . import parallel
         V = self.function_space
         if V.degree() != 1:
             raise SolverError('ViscoelasticitySolver: CG{} displacements are not supported (vector CG1 only: a P2 strain varies over '
                               'the cell and needs a history per quadrature point)'.format(V.degree()))
-        if parallel.world()[1] > 1:
-            raise SolverError('ViscoelasticitySolver runs on one rank')
-        if (hasattr(V, 'periodic_pairs') and V.periodic_pairs() is not None) or self.settings.get('periodic_boundary'):
-            raise SolverError('ViscoelasticitySolver: periodic spaces are not supported')
-        T = getattr(self, 'temperature_distribution', None) or self.settings.get('temperature_distribution')
-        if T is not None and not (isinstance(T, (int, float)) and T == 0):
-            raise SolverError('ViscoelasticitySolver: temperature_distribution is not supported (no thermal strain in the model)')
-        for key in ('point_source', 'surface_source'):
-            if self.settings.get(key):
-                raise SolverError('ViscoelasticitySolver: {} is not supported'.format(key))
+        solid_steps.refuse_unsupported(self, 'ViscoelasticitySolver', ' (no thermal strain in the model)', ('point_source', 'surface_source'))
 
     def _series_value(self, v, what):
         if isinstance(v, numbers.Number) and not isinstance(v, bool):
@@ -189,7 +179,7 @@ class ViscoelasticitySolver(StoredStressVonMises, LinearElasticitySolver):
 
     def solve_form(self, F, u_, bcs):
         F.history = self._history(0 if F.steady else len(F.terms))
-        return self._viscoelastic_step(F, u_, bcs)
+        return solid_steps.viscoelastic_step(self, F, u_, bcs)
 
     # ------------------------------------------------------------------ results
     def _committed(self):

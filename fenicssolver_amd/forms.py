@@ -199,7 +199,7 @@ HYPER_PARAMETER_NAMES = {"mooney_rivlin": ("c10", "c01", "bulk_modulus"), "yeoh"
 
 
 class HyperelasticForm:
-    """Pi = int psi(F) dx - int B.u dx - loads.u ds; the Newton iteration solves dPi/du = 0 (SolverBase._hyperelastic_newton).
+    """Pi = int psi(F) dx - int B.u dx - loads.u ds; the Newton iteration solves dPi/du = 0 (solid_steps.hyperelastic_newton).
     ``model``: 'neo_hookean' (the compressible neo-Hookean energy of NonlinearElasticitySolver.py:41-98) or 'st_venant_kirchhoff',
     both with the Lame parameters mu / lmbda; 'mooney_rivlin' or 'yeoh' with the parameter table ``params``.  Only the first has a
     counterpart upstream.  The loads are dead loads with their PHYSICAL sign (the reference subtracts them from Pi; no
@@ -250,7 +250,7 @@ class HyperelasticForm:
 
 class PlasticForm:
     """r(u) = int sigma(eps(u); history) : grad v dx - int B.v dx - loads.v ds with sigma the radial return of small-strain J2
-    plasticity with linear isotropic hardening (PlasticitySolver); SolverBase._plastic_newton solves r = 0 per load step.  Dead
+    plasticity with linear isotropic hardening (PlasticitySolver); solid_steps.plastic_newton solves r = 0 per load step.  Dead
     loads with their physical sign, as in HyperelasticForm.  ``history``: the backend.PlasticHistory the solver keeps across steps."""
 
     def __init__(self, space):
@@ -300,7 +300,7 @@ def prony_step_coefficients(x):
 
 class ViscoelasticForm:
     """One step of small-strain linear viscoelasticity (generalized Maxwell solid, ViscoelasticitySolver):
-    K(mu_eff, lambda_eff) u = int B.v dx + loads.v ds - int B^T s_hist dx, solved by SolverBase._viscoelastic_step.  ``mu``, ``lmbda``:
+    K(mu_eff, lambda_eff) u = int B.v dx + loads.v ds - int B^T s_hist dx, solved by solid_steps.viscoelastic_step.  ``mu``, ``lmbda``:
     the INSTANTANEOUS Lame parameters, ``terms``: the Prony series [(g_k, tau_k), ...]; each value a number or an array [n_cells]
     in host cell order.  ``dt``: the step length; ``steady``: the long-term equilibrium (mu = G0 g_inf, no history).  Dead loads with
     their physical sign, as in PlasticForm.  ``history``: the backend.ViscoHistory the solver keeps across steps."""

@@ -12,9 +12,9 @@ class StoredStressVonMises:
     its CG1 projection - for solver classes whose stress is not C : eps(u) (PlasticitySolver, ViscoelasticitySolver).  Listed before
     LinearElasticitySolver among the bases, so that it replaces the inherited von_Mises()."""
 
-    def von_Mises_cells(self):
-        """sqrt(3/2) |dev sigma| of the returned stress, per cell"""
-        s = self.stress()
+    def von_Mises_cells(self, stress=None):
+        """sqrt(3/2) |dev sigma| per cell of ``stress`` (default: the stored stress)"""
+        s = self.stress() if stress is None else stress
         m = s[:, :3].mean(axis=1)
         dev2 = ((s[:, :3] - m[:, None]) ** 2).sum(axis=1) + 2.0 * (s[:, 3:] ** 2).sum(axis=1)
         return np.sqrt(1.5 * dev2)
