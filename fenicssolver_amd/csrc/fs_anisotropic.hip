@@ -418,7 +418,8 @@ extern "C" int fs_anisotropic_stress(fs_space_t space, fs_vector_t u, const fs_a
     if (vm_rhs) {
         FS_REFUSE_DG_SPACE(p1_space, "fs_anisotropic_stress");
         FS_REQUIRE(p1_space->mesh == m, "%s: the two spaces live on different meshes", who);
-        FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1 && p1_space->inc_cell.p, "%s: the target is the scalar CG1 space of the mesh", who);
+        FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1, "%s: the target is the scalar CG1 space of the mesh", who);
+        FS_REQUIRE_TABLES(p1_space, who);
         FS_REQUIRE(vm_rhs->d.n >= p1_space->n_dofs_owned, "%s: vector too short", who);
     }
     hipStream_t s = fs_rt().stream;

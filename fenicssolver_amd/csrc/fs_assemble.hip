@@ -82,12 +82,20 @@ struct row_gather_shape {
     size_t lds;
     int grid;
 };
+static bool space_debug() {
+    static const bool on = getenv("FS_SPACE_DEBUG") != nullptr;
+    return on;
+}
 static int make_row_gather_shape(const fs_space_s* sp, row_gather_shape* out) {
     out->bd = (int64_t)sp->max_row * FS_BLOCK * 8 <= 64 * 1024 ? FS_BLOCK : 64;
     out->lds = (size_t)sp->max_row * out->bd * sizeof(double);
-    FS_REQUIRE(out->lds <= 64 * 1024, "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator", sp->max_row);
+    FS_REQUIRE(sp->max_row <= FS_GATHER_MAX_ROW && out->lds <= 64 * 1024,
+               "fs_assemble_matrix: rows of %d entries exceed the LDS accumulator of the row-gather kernels (at most %d entries per row)", sp->max_row,
+               FS_GATHER_MAX_ROW);
     const int wpb = out->bd / 64;
     out->grid = (fs_grid_for((sp->n_slices + wpb - 1) / wpb, 1, 8192) + 7) & ~7;
+    if (space_debug())
+        fprintf(stderr, "[fs_assemble] scalar matrix by rows: workgroups of %d threads, %zu B of LDS (longest row %d)\n", out->bd, out->lds, sp->max_row);
     return FS_OK;
 }
 
@@ -2669,7 +2677,8 @@ static int assemble_matrix_scalar_tri(fs_matrix_s* A, const fs_bilinear_form* fo
     coef_dev kc, ac;
     row_gather_shape sh;
     if (sp->degree == 2) {
-        FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: CG2 space on triangles without assembly tables");
+        FS_REQUIRE(A->bs == 1, "fs_assemble_matrix: triangular meshes carry scalar and 2-vector spaces");
+        FS_REQUIRE_TABLES(sp, "fs_assemble_matrix (CG2 on triangles)");
         FS_CHECK(make_coef(form->advection, 3 * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
         FS_REQUIRE(ac.mode == FS_COEF_NONE || ac.mode == FS_COEF_CONST || ac.mode == FS_COEF_CELL,
                    "fs_assemble_matrix: CG2 advection (and its SUPG test function) takes a constant or per-cell velocity");
@@ -2684,7 +2693,8 @@ static int assemble_matrix_scalar_tri(fs_matrix_s* A, const fs_bilinear_form* fo
         });
         return FS_OK;
     }
-    FS_REQUIRE(A->bs == 1 && sp->inc_cell.p, "fs_assemble_matrix: triangular meshes carry scalar CG1 spaces");
+    FS_REQUIRE(A->bs == 1, "fs_assemble_matrix: triangular meshes carry scalar and 2-vector spaces");
+    FS_REQUIRE_TABLES(sp, "fs_assemble_matrix (CG1 on triangles)");
     FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
     FS_REQUIRE(kc.mode != FS_COEF_NODAL, "fs_assemble_matrix: nodal stiffness coefficient is not supported");
     FS_CHECK(make_coef(form->advection, (form->advection.mode == FS_COEF_CELL_ROW ? 9 : 3) * m->nc, astore, &ac, "fs_assemble_matrix(advection)"));
@@ -2704,7 +2714,7 @@ static int assemble_matrix_p2_scalar(fs_matrix_s* A, const fs_bilinear_form* for
     fs_space_s* sp = A->space;
     fs_mesh_s* m = sp->mesh;
     hipStream_t s = fs_rt().stream;
-    FS_REQUIRE(sp->inc_cell.p, "fs_assemble_matrix: CG2 space has no assembly tables");
+    FS_REQUIRE_TABLES(sp, "fs_assemble_matrix (CG2)");
     dbuf<double> kstore, astore;
     coef_dev kc, ac;
     FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
@@ -2794,12 +2804,14 @@ static int assemble_matrix_scalar(fs_matrix_s* A, const fs_bilinear_form* form, 
     fs_mesh_s* m = sp->mesh;
     hipStream_t s = fs_rt().stream;
     FS_REQUIRE(sp->slots.p, "fs_assemble_matrix: space has no assembly tables");
-    FS_REQUIRE(form->advection.mode == FS_COEF_NONE, "fs_assemble_matrix: advection needs the row-gather tables");
+    if (form->advection.mode != FS_COEF_NONE) FS_REQUIRE_TABLES(sp, "fs_assemble_matrix (advection)");
     if (!add) FS_CHECK(A->val.zero(s));
     dbuf<double> kstore;
     coef_dev kc;
     FS_CHECK(make_coef(form->stiffness, m->nc, kstore, &kc, "fs_assemble_matrix(stiffness)"));
-    FS_REQUIRE(kc.mode != FS_COEF_NODAL && kc.mode != FS_COEF_CELL_TENSOR, "fs_assemble_matrix: nodal / per-cell tensor stiffness coefficients need the row-gather tables");
+    FS_REQUIRE(kc.mode != FS_COEF_NODAL, "fs_assemble_matrix: nodal stiffness coefficient is not supported");
+    if (kc.mode == FS_COEF_CELL_TENSOR) FS_REQUIRE_TABLES(sp, "fs_assemble_matrix (per-cell tensor stiffness)");
+    if (space_debug()) fprintf(stderr, "[fs_assemble] scalar matrix by cells: atomic kernel over the slot table (longest row %d)\n", sp->max_row);
     hipLaunchKernelGGL(k_assemble_p1_scalar, dim3(fs_grid_for(m->nc, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, m->cells.p, m->xyz.p, sp->slots.p, m->nc, kc, mc, A->val.p);
     return FS_OK;
 }
@@ -3269,8 +3281,8 @@ extern "C" int fs_operator_apply(fs_space_t V, const fs_bilinear_form* form, fs_
     FS_REQUIRE(V && form && x && y, "fs_operator_apply: null pointer");
     fs_space_s* sp = V;
     fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(m->tdim == 3 && (sp->degree == 1 || sp->degree == 2) && sp->ncomp == 1 && sp->inc_cell.p,
-               "fs_operator_apply: built for scalar CG1 / CG2 spaces on tetrahedra");
+    FS_REQUIRE(m->tdim == 3 && (sp->degree == 1 || sp->degree == 2) && sp->ncomp == 1, "fs_operator_apply: built for scalar CG1 / CG2 spaces on tetrahedra");
+    FS_REQUIRE_TABLES(sp, "fs_operator_apply");
     FS_REQUIRE(x->d.n >= sp->n_dofs_local && y->d.n >= sp->n_dofs_owned && x != y, "fs_operator_apply: vector too short (or x is y)");
     hipStream_t s = fs_rt().stream;
     dbuf<double> kstore, mstore, astore;
@@ -3329,7 +3341,8 @@ extern "C" int fs_assemble_viscous_stress_nn(fs_space_t th_space, fs_vector_t w,
     FS_REQUIRE(th_space && w && p1_space && b && nn_pref >= 0.0, "fs_assemble_viscous_stress: null pointer / negative reference pressure");
     FS_REQUIRE(th_space->mesh == p1_space->mesh, "fs_assemble_viscous_stress: the two spaces live on different meshes");
     FS_REQUIRE(th_space->ncomp == 4 && th_space->degree == 2, "fs_assemble_viscous_stress: needs the Taylor-Hood node-block space");
-    FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1 && p1_space->inc_cell.p, "fs_assemble_viscous_stress: the target is the scalar CG1 space of the mesh");
+    FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1, "fs_assemble_viscous_stress: the target is the scalar CG1 space of the mesh");
+    FS_REQUIRE_TABLES(p1_space, "fs_assemble_viscous_stress (target space)");
     fs_mesh_s* m = p1_space->mesh;
     const int nt = m->tdim * m->tdim;           // tensor components per vertex: 9 (tetrahedra) or 4 (triangles)
     FS_REQUIRE(w->d.n >= th_space->n_dofs_local && b->d.n >= nt * p1_space->n_dofs_owned, "fs_assemble_viscous_stress: vector too short");
@@ -3372,7 +3385,8 @@ static int von_mises_check(fs_space_t disp_space, fs_vector_t u, fs_space_t p1_s
     FS_REQUIRE(disp_space->mesh == p1_space->mesh, "%s: the two spaces live on different meshes", what);
     FS_REQUIRE((disp_space->ncomp == 3 && disp_space->mesh->tdim == 3) || (disp_space->ncomp == 2 && disp_space->mesh->tdim == 2),
                "%s: needs a 3-vector displacement space on tetrahedra or a 2-vector space on triangles", what);
-    FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1 && p1_space->inc_cell.p, "%s: the target is the scalar CG1 space of the mesh", what);
+    FS_REQUIRE(p1_space->ncomp == 1 && p1_space->degree == 1, "%s: the target is the scalar CG1 space of the mesh", what);
+    FS_REQUIRE_TABLES(p1_space, what);
     FS_REQUIRE(u->d.n >= disp_space->n_dofs_local && b->d.n >= p1_space->n_dofs_owned, "%s: vector too short", what);
     return FS_OK;
 }
@@ -3466,10 +3480,8 @@ __global__ void __launch_bounds__(FS_BLOCK) k_assemble_p1_vector_source_gather(i
 static int assemble_vector_scalar_tri(fs_space_s* space, const fs_linear_form* form, const coef_dev& f, fs_vector_s* b) {
     fs_mesh_s* m = space->mesh;
     hipStream_t s = fs_rt().stream;
-    if (space->degree == 2)
-        FS_REQUIRE(f.mode != FS_COEF_TENSOR && space->inc_cell.p, "fs_assemble_vector: unsupported option on a CG2 space on triangles");
-    else
-        FS_REQUIRE(f.mode != FS_COEF_TENSOR, "fs_assemble_vector: unsupported option on a triangular mesh");
+    FS_REQUIRE(f.mode != FS_COEF_TENSOR, "fs_assemble_vector: unsupported option on a triangular mesh");
+    if (space->degree == 2) FS_REQUIRE_TABLES(space, "fs_assemble_vector (CG2 on triangles)");
     dbuf<double> sstore;
     coef_dev sv;
     FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore, &sv, "fs_assemble_vector(supg_velocity)"));
@@ -3494,8 +3506,8 @@ static int assemble_vector_p2_scalar(fs_space_s* space, const fs_linear_form* fo
     coef_dev sv;
     FS_CHECK(make_coef(form->supg_velocity, 3 * m->nc, sstore, &sv, "fs_assemble_vector(supg_velocity)"));
     const bool supg = form->supg_pe > 0.0 && sv.mode != FS_COEF_NONE;
-    FS_REQUIRE(!supg || ((sv.mode == FS_COEF_CONST || sv.mode == FS_COEF_CELL) && space->inc_cell.p),
-               "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
+    FS_REQUIRE(!supg || sv.mode == FS_COEF_CONST || sv.mode == FS_COEF_CELL, "fs_assemble_vector: the SUPG source term is built for constant / per-cell velocities");
+    if (supg) FS_REQUIRE_TABLES(space, "fs_assemble_vector (SUPG source on CG2)");
     if (space->ncomp == 1 && space->inc_cell.p && (supg || !getenv("FS_SOURCE_ATOMIC")))
         hipLaunchKernelGGL(k_assemble_p2_source_gather, dim3(fs_grid_for(space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s,
                            space->n_nodes_owned, space->n_slices, space->inc_slice_ptr.p, space->inc_cell.p, space->cell_dofs, m->cells.p,

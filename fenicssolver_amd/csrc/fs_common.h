@@ -16,6 +16,9 @@
 #define FS_SLICE 64           // SELL slice height = one wavefront
 #define FS_BLOCK 256          // workgroup size of every kernel (4 waves)
 #define FS_MAX_PARTIAL_BLOCKS 4096
+// Longest row (stored entries, fs_space_s::max_row) of a scalar space that ...
+#define FS_TABLE_MAX_ROW 255   // ... gets row-gather incidence tables: their in-row positions are 8-bit fields (k_inc_fill)
+#define FS_GATHER_MAX_ROW 128  // ... the row-gather MATRIX kernels take: one LDS column of max_row doubles per lane, 64 lanes, 64 KB
 
 // ---- error plumbing -----------------------------------------------------------
 void fs_set_error(const char* fmt, ...);
@@ -354,6 +357,17 @@ struct fs_space_s {
     dbuf<double> bc_g;            // [n_dofs_local]
     dbuf<int32_t> bc_idx;         // [n_dofs_local] index of the last list entry naming the dof
 };
+// Longest row up to which a scalar space gets incidence tables (fs_space_create, step 5a).  CG1 on tetrahedra has a second matrix
+// kernel, k_assemble_p1_scalar over the slot table: such a space takes the tables only where the row-gather matrix kernels can be
+// launched, so that its matrix assembles at every row length.  The other scalar spaces keep them up to the 8-bit positions: their
+// load vectors and projections walk the tables at any length.
+static inline int fs_table_max_row(const fs_space_s* sp) {
+    return (sp->degree == 1 && sp->mesh->tdim == 3) ? FS_GATHER_MAX_ROW : FS_TABLE_MAX_ROW;
+}
+// what the entry points that walk the tables say of a space without them
+#define FS_REQUIRE_TABLES(sp, what)                                                                                                     \
+    FS_REQUIRE((sp)->inc_cell.p, "%s: the space has no row-gather tables: its longest row has %d entries, tables are built up to %d", what, \
+               (sp)->max_row, fs_table_max_row(sp))
 
 struct fs_matrix_s {
     const uint64_t serial = fs_next_serial();

@@ -1405,7 +1405,13 @@ static int space_create_impl(fs_mesh_t mesh, int family, int degree, int ncomp, 
         FS_SP_HIP(hipStreamSynchronize(s));
         }
     }
-    if (ncomp == 1 && sp->max_row <= 255) {
+    const int table_max_row = fs_table_max_row(sp);
+    if (getenv("FS_SPACE_DEBUG"))
+        fprintf(stderr, "[fs_symbolic] longest row %d: %s%s\n", sp->max_row,
+                ncomp != 1 ? "slot table (vector space)" : sp->max_row <= table_max_row ? "row-gather incidence tables" : "slot table, no incidence tables",
+                ncomp != 1 || sp->max_row > table_max_row ? "" : sp->max_row <= 16 ? ", positions of its slice from 16 registers"
+                : sp->max_row <= 32 ? ", positions of its slice from 32 registers" : ", positions of its slice by search in memory");
+    if (ncomp == 1 && sp->max_row <= table_max_row) {
         // 5a. scalar spaces: row-gather incidence tables (deterministic, atomic-free assembly)
         const int64_t n_inc = (int64_t)nd * nc;
         FS_REQUIRE(n_inc < (int64_t)INT32_MAX, "fs_space_create: cell-vertex incidences exceed int32");

@@ -1,5 +1,5 @@
 """Run by tests/test_gpu_kernels.py in two processes (FS_PATTERN_BY_ROWS unset / 0): the sparsity patterns and assembled operators of
-a few CG1 spaces, written to an .npz file (argv[1]) for comparison."""
+a few CG1 / CG2 spaces, written to an .npz file (argv[1]) for comparison."""
 import os
 import sys
 
@@ -50,5 +50,12 @@ ang = 2.0 * np.pi * np.arange(m) / m
 cof = np.vstack([[0.0, 0.0], np.stack([np.cos(ang), np.sin(ang)], axis=1)])
 cef = np.stack([np.zeros(m, dtype=np.int32), 1 + np.arange(m, dtype=np.int32), 1 + (np.arange(m, dtype=np.int32) + 1) % m], axis=1)
 record("fan", B.DeviceMesh(cof, np.sort(cef, axis=1).astype(np.int32)), 1, stiffness=1.0)
+# the same in 3-D (tests/hub_meshes.py): a ball whose hub has 33 entries in its CG1 row, one whose hub has 165 in its CG2 row - one more
+# than the per-row sets of 32 / 160 hold
+import hub_meshes as hm  # noqa: E402
+cob, ceb, _ = hm.ball(32)
+record("ball", B.DeviceMesh(cob, ceb), 1, stiffness=1.0)
+cob, ceb, _ = hm.ball(34)
+record("ball_p2_vector", B.DeviceMesh(cob, ceb), 3, 2, lame=(1.0, 1.5))
 np.savez(sys.argv[1], **out)
 print("ok")
