@@ -332,20 +332,12 @@ static int aniso_upload(const fs_aniso_material* mat, const fs_mesh_s* m, aniso_
     return FS_OK;
 }
 
-static int aniso_require_space(const fs_space_s* sp, const char* who) {
-    FS_REQUIRE(sp, "%s: null space", who);
-    FS_CHECK(fs_require_vector_cg1(sp, who));
-    FS_REQUIRE(sp->slots.p, "%s: vector space without slot table", who);
-    return FS_OK;
-}
-
 static int aniso_upload_eigenstrain(const double* eig, const fs_mesh_s* m, dbuf<double>& store, hipStream_t s, const char* who) {
     if (!eig) return FS_OK;
     const int ne = m->tdim == 3 ? 6 : 4;
     for (int64_t k = 0; k < ne * m->nc; ++k)
         FS_REQUIRE(isfinite(eig[k]), "%s: the eigenstrain of cell %lld (device order) is not finite", who, (long long)(k / ne));
-    FS_CHECK(store.alloc(ne * m->nc));
-    return store.upload(eig, ne * m->nc, s);
+    return fs_upload_cell_rows(store, eig, ne, m->nc, s);
 }
 
 // sigma = C : (eps(u) + scale eps*) of every cell into out (device)
@@ -353,13 +345,11 @@ static void aniso_launch_stress(const fs_space_s* sp, const double* u, const ani
                                 hipStream_t s) {
     const fs_mesh_s* m = sp->mesh;
     const box_snap bx = make_box_snap(m);
-    fs_dispatch_bool(M.frame != nullptr, [&](auto FRAME) {
-        constexpr bool f = decltype(FRAME)::value;
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(m->nc)), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u, M, eig, scale, bx, out);
-        };
-        if (m->tdim == 3) go(k_aniso_cell_stress<3, f>);
-        else go(k_aniso_cell_stress<2, f>);
+    fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+        fs_dispatch_bool(M.frame != nullptr, [&](auto FRAME) {
+            hipLaunchKernelGGL((k_aniso_cell_stress<decltype(TD)::value, decltype(FRAME)::value>), dim3(fs_grid_for(m->nc)), dim3(FS_BLOCK), 0, s, m->nc,
+                               m->cells.p, m->xyz.p, u, M, eig, scale, bx, out);
+        });
     });
 }
 
@@ -369,7 +359,7 @@ extern "C" int fs_assemble_anisotropic(fs_matrix_t A, const fs_aniso_material* m
     FS_CHECK(fs_require_init());
     FS_REQUIRE(A, "%s: null matrix", who);
     fs_space_s* sp = A->space;
-    FS_CHECK(aniso_require_space(sp, who));
+    FS_CHECK(fs_require_solid_space(sp, who));
     FS_REQUIRE(A->bs == sp->ncomp, "%s: the matrix is not on a vector space", who);
     fs_mesh_s* m = sp->mesh;
     const int mmode = mass ? mass->mode : FS_COEF_NONE;
@@ -380,26 +370,19 @@ extern "C" int fs_assemble_anisotropic(fs_matrix_t A, const fs_aniso_material* m
     aniso_store st;
     FS_CHECK(aniso_upload(mat, m, st, s, who));
     dbuf<double> mstore;
-    if (mmode == FS_COEF_CELL) {
-        FS_CHECK(mstore.alloc(m->nc));
-        FS_CHECK(mstore.upload(mass->data, m->nc, s));
-    }
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    if (mmode == FS_COEF_CELL) FS_CHECK(fs_upload_cell_rows(mstore, mass->data, 1, m->nc, s));
     const box_snap bx = make_box_snap(m);
     const double mval = mmode == FS_COEF_CONST ? mass->value : 0.0;
-    fs_dispatch_bool(add != 0, [&](auto ADD) {
-        fs_dispatch_bool(st.dev.frame != nullptr, [&](auto FRAME) {
-            constexpr bool a = decltype(ADD)::value, f = decltype(FRAME)::value;
-            auto gather = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries,
-                                   sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, st.dev, mmode, mval, mstore.p, sp->sell_entries, A->val.p,
-                                   bx);
-            };
-            if (m->tdim == 3) gather(k_assemble_aniso_gather<3, a, f>);
-            else gather(k_assemble_aniso_gather<2, a, f>);
+    int rc = FS_OK;
+    fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+        fs_dispatch_bool(add != 0, [&](auto ADD) {
+            fs_dispatch_bool(st.dev.frame != nullptr, [&](auto FRAME) {
+                rc = p1_launch_blocks(sp, s, k_assemble_aniso_gather<decltype(TD)::value, decltype(ADD)::value, decltype(FRAME)::value>, st.dev, mmode,
+                                      mval, mstore.p, sp->sell_entries, A->val.p, bx);
+            });
         });
     });
-    FS_KERNEL_CHECK();
+    FS_CHECK(rc);
     // (no wait, as fs_assemble_matrix: the host arrays were consumed by the uploads, the stores go back to the pool in stream order)
     return FS_OK;
 }
@@ -411,9 +394,9 @@ extern "C" int fs_anisotropic_stress(fs_space_t space, fs_vector_t u, const fs_a
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     fs_space_s* sp = space;
-    FS_CHECK(aniso_require_space(sp, who));
+    FS_CHECK(fs_require_solid_space(sp, who));
     fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(!u || u->d.n >= sp->n_dofs_local, "%s: displacement vector shorter than the space's dofs", who);
+    if (u) FS_CHECK(fs_require_displacement(u, sp, who));
     FS_REQUIRE((p1_space != nullptr) == (vm_rhs != nullptr), "%s: the von Mises load needs both the scalar CG1 space and its vector", who);
     if (vm_rhs) {
         FS_REFUSE_DG_SPACE(p1_space, "fs_anisotropic_stress");
@@ -431,12 +414,11 @@ extern "C" int fs_anisotropic_stress(fs_space_t space, fs_vector_t u, const fs_a
     FS_CHECK(sstore.alloc(ne * m->nc));
     aniso_launch_stress(sp, u ? u->d.p : nullptr, st.dev, estore.p, -1.0, sstore.p, s);
     if (vm_rhs) {
-        auto load = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(p1_space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, p1_space->n_nodes_owned,
-                               p1_space->n_slices, p1_space->inc_slice_ptr.p, p1_space->inc_cell.p, m->cells.p, m->xyz.p, sstore.p, vm_rhs->d.p);
-        };
-        if (m->tdim == 3) load(k_aniso_von_mises_load<3>);
-        else load(k_aniso_von_mises_load<2>);
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+            hipLaunchKernelGGL(k_aniso_von_mises_load<decltype(TD)::value>, dim3(fs_grid_for(p1_space->n_slices * 64, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0,
+                               s, p1_space->n_nodes_owned, p1_space->n_slices, p1_space->inc_slice_ptr.p, p1_space->inc_cell.p, m->cells.p, m->xyz.p,
+                               sstore.p, vm_rhs->d.p);
+        });
     }
     FS_KERNEL_CHECK();
     if (cell_stress_out) FS_CHECK(sstore.download(cell_stress_out, ne * m->nc, s));
@@ -450,7 +432,7 @@ extern "C" int fs_assemble_anisotropic_load(fs_space_t space, const fs_aniso_mat
     std::lock_guard<std::recursive_mutex> solve_lock(fs_solve_mutex());
     FS_CHECK(fs_require_init());
     fs_space_s* sp = space;
-    FS_CHECK(aniso_require_space(sp, who));
+    FS_CHECK(fs_require_solid_space(sp, who));
     fs_mesh_s* m = sp->mesh;
     FS_REQUIRE(eigenstrain && b, "%s: null pointer", who);
     FS_REQUIRE(b->d.n >= sp->n_dofs_owned, "%s: vector too short", who);
@@ -461,18 +443,14 @@ extern "C" int fs_assemble_anisotropic_load(fs_space_t space, const fs_aniso_mat
     FS_CHECK(aniso_upload_eigenstrain(eigenstrain, m, estore, s, who));
     FS_CHECK(sstore.alloc((m->tdim == 3 ? 6 : 4) * m->nc));
     aniso_launch_stress(sp, nullptr, st.dev, estore.p, 1.0, sstore.p, s);        // C : eps*
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
     const box_snap bx = make_box_snap(m);
-    fs_dispatch_bool(add != 0, [&](auto ADD) {
-        constexpr bool a = decltype(ADD)::value;
-        auto force = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p,
-                               sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, sstore.p, bx, b->d.p);
-        };
-        if (m->tdim == 3) force(k_p1_stress_force_gather<3, a>);
-        else force(k_p1_stress_force_gather<2, a>);
+    int rc = FS_OK;
+    fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+        fs_dispatch_bool(add != 0, [&](auto ADD) {
+            rc = p1_launch_nodes(sp, s, k_p1_stress_force_gather<decltype(TD)::value, decltype(ADD)::value>, sstore.p, bx, b->d.p);
+        });
     });
-    FS_KERNEL_CHECK();
+    FS_CHECK(rc);
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;
 }

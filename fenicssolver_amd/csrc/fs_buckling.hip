@@ -35,37 +35,6 @@ __device__ __forceinline__ void gs_stress(const double (&e)[TD == 3 ? 6 : 4], do
     for (int k = 3; k < (TD == 3 ? 6 : 4); ++k) s[k] = m2 * e[k];
 }
 
-// sym grad u on a tetrahedron whose geometry is at hand (the sum of p1_strain, fs_p1_cell.h)
-__device__ __forceinline__ void gs_strain3(const tet_geom& t, const int32_t (&v)[4], const double* __restrict__ u, double (&e)[6]) {
-    double H[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double ua = u[3 * (int64_t)v[a] + i];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) H[i][j] += ua * t.g[a][j];
-        }
-    e[0] = H[0][0]; e[1] = H[1][1]; e[2] = H[2][2];
-    e[3] = 0.5 * (H[0][1] + H[1][0]); e[4] = 0.5 * (H[0][2] + H[2][0]); e[5] = 0.5 * (H[1][2] + H[2][1]);
-}
-
-__device__ __forceinline__ void gs_strain2(const tri_geom& t, int4 v4, const double* __restrict__ u, double (&e)[4]) {
-    const int32_t v[3] = {v4.x, v4.y, v4.z};
-    double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double2 ua = reinterpret_cast<const double2*>(u)[v[a]];
-        H[0][0] += ua.x * t.g[a][0]; H[0][1] += ua.x * t.g[a][1];
-        H[1][0] += ua.y * t.g[a][0]; H[1][1] += ua.y * t.g[a][1];
-    }
-    e[0] = H[0][0]; e[1] = H[1][1]; e[2] = 0.0; e[3] = 0.5 * (H[0][1] + H[1][0]);
-}
-
 // ---- K_G: one thread per stored block ------------------------------------------------------------------------------------------
 template <int TD, bool CELL>
 __global__ void __launch_bounds__(FS_BLOCK) k_geometric_stiffness_gather(int64_t n_entries, const int32_t* __restrict__ ptr,
@@ -90,13 +59,13 @@ __global__ void __launch_bounds__(FS_BLOCK) k_geometric_stiffness_gather(int64_t
                 const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
                 const tet_geom t = tet_geometry_box(xyz4, v, bx);
                 vol = t.adet * (1.0 / 6.0);
-                gs_strain3(t, v, u, eps);
+                p1_strain_of(t, v, u, eps);
                 P1_GRAD_TET(t, a, ga);
                 P1_GRAD_TET(t, b, gb);
             } else {
                 const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
                 vol = t.area;
-                gs_strain2(t, v4, u, eps);
+                p1_strain_of(t, v4, u, eps);
                 p1_grad(t, a, ga);
                 p1_grad(t, b, gb);
             }
@@ -128,10 +97,10 @@ __global__ void __launch_bounds__(FS_BLOCK) k_cell_stress(int64_t nc, const int3
         if constexpr (TD == 3) {
             const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
             const tet_geom t = tet_geometry_box(xyz4, v, bx);
-            gs_strain3(t, v, u, eps);
+            p1_strain_of(t, v, u, eps);
         } else {
             const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-            gs_strain2(t, v4, u, eps);
+            p1_strain_of(t, v4, u, eps);
         }
         gs_stress<TD>(eps, ml.x, ml.y, sig);
 #pragma unroll
@@ -147,11 +116,10 @@ extern "C" int fs_assemble_geometric_stiffness(fs_space_t space, double mu, doub
     FS_CHECK(fs_require_init());
     FS_REQUIRE(space && u && KG, "fs_assemble_geometric_stiffness: null pointer");
     fs_space_s* sp = space;
-    FS_CHECK(fs_require_vector_cg1(sp, "fs_assemble_geometric_stiffness"));
+    FS_CHECK(fs_require_solid_space(sp, "fs_assemble_geometric_stiffness"));
     fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(sp->slots.p, "fs_assemble_geometric_stiffness: vector space without slot table");
     FS_REQUIRE(KG->space == sp && KG->bs == sp->ncomp, "fs_assemble_geometric_stiffness: the matrix is not on this space");
-    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "fs_assemble_geometric_stiffness: displacement vector shorter than the space's dofs");
+    FS_CHECK(fs_require_displacement(u, sp, "fs_assemble_geometric_stiffness"));
     const bool cellw = lame_cells != nullptr;
     FS_REQUIRE(cellw || (isfinite(mu) && isfinite(lambda)), "fs_assemble_geometric_stiffness: mu = %g, lambda = %g are not finite", mu, lambda);
     hipStream_t s = fs_rt().stream;
@@ -161,31 +129,25 @@ extern "C" int fs_assemble_geometric_stiffness(fs_space_t space, double mu, doub
             FS_REQUIRE(isfinite(lame_cells[2 * c]) && isfinite(lame_cells[2 * c + 1]),
                        "fs_assemble_geometric_stiffness: cell %lld (device order) has mu = %g, lambda = %g", (long long)c, lame_cells[2 * c],
                        lame_cells[2 * c + 1]);
-        FS_CHECK(lstore.alloc(2 * m->nc));
-        FS_CHECK(lstore.upload(lame_cells, 2 * m->nc, s));
+        FS_CHECK(fs_upload_cell_rows(lstore, lame_cells, 2, m->nc, s));
     }
     const double2* lc = reinterpret_cast<const double2*>(lstore.p);
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    FS_CHECK(p1_gather_map(sp, s));          // ahead of the allocation below, as it was
     const box_snap bx = make_box_snap(m);
     const int ne = m->tdim == 3 ? 6 : 4;
     if (cell_stress_out) FS_CHECK(sstore.alloc(ne * m->nc));
-    fs_dispatch_bool(cellw, [&](auto CELL) {
-        constexpr bool c = decltype(CELL)::value;
-        auto gather = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p,
-                               sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, sp->sell_entries, KG->val.p, bx);
-        };
-        auto stress = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(m->nc)), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, bx,
-                               sstore.p);
-        };
-        if (m->tdim == 3) gather(k_geometric_stiffness_gather<3, c>);
-        else gather(k_geometric_stiffness_gather<2, c>);
-        if (cell_stress_out) {
-            if (m->tdim == 3) stress(k_cell_stress<3, c>);
-            else stress(k_cell_stress<2, c>);
-        }
+    int rc = FS_OK;
+    fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+        fs_dispatch_bool(cellw, [&](auto CELL) {
+            constexpr int td = decltype(TD)::value;
+            constexpr bool c = decltype(CELL)::value;
+            rc = p1_launch_blocks(sp, s, k_geometric_stiffness_gather<td, c>, u->d.p, mu, lambda, lc, sp->sell_entries, KG->val.p, bx);
+            if (rc == FS_OK && cell_stress_out)
+                hipLaunchKernelGGL((k_cell_stress<td, c>), dim3(fs_grid_for(m->nc)), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu,
+                                   lambda, lc, bx, sstore.p);
+        });
     });
+    FS_CHECK(rc);
     FS_KERNEL_CHECK();
     if (cell_stress_out) FS_CHECK(sstore.download(cell_stress_out, ne * m->nc, s));
     FS_HIP(hipStreamSynchronize(s));

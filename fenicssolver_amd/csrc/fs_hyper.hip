@@ -27,8 +27,6 @@
 #include "fs_p1_cell.h"
 #include <math.h>
 
-#define FS_HYPER_CELL_BLOCKS 1024      // workgroups of the per-cell pass (its partials are summed in this order)
-
 // ---- kinematics ----------------------------------------------------------------------------------------------------------
 // F = I + sum_a u_a g_a^T, its cofactor matrix (F^-T = cof / J) and J
 // (ld_kinematics of fs_large_deformation.hip computes the same F but sums the vertices into an accumulator that starts at 0, where
@@ -378,14 +376,12 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
     FS_REQUIRE(form->model == FS_HYPER_NEO_HOOKEAN || form->model == FS_HYPER_ST_VENANT_KIRCHHOFF || form->model == FS_HYPER_MOONEY_RIVLIN ||
                    form->model == FS_HYPER_YEOH,
                "fs_assemble_hyperelastic: unknown energy model %d (FS_HYPER_NEO_HOOKEAN, _ST_VENANT_KIRCHHOFF, _MOONEY_RIVLIN, _YEOH)", form->model);
+    const char* who = "fs_assemble_hyperelastic";
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
-    FS_CHECK(fs_require_vector_cg1(sp, "fs_assemble_hyperelastic"));
-    FS_REQUIRE(sp->slots.p, "fs_assemble_hyperelastic: vector space without slot table");
-    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "fs_assemble_hyperelastic: displacement vector shorter than the space's dofs");
-    FS_REQUIRE(!(what & FS_HYPER_TANGENT) || (K && K->space == sp), "fs_assemble_hyperelastic: the tangent needs a matrix on this space");
-    FS_REQUIRE(!(what & FS_HYPER_FORCE) || (r && r->d.n >= sp->n_dofs_owned), "fs_assemble_hyperelastic: the internal force needs a vector of "
-               "the space's owned dofs");
+    FS_CHECK(fs_require_solid_space(sp, who));
+    FS_CHECK(fs_require_displacement(u, sp, who));
+    FS_CHECK(fs_require_tangent_force(what & FS_HYPER_TANGENT, K, what & FS_HYPER_FORCE, r, sp, who));
     FS_REQUIRE(!(what & FS_HYPER_ENERGY) || info, "fs_assemble_hyperelastic: the energy needs an info struct");
     if (form->model != FS_HYPER_NEO_HOOKEAN) return fs_hyper_models_assemble(sp, K, r, u, form, what, info);      // fs_hyper_models.hip
     FS_REQUIRE(form->lame.mode == FS_COEF_NONE || form->lame.mode == FS_COEF_CELL_LAME,
@@ -403,64 +399,47 @@ extern "C" int fs_assemble_hyperelastic(fs_space_t space, fs_matrix_t K, fs_vect
                        "fs_assemble_hyperelastic: cell %lld (device order) has mu = %g, lambda = %g: mu > 0 and lambda >= 0 are required",
                        (long long)c, mc, lc);
         }
-        FS_CHECK(lstore.alloc(2 * m->nc));
-        FS_CHECK(lstore.upload(form->lame.data, 2 * m->nc, s));
+        FS_CHECK(fs_upload_cell_rows(lstore, form->lame.data, 2, m->nc, s));
     }
     const double2* lc = reinterpret_cast<const double2*>(lstore.p);
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    FS_CHECK(p1_gather_map(sp, s));          // ahead of the first launch, also where only the energy is asked for
     const box_snap bx = make_box_snap(m);
     const double mu = form->mu, lambda = form->lambda, ms0 = 0.0;
-    const bool add = form->add != 0;
-    if (what & FS_HYPER_TANGENT) {
-        auto gather = [&](auto kernel, auto... tail) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p,
-                               m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p, tail...);
-        };
-        fs_dispatch_bool(add, [&](auto ADD) {
+    int rc = FS_OK;
+    // the tetrahedron's kernels take the box snap, the triangle's do not: two names, selected with the dimension
+    fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+        fs_dispatch_bool(form->add != 0, [&](auto ADD) {
             fs_dispatch_bool(cellw, [&](auto CELL) {
                 constexpr bool a = decltype(ADD)::value, c = decltype(CELL)::value;
-                if (m->tdim == 3) gather(k_hyper_tangent_gather<a, c>, bx);
-                else gather(k_hyper_tangent_tri_gather<a, c>);
+                if (rc == FS_OK && (what & FS_HYPER_TANGENT)) {
+                    if constexpr (decltype(TD)::value == 3)
+                        rc = p1_launch_blocks(sp, s, k_hyper_tangent_gather<a, c>, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p, bx);
+                    else
+                        rc = p1_launch_blocks(sp, s, k_hyper_tangent_tri_gather<a, c>, u->d.p, mu, lambda, lc, ms0, sp->sell_entries, K->val.p);
+                }
+                if (rc == FS_OK && (what & FS_HYPER_FORCE)) {
+                    if constexpr (decltype(TD)::value == 3) rc = p1_launch_nodes(sp, s, k_hyper_force_gather<a, c>, u->d.p, mu, lambda, lc, bx, r->d.p);
+                    else rc = p1_launch_nodes(sp, s, k_hyper_force_tri_gather<a, c>, u->d.p, mu, lambda, lc, r->d.p);
+                }
             });
         });
-        FS_KERNEL_CHECK();
-    }
-    if (what & FS_HYPER_FORCE) {
-        auto gather = [&](auto kernel, auto... tail) {
-            hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p,
-                               sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, tail...);
-        };
-        fs_dispatch_bool(add, [&](auto ADD) {
-            fs_dispatch_bool(cellw, [&](auto CELL) {
-                constexpr bool a = decltype(ADD)::value, c = decltype(CELL)::value;
-                if (m->tdim == 3) gather(k_hyper_force_gather<a, c>, bx, r->d.p);
-                else gather(k_hyper_force_tri_gather<a, c>, r->d.p);
-            });
-        });
-        FS_KERNEL_CHECK();
-    }
+    });
+    FS_CHECK(rc);
     if (info) {
-        const int nb = FS_HYPER_CELL_BLOCKS;
-        dbuf<double> pe, oe;
-        dbuf<int64_t> part, on;
-        FS_CHECK(pe.alloc(nb)); FS_CHECK(part.alloc(2 * nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
-        fs_dispatch_bool(cellw, [&](auto CELL) {
-            auto cells = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, bx, pe.p, part.p);
-            };
-            if (m->tdim == 3) cells(k_hyper_cells<3, decltype(CELL)::value>);
-            else cells(k_hyper_cells<2, decltype(CELL)::value>);
+        fs_cell_tally<1, true> tally;
+        FS_CHECK(tally.alloc());
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+            fs_dispatch_bool(cellw, [&](auto CELL) {
+                hipLaunchKernelGGL((k_hyper_cells<decltype(TD)::value, decltype(CELL)::value>), dim3(tally.nb), dim3(FS_BLOCK), 0, s, m->nc,
+                                   m->cells.p, m->xyz.p, u->d.p, mu, lambda, lc, bx, tally.part_sum.p, tally.part.p);
+            });
         });
         FS_KERNEL_CHECK();
-        hipLaunchKernelGGL((k_cell_tally_finish<1, true>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
-        FS_KERNEL_CHECK();
-        double e_host = 0.0;
-        int64_t n_host[2] = {0, 0};
-        FS_CHECK(oe.download(&e_host, 1, s));
-        FS_CHECK(on.download(n_host, 2, s));
-        info->energy = e_host;
-        info->n_inverted = n_host[0];
-        info->first_inverted_cell = fs_first_cell(m, n_host[0], n_host[1]);
+        FS_CHECK(tally.finish(s));
+        FS_CHECK(tally.get(s));
+        info->energy = tally.sum;
+        info->n_inverted = tally.n[0];
+        info->first_inverted_cell = fs_first_cell(m, tally.n[0], tally.n[1]);
     }
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;

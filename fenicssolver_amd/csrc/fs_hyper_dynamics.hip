@@ -177,8 +177,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_hdyn_step(int64_t n_nodes, const i
 static int hdyn_space_ok(const fs_space_s* sp, const char* who) {
     FS_REQUIRE(sp, "%s: null space", who);
     FS_REQUIRE(!fs_is_dg(sp), "%s: not built for DG spaces (vector CG1 spaces only)", who);
-    FS_CHECK(fs_require_vector_cg1(sp, who));
-    FS_REQUIRE(sp->slots.p, "%s: vector space without slot table", who);
+    FS_CHECK(fs_require_solid_space(sp, who));
     return fs_march_one_rank(sp, who);
 }
 
@@ -190,15 +189,13 @@ static int hdyn_material(fs_hyper_dyn_state_s* st, const fs_hyper_form* form, co
     std::vector<double> host_rows;
     FS_CHECK(hm_material(form, nc, who, par, host_rows));
     if (!host_rows.empty() && (st->model != form->model || host_rows != st->rows_host)) {
-        FS_CHECK(st->rows.alloc(4 * nc));
-        FS_CHECK(st->rows.upload(host_rows.data(), 4 * nc, s));
+        FS_CHECK(fs_upload_cell_rows(st->rows, host_rows.data(), 4, nc, s));
         FS_HIP(hipStreamSynchronize(s));
     }
     st->rows_host.swap(host_rows);
     st->par = par;
     st->model = form->model;
-    if (!st->space->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(st->space, s));
-    return FS_OK;
+    return p1_gather_map(st->space, s);          // (k_hdyn_step has the marchers' grid: its launch is its own)
 }
 
 template <int MODE>
@@ -209,9 +206,9 @@ static void hdyn_launch(fs_hyper_dyn_state_s* st, const hdyn_rows& R, double sf,
     const double2* rows = st->rows_host.empty() ? nullptr : reinterpret_cast<const double2*>(st->rows.p);
     const int g = fs_march_grid(st->n);
     hm_dispatch_model(st->model, [&](auto M) {
-        fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
             fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
-                hipLaunchKernelGGL((k_hdyn_step<decltype(M), decltype(T3)::value ? 3 : 2, decltype(CELL)::value, MODE>), dim3(g), dim3(FS_BLOCK), 0,
+                hipLaunchKernelGGL((k_hdyn_step<decltype(M), decltype(TD)::value, decltype(CELL)::value, MODE>), dim3(g), dim3(FS_BLOCK), 0,
                                    s, sp->n_nodes_owned, sp->slice_ptr.p, sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p,
                                    st->par, rows, bx, R, st->c, sf, sg);
             });

@@ -41,8 +41,6 @@
 // fs_hyper_energy.h, which fs_hyper_dynamics.hip includes as well.
 #include "fs_hyper_energy.h"
 
-#define FS_HM_CELL_BLOCKS 1024      // workgroups of the per-cell passes (their partials are summed in this order)
-
 // ---- tangent ---------------------------------------------------------------------------------------------------------------------
 template <class M, int TD, bool ADD, bool CELL>
 __global__ void __launch_bounds__(FS_BLOCK) k_hm_tangent(int64_t n_entries, const int32_t* __restrict__ ptr, const int32_t* __restrict__ src,
@@ -203,65 +201,57 @@ static int hm_cells_pass(fs_space_s* sp, fs_vector_s* u, const hm_par& par, cons
     fs_mesh_s* m = sp->mesh;
     hipStream_t s = fs_rt().stream;
     const box_snap bx = make_box_snap(m);
-    const int nb = FS_HM_CELL_BLOCKS;
-    dbuf<double> pe, oe;
-    dbuf<int64_t> part, on;
-    FS_CHECK(pe.alloc(nb)); FS_CHECK(part.alloc(2 * nb)); FS_CHECK(oe.alloc(1)); FS_CHECK(on.alloc(2));
-    fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
-        fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
-            fs_dispatch_bool(stress, [&](auto ST) {
-                hipLaunchKernelGGL((k_hm_cells<M, decltype(T3)::value ? 3 : 2, decltype(CELL)::value, decltype(ST)::value>), dim3(nb),
-                                   dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, par, rows, bx, pe.p, part.p, sig_dev);
+    int rc = FS_OK;
+    fs_dispatch_bool(stress, [&](auto ST) {
+        constexpr bool st = decltype(ST)::value;
+        fs_cell_tally<1, true> tally;                  // the energy is summed where no stress is asked for
+        if ((rc = tally.alloc()) != FS_OK) return;
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+            fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
+                hipLaunchKernelGGL((k_hm_cells<M, decltype(TD)::value, decltype(CELL)::value, st>), dim3(tally.nb), dim3(FS_BLOCK), 0, s, m->nc,
+                                   m->cells.p, m->xyz.p, u->d.p, par, rows, bx, tally.part_sum.p, tally.part.p, sig_dev);
             });
         });
+        if ((rc = tally.finish<!st>(s)) != FS_OK || (rc = tally.get<!st>(s)) != FS_OK) return;
+        info->energy = tally.sum;
+        info->n_inverted = tally.n[0];
+        info->first_inverted_cell = fs_first_cell(m, tally.n[0], tally.n[1]);
     });
-    FS_KERNEL_CHECK();
-    if (stress) hipLaunchKernelGGL((k_cell_tally_finish<1, false>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
-    else hipLaunchKernelGGL((k_cell_tally_finish<1, true>), dim3(1), dim3(64), 0, s, nb, part.p, pe.p, on.p, oe.p);
-    FS_KERNEL_CHECK();
-    double e_host = 0.0;
-    int64_t n_host[2] = {0, 0};
-    if (!stress) FS_CHECK(oe.download(&e_host, 1, s));
-    FS_CHECK(on.download(n_host, 2, s));
+    FS_CHECK(rc);
     FS_HIP(hipStreamSynchronize(s));
-    info->energy = e_host;
-    info->n_inverted = n_host[0];
-    info->first_inverted_cell = fs_first_cell(m, n_host[0], n_host[1]);
     return FS_OK;
 }
 
 template <class M>
 static int hm_assemble(fs_space_s* sp, fs_matrix_s* K, fs_vector_s* r, fs_vector_s* u, const hm_par& par, const double2* rows, bool add,
                        int what, fs_hyper_info* info) {
-    fs_mesh_s* m = sp->mesh;
     hipStream_t s = fs_rt().stream;
-    const box_snap bx = make_box_snap(m);
-    if (what & FS_HYPER_TANGENT) {
-        fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
-            fs_dispatch_bool(add, [&](auto ADD) {
-                fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
-                    hipLaunchKernelGGL((k_hm_tangent<M, decltype(T3)::value ? 3 : 2, decltype(ADD)::value, decltype(CELL)::value>),
-                                       dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p,
-                                       sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, par, rows, sp->sell_entries, K->val.p, bx);
-                });
+    const box_snap bx = make_box_snap(sp->mesh);
+    int rc = FS_OK;
+    fs_dispatch_int<3, 2>(sp->mesh->tdim, [&](auto TD) {
+        fs_dispatch_bool(add, [&](auto ADD) {
+            fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
+                constexpr int td = decltype(TD)::value;
+                constexpr bool a = decltype(ADD)::value, c = decltype(CELL)::value;
+                if (rc == FS_OK && (what & FS_HYPER_TANGENT))
+                    rc = p1_launch_blocks(sp, s, k_hm_tangent<M, td, a, c>, u->d.p, par, rows, sp->sell_entries, K->val.p, bx);
+                if (rc == FS_OK && (what & FS_HYPER_FORCE)) rc = p1_launch_nodes(sp, s, k_hm_force<M, td, a, c>, u->d.p, par, rows, bx, r->d.p);
             });
         });
-        FS_KERNEL_CHECK();
-    }
-    if (what & FS_HYPER_FORCE) {
-        fs_dispatch_bool(m->tdim == 3, [&](auto T3) {
-            fs_dispatch_bool(add, [&](auto ADD) {
-                fs_dispatch_bool(rows != nullptr, [&](auto CELL) {
-                    hipLaunchKernelGGL((k_hm_force<M, decltype(T3)::value ? 3 : 2, decltype(ADD)::value, decltype(CELL)::value>),
-                                       dim3(fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p,
-                                       sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, u->d.p, par, rows, bx, r->d.p);
-                });
-            });
-        });
-        FS_KERNEL_CHECK();
-    }
+    });
+    FS_CHECK(rc);
     if (info) FS_CHECK((hm_cells_pass<M>(sp, u, par, rows, false, nullptr, info)));
     FS_HIP(hipStreamSynchronize(s));
+    return FS_OK;
+}
+
+// the form's material, checked: the parameter row in par, or (per-cell) the rows on the device in store and `rows` pointing at them
+static int hm_material_dev(const fs_hyper_form* form, int64_t nc, const char* who, hm_par& par, dbuf<double>& store, const double2*& rows,
+                           hipStream_t s) {
+    std::vector<double> host_rows;
+    FS_CHECK(hm_material(form, nc, who, par, host_rows));
+    if (!host_rows.empty()) FS_CHECK(fs_upload_cell_rows(store, host_rows.data(), 4, nc, s));
+    rows = host_rows.empty() ? nullptr : reinterpret_cast<const double2*>(store.p);
     return FS_OK;
 }
 
@@ -269,19 +259,13 @@ static int hm_assemble(fs_space_s* sp, fs_matrix_s* K, fs_vector_s* r, fs_vector
 int fs_hyper_models_assemble(fs_space_s* sp, fs_matrix_s* K, fs_vector_s* r, fs_vector_s* u, const fs_hyper_form* form, int what,
                              fs_hyper_info* info) {
     const char* who = "fs_assemble_hyperelastic";
-    fs_mesh_s* m = sp->mesh;
-    hm_par par;
-    std::vector<double> host_rows;
-    FS_CHECK(hm_material(form, m->nc, who, par, host_rows));
-    FS_REQUIRE(form->model != FS_HYPER_NEO_HOOKEAN, "%s: the neo-Hookean energy is assembled by its own kernels", who);
     hipStream_t s = fs_rt().stream;
+    hm_par par;
     dbuf<double> rstore;
-    if (!host_rows.empty()) {
-        FS_CHECK(rstore.alloc(4 * m->nc));
-        FS_CHECK(rstore.upload(host_rows.data(), 4 * m->nc, s));
-    }
-    const double2* rows = host_rows.empty() ? nullptr : reinterpret_cast<const double2*>(rstore.p);
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    const double2* rows = nullptr;
+    FS_CHECK(hm_material_dev(form, sp->mesh->nc, who, par, rstore, rows, s));
+    FS_REQUIRE(form->model != FS_HYPER_NEO_HOOKEAN, "%s: the neo-Hookean energy is assembled by its own kernels", who);
+    FS_CHECK(p1_gather_map(sp, s));          // ahead of the first launch, also where only the energy is asked for
     int rc = FS_OK;
     hm_dispatch_model(form->model, [&](auto M) {
         using model_t = decltype(M);
@@ -296,19 +280,14 @@ extern "C" int fs_hyper_stress(fs_space_t space, fs_vector_t u, const fs_hyper_f
     FS_REQUIRE(space && u && form && sigma, "%s: null pointer", who);
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
-    FS_CHECK(fs_require_vector_cg1(sp, who));
-    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "%s: displacement vector shorter than the space's dofs", who);
-    hm_par par;
-    std::vector<double> host_rows;
-    FS_CHECK(hm_material(form, m->nc, who, par, host_rows));
+    FS_CHECK(fs_require_vector_cg1(sp, who));          // (no gather here: the slot table is not asked for)
+    FS_CHECK(fs_require_displacement(u, sp, who));
     hipStream_t s = fs_rt().stream;
-    const int ne = m->tdim == 3 ? 6 : 4;
+    hm_par par;
     dbuf<double> rstore, sig;
-    if (!host_rows.empty()) {
-        FS_CHECK(rstore.alloc(4 * m->nc));
-        FS_CHECK(rstore.upload(host_rows.data(), 4 * m->nc, s));
-    }
-    const double2* rows = host_rows.empty() ? nullptr : reinterpret_cast<const double2*>(rstore.p);
+    const double2* rows = nullptr;
+    FS_CHECK(hm_material_dev(form, m->nc, who, par, rstore, rows, s));
+    const int ne = m->tdim == 3 ? 6 : 4;
     FS_CHECK(sig.alloc((int64_t)ne * m->nc));
     fs_hyper_info local;
     int rc = FS_OK;

@@ -642,44 +642,30 @@ extern "C" int fs_assemble_large_deformation(fs_matrix_t Jr, fs_vector_t rhs, fs
             for (int i = 0; i < td; ++i) g3[3 * f + i] = form->facet_g[3 * f + i];
         FS_CHECK(C.fg.upload(g3.data(), 3 * nf, s));
     }
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
     const box_snap bx = make_box_snap(m);
     ld_params P;
     P.dt = form->dt; P.q = form->q; P.mu = form->mu; P.lambda = form->lambda;
     for (int i = 0; i < 3; ++i) P.body[i] = form->body_force[i];
     const int64_t plane = sp->sell_entries;
-    const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-    const int gr = fs_grid_for(nn, FS_BLOCK, 8192);
     const int gf = fs_grid_for(std::max<int64_t>(nf, 1));
-    if (td == 3) {
-        hipLaunchKernelGGL(k_ld_jacobian<3>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p,
-                           m->xyz.p, u->d.p, w->d.p, C.d_mask.p, P, bx, plane, Jr->val.p);
+    int rc = FS_OK;
+    fs_dispatch_int<3, 2>(td, [&](auto TD) {          // (the space is one rank's: nn = n_nodes_owned, the node launch's count)
+        constexpr int d = decltype(TD)::value;
+        rc = p1_launch_blocks(sp, s, k_ld_jacobian<d>, u->d.p, w->d.p, C.d_mask.p, P, bx, plane, Jr->val.p);
+        if (rc != FS_OK) return;
         if (nf) {
-            hipLaunchKernelGGL(k_ld_facets<3>, dim3(gf), dim3(FS_BLOCK), 0, s, nf, C.d_fcell.p, C.d_fopp.p, C.fg.p, m->cells.p, m->xyz.p,
+            hipLaunchKernelGGL(k_ld_facets<d>, dim3(gf), dim3(FS_BLOCK), 0, s, nf, C.d_fcell.p, C.d_fopp.p, C.fg.p, m->cells.p, m->xyz.p,
                                u->d.p, bx, C.fr.p, C.fk.p);
-            hipLaunchKernelGGL(k_ld_facet_entries<3>, dim3(fs_grid_for(C.n_touched)), dim3(FS_BLOCK), 0, s, C.n_touched, C.ent.p, C.eptr.p,
+            hipLaunchKernelGGL(k_ld_facet_entries<d>, dim3(fs_grid_for(C.n_touched)), dim3(FS_BLOCK), 0, s, C.n_touched, C.ent.p, C.eptr.p,
                                C.esrc.p, C.d_fcell.p, m->cells.p, C.fk.p, C.d_mask.p, P.dt * P.q, plane, Jr->val.p);
         }
-        hipLaunchKernelGGL(k_ld_nodes<3>, dim3(gr), dim3(FS_BLOCK), 0, s, nn, sp->slice_ptr.p, sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p,
-                           m->cells.p, m->xyz.p, u->d.p, w->d.p, u0->d.p, w0->d.p, C.d_mask.p, P, bx, C.nptr.p, C.nsrc.p, C.d_fcell.p,
-                           C.fr.p, C.fk.p, plane, Jr->val.p, rhs->d.p, C.rn2.p);
-        hipLaunchKernelGGL(k_ld_cells<3>, dim3(FS_LD_BLOCKS), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, bx, nn, C.rn2.p,
+        rc = p1_launch_nodes(sp, s, k_ld_nodes<d>, u->d.p, w->d.p, u0->d.p, w0->d.p, C.d_mask.p, P, bx, C.nptr.p, C.nsrc.p, C.d_fcell.p, C.fr.p,
+                             C.fk.p, plane, Jr->val.p, rhs->d.p, C.rn2.p);
+        if (rc != FS_OK) return;
+        hipLaunchKernelGGL(k_ld_cells<d>, dim3(FS_LD_BLOCKS), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, bx, nn, C.rn2.p,
                            C.part_r.p, C.part.p);
-    } else {
-        hipLaunchKernelGGL(k_ld_jacobian<2>, dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p,
-                           m->xyz.p, u->d.p, w->d.p, C.d_mask.p, P, bx, plane, Jr->val.p);
-        if (nf) {
-            hipLaunchKernelGGL(k_ld_facets<2>, dim3(gf), dim3(FS_BLOCK), 0, s, nf, C.d_fcell.p, C.d_fopp.p, C.fg.p, m->cells.p, m->xyz.p,
-                               u->d.p, bx, C.fr.p, C.fk.p);
-            hipLaunchKernelGGL(k_ld_facet_entries<2>, dim3(fs_grid_for(C.n_touched)), dim3(FS_BLOCK), 0, s, C.n_touched, C.ent.p, C.eptr.p,
-                               C.esrc.p, C.d_fcell.p, m->cells.p, C.fk.p, C.d_mask.p, P.dt * P.q, plane, Jr->val.p);
-        }
-        hipLaunchKernelGGL(k_ld_nodes<2>, dim3(gr), dim3(FS_BLOCK), 0, s, nn, sp->slice_ptr.p, sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p,
-                           m->cells.p, m->xyz.p, u->d.p, w->d.p, u0->d.p, w0->d.p, C.d_mask.p, P, bx, C.nptr.p, C.nsrc.p, C.d_fcell.p,
-                           C.fr.p, C.fk.p, plane, Jr->val.p, rhs->d.p, C.rn2.p);
-        hipLaunchKernelGGL(k_ld_cells<2>, dim3(FS_LD_BLOCKS), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, bx, nn, C.rn2.p,
-                           C.part_r.p, C.part.p);
-    }
+    });
+    FS_CHECK(rc);
     FS_KERNEL_CHECK();
     hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(FS_BLOCK), 0, s, FS_LD_BLOCKS, C.part_r.p, C.part.p, C.part.p + FS_LD_BLOCKS, C.out_r.p,
                        C.out_n.p);

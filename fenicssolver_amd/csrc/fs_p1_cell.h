@@ -1,7 +1,11 @@
-// P1 cell helpers shared by the solid-mechanics kernel files (fs_hyper.hip, fs_buckling.hip, fs_large_deformation.hip,
-// fs_plasticity.hip, fs_viscoelasticity.hip): the gather-map source decode, the diagonal-block lookup, the gradient pick, the strain of a P1 cell,
-// symmetric tensor times vector, the stored-stress force gather, the per-cell tally and the host pieces every such solver repeats
-// (space check, committed / trial buffer pair, first-cell number).
+// P1 cell helpers shared by the solid-mechanics kernel files (fs_hyper.hip, fs_hyper_models.hip, fs_hyper_dynamics.hip,
+// fs_buckling.hip, fs_anisotropic.hip, fs_large_deformation.hip, fs_plasticity.hip, fs_viscoelasticity.hip).
+// Device side: the gather-map source decode, the diagonal-block lookup, the gradient pick, the strain of a P1 cell, symmetric tensor
+// times vector, the stored-stress force gather and the per-cell tally.
+// Host side, the body every entry point of these files shares: the checks of the space and of the handles (fs_require_*), the upload
+// of a checked per-cell table, the two launch shapes of the gathers (p1_launch_blocks, p1_launch_nodes - they own the grids, the
+// leading arguments and the lazy build of the gather map), the cell tally's buffers (fs_cell_tally), the committed / trial buffer
+// pair and the space binding of a per-cell history, and the first-cell number.
 //
 // Tensor storage: 3-D (xx, yy, zz, xy, xz, yz), plane strain (xx, yy, zz, xy) - tensor components, not engineering shears.
 // Nothing here sets fp contraction: a helper takes the default of the file, and a caller's "#pragma clang fp contract(off)" region
@@ -83,39 +87,46 @@ __device__ __forceinline__ void p1_sym_mul(const double (&s)[TD == 3 ? 6 : 4], c
 }
 
 // ---- strain and stress ---------------------------------------------------------------------------------------------------------
-// sym grad u of the P1 displacement u on the cell v4, in the tensor storage (plane strain: e_zz = 0)
+// sym grad u of the P1 displacement u on a cell whose geometry is at hand, in the tensor storage (plane strain: e_zz = 0)
+__device__ __forceinline__ void p1_strain_of(const tet_geom& t, const int32_t (&v)[4], const double* __restrict__ u, double (&e)[6]) {
+    double H[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double ua = u[3 * (int64_t)v[a] + i];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) H[i][j] += ua * t.g[a][j];
+        }
+    e[0] = H[0][0]; e[1] = H[1][1]; e[2] = H[2][2];
+    e[3] = 0.5 * (H[0][1] + H[1][0]); e[4] = 0.5 * (H[0][2] + H[2][0]); e[5] = 0.5 * (H[1][2] + H[2][1]);
+}
+
+__device__ __forceinline__ void p1_strain_of(const tri_geom& t, int4 v4, const double* __restrict__ u, double (&e)[4]) {
+    const int32_t v[3] = {v4.x, v4.y, v4.z};
+    double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double2 ua = reinterpret_cast<const double2*>(u)[v[a]];
+        H[0][0] += ua.x * t.g[a][0]; H[0][1] += ua.x * t.g[a][1];
+        H[1][0] += ua.y * t.g[a][0]; H[1][1] += ua.y * t.g[a][1];
+    }
+    e[0] = H[0][0]; e[1] = H[1][1]; e[2] = 0.0; e[3] = 0.5 * (H[0][1] + H[1][0]);
+}
+
+// ... and on the cell v4
 template <int TD>
 __device__ __forceinline__ void p1_strain(int4 v4, const double* __restrict__ xyz4, const double* __restrict__ u, const box_snap& bx,
                                           double (&e)[TD == 3 ? 6 : 4]) {
     if constexpr (TD == 3) {
         const int32_t v[4] = {v4.x, v4.y, v4.z, v4.w};
-        const tet_geom t = tet_geometry_box(xyz4, v, bx);
-        double H[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double ua = u[3 * (int64_t)v[a] + i];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) H[i][j] += ua * t.g[a][j];
-            }
-        e[0] = H[0][0]; e[1] = H[1][1]; e[2] = H[2][2];
-        e[3] = 0.5 * (H[0][1] + H[1][0]); e[4] = 0.5 * (H[0][2] + H[2][0]); e[5] = 0.5 * (H[1][2] + H[2][1]);
+        p1_strain_of(tet_geometry_box(xyz4, v, bx), v, u, e);
     } else {
-        const tri_geom t = tri_geometry2(xyz4, v4.x, v4.y, v4.z);
-        const int32_t v[3] = {v4.x, v4.y, v4.z};
-        double H[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double2 ua = reinterpret_cast<const double2*>(u)[v[a]];
-            H[0][0] += ua.x * t.g[a][0]; H[0][1] += ua.x * t.g[a][1];
-            H[1][0] += ua.y * t.g[a][0]; H[1][1] += ua.y * t.g[a][1];
-        }
-        e[0] = H[0][0]; e[1] = H[1][1]; e[2] = 0.0; e[3] = 0.5 * (H[0][1] + H[1][0]);
+        p1_strain_of(tri_geometry2(xyz4, v4.x, v4.y, v4.z), v4, u, e);
     }
 }
 
@@ -223,7 +234,8 @@ __global__ void k_cell_tally_finish(int nb, const int64_t* __restrict__ part, co
     out[N] = tf;
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------------------
+// ---- host side: the checks of an entry point ------------------------------------------------------------------------------------
+// `who` is the name of the C entry point, as its messages give it.
 // the spaces these solvers are written for: vector CG1 on tetrahedra or triangles, one rank
 static inline int fs_require_vector_cg1(const fs_space_s* sp, const char* who) {
     FS_REFUSE_DG_SPACE(sp, who);
@@ -235,6 +247,93 @@ static inline int fs_require_vector_cg1(const fs_space_s* sp, const char* who) {
     FS_REQUIRE(m->n_owned == m->nv && sp->n_nodes_owned == sp->n_nodes_local, "%s: the space has ghost nodes (several ranks): not supported", who);
     return FS_OK;
 }
+
+// ... with the slot table that the gather map inverts: what an entry point that launches a gather asks of its space
+static inline int fs_require_solid_space(const fs_space_s* sp, const char* who) {
+    FS_CHECK(fs_require_vector_cg1(sp, who));
+    FS_REQUIRE(sp->slots.p, "%s: vector space without slot table", who);
+    return FS_OK;
+}
+
+static inline int fs_require_displacement(const fs_vector_s* u, const fs_space_s* sp, const char* who) {
+    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "%s: displacement vector shorter than the space's dofs", who);
+    return FS_OK;
+}
+
+// the outputs of a tangent / internal-force assembly: K where the tangent is asked for, r where the force is
+static inline int fs_require_tangent_force(bool tangent, const fs_matrix_s* K, bool force, const fs_vector_s* r, const fs_space_s* sp,
+                                           const char* who) {
+    FS_REQUIRE(!tangent || (K && K->space == sp), "%s: the tangent needs a matrix on this space", who);
+    FS_REQUIRE(!force || (r && r->d.n >= sp->n_dofs_owned), "%s: the internal force needs a vector of the space's owned dofs", who);
+    return FS_OK;
+}
+
+// a per-cell table [nc][width] whose rows the caller has checked, on the device
+static inline int fs_upload_cell_rows(dbuf<double>& store, const double* rows, int width, int64_t nc, hipStream_t s) {
+    FS_CHECK(store.alloc((int64_t)width * nc));
+    return store.upload(rows, (int64_t)width * nc, s);
+}
+
+// ---- host side: the two launch shapes --------------------------------------------------------------------------------------------
+// Every gather of these files is launched one of two ways, and reads the gather map (the inverse of the slot table, built on the
+// first use of a space and kept by it).  The two helpers below build it when it is missing, so no caller needs to.  Some callers
+// still call p1_gather_map themselves, to keep the build where it was in the stream: fs_assemble_viscoelastic outside the events
+// that time its passes, fs_hyper_dyn_* because k_hdyn_step is not launched through a helper, and the hyperelastic, plasticity and
+// geometric-stiffness entry points ahead of a per-cell pass or an allocation that used to follow the build (for these the place
+// does not matter to the result; it keeps the order of launches of a space's first call what it was).
+static inline int p1_gather_map(fs_space_s* sp, hipStream_t s) { return sp->gmap_ptr.p ? (int)FS_OK : fs_space_build_gather_map(sp, s); }
+
+// one thread per STORED block: kernel(sell_entries, gmap_ptr, gmap_src, cells, xyz, tail...)
+template <class K, class... Tail>
+static inline int p1_launch_blocks(fs_space_s* sp, hipStream_t s, K kernel, Tail... tail) {
+    FS_CHECK(p1_gather_map(sp, s));
+    const fs_mesh_s* m = sp->mesh;
+    hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16)), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p,
+                       sp->gmap_src.p, m->cells.p, m->xyz.p, tail...);
+    FS_KERNEL_CHECK();
+    return FS_OK;
+}
+
+// one thread per owned node: kernel(n_nodes_owned, slice_ptr, sell_col, gmap_ptr, gmap_src, cells, xyz, tail...)
+template <class K, class... Tail>
+static inline int p1_launch_nodes(fs_space_s* sp, hipStream_t s, K kernel, Tail... tail) {
+    FS_CHECK(p1_gather_map(sp, s));
+    const fs_mesh_s* m = sp->mesh;
+    hipLaunchKernelGGL(kernel, dim3(fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192)), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p,
+                       sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, tail...);
+    FS_KERNEL_CHECK();
+    return FS_OK;
+}
+
+// ---- host side: the cell tally ---------------------------------------------------------------------------------------------------
+#define FS_CELL_TALLY_BLOCKS 1024      // workgroups of a per-cell pass: its partials are summed in this order, so the number is fixed
+
+// The buffers of p1_cell_tally / k_cell_tally_finish<N, SUM>: the per-cell kernel is launched on nb workgroups with part.p (and
+// part_sum.p), finish() sums the partials, get() brings n[0 .. N - 1] (the counts), n[N] (the smallest index) and sum to the host.
+// A pass that sums in one mode only (hm_cells_pass: the energy, not with the stress) holds the SUM buffers and finishes with S = false.
+template <int N, bool SUM>
+struct fs_cell_tally {
+    static constexpr int nb = FS_CELL_TALLY_BLOCKS;
+    dbuf<double> part_sum, out_sum;          // empty without SUM.  (Declared first: the pool gets the blocks back in the order out,
+    dbuf<int64_t> part, out;                 //  part, out_sum, part_sum, and hands them out again in the order of alloc().)
+    int64_t n[N + 1] = {};
+    double sum = 0.0;
+    int alloc() {
+        if (SUM) FS_CHECK(part_sum.alloc(nb));
+        FS_CHECK(part.alloc((N + 1) * nb));
+        if (SUM) FS_CHECK(out_sum.alloc(1));
+        return out.alloc(N + 1);
+    }
+    template <bool S = SUM> int finish(hipStream_t s) {
+        hipLaunchKernelGGL((k_cell_tally_finish<N, S>), dim3(1), dim3(64), 0, s, nb, part.p, part_sum.p, out.p, out_sum.p);
+        FS_KERNEL_CHECK();
+        return FS_OK;
+    }
+    template <bool S = SUM> int get(hipStream_t s) {
+        if (S) FS_CHECK(out_sum.download(&sum, 1, s));
+        return out.download(n, N + 1, s);
+    }
+};
 
 // one field of a per-cell history: the committed state and the trial state of the last evaluation
 struct fs_history_pair {
@@ -252,6 +351,21 @@ struct fs_history_pair {
         return FS_OK;
     }
     const dbuf<double>& pick(bool trial_) const { return trial_ ? trial : committed; }
+};
+
+// what a per-cell history knows of the space it was created on
+struct fs_cell_history {
+    fs_space_s* space = nullptr;
+    int tdim = 3;
+    int ne = 6;                          // stored tensor components (4 in plane strain)
+    int64_t nc = 0;
+    void bind(fs_space_s* sp) {
+        space = sp;
+        tdim = sp->mesh->tdim;
+        ne = tdim == 3 ? 6 : 4;
+        nc = sp->mesh->nc;
+    }
+    bool owns(const fs_space_s* sp, const fs_mesh_s* m) const { return space == sp && nc == m->nc; }
 };
 
 // the first flagged cell of a tally (a device cell index, meaningful when n_flagged > 0) in the caller's numbering; -1: none

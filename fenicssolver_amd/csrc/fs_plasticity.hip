@@ -28,15 +28,10 @@
 #include "fs_p1_cell.h"
 #include <math.h>
 
-#define FS_PLASTIC_CELL_BLOCKS 1024      // workgroups of the per-cell pass (its partials are summed in this order)
 #define FS_PLASTIC_REC3 10               // doubles per cell of the 3-D tangent record: mu', lambda', c, 0, N[6]
 #define FS_PLASTIC_REC2 6                // plane strain: mu', lambda', c, Nxx, Nyy, Nxy
 
-struct fs_plastic_state_s {
-    fs_space_s* space = nullptr;
-    int tdim = 3;
-    int ne = 6;                          // stored components of eps_p and sigma (4 in plane strain)
-    int64_t nc = 0;
+struct fs_plastic_state_s : fs_cell_history {      // ne: the stored components of eps_p and sigma
     fs_history_pair ep, p, sig;          // plastic strain [nc][ne], cumulative plastic strain [nc], returned stress [nc][ne]
     dbuf<double> rec;                    // tangent record of the last evaluation
 };
@@ -263,10 +258,7 @@ extern "C" int fs_plastic_state_create(fs_space_t space, fs_plastic_state_t* out
     FS_REQUIRE(out, "fs_plastic_state_create: null pointer");
     FS_CHECK(fs_require_vector_cg1(space, "fs_plastic_state_create"));
     fs_plastic_state_s* st = new fs_plastic_state_s();
-    st->space = space;
-    st->tdim = space->mesh->tdim;
-    st->ne = st->tdim == 3 ? 6 : 4;
-    st->nc = space->mesh->nc;
+    st->bind(space);
     const int64_t ne = st->nc * st->ne;
     int rc = FS_OK;
     if ((rc = st->ep.alloc(ne)) || (rc = st->sig.alloc(ne)) || (rc = st->p.alloc(st->nc)) ||
@@ -331,15 +323,13 @@ extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector
     FS_REFUSE_DG_SPACE(space, "fs_assemble_plasticity"); FS_REFUSE_DG(K, "fs_assemble_plasticity");
     FS_REQUIRE(space && u && form && state, "fs_assemble_plasticity: null pointer");
     FS_REQUIRE((what & ~(FS_PLASTIC_TANGENT | FS_PLASTIC_FORCE)) == 0, "fs_assemble_plasticity: unknown bits in what (%d)", what);
-    FS_CHECK(fs_require_vector_cg1(space, "fs_assemble_plasticity"));
+    const char* who = "fs_assemble_plasticity";
+    FS_CHECK(fs_require_solid_space(space, who));
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(state->space == sp && state->nc == m->nc, "fs_assemble_plasticity: the history belongs to another space");
-    FS_REQUIRE(sp->slots.p, "fs_assemble_plasticity: vector space without slot table");
-    FS_REQUIRE(u->d.n >= sp->n_dofs_local, "fs_assemble_plasticity: displacement vector shorter than the space's dofs");
-    FS_REQUIRE(!(what & FS_PLASTIC_TANGENT) || (K && K->space == sp), "fs_assemble_plasticity: the tangent needs a matrix on this space");
-    FS_REQUIRE(!(what & FS_PLASTIC_FORCE) || (r && r->d.n >= sp->n_dofs_owned), "fs_assemble_plasticity: the internal force needs a vector of "
-               "the space's owned dofs");
+    FS_REQUIRE(state->owns(sp, m), "fs_assemble_plasticity: the history belongs to another space");
+    FS_CHECK(fs_require_displacement(u, sp, who));
+    FS_CHECK(fs_require_tangent_force(what & FS_PLASTIC_TANGENT, K, what & FS_PLASTIC_FORCE, r, sp, who));
     FS_REQUIRE(form->material.mode == FS_COEF_NONE || form->material.mode == FS_COEF_CELL_PLASTIC,
                "fs_assemble_plasticity: the material is FS_COEF_NONE (mu, lambda, yield_stress, hardening) or FS_COEF_CELL_PLASTIC");
     const bool cellw = form->material.mode == FS_COEF_CELL_PLASTIC;
@@ -353,60 +343,46 @@ extern "C" int fs_assemble_plasticity(fs_space_t space, fs_matrix_t K, fs_vector
                        isfinite(mc[3]), "fs_assemble_plasticity: cell %lld (device order) has mu = %g, lambda = %g, yield stress = %g, hardening "
                        "= %g: mu > 0, lambda >= 0, yield stress > 0 and hardening >= 0 are required", (long long)c, mc[0], mc[1], mc[2], mc[3]);
         }
-        FS_CHECK(mstore.alloc(4 * m->nc));
-        FS_CHECK(mstore.upload(form->material.data, 4 * m->nc, s));
+        FS_CHECK(fs_upload_cell_rows(mstore, form->material.data, 4, m->nc, s));
     } else {
         FS_REQUIRE(form->mu > 0.0 && form->lambda >= 0.0 && form->yield_stress > 0.0 && form->hardening >= 0.0 && isfinite(form->mu) &&
                    isfinite(form->lambda) && isfinite(form->yield_stress) && isfinite(form->hardening),
                    "fs_assemble_plasticity: mu > 0, lambda >= 0, yield stress > 0 and hardening >= 0 are required (mu = %g, lambda = %g, yield "
                    "stress = %g, hardening = %g)", form->mu, form->lambda, form->yield_stress, form->hardening);
     }
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    FS_CHECK(p1_gather_map(sp, s));          // ahead of the per-cell pass, the first launch
     const box_snap bx = make_box_snap(m);
-    const bool add = form->add != 0;
     const double ms0 = 0.0;
-    // 1. the return mapping, once per cell
-    const int nb = FS_PLASTIC_CELL_BLOCKS;
-    dbuf<int64_t> part, on;
-    FS_CHECK(part.alloc(3 * nb)); FS_CHECK(on.alloc(3));
-#define FS_PC(T_, C_) hipLaunchKernelGGL((k_plastic_cells<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, form->mu, \
-                                         form->lambda, form->yield_stress, form->hardening, mstore.p, bx, state->ep.committed.p,                 \
-                                         state->p.committed.p, state->ep.trial.p, state->p.trial.p, state->sig.trial.p, state->rec.p, part.p)
-    if (m->tdim == 3) { if (cellw) FS_PC(3, true); else FS_PC(3, false); }
-    else { if (cellw) FS_PC(2, true); else FS_PC(2, false); }
-#undef FS_PC
-    FS_KERNEL_CHECK();
-    hipLaunchKernelGGL((k_cell_tally_finish<2, false>), dim3(1), dim3(64), 0, s, nb, part.p, nullptr, on.p, nullptr);
-    FS_KERNEL_CHECK();
-    // 2. the tangent, per stored block
-    if (what & FS_PLASTIC_TANGENT) {
-        const int gg = fs_grid_for(sp->sell_entries, FS_BLOCK, 1 << 16);
-#define FS_PT3(A_) hipLaunchKernelGGL((k_plastic_tangent_gather<A_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
-                                      sp->gmap_src.p, m->cells.p, m->xyz.p, state->rec.p, ms0, sp->sell_entries, K->val.p, bx)
-#define FS_PT2(A_) hipLaunchKernelGGL((k_plastic_tangent_tri_gather<A_>), dim3(gg), dim3(FS_BLOCK), 0, s, sp->sell_entries, sp->gmap_ptr.p, \
-                                      sp->gmap_src.p, m->cells.p, m->xyz.p, state->rec.p, ms0, sp->sell_entries, K->val.p)
-        if (m->tdim == 3) { if (add) FS_PT3(true); else FS_PT3(false); }
-        else { if (add) FS_PT2(true); else FS_PT2(false); }
-#undef FS_PT3
-#undef FS_PT2
-        FS_KERNEL_CHECK();
-    }
-    // 3. the internal force, per owned node
-    if (what & FS_PLASTIC_FORCE) {
-        const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
-#define FS_PF(T_, A_) hipLaunchKernelGGL((k_p1_stress_force_gather<T_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
-                                         sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig.trial.p, bx, r->d.p)
-        if (m->tdim == 3) { if (add) FS_PF(3, true); else FS_PF(3, false); }
-        else { if (add) FS_PF(2, true); else FS_PF(2, false); }
-#undef FS_PF
-        FS_KERNEL_CHECK();
-    }
+    fs_cell_tally<2, false> tally;             // yielded, non-finite
+    FS_CHECK(tally.alloc());
+    int rc = FS_OK;
+    fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+        constexpr int td = decltype(TD)::value;
+        // 1. the return mapping, once per cell
+        fs_dispatch_bool(cellw, [&](auto CELL) {
+            hipLaunchKernelGGL((k_plastic_cells<td, decltype(CELL)::value>), dim3(tally.nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p,
+                               form->mu, form->lambda, form->yield_stress, form->hardening, mstore.p, bx, state->ep.committed.p,
+                               state->p.committed.p, state->ep.trial.p, state->p.trial.p, state->sig.trial.p, state->rec.p, tally.part.p);
+        });
+        if ((rc = tally.finish(s)) != FS_OK) return;
+        fs_dispatch_bool(form->add != 0, [&](auto ADD) {
+            constexpr bool a = decltype(ADD)::value;
+            // 2. the tangent, per stored block (the tetrahedron's kernel takes the box snap: another name)
+            if (what & FS_PLASTIC_TANGENT) {
+                if constexpr (td == 3) rc = p1_launch_blocks(sp, s, k_plastic_tangent_gather<a>, state->rec.p, ms0, sp->sell_entries, K->val.p, bx);
+                else rc = p1_launch_blocks(sp, s, k_plastic_tangent_tri_gather<a>, state->rec.p, ms0, sp->sell_entries, K->val.p);
+            }
+            // 3. the internal force, per owned node
+            if (rc == FS_OK && (what & FS_PLASTIC_FORCE))
+                rc = p1_launch_nodes(sp, s, k_p1_stress_force_gather<td, a>, state->sig.trial.p, bx, r->d.p);
+        });
+    });
+    FS_CHECK(rc);
     if (info) {
-        int64_t n_host[3] = {0, 0, 0};
-        FS_CHECK(on.download(n_host, 3, s));
-        info->n_yielded = n_host[0];
-        info->n_nonfinite = n_host[1];
-        info->first_nonfinite_cell = fs_first_cell(m, n_host[1], n_host[2]);
+        FS_CHECK(tally.get(s));
+        info->n_yielded = tally.n[0];
+        info->n_nonfinite = tally.n[1];
+        info->first_nonfinite_cell = fs_first_cell(m, tally.n[1], tally.n[2]);
     }
     FS_HIP(hipStreamSynchronize(s));
     return FS_OK;

@@ -31,15 +31,10 @@
 #include "fs_p1_cell.h"
 #include <math.h>
 
-#define FS_VISCO_CELL_BLOCKS 1024        // workgroups of the per-cell pass (its partials are summed in this order)
 #define FS_VISCO_SERIES_X 1e-5           // below this dt/tau, b_k comes from its series (see the file header)
 
-struct fs_visco_state_s {
-    fs_space_s* space = nullptr;
-    int tdim = 3;
-    int ne = 6;                          // stored tensor components (4 in plane strain)
+struct fs_visco_state_s : fs_cell_history {
     int nt = 0;                          // Prony terms
-    int64_t nc = 0;
     fs_history_pair e, h, sig;           // dev eps [nc][ne], h_k [nc][nt][ne], stress [nc][ne]
     hipEvent_t ev[8] = {};               // (start, stop) of the table launch and of the three passes: created once, on first use
     ~fs_visco_state_s() {
@@ -242,11 +237,8 @@ extern "C" int fs_visco_state_create(fs_space_t space, int n_terms, fs_visco_sta
     FS_REQUIRE(n_terms >= 0 && n_terms <= FS_VISCO_MAX_TERMS, "fs_visco_state_create: %d Prony terms: 0 to FS_VISCO_MAX_TERMS = %d are "
                "supported", n_terms, FS_VISCO_MAX_TERMS);
     fs_visco_state_s* st = new fs_visco_state_s();
-    st->space = space;
-    st->tdim = space->mesh->tdim;
-    st->ne = st->tdim == 3 ? 6 : 4;
+    st->bind(space);
     st->nt = n_terms;
-    st->nc = space->mesh->nc;
     const int64_t ne = st->nc * st->ne;
     const int64_t nh = ne * (n_terms > 0 ? n_terms : 1);          // (never an empty allocation)
     int rc = FS_OK;
@@ -335,16 +327,15 @@ extern "C" int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vect
     FS_REQUIRE((what & ~(FS_VISCO_LOAD | FS_VISCO_UPDATE | FS_VISCO_FORCE)) == 0, "fs_assemble_viscoelastic: unknown bits in what (%d)", what);
     FS_REQUIRE(!((what & FS_VISCO_LOAD) && (what & FS_VISCO_FORCE)), "fs_assemble_viscoelastic: FS_VISCO_LOAD and FS_VISCO_FORCE write the "
                "same vector: one of them per call");
-    FS_CHECK(fs_require_vector_cg1(space, "fs_assemble_viscoelastic"));
+    FS_CHECK(fs_require_solid_space(space, "fs_assemble_viscoelastic"));
     fs_space_s* sp = space;
     fs_mesh_s* m = sp->mesh;
-    FS_REQUIRE(state->space == sp && state->nc == m->nc, "fs_assemble_viscoelastic: the history belongs to another space");
+    FS_REQUIRE(state->owns(sp, m), "fs_assemble_viscoelastic: the history belongs to another space");
     const int nt = form->n_terms;
     FS_REQUIRE(nt >= 0 && nt <= FS_VISCO_MAX_TERMS, "fs_assemble_viscoelastic: %d Prony terms: at most FS_VISCO_MAX_TERMS = %d are supported",
                nt, FS_VISCO_MAX_TERMS);
     FS_REQUIRE(nt == state->nt, "fs_assemble_viscoelastic: the form has %d Prony terms, the history was created for %d", nt, state->nt);
     FS_REQUIRE(form->dt > 0.0 && isfinite(form->dt), "fs_assemble_viscoelastic: the step length is %g: dt > 0 and finite is required", form->dt);
-    FS_REQUIRE(sp->slots.p, "fs_assemble_viscoelastic: vector space without slot table");
     FS_REQUIRE(!(what & FS_VISCO_UPDATE) || (u && u->d.n >= sp->n_dofs_local), "fs_assemble_viscoelastic: the update needs a displacement "
                "vector of the space's dofs");
     FS_REQUIRE(!(what & (FS_VISCO_LOAD | FS_VISCO_FORCE)) || (r && r->d.n >= sp->n_dofs_owned), "fs_assemble_viscoelastic: the history load "
@@ -368,8 +359,7 @@ extern "C" int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vect
             const double* mc = form->material.data + (int64_t)ms * c;
             FS_CHECK(visco_material_ok(mc[0], mc[1], nt, mc + 2, (long long)c));
         }
-        FS_CHECK(mstore.alloc((int64_t)ms * m->nc));
-        FS_CHECK(mstore.upload(form->material.data, (int64_t)ms * m->nc, s));
+        FS_CHECK(fs_upload_cell_rows(mstore, form->material.data, ms, m->nc, s));
     } else {
         double gt[2 * FS_VISCO_MAX_TERMS];
         for (int k = 0; k < nt; ++k) { gt[2 * k] = form->g[k]; gt[2 * k + 1] = form->tau[k]; }
@@ -383,61 +373,57 @@ extern "C" int fs_assemble_viscoelastic(fs_space_t space, fs_vector_t r, fs_vect
             FS_VT(1);
         }
     }
-    if (!sp->gmap_ptr.p) FS_CHECK(fs_space_build_gather_map(sp, s));
+    FS_CHECK(p1_gather_map(sp, s));          // ahead of the passes, outside the events that time them
     const box_snap bx = make_box_snap(m);
-    const bool add = form->add != 0;
-    const int gr = fs_grid_for(sp->n_nodes_owned, FS_BLOCK, 8192);
-#define FS_VG(T_, C_, A_) hipLaunchKernelGGL((k_visco_gather<T_, C_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p,   \
-                                             sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, bx, form->mu, nt, tm, coef.p, \
-                                             form->dt, mstore.p, state->e.committed.p, state->h.committed.p, r->d.p)
-#define FS_VG_ADD(T_, C_) do { if (add) FS_VG(T_, C_, true); else FS_VG(T_, C_, false); } while (0)
-#define FS_VF(T_, A_) hipLaunchKernelGGL((k_p1_stress_force_gather<T_, A_>), dim3(gr), dim3(FS_BLOCK), 0, s, sp->n_nodes_owned, sp->slice_ptr.p, \
-                                         sp->sell_col.p, sp->gmap_ptr.p, sp->gmap_src.p, m->cells.p, m->xyz.p, state->sig.trial.p, bx, r->d.p)
+    fs_cell_tally<1, false> tally;
+    int rc = FS_OK;
     // 1. the history load, from the committed state
     if (what & FS_VISCO_LOAD) {
         FS_VT(2);
-        if (m->tdim == 3) { if (cellw) FS_VG_ADD(3, true); else FS_VG_ADD(3, false); }
-        else { if (cellw) FS_VG_ADD(2, true); else FS_VG_ADD(2, false); }
-        FS_KERNEL_CHECK();
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+            fs_dispatch_bool(cellw, [&](auto CELL) {
+                fs_dispatch_bool(form->add != 0, [&](auto ADD) {
+                    rc = p1_launch_nodes(sp, s, k_visco_gather<decltype(TD)::value, decltype(CELL)::value, decltype(ADD)::value>, bx, form->mu, nt, tm,
+                                         coef.p, form->dt, mstore.p, state->e.committed.p, state->h.committed.p, r->d.p);
+                });
+            });
+        });
+        FS_CHECK(rc);
         FS_VT(3);
     }
     // 2. the update, once per cell
-    dbuf<int64_t> part, on;
     if (what & FS_VISCO_UPDATE) {
-        const int nb = FS_VISCO_CELL_BLOCKS;
-        FS_CHECK(part.alloc(2 * nb)); FS_CHECK(on.alloc(2));
+        FS_CHECK(tally.alloc());
         FS_VT(4);
-#define FS_VU(T_, C_) hipLaunchKernelGGL((k_visco_update<T_, C_>), dim3(nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p, m->xyz.p, u->d.p, form->mu, \
-                                         form->lambda, nt, tm, coef.p, form->dt, mstore.p, bx, state->e.committed.p, state->h.committed.p,       \
-                                         state->e.trial.p, state->h.trial.p, state->sig.trial.p, part.p)
-        if (m->tdim == 3) { if (cellw) FS_VU(3, true); else FS_VU(3, false); }
-        else { if (cellw) FS_VU(2, true); else FS_VU(2, false); }
-#undef FS_VU
-        FS_KERNEL_CHECK();
-        hipLaunchKernelGGL((k_cell_tally_finish<1, false>), dim3(1), dim3(64), 0, s, nb, part.p, nullptr, on.p, nullptr);
-        FS_KERNEL_CHECK();
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+            fs_dispatch_bool(cellw, [&](auto CELL) {
+                hipLaunchKernelGGL((k_visco_update<decltype(TD)::value, decltype(CELL)::value>), dim3(tally.nb), dim3(FS_BLOCK), 0, s, m->nc, m->cells.p,
+                                   m->xyz.p, u->d.p, form->mu, form->lambda, nt, tm, coef.p, form->dt, mstore.p, bx, state->e.committed.p,
+                                   state->h.committed.p, state->e.trial.p, state->h.trial.p, state->sig.trial.p, tally.part.p);
+            });
+        });
+        FS_CHECK(tally.finish(s));
         FS_VT(5);
     }
     // 3. the internal force of the trial stress
     if (what & FS_VISCO_FORCE) {
         FS_VT(6);
-        if (m->tdim == 3) { if (add) FS_VF(3, true); else FS_VF(3, false); }
-        else { if (add) FS_VF(2, true); else FS_VF(2, false); }
-        FS_KERNEL_CHECK();
+        fs_dispatch_int<3, 2>(m->tdim, [&](auto TD) {
+            fs_dispatch_bool(form->add != 0, [&](auto ADD) {
+                rc = p1_launch_nodes(sp, s, k_p1_stress_force_gather<decltype(TD)::value, decltype(ADD)::value>, state->sig.trial.p, bx, r->d.p);
+            });
+        });
+        FS_CHECK(rc);
         FS_VT(7);
     }
 #undef FS_VT
-#undef FS_VG_ADD
-#undef FS_VG
-#undef FS_VF
     if (info) {
         info->n_nonfinite = 0;
         info->first_nonfinite_cell = -1;
         if (what & FS_VISCO_UPDATE) {
-            int64_t n_host[2] = {0, 0};
-            FS_CHECK(on.download(n_host, 2, s));
-            info->n_nonfinite = n_host[0];
-            info->first_nonfinite_cell = fs_first_cell(m, n_host[0], n_host[1]);
+            FS_CHECK(tally.get(s));
+            info->n_nonfinite = tally.n[0];
+            info->first_nonfinite_cell = fs_first_cell(m, tally.n[0], tally.n[1]);
         }
     }
     FS_HIP(hipStreamSynchronize(s));
